@@ -9,7 +9,14 @@ With --gpus N every rank solves its own 65536-trajectory shard (weak scaling; 8 
 524288 trajectories) and the step ends with the RCCL gather of sd^2 to rank 0 that the north star
 names.  `value` is whole-job trajectories/s.
 
+A plain run sets up, warms up, times the steps and prints the line.  Everything beside the headline figure
+(HIP-event kernel time and roofline, full-iteration / family-2 / measurement-build kernels, BASELINE configs,
+end-to-end pipeline, CPU baselines, rocprofv3 counter passes, per-rank kernel and gather-alone times) runs
+with --full only.  --dump-outputs DIR writes what the last timed step computed (a fixed sample of its
+trajectories) as DIR/<name>.npy, for comparing two builds output for output.
+
   python bench.py                      # 1 GPU
+  python bench.py --full               # + every secondary measurement
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -578,6 +585,34 @@ def end_to_end(torch, tb, dev, B=65536, d=7, N=200, samples=64):
                     "cache-line granularity" % (8 * B * 4 * N * d / 1e9, samples)}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # well under the 64 MB the dump may hold
+DUMP_MAX_TRAJECTORIES = 4096
+
+
+def dump_outputs(path, out, gathered=None):
+    """Write what the last timed step returned -- sd2 [B, N+1], u [B, N], K [B, N+1, 2], status [B] (float64; status
+    holds small integers) and, with N > 1 ranks, the sd2 shards that the gather delivered to rank 0 -- as
+    `path`/<name>.npy.  Rows are a fixed sample of the trajectories (seeded, sorted; every trajectory when the batch
+    is small), listed in `trajectory_index.npy`; the same sample for every build, so two runs compare row for row."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    B = int(arrays["sd2"].shape[0])
+    per_traj = sum(8 * int(np.prod(v.shape[1:])) for v in arrays.values())
+    if gathered:
+        per_traj += 8 * len(gathered) * int(np.prod(gathered[0].shape[1:]))
+    n = max(1, min(B, DUMP_MAX_TRAJECTORIES, DUMP_BUDGET_BYTES // max(1, per_traj)))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(20240924).choice(B, n, replace=False))
+    sel = torch.from_numpy(idx)
+    files = {"trajectory_index": idx.astype(np.float64)}
+    for k, v in arrays.items():
+        files[k] = v.index_select(0, sel.to(v.device)).to(torch.float64).cpu().numpy()
+    if gathered:
+        files["gathered_sd2"] = np.stack([g.index_select(0, sel.to(g.device)).to(torch.float64).cpu().numpy() for g in gathered])
+    for name, arr in files.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr))
+
+
 def self_launch(n):
     """Re-run this command line under torch.distributed.run with n ranks on this node; returns its exit code."""
     import socket
@@ -601,6 +636,14 @@ def main():
     ap.add_argument("--dof", type=int, default=7)
     ap.add_argument("--gridpoints", type=int, default=200, help="N (stages)")
     ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beside the headline figure: HIP-event kernel time and roofline (with the "
+                         "rocprofv3 counter passes), full-iteration / family-2 kernels, the two measurement builds, the "
+                         "BASELINE configs, the end-to-end pipeline, the CPU baselines, per-rank kernel and gather-alone "
+                         "times (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed sample of its trajectories) "
+                         "as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-reps", type=int, default=5)
     ap.add_argument("--gather", choices=["auto", "overlap", "sequential"], default="auto",
@@ -619,6 +662,8 @@ def main():
                     help="skip the secondary (full iteration, family 2) measurements (used under rocprofv3 so that the "
                          "kernel statistics cover the headline mode only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: launch the N ranks ourselves, exactly as the driver's own command would
@@ -741,23 +786,28 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # (before anything else launches into `out`: what the last timed step returned)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, gatherer.bufs if gatherer is not None else None)
 
     gather_check = None
     if stub and gatherer is not None and rank == 0:
         # after the last fence the receive buffers hold every rank's LAST step: tag = 1000 r + (number of steps it ran)
         bufs = gatherer.bufs
         gather_check = all(bool((bufs[r] == float(1000 * r + stub_step["n"])).all()) for r in range(world))
-    # dominant kernel: average launch duration with HIP events on the launch stream
+    # dominant kernel (--full): average launch duration with HIP events on the launch stream
+    kernel_ms = None
     if stub:
         kernel_ms = 1.0 + 0.01 * rank
-    else:
+    elif args.full:
         kernel_ms = tb.solve_batch_timed(dv["coef"], dv["breaks"], dv["grid"], dv["vlim"], dv["alim"], out,
                                          reps=args.kernel_reps, variant=args.variant)
-    # secondary (single-GPU kernel times, not the headline): the reference's full Seidel iteration for
+    # secondary (--full; single-GPU kernel times, not the headline): the reference's full Seidel iteration for
     # every LP (TPR_STRICT_SEIDEL, kernel family 2) and family 2 with its certified shortcuts; the
     # default path must return the same bits as the full iteration
     strict_ms = family2_ms = same_bits = None
-    if not args.no_secondary and world == 1:
+    secondary = args.full and not args.no_secondary and world == 1
+    if secondary:
         reps = max(2, args.kernel_reps // 2)
         full = tb.solve_batch(dv["coef"], dv["breaks"], dv["grid"], dv["vlim"], dv["alim"], strict=True)
         same_bits = all(bool(torch.equal(torch.nan_to_num(out[k], nan=-7.0), torch.nan_to_num(full[k], nan=-7.0)))
@@ -768,10 +818,10 @@ def main():
                                           reps=reps, variant=2)
     ok_frac = float((out["status"] == 0).double().mean().item())
 
-    # multi-GPU: what each rank's kernel took and what the gather costs on its own (outside the timed region),
-    # so that an N > 1 line explains itself
+    # multi-GPU (--full): what each rank's kernel took and what the gather costs on its own (outside the timed
+    # region), so that an N > 1 line explains itself
     per_rank_kernel_ms = gather_alone_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         t = torch.zeros(world, dtype=torch.float64, device=cdev)
         t[rank] = kernel_ms
         dist.all_reduce(t)
@@ -789,14 +839,7 @@ def main():
         gather_alone_ms = float(tg.item())
 
     if rank == 0:
-        bytes_per_traj = algorithmic_bytes(d, N, nseg)
-        achieved = bytes_per_traj * B / (kernel_ms * 1e-3) / 1e9
         traj_per_s = world * B * args.steps / elapsed
-        pmc = None
-        if not stub and world == 1 and not args.no_configs:  # (the full default run; short / profiled runs replay the committed passes)
-            pmc = pmc_measure(B, d, N, args.variant, kernel_ms)
-        if pmc is None and not stub:
-            pmc = pmc_traffic(B, d, N, kernel_ms)
         line = {
             "metric": "trajectories/sec (7-DoF N=200 batch; waypoint-LPs/sec = 3N x this)",
             "value": traj_per_s,
@@ -821,60 +864,71 @@ def main():
             },
             "waypoint_lps_per_s": 3 * N * traj_per_s,
             "gather_placement": (calibration or {"chosen": gather_mode["value"]}) if world > 1 else None,
-            "per_rank_kernel_ms": per_rank_kernel_ms,
-            "gather_alone_ms": gather_alone_ms,
-            "secondary_measured": (not args.no_secondary) and world == 1,
-            "full_iteration": {
-                "note": "TPR_STRICT_SEIDEL: every stage LP through the reference's full Seidel iteration (kernel "
-                        "family 2) instead of the certified answers; single-GPU kernel time only",
-                "kernel_ms": strict_ms, "value_per_gpu": (B / strict_ms * 1e3) if strict_ms else None,
-                "unit": "trajectories/s",
-                "default_path_returns_identical_bits": same_bits,
-            },
-            "certificates": "trace-following (sound) certificates are the only mode since round 4: a stage LP is answered from a "
-                            "certificate only where the reference's whole pivot sequence is predictable (DESIGN.md 3.1); "
-                            "TPR_SOUND_CERTIFICATES is accepted and ignored",
-            "family2_rows_across_lanes": {
-                "note": "kernel family 2 (8 lanes per trajectory) with its certified shortcuts; serves d > 8 and the "
-                        "strict mode; single-GPU kernel time only",
-                "kernel_ms": family2_ms, "value_per_gpu": (B / family2_ms * 1e3) if family2_ms else None,
-                "unit": "trajectories/s",
-            },
             "ok_fraction": ok_frac,
-            "roofline": {
-                # bound / achieved / peak / unit / frac are ONE consistent set: the HBM figures the contract defines --
-                # algorithmic bytes per launch / kernel time measured in this run against the 8 TB/s peak (BASELINE's target is
-                # quoted against HBM).  What actually BINDS the kernel is fp64 VALU instruction issue: `binding_resource` here
-                # and the separate roofline_compute block (no MFMA on this path: there is no dense contraction)
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "hbm_frac": achieved / HBM_PEAK_GBS,
-                "binding_resource": "valu_issue",
-                "binding_resource_frac": (compute_roofline(pmc, kernel_ms) or {}).get("frac"),
-                "traffic": pmc["bytes_per_launch"] if pmc else None,
-                "algorithmic_bytes_per_launch": bytes_per_traj * B,
-                "kernel_ms": kernel_ms,
-                "algorithmic_bytes_per_trajectory": bytes_per_traj,
-                "traffic_source": (pmc["source"] + ("" if pmc.get("measured_in_this_run") else " -- REPLAYED from the committed profile, not measured in this run")) if pmc else None,
-                "pmc": pmc,
-                "note": "the fused path is bound by fp64 VALU issue and, at one wave per SIMD, by its own dependency "
-                        "latencies -- not by HBM: DESIGN.md section 3.8; see roofline_compute",
-            },
-            "roofline_compute": compute_roofline(pmc, kernel_ms),
+            "full": bool(args.full),
         }
+        if args.full:
+            bytes_per_traj = algorithmic_bytes(d, N, nseg)
+            achieved = bytes_per_traj * B / (kernel_ms * 1e-3) / 1e9
+            pmc = None
+            if not stub and world == 1 and not args.no_configs:  # (a full run's own counter passes; short / profiled runs replay the committed ones)
+                pmc = pmc_measure(B, d, N, args.variant, kernel_ms)
+            if pmc is None and not stub:
+                pmc = pmc_traffic(B, d, N, kernel_ms)
+            line.update({
+                "per_rank_kernel_ms": per_rank_kernel_ms,
+                "gather_alone_ms": gather_alone_ms,
+                "secondary_measured": secondary,
+                "full_iteration": {
+                    "note": "TPR_STRICT_SEIDEL: every stage LP through the reference's full Seidel iteration (kernel "
+                            "family 2) instead of the certified answers; single-GPU kernel time only",
+                    "kernel_ms": strict_ms, "value_per_gpu": (B / strict_ms * 1e3) if strict_ms else None,
+                    "unit": "trajectories/s",
+                    "default_path_returns_identical_bits": same_bits,
+                },
+                "certificates": "trace-following (sound) certificates are the only mode since round 4: a stage LP is answered from a "
+                                "certificate only where the reference's whole pivot sequence is predictable (DESIGN.md 3.1); "
+                                "TPR_SOUND_CERTIFICATES is accepted and ignored",
+                "family2_rows_across_lanes": {
+                    "note": "kernel family 2 (8 lanes per trajectory) with its certified shortcuts; serves d > 8 and the "
+                            "strict mode; single-GPU kernel time only",
+                    "kernel_ms": family2_ms, "value_per_gpu": (B / family2_ms * 1e3) if family2_ms else None,
+                    "unit": "trajectories/s",
+                },
+                "roofline": {
+                    # bound / achieved / peak / unit / frac are ONE consistent set: the HBM figures the contract defines --
+                    # algorithmic bytes per launch / kernel time measured in this run against the 8 TB/s peak (BASELINE's target is
+                    # quoted against HBM).  What actually BINDS the kernel is fp64 VALU instruction issue: `binding_resource` here
+                    # and the separate roofline_compute block (no MFMA on this path: there is no dense contraction)
+                    "bound": "hbm",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "hbm_frac": achieved / HBM_PEAK_GBS,
+                    "binding_resource": "valu_issue",
+                    "binding_resource_frac": (compute_roofline(pmc, kernel_ms) or {}).get("frac"),
+                    "traffic": pmc["bytes_per_launch"] if pmc else None,
+                    "algorithmic_bytes_per_launch": bytes_per_traj * B,
+                    "kernel_ms": kernel_ms,
+                    "algorithmic_bytes_per_trajectory": bytes_per_traj,
+                    "traffic_source": (pmc["source"] + ("" if pmc.get("measured_in_this_run") else " -- REPLAYED from the committed profile, not measured in this run")) if pmc else None,
+                    "pmc": pmc,
+                    "note": "the fused path is bound by fp64 VALU issue and, at one wave per SIMD, by its own dependency "
+                            "latencies -- not by HBM: DESIGN.md section 3.8; see roofline_compute",
+                },
+                "roofline_compute": compute_roofline(pmc, kernel_ms),
+            })
         if stub:
             line["stub_gather_delivered_every_ranks_last_step"] = gather_check
-        if not args.no_secondary and world == 1:
+        if secondary:
             line["tolerance_build"] = tolerance_probe(B, d, N, 20240924 + rank, out["sd2"].cpu().numpy(), out["status"].cpu().numpy())
             line["sound_tolerance_build"] = tolerance_probe(B, d, N, 20240924 + rank, out["sd2"].cpu().numpy(), out["status"].cpu().numpy(),
                                                             libname="libtoppra_hip_stol.so", note=NOTE_SOUND_TOLERANCE)
-        if not args.no_configs and world == 1:
+        if args.full and not args.no_configs and world == 1:
             line["configs"] = baseline_configs(torch, tb, dev)
             line["end_to_end"] = end_to_end(torch, tb, dev)
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0's host cores)
             line["cpu_baseline"] = cpu_baseline(data)
         print(json.dumps(line))
     if world > 1:

@@ -130,7 +130,7 @@ def test_bench_multi_rank_control_flow_world8(gather):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), OMP_NUM_THREADS="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--stub-solver", "--steps", "4",
-                                       "--warmup", "3", "--batch", "37", "--gridpoints", "20", "--gather", gather],
+                                       "--warmup", "3", "--batch", "37", "--gridpoints", "20", "--gather", gather, "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for pr in procs:

@@ -1,12 +1,27 @@
-"""Live pinning of the CPU oracle against the REAL reference (build container only: needs
-/root/reference; skipped on the GPU box).  Fresh seeds, bit-exact."""
+"""Pinning of the CPU oracle against the REAL reference on fresh seeds, bit-exact.  The problems are generated here
+(the functions below); the reference's outputs on exactly these problems are stored in
+tests/golden/oracle_vs_reference_*.npz by tools/make_oracle_vs_reference_golden.py, which runs the reference on
+them -- so the pin holds wherever the suite runs, the reference itself being absent there."""
+import functools
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
-from tests.helpers import assert_same
+from tests.helpers import GOLDEN, assert_same, torque_model
 
-pytestmark = pytest.mark.reference
+PARAMETERIZATION_CASES = [(7, 200, 1, (0, 0)), (6, 500, 1, (0, 0)), (3, 60, 0, (0.1, 0.05)), (2, 40, 1, (3.0, 0.0)), (5, 77, 1, (0, 0.2))]
+IRREGULAR_CASES = [(6, 90, 9, 1), (7, 120, 6, 2), (9, 50, 7, 3), (14, 40, 5, 4), (3, 150, 4, 5)]
+REACHABLE_CASES = [(7, 100, 1, (0.0, 0.0)), (5, 60, 1, (0.0, 0.3)), (3, 40, 0, (0.1, 0.4)), (6, 80, 1, (0.5, 0.5))]
+GENERAL_CASES = [0, 1]
 
+
+def case_id(*params):
+    return "_".join(str(p) for p in params)
+
+
+# ---- the problems (shared with tools/make_oracle_vs_reference_golden.py) ----
 
 def _problem(rng, d, nway=5):
     way = rng.standard_normal((nway, d))
@@ -15,48 +30,20 @@ def _problem(rng, d, nway=5):
     return way, np.stack([-vmax, vmax], 1), np.stack([-amax, amax], 1)
 
 
-@pytest.mark.parametrize("d,N,scheme,sd", [(7, 200, 1, (0, 0)), (6, 500, 1, (0, 0)), (3, 60, 0, (0.1, 0.05)),
-                                           (2, 40, 1, (3.0, 0.0)), (5, 77, 1, (0, 0.2))])
-def test_parameterization_matches_reference(reference, oracle, d, N, scheme, sd):
-    import toppra.algorithm as algo
-    import toppra.constraint as constraint
+def parameterization_problems(d, N):
+    """12 x (knots, grid, waypoints, vlim, alim)."""
     rng = np.random.default_rng(d * 1000 + N)
-    knots = np.linspace(0, 1, 5)
-    grid = np.linspace(0, 1, N + 1)
+    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
     for _ in range(12):
-        way, vl, al = _problem(rng, d)
-        path = reference.SplineInterpolator(knots, way)
-        cons = [constraint.JointVelocityConstraint(vl),
-                constraint.JointAccelerationConstraint(al, discretization_scheme=scheme)]
-        inst = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel")
-        sdd, sdv, _, K = inst.compute_parameterization(sd[0], sd[1], return_data=True)
-        flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
-        w = oracle.Wrapper(path.cspl.c, path.cspl.x, grid, vl, al, flags=flags)
-        st, osdd, osd, oxs, oK = w.compute_parameterization(*sd)
-        assert_same(oK, K, "K")
-        if sdv is None:
-            assert st == 1
-        else:
-            assert_same(osd, sdv, "sd")
-            assert_same(osdd, sdd, "sdd")
-        # wrapper internals: dense rows and the variable box
-        sw = inst.solver_wrapper
-        X = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel").compute_feasible_sets()
-        w2 = oracle.Wrapper(path.cspl.c, path.cspl.x, grid, vl, al, flags=flags)
-        assert_same(w2.compute_feasible_sets(), X, "X")
-        assert sw.get_no_stages() == N
+        yield (knots, grid) + _problem(rng, d)
 
 
-@pytest.mark.parametrize("d,N,nway,seed", [(6, 90, 9, 1), (7, 120, 6, 2), (9, 50, 7, 3), (14, 40, 5, 4), (3, 150, 4, 5)])
-def test_irregular_problems_match_reference(reference, oracle, d, N, nway, seed):
-    """Asymmetric limits incl. positive lower velocity limits, joints that stand still, non-uniform knots
-    and grids, non-zero boundary velocities, up to 14 dof: the oracle against the live reference."""
-    import toppra.algorithm as algo
-    import toppra.constraint as constraint
+def irregular_problems(d, N, nway, seed):
+    """Asymmetric limits incl. positive lower velocity limits, joints that stand still, non-uniform knots and grids,
+    non-zero boundary velocities: 10 x (knots, grid, waypoints, vlim, alim, sd_start, sd_end)."""
     rng = np.random.default_rng(9000 + seed)
     knots = np.concatenate([[0.0], np.sort(rng.random(nway - 2)) * 0.9 + 0.05, [1.0]])
     grid = 0.6 * np.concatenate([[0.0], np.sort(rng.random(N - 1)), [1.0]]) + 0.4 * np.linspace(0, 1, N + 1)
-    seen = set()
     for _ in range(10):
         way = rng.standard_normal((nway, d))
         still = rng.random(d) < 0.15
@@ -67,24 +54,11 @@ def test_irregular_problems_match_reference(reference, oracle, d, N, nway, seed)
         vl, al = np.stack([vlo, vhi], 1), np.stack([alo, ahi], 1)
         sd0 = 0.3 * rng.random() if rng.random() < 0.5 else 0.0
         sd1 = 0.3 * rng.random() if rng.random() < 0.5 else 0.0
-        path = reference.SplineInterpolator(knots, way)
-        cons = [constraint.JointVelocityConstraint(vl), constraint.JointAccelerationConstraint(al)]
-        inst = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel")
-        sdd, sdv, _, K = inst.compute_parameterization(sd0, sd1, return_data=True)
-        w = oracle.Wrapper(path.cspl.c, path.cspl.x, grid, vl, al)
-        st, osdd, osd, oxs, oK = w.compute_parameterization(sd0, sd1)
-        assert_same(oK, K, "K")
-        seen.add(st)
-        if sdv is None:
-            assert st == 1
-        else:
-            assert_same(osd, sdv, "sd")
-            assert_same(osdd, sdd, "sdd")
-    assert 0 in seen
+        yield knots, grid, way, vl, al, sd0, sd1
 
 
-def test_lp2d_matches_reference(reference, oracle):
-    import toppra.solverwrapper.cy_seidel_solverwrapper as seidel
+def lp2d_problems():
+    """300 x (v, a, b, c, low, high, active_c)."""
     for seed in range(300):
         rng = np.random.default_rng(seed + 5000)
         n = int(rng.integers(1, 60))
@@ -93,93 +67,58 @@ def test_lp2d_matches_reference(reference, oracle):
         c = -rng.random(n) if seed % 2 == 0 else rng.standard_normal(n)
         low, high = np.array([-0.5, -0.9]), np.array([0.5, 0.9])
         ac = rng.integers(-1, n + 1, size=2)
-        want = seidel.solve_lp2d(v, a, b, c, low, high, ac.astype(int))
-        got = oracle.lp2d(v, a, b, c, low, high, ac)
-        assert got[0] == want[0]
-        if want[0]:
-            assert got[1] == want[1] and list(got[2]) == list(want[2]) and list(got[3]) == list(want[3])
+        yield v, a, b, c, low, high, ac
 
 
-def test_velocity_bound_is_fp32(reference, oracle):
-    """The fp32 rounding of the velocity bound (SURVEY.md trap 1) is reproduced exactly."""
-    from toppra._CythonUtils import _create_velocity_constraint
+def velocity_bound_problem():
+    """(path velocities qs [500, 7], vlim [7, 2]): zero rows, and a positive lower limit (the sdmin branch)."""
     rng = np.random.default_rng(3)
     qs = rng.standard_normal((500, 7))
     qs[::17] = 0.0
     vmax = 10 + 20 * rng.random(7)
     vlim = np.stack([-vmax, 0.5 * vmax + rng.random(7)], 1)
-    vlim[3] = [0.5, 2.0]  # positive lower limit exercises the sdmin branch
-    _, _, cc = _create_velocity_constraint(qs, vlim)
-    want = np.stack([cc[:, 1], -cc[:, 0]], 1)
-    got = np.array([oracle.velocity_xbound(q, vlim) for q in qs])
-    assert_same(got, want, "xbound")
-    # and it is NOT what fp64 arithmetic would give
-    assert np.any(got[:, 1] != np.array([np.min(np.where(q > 0, vlim[:, 1] / q, vlim[:, 0] / q)) ** 2
-                                         for q in np.where(qs == 0, 1e-30, qs)]))
+    vlim[3] = [0.5, 2.0]
+    return qs, vlim
 
 
-@pytest.mark.parametrize("d,N,scheme,sds", [(7, 100, 1, (0.0, 0.0)), (5, 60, 1, (0.0, 0.3)), (3, 40, 0, (0.1, 0.4)), (6, 80, 1, (0.5, 0.5))])
-def test_reachable_sets_match_reference(reference, oracle, d, N, scheme, sds):
-    """compute_reachable_sets (reachability_algorithm.py:378-431) incl. its deltas[i-1] objective and the
-    warm-start state carried over from the feasible-set pass it runs first."""
-    import toppra.algorithm as algo
-    import toppra.constraint as constraint
+def reachable_problems(d, N):
+    """8 x (knots, grid, waypoints, vlim, alim) on a non-uniform grid (deltas[i-1] != deltas[i])."""
     rng = np.random.default_rng(77 * d + N)
     knots = np.linspace(0, 1, 5)
     grid = np.concatenate([[0.0], np.sort(rng.random(N - 1)), [1.0]])
-    grid = 0.5 * grid + 0.5 * np.linspace(0, 1, N + 1)   # non-uniform: deltas[i-1] != deltas[i]
+    grid = 0.5 * grid + 0.5 * np.linspace(0, 1, N + 1)
     for _ in range(8):
-        way, vl, al = _problem(rng, d)
-        path = reference.SplineInterpolator(knots, way)
-        cons = [constraint.JointVelocityConstraint(vl),
-                constraint.JointAccelerationConstraint(al, discretization_scheme=scheme)]
-        inst = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel")
-        L = inst.compute_reachable_sets(*sds)
-        flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
-        w = oracle.Wrapper(path.cspl.c, path.cspl.x, grid, vl, al, flags=flags)
-        oL, oX = w.compute_reachable_sets(*sds)
-        assert_same(oL, L, "L")
-        assert_same(oX, inst.problem_data.X, "X")
+        yield (knots, grid) + _problem(rng, d)
 
 
-def test_host_glue_matches_reference(reference):
-    """propose_gridpoints and ParametrizeSpline (vectorised host code here, loops in the reference) give the
-    reference's grids, knot times and spline coefficients value for value."""
-    import toppra.interpolator as ri
-    import toppra.parametrizer as rp
-    import toppra_amd as ta
-    from toppra_amd.interpolator import propose_gridpoints
+def host_glue_problems():
+    """20 x (t, waypoints, propose_gridpoints keywords, rng); host_glue_sd(rng, ...) draws the trial's sd from the same
+    stream once the grid's length is known."""
     rng = np.random.default_rng(0)
     for t in range(20):
         d, m = int(rng.integers(1, 8)), int(rng.integers(3, 9))
         way = rng.standard_normal((m, d)) * float(rng.choice([0.1, 1, 5]))
-        p1 = ta.SplineInterpolator(np.linspace(0, 1, m), way)
-        p2 = reference.SplineInterpolator(np.linspace(0, 1, m), way)
         kw = dict(max_err_threshold=float(rng.choice([1e-4, 1e-3, 1e-5])), max_seg_length=float(rng.choice([0.05, 0.02, 0.2])),
                   min_nb_points=int(rng.choice([100, 30, 250])))
-        g1, g2 = propose_gridpoints(p1, **kw), ri.propose_gridpoints(p2, **kw)
-        assert np.array_equal(np.array(g1), np.array(g2))
-        sd = np.abs(rng.standard_normal(len(g1)))
-        sd[0] = sd[-1] = 0
-        if t % 3 == 0:
-            sd[5:8] = 0  # a standing stretch (the 5 s rule)
-        a, b = ta.ParametrizeSpline(p1, g1, sd), rp.ParametrizeSpline(p2, g2, sd)
-        assert np.array_equal(a.cspl.x, b.cspl.x) and np.array_equal(a.cspl.c, b.cspl.c)
+        yield t, way, kw, rng
 
 
-@pytest.mark.parametrize("scheme", [0, 1])
-def test_general_constraint_lists_match_reference(reference, oracle, scheme):
-    """Constraint lists beyond velocity + acceleration, live: the reference's TOPPRA (seidel) on [varying velocity limits,
-    JointTorqueConstraint, SecondOrderConstraint] against (1) toppra_amd's mirror classes (host numpy through the same
-    callbacks) -- same parameters --, (2) toppra_amd.solverwrapper.dense_rows -- the wrapper's row assembly --, (3) the
-    oracle's DenseWrapper on those rows: K, sd, u, feasible sets bit for bit."""
-    import toppra.algorithm as algo
-    import toppra.constraint as rc
-    import toppra_amd as ta
-    from tests.helpers import torque_model
-    from toppra_amd.solverwrapper import dense_rows
+def array_digest(a):
+    """SHA-256 of an array's float64 bytes (C order): bit-for-bit equality of tables too large to store."""
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def host_glue_sd(rng, n, t):
+    sd = np.abs(rng.standard_normal(n))
+    sd[0] = sd[-1] = 0
+    if t % 3 == 0:
+        sd[5:8] = 0  # a standing stretch (the 5 s rule)
+    return sd
+
+
+def general_problems(scheme):
+    """6 x (d, waypoints, inverse dynamics, torque limits, friction, varying velocity limits) on 40 stages."""
     rng = np.random.default_rng(40 + scheme)
-    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, 41)
     for trial in range(6):
         d = int(rng.integers(2, 7))
         way = rng.standard_normal((5, d))
@@ -187,28 +126,153 @@ def test_general_constraint_lists_match_reference(reference, oracle, scheme):
         taulim = np.stack([-6 - 6 * rng.random(d), 6 + 6 * rng.random(d)], axis=1)
         fric = 0.1 * rng.random(d)
         base = np.stack([-10 - 5 * rng.random(d), 10 + 5 * rng.random(d)], axis=1)
-        vfun = lambda s: base * (1 + 0.4 * np.sin(5 * s))  # noqa: E731
-        rpath, mpath = reference.SplineInterpolator(knots, way), ta.SplineInterpolator(knots, way)
-        lists = []
-        for mod in (rc, ta.constraint):
-            DT = mod.DiscretizationType(scheme)
-            lists.append([mod.JointVelocityConstraintVarying(vfun), mod.JointTorqueConstraint(inv_dyn, taulim, fric, discretization_scheme=DT),
-                          mod.SecondOrderConstraint.joint_torque_constraint(inv_dyn, 1.3 * taulim, fric, discretization_scheme=DT)])
-        rrows, mrows = dense_rows(lists[0], rpath, grid), dense_rows(lists[1], mpath, grid)
+        vfun = lambda s, base=base: base * (1 + 0.4 * np.sin(5 * s))  # noqa: E731
+        yield trial, d, way, inv_dyn, taulim, fric, vfun
+
+
+GENERAL_KNOTS, GENERAL_GRID = np.linspace(0, 1, 5), np.linspace(0, 1, 41)
+
+
+def general_constraint_lists(mod, scheme, inv_dyn, taulim, fric, vfun):
+    DT = mod.DiscretizationType(scheme)
+    return [mod.JointVelocityConstraintVarying(vfun), mod.JointTorqueConstraint(inv_dyn, taulim, fric, discretization_scheme=DT),
+            mod.SecondOrderConstraint.joint_torque_constraint(inv_dyn, 1.3 * taulim, fric, discretization_scheme=DT)]
+
+
+# ---- the reference's outputs ----
+
+def golden_path(test):
+    return os.path.join(GOLDEN, "oracle_vs_reference_%s.npz" % test)
+
+
+@functools.lru_cache(maxsize=None)
+def _golden(test):
+    with np.load(golden_path(test)) as z:
+        return {k: z[k] for k in z.files}
+
+
+def reference_outputs(test, case, trial):
+    """The reference's arrays for one trial: {name: array} from the stored key '<case>__<trial>__<name>'."""
+    prefix = "%s__%s__" % (case, trial)
+    out = {k[len(prefix):]: v for k, v in _golden(test).items() if k.startswith(prefix)}
+    assert out, "tests/golden/oracle_vs_reference_%s.npz holds nothing for %s" % (test, prefix)
+    return out
+
+
+# ---- the oracle against them ----
+
+@pytest.mark.parametrize("d,N,scheme,sd", PARAMETERIZATION_CASES)
+def test_parameterization_matches_reference(oracle, d, N, scheme, sd):
+    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
+    for t, (knots, grid, way, vl, al) in enumerate(parameterization_problems(d, N)):
+        ref = reference_outputs("parameterization", case_id(d, N, scheme, *sd), t)
+        # the reference's own spline tables (path.cspl.c / .x) are the oracle's input
+        w = oracle.Wrapper(ref["c"], ref["x"], grid, vl, al, flags=flags)
+        st, osdd, osd, oxs, oK = w.compute_parameterization(*sd)
+        assert_same(oK, ref["K"], "K")
+        if ref["failed"]:
+            assert st == 1
+        else:
+            assert_same(osd, ref["sd"], "sd")
+            assert_same(osdd, ref["sdd"], "sdd")
+        # wrapper internals: the feasible sets (dense rows and the variable box) and the stage count
+        w2 = oracle.Wrapper(ref["c"], ref["x"], grid, vl, al, flags=flags)
+        assert_same(w2.compute_feasible_sets(), ref["X"], "X")
+        assert int(ref["stages"]) == N
+
+
+@pytest.mark.parametrize("d,N,nway,seed", IRREGULAR_CASES)
+def test_irregular_problems_match_reference(oracle, d, N, nway, seed):
+    """Asymmetric limits incl. positive lower velocity limits, joints that stand still, non-uniform knots
+    and grids, non-zero boundary velocities, up to 14 dof: the oracle against the reference."""
+    seen = set()
+    for t, (knots, grid, way, vl, al, sd0, sd1) in enumerate(irregular_problems(d, N, nway, seed)):
+        ref = reference_outputs("irregular", case_id(d, N, nway, seed), t)
+        w = oracle.Wrapper(ref["c"], ref["x"], grid, vl, al)
+        st, osdd, osd, oxs, oK = w.compute_parameterization(sd0, sd1)
+        assert_same(oK, ref["K"], "K")
+        seen.add(st)
+        if ref["failed"]:
+            assert st == 1
+        else:
+            assert_same(osd, ref["sd"], "sd")
+            assert_same(osdd, ref["sdd"], "sdd")
+    assert 0 in seen
+
+
+def test_lp2d_matches_reference(oracle):
+    for t, (v, a, b, c, low, high, ac) in enumerate(lp2d_problems()):
+        want = reference_outputs("lp2d", "all", t)
+        got = oracle.lp2d(v, a, b, c, low, high, ac)
+        assert got[0] == want["result"]
+        if want["result"]:
+            assert got[1] == want["optval"] and list(got[2]) == list(want["optvar"]) and list(got[3]) == list(want["active_c"])
+
+
+def test_velocity_bound_is_fp32(oracle):
+    """The fp32 rounding of the velocity bound (SURVEY.md trap 1) is reproduced exactly."""
+    qs, vlim = velocity_bound_problem()
+    want = reference_outputs("velocity_bound", "all", 0)["xbound"]
+    got = np.array([oracle.velocity_xbound(q, vlim) for q in qs])
+    assert_same(got, want, "xbound")
+    # and it is NOT what fp64 arithmetic would give
+    assert np.any(got[:, 1] != np.array([np.min(np.where(q > 0, vlim[:, 1] / q, vlim[:, 0] / q)) ** 2
+                                         for q in np.where(qs == 0, 1e-30, qs)]))
+
+
+@pytest.mark.parametrize("d,N,scheme,sds", REACHABLE_CASES)
+def test_reachable_sets_match_reference(oracle, d, N, scheme, sds):
+    """compute_reachable_sets (reachability_algorithm.py:378-431) incl. its deltas[i-1] objective and the
+    warm-start state carried over from the feasible-set pass it runs first."""
+    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
+    for t, (knots, grid, way, vl, al) in enumerate(reachable_problems(d, N)):
+        ref = reference_outputs("reachable", case_id(d, N, scheme, *sds), t)
+        w = oracle.Wrapper(ref["c"], ref["x"], grid, vl, al, flags=flags)
+        oL, oX = w.compute_reachable_sets(*sds)
+        assert_same(oL, ref["L"], "L")
+        assert_same(oX, ref["X"], "X")
+
+
+def test_host_glue_matches_reference():
+    """propose_gridpoints and ParametrizeSpline (vectorised host code here, loops in the reference) give the
+    reference's grids, knot times and spline coefficients value for value."""
+    import toppra_amd as ta
+    from toppra_amd.interpolator import propose_gridpoints
+    for t, way, kw, rng in host_glue_problems():
+        ref = reference_outputs("host_glue", "all", t)
+        p1 = ta.SplineInterpolator(np.linspace(0, 1, len(way)), way)
+        g1 = propose_gridpoints(p1, **kw)
+        assert np.array_equal(np.array(g1), ref["grid"])
+        sd = host_glue_sd(rng, len(g1), t)
+        a = ta.ParametrizeSpline(p1, g1, sd)
+        assert np.array_equal(a.cspl.x, ref["x"])
+        assert np.shape(a.cspl.c) == tuple(ref["c_shape"]) and array_digest(a.cspl.c) == str(ref["c_sha256"])
+
+
+@pytest.mark.parametrize("scheme", GENERAL_CASES)
+def test_general_constraint_lists_match_reference(oracle, scheme):
+    """Constraint lists beyond velocity + acceleration: the reference's TOPPRA (seidel) on [varying velocity limits,
+    JointTorqueConstraint, SecondOrderConstraint] against (1) toppra_amd's mirror classes (host numpy through the same
+    callbacks) -- same parameters --, (2) toppra_amd.solverwrapper.dense_rows -- the wrapper's row assembly, which the
+    reference's rows stored here came from --, (3) the oracle's DenseWrapper on those rows: K, sd, u, feasible sets bit
+    for bit."""
+    import toppra_amd as ta
+    from toppra_amd.solverwrapper import dense_rows
+    for trial, d, way, inv_dyn, taulim, fric, vfun in general_problems(scheme):
+        ref = reference_outputs("general", case_id(scheme), trial)
+        mpath = ta.SplineInterpolator(GENERAL_KNOTS, way)
+        mrows = dense_rows(general_constraint_lists(ta.constraint, scheme, inv_dyn, taulim, fric, vfun), mpath, GENERAL_GRID)
         for k in ("a", "b", "c", "low", "high", "deltas"):
-            assert_same(mrows[k], rrows[k], "rows %s (mirror classes vs the reference's)" % k)
+            assert_same(mrows[k], ref["rows_" + k], "rows %s (mirror classes vs the reference's)" % k)
         sd0, sd1 = (0.0, 0.0) if trial % 2 else (0.1, 0.05)
-        inst = algo.TOPPRA(lists[0], rpath, gridpoints=grid, solver_wrapper="seidel")
-        sdd, sdv, _, K = inst.compute_parameterization(sd0, sd1, return_data=True)
-        X = algo.TOPPRA(lists[0], rpath, gridpoints=grid, solver_wrapper="seidel").compute_feasible_sets()
         w = oracle.DenseWrapper(mrows["a"], mrows["b"], mrows["c"], mrows["low"], mrows["high"], mrows["deltas"])
         st, osdd, osd, oxs, oK = w.compute_parameterization(sd0, sd1)
-        assert_same(oK, K, "K")
-        if sdv is None:
+        assert_same(oK, ref["K"], "K")
+        if ref["failed"]:
             assert st == 1
         else:
             assert st == 0
-            assert_same(osd, sdv, "sd")
-            assert_same(osdd, sdd, "u")
+            assert_same(osd, ref["sd"], "sd")
+            assert_same(osdd, ref["sdd"], "u")
         w2 = oracle.DenseWrapper(mrows["a"], mrows["b"], mrows["c"], mrows["low"], mrows["high"], mrows["deltas"])
-        assert_same(w2.compute_feasible_sets(), X, "X")
+        assert_same(w2.compute_feasible_sets(), ref["X"], "X")

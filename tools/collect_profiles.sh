@@ -2,7 +2,7 @@
 # Copy the judged summaries of the last tools/gpu_full.sh visit from gpurun_out/ into profiles/ (round tag $1).
 set -eu
 R=${1:-r01}
-cp gpurun_out/bench.log profiles/${R}_bench_n1.json
+cp "${LOGS:-logs}/bench.log" profiles/${R}_bench_n1.json
 cp gpurun_out/pmc.json profiles/${R}_pmc.json
 cp gpurun_out/pmc_summary.txt profiles/${R}_rocprofv3_pmc_summary.txt
 cp gpurun_out/prof_stats/run_kernel_stats.csv profiles/${R}_rocprofv3_kernel_stats.csv

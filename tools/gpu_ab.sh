@@ -2,7 +2,7 @@
 # A/B of alternative library builds on the headline bench: tools/gpu_ab.sh libA.so libB.so ...
 for lib in "$@"; do
   for rep in 1 2; do
-    TOPPRA_HIP_LIB=$PWD/$lib python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_EXTRA:-} 2>/dev/null | python -c "
+    TOPPRA_HIP_LIB=$PWD/$lib python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_EXTRA:-} 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,6 +8,7 @@
 set -u
 mkdir -p gpurun_out; export TMPDIR=/tmp
 export TOPPRA_EXPECT_REF=1   # the reference-solver tests FAIL (not skip) if oracle/_ref did not travel
+LOGS=${LOGS:-logs}           # the full bench line (tools/collect_profiles.sh reads it there)
 timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -5 | tee gpurun_out/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/smoke.log
 timeout 600 python tools/gpu_measure.py 2>/dev/null > gpurun_out/measure.json; tail -5 gpurun_out/measure.json
@@ -20,7 +21,8 @@ tail -3 gpurun_out/profile.log
 python tools/pmc_summary.py gpurun_out solve_kernel > gpurun_out/pmc_summary.txt
 python tools/pmc_summary.py gpurun_out solve_kernel --json > gpurun_out/pmc.json
 cp gpurun_out/pmc.json profiles/${ROUND:-r01}_pmc.json   # bench.py reads roofline.traffic from the latest profiles/r*_pmc.json
-timeout 900 python bench.py 2>&1 | tail -1 | tee gpurun_out/bench.log
+mkdir -p "$LOGS"
+timeout 900 python bench.py --full 2>&1 | tail -1 | tee "$LOGS/bench.log"   # (every secondary measurement: --full)
 timeout 900 python tools/gpu_shortcut_stress.py ${STRESS_ROUNDS:-2} > gpurun_out/stress.log 2>&1; grep total gpurun_out/stress.log
 timeout 600 python tools/gpu_near_parallel.py > gpurun_out/near_parallel.log 2>&1; tail -1 gpurun_out/near_parallel.log
 timeout 600 python tools/gpu_tolerance_report.py 2>/dev/null > gpurun_out/tolerance_report.json; tail -5 gpurun_out/tolerance_report.json

@@ -16,7 +16,7 @@ for v in (1, 2):
     print("variant", v, "bit-exact" if ok else "MISMATCH maxdev %g" % np.nanmax(np.abs(got["sd2"] - ref["sd2"])))
 PY
 for v in ${VARIANTS:-2}; do
-  python bench.py --steps 5 --warmup 2 --variant $v --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --steps 5 --warmup 2 --variant $v --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
