@@ -55,7 +55,7 @@ def test_scratch_lds_and_registers_of_the_certified_lane_kernels(resources):
 
 # (dof, grid in LDS): instructions and divergent-region branches (s_cbranch_exec*) of cert_solve_kernel<dof, 64, no sd output, ...,
 # Interpolation, sound, not TOPPRAsd> as built in round 6 (7 dof: round 5's figures; 9..13 dof: with the transposed workspace's
-# prologue and the per-dof flags of build.py::CERT_UNIT_FLAGS), with 5 % / 10 % of headroom.  Round 4's pathological fetch took the
+# prologue and the per-dof flags of build.py::CERT_UNITS), with 5 % / 10 % of headroom.  Round 4's pathological fetch took the
 # 9-dof kernel from 129 to 172 such branches.
 CEILINGS = {(7, 1): (10884, 123), (9, 0): (13329, 142), (12, 0): (18239, 167), (13, 0): (18784, 175)}
 

@@ -21,8 +21,9 @@ TWO MODES.
                     `s_cbranch_execz`; flags vector / memory instructions between such a target and its `s_or_b64 exec, exec, ..`.
                     Cheap (no compile) and what tests/test_kernel_resources.py runs on the product library; it cannot see a
                     join block whose skip branch was removed (short regions), the MIR mode can.
-  --tu DOF [flags]  compile csrc/tpr_cert_tu.hip for DOF to that MIR with the product's flags (+ extra flags) and scan it.
-  --product         every translation unit of the product library (toppra_amd/build.py's job list) through the MIR mode: the
+  --tu DOF [flags]  family 3's units of DOF (csrc/tpr_cert_tu.hip, as toppra_amd/build.py compiles them: the unit's flags and
+                    split, + extra flags) to that MIR, and scan them.
+  --product [flags] every translation unit of the product library (toppra_amd/build.py's job list) through the MIR mode: the
                     release check (minutes: one more device compile per unit); log under profiles/.
 
 Exit status 1 when anything is flagged.
@@ -103,33 +104,25 @@ def main(argv):
             hits += scan_mir(p)
     elif argv and argv[0] == "--lib":
         hits = scan_lib(argv[1] if len(argv) > 1 else os.path.join(ROOT, "toppra_amd", "libtoppra_hip.so"))
-    elif argv and argv[0] == "--tu":
-        p = tu_mir(int(argv[1]), argv[2:])
-        hits = scan_mir(p)
-        os.unlink(p)
-    elif argv and argv[0] == "--product":
+    elif argv and argv[0] in ("--tu", "--product"):
         from concurrent.futures import ThreadPoolExecutor
-        sys.path.insert(0, ROOT)
         from toppra_amd import build as B
-        # (source, defines, the unit's own flags): family 3's units as build.py compiles them -- per-dof flags, split units
-        units = [("tpr_kernels.hip", ["-DTPR_CERT_MAX_DOF=%d" % B.CERT_MAX_DOF], [])]
-        for d in B.CERT_DOFS:
-            if d in B.CERT_UNIT_PARTS:
-                units += [("tpr_cert_tu.hip", ["-DTPR_TU_D=%d" % d, "-DTPR_TU_PART=%d" % part], list(fl)) for part, fl in sorted(B.CERT_UNIT_PARTS[d].items())]
-            else:
-                units.append(("tpr_cert_tu.hip", ["-DTPR_TU_D=%d" % d], list(B.CERT_UNIT_FLAGS.get(d, []))))
-        units += [("tpr_robust_tu.hip", ["-DTPR_TU_HALF=%d" % h], []) for h in (0, 1)] + [("tpr_dense_tu.hip", [], [])]
+        if argv[0] == "--tu":
+            units = [u for u in B.compile_jobs() if "-DTPR_TU_D=%d" % int(argv[1]) in u[2]]
+            extra = argv[2:]
+        else:
+            units, extra = B.compile_jobs(), argv[1:]
 
         def one(u):
-            p = tu_mir(0, list(u[2]) + argv[1:], source=u[0], defines=u[1])
+            p = tu_mir(u[1], u[2] + extra)
             try:
                 nblk = sum(1 for l in open(p, errors="replace") if l.startswith("  bb."))
                 return u, scan_mir(p), nblk
             finally:
                 os.unlink(p)
-        with ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as pool:
+        with ThreadPoolExecutor(max_workers=B.max_jobs()) as pool:
             for u, h, nblk in pool.map(one, units):
-                print("%-20s %-34s %-70s %6d blocks  %d flagged" % (u[0], " ".join(u[1]), " ".join(u[2]), nblk, len(h)), flush=True)
+                print("%-20s %-8s %-100s %6d blocks  %d flagged" % (u[1], u[0], " ".join(u[2] + extra), nblk, len(h)), flush=True)
                 hits += h
     else:
         print(__doc__)

@@ -1,10 +1,7 @@
 #!/bin/bash
 # Full GPU visit: tests, smoke, bench (+cpu baseline), secondary measurements, rocprof stats + PMC (then a
-# second bench run that picks the fresh PMC numbers up), stress, and -- when the instrumented builds of
-# `python -m toppra_amd.build -DTPR_CERT_TIMING -DTPR_CERT_DEV --out=build_dbg/libtoppra_tim.so` and
-# `... -DTPR_DEBUG_PREDICT -DTPR_CERT_DEV --out=build_dbg/libtoppra_dbg.so` are present -- the in-kernel
-# cycle breakdown and the certificate hit rates.  Everything lands under gpurun_out/; copy what should be
-# judged into profiles/ (tools/collect_profiles.sh).
+# second bench run that picks the fresh PMC numbers up) and stress.  Everything lands in the output directory made
+# below; copy what should be judged into profiles/ (tools/collect_profiles.sh).
 set -u
 mkdir -p gpurun_out; export TMPDIR=/tmp
 export TOPPRA_EXPECT_REF=1   # the reference-solver tests FAIL (not skip) if oracle/_ref did not travel
@@ -39,13 +36,3 @@ timeout 300 python tools/gpu_mode_times.py > gpurun_out/mode_times.log 2>&1; cat
 timeout 300 python tools/gpu_param_pcr_check.py > gpurun_out/param_pcr_check.log 2>&1; tail -4 gpurun_out/param_pcr_check.log
 timeout 300 python tools/gpu_dense_check.py > gpurun_out/dense_check.log 2>&1; tail -5 gpurun_out/dense_check.log
 bash tools/gpu_profile_secondary.sh all > gpurun_out/sec_profile.log 2>&1; tail -3 gpurun_out/sec_profile.log
-if [ -f build_dbg/libtoppra_wtim.so ]; then
-  (TOPPRA_HIP_LIB=build_dbg/libtoppra_wtim.so timeout 120 python tools/gpu_wave_phases.py timing 4096 7 200; TOPPRA_HIP_LIB=build_dbg/libtoppra_wtim.so timeout 120 python tools/gpu_wave_phases.py timing 1 7 100) > gpurun_out/wave_phases.log 2>&1; tail -4 gpurun_out/wave_phases.log
-fi
-if [ -f build_dbg/libtoppra_tim.so ]; then
-  TOPPRA_HIP_LIB=build_dbg/libtoppra_tim.so timeout 300 python tools/gpu_cert_phases.py > gpurun_out/phases.log 2>&1; tail -3 gpurun_out/phases.log
-fi
-if [ -f build_dbg/libtoppra_dbg.so ]; then
-  TOPPRA_HIP_LIB=build_dbg/libtoppra_dbg.so TPR_DEV_BUILD=1 timeout 300 python tools/gpu_shortcut_hitrate.py > gpurun_out/hitrate.log 2>&1; tail -3 gpurun_out/hitrate.log
-  TOPPRA_HIP_LIB=$PWD/build_dbg/libtoppra_dbg.so timeout 300 python tools/gpu_walk_fail.py > gpurun_out/walk_fail.log 2>&1; head -8 gpurun_out/walk_fail.log
-fi

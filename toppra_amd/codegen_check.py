@@ -13,7 +13,7 @@ of them).  The VGPR phase's split then stops at that COPY and puts its own copy 
 `scan_mir` reads MIR taken after the LAST register-allocation phase (`-mllvm -stop-after=virtregrewriter,2`), where every basic
 block is still its own block, and reports each instruction that touches a VGPR / AGPR above a block's exec-widening instruction
 (V_READLANE / V_WRITELANE / SGPR spill pseudos ignore exec and are fine).  `toppra_amd.build` runs it on every translation unit of
-kernel family 3 (TPR_BUILD_VERIFY=0 turns that off) and refuses to link a library that contains the pattern;
+kernel family 3 of the product and refuses to link a library that contains the pattern;
 `tools/exec_restore_scan.py` is the command-line front end (+ a disassembly-based variant for built libraries)."""
 import os
 import re
@@ -55,15 +55,12 @@ def scan_mir(path):
     return hits
 
 
-def tu_mir(dof, extra=(), source="tpr_cert_tu.hip", defines=None):
-    """MIR of one translation unit after the last register-allocation phase, with the product's flags."""
+def tu_mir(source, unit_flags=()):
+    """MIR of one translation unit of csrc/ after the last register-allocation phase, with the product's flags + the unit's."""
     from . import build as B
     flags = [f for f in B.FLAGS if f not in ("-shared",)]
-    defs = defines if defines is not None else ["-DTPR_TU_D=%d" % dof]
     out = tempfile.NamedTemporaryFile(suffix=".mir", delete=False).name
-    cmd = [B.hipcc()] + flags + defs + list(extra) + ["--cuda-device-only", "-S", "-mllvm", "-stop-after=virtregrewriter,2", "-o", out,
-                                                      os.path.join(B.CSRC, source)]
+    cmd = [B.hipcc()] + flags + list(unit_flags) + ["--cuda-device-only", "-S", "-mllvm", "-stop-after=virtregrewriter,2", "-o", out,
+                                                   os.path.join(B.CSRC, source)]
     subprocess.run(cmd, cwd=B.CSRC, check=True, capture_output=True)
     return out
-
-

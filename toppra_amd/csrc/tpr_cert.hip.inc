@@ -21,17 +21,6 @@
 #pragma once
 namespace tpr {
 
-#ifdef TPR_CERT_TIMING  // per-phase cycle counters of each wave, dumped into u[b][0..] (debug builds only)
-#define TPR_T0() unsigned long long t_prev = __builtin_readcyclecounter(), t_acc[12] = {0}
-#define TPR_TICK(k) { const unsigned long long t_now = __builtin_readcyclecounter(); t_acc[k] += t_now - t_prev; t_prev = t_now; }
-#define TPR_TACC_PARAM , unsigned long long (&t_acc)[12], unsigned long long &t_prev
-#define TPR_TACC_ARG , t_acc, t_prev
-#else
-#define TPR_T0()
-#define TPR_TICK(k)
-#define TPR_TACC_PARAM
-#define TPR_TACC_ARG
-#endif
 // A cross-lane hand-off through LDS inside ONE wave: the lanes run in lockstep and the LDS queue is in order, so all the
 // hardware needs is that the compiler keeps the stores before and the loads after this point.  wave_barrier() alone is a
 // scheduling barrier WITHOUT memory semantics; the wavefront-scope fences state the ordering in the memory model as well
@@ -42,17 +31,6 @@ namespace tpr {
         __builtin_amdgcn_wave_barrier();                             \
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       \
     } while (0)
-#ifdef TPR_BARE_WAVE_BARRIER  // (round-6 forensics: the hand-offs as they were up to round 5)
-#undef TPR_WAVE_SYNC
-#define TPR_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
-#endif
-#ifdef TPR_DEBUG_PREDICT  // per-trajectory counters returned in `status` (debug builds only)
-#define TPR_DBG_PARAM , int &dbg
-#define TPR_DBG_ARG , dbg
-#else
-#define TPR_DBG_PARAM
-#define TPR_DBG_ARG
-#endif
 
 }  // namespace tpr
 #include "tpr_cert_lane.hip.inc"
@@ -89,7 +67,7 @@ template <int D, int BS, bool INTERP = true, int MODE = 0, bool SOUNDB = false>
 __device__ inline void cert_needy_batch(const CertStage<D, BS> &S, const double *qtab, int pc, const double *limtab,
                                         const double *alim_blk, int ntraj_blk,
                                         double *xch, int *queue, double *rowbufs, bool need_u, bool need_l, int dn0, int dn1,
-                                        int up0, int up1, Lp2dOut &out_u, Lp2dOut &out_l TPR_TACC_PARAM TPR_DBG_PARAM, int dbg_stage = 0) {
+                                        int up0, int up1, Lp2dOut &out_u, Lp2dOut &out_l) {
     constexpr bool sound = SOUNDB;  // (a template parameter: the sound kernels carry no simplex-walk code at all)
     static_assert(BS == 64, "one wave per block");
     constexpr int L = kCertBatchLanes;
@@ -114,7 +92,6 @@ __device__ inline void cert_needy_batch(const CertStage<D, BS> &S, const double 
     if (need_u) queue[below_u] = lane | ((MODE == 2 || sound || out_u.hint_full) ? 512 : 0);
     if (need_l) queue[n_u + below_l] = lane | 256 | ((MODE == 2 || sound) ? 512 : 0);
     TPR_WAVE_SYNC();
-    TPR_TICK(2);
     constexpr int kGroups = cert_batch_groups<D>();
     const bool working = g < kGroups;  // the other groups idle (and own no row mirror)
     double *rowbuf_w = rowbufs + (working ? g : 0) * G::kRowBuf;
@@ -125,7 +102,6 @@ __device__ inline void cert_needy_batch(const CertStage<D, BS> &S, const double 
         const int src = have ? (e & 255) : -1;
         const bool lower = have & ((e & 256) != 0);
         const bool skip_walk = have & ((e & 512) != 0);
-        TPR_TICK(6);
         const bool act = src >= 0;
         const int sl = act ? src : 0;
         const double two_delta = xch[0 * BS + sl], n0 = limtab[4 * BS + sl], n1 = -limtab[5 * BS + sl],
@@ -176,17 +152,14 @@ __device__ inline void cert_needy_batch(const CertStage<D, BS> &S, const double 
             if (working && vi < G::nV) { rowbuf_w[vi] = a; rowbuf_w[G::nV + vi] = b; rowbuf_w[2 * G::nV + vi] = c; }
         }
         TPR_WAVE_SYNC();
-        TPR_TICK(4);
         GroupLp r;
         const double bl1 = act ? low1 : 0.0, bh1 = act ? high1 : 1.0;
         bool got = false;
         if constexpr (!(SOUNDB || MODE == 2)) {
             if (__builtin_amdgcn_ballot_w64(act & !skip_walk) != 0)  // (wave-uniform; a skipped group idles through the others' walk)
-                got = predict_upper_lp<D, L>(R, rowbuf_w, gl, v0, v1, bl1, bh1, w0, w1, r, sound, act & !skip_walk, dbg_stage);
+                got = predict_upper_lp<D, L>(R, rowbuf_w, gl, v0, v1, bl1, bh1, w0, w1, r, sound);
         }
-        TPR_TICK(10);
         if (!got) r = group_lp2d<D, L>(R, rowbuf_w, gl, v0, v1, kVarMin, kVarMax, bl1, bh1, w0, w1);
-        TPR_TICK(11);
         if (act && gl == 0) {
             const int f = lower ? 6 : 3;
             xch[f * BS + sl] = r.u; xch[(f + 1) * BS + sl] = r.x;
@@ -205,10 +178,6 @@ __device__ inline void cert_needy_batch(const CertStage<D, BS> &S, const double 
     };
     if (need_u) take(3, out_u);
     if (need_l) take(6, out_l);
-#ifdef TPR_DEBUG_PREDICT
-    if (need_u && (__double2hiint(xch[5 * BS + lane]) & 2)) dbg += 1 << 26;
-    if (need_l && (__double2hiint(xch[8 * BS + lane]) & 2)) dbg += 1 << 20;
-#endif
 }
 
 // Output staging.  A lane produces W doubles per stage for its own trajectory; written directly that
@@ -253,14 +222,6 @@ struct StagedOut {
     }
 };
 
-// cert_pair_rows' TRACE mode skips the role derivation and the violation bound because cert_propose_sound has established them;
-// the instrumented builds (TPR_DEBUG_PREDICT) take their proposal from TPR_PROPOSE, which has not (ADVICE r5).
-#ifdef TPR_DEBUG_PREDICT
-template <bool SOUND> constexpr bool kTraceProposal = false;
-#else
-template <bool SOUND> constexpr bool kTraceProposal = SOUND;
-#endif
-
 // WANT_SD: also write sd = sqrt(sd2).  GRID_LDS: the grid is shared by the batch and staged in
 // (dynamic) LDS, so that the per-stage gridpoint is a broadcast LDS read instead of a global load.
 // sd2, u, K and status are required (launch_solve routes other requests to family 2), or
@@ -283,19 +244,14 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
     // dofs that use the sign bits.  Round 5 took <5 dof, TOPPRAsd, sign bits> for a miscompile of the form itself; it is the
     // register allocator's copy above an exec restore (profiles/r06_miscompile_root_cause.md), which ANY spelling can trigger and
     // which the build now checks every unit for (toppra_amd/codegen_check.py): of the 13 TOPPRAsd instantiations with sign bits,
-    // 5 and 13 dof show the pattern and therefore keep the running minimum.  -DTPR_REPRO_SD5_SIGNBITS forces the sign bits
-    // everywhere (the reproducer of tools/r5/README.md; such a unit fails the build's check).
+    // 5 and 13 dof show the pattern and therefore keep the running minimum.
 #ifndef TPR_SIGNBITS_DOFS
 #define TPR_SIGNBITS_DOFS 0x09feu  /* 1..8, 11 (round 6, with the transposed workspace: 12 dof 5.15 / 4.76 ms with / without) */
 #endif
 #ifndef TPR_SIGNBITS_SD_DOFS
 #define TPR_SIGNBITS_SD_DOFS 0x01deu  /* 1..4, 6..8 */
 #endif
-#ifdef TPR_REPRO_SD5_SIGNBITS
-    constexpr bool kSignBits = true;
-#else
     constexpr bool kSignBits = ((SDFWD ? TPR_SIGNBITS_SD_DOFS : TPR_SIGNBITS_DOFS) >> D) & 1u;
-#endif
     // q', q'' columns (two gridpoint parities), then the row constants (c of rows 0..5 per stage, cpos / cneg
     // columns); the forward scan, which fetches no rows by index, reuses the front as its output staging
     constexpr int kStageDoubles = (SDFWD ? 32 : 24) * BS;  // forward output staging: 3 (TOPPRAsd: 4) arrays x 8 stages
@@ -495,14 +451,7 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
     const double sd_end = A.sd_end ? A.sd_end[bb] : 0.0;
 
     // ---- backward scan: controllable sets ------------------------------------------------
-    TPR_T0();
-#ifdef TPR_CERT_TIMING
-    int batch_entries = 0, batch_lps = 0;  // stages at which the wave entered the cooperative batches; LPs it took there
-#endif
     int up0 = 4, up1 = 4, dn0 = 4, dn1 = 4;  // warm-start state (active_c_up / active_c_down = {0, 0}) in the internal row numbering
-#ifdef TPR_DEBUG_PREDICT
-    int dbg = 0;
-#endif
     double kn0 = boundary_x(A.flags, sd_end), kn1 = A.sd_end_hi ? boundary_x(A.flags, A.sd_end_hi[bb]) : kn0;
     // K rows go to LDS as they are produced (slot = stage & (kRing - 1)) and are written out every kRing stages,
     // transposed: kRing adjacent lanes store one trajectory's kRing stages = 64 (slim blocks: 32) contiguous bytes
@@ -537,9 +486,6 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
     };
     k_put(N, kn0, kn1);
     if ((N & (kRing - 1)) == 0) k_flush(N, 1);
-#ifdef TPR_DEBUG_STAGE
-    double dbg_stage_u = 0, dbg_stage_code = 0, dbg_stage_low1 = 0;
-#endif
     bool failed = false;
     double s_n = grid(N);
     double dummy0, dummy1;
@@ -552,9 +498,7 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         double low1, high1;
 #pragma unroll
         for (int k = 0; k < D; ++k) { S.rn1[k] = INTERP ? S.rc1[k] : 0.0; S.rn2[k] = INTERP ? S.rc2[k] : 0.0; }
-        TPR_TICK(0);
         eval(s_i, i & 1, has_vel, S.rc1, S.rc2, low1, high1);
-        TPR_TICK(1);
         double lo = 0, hi = 0;
         // `solve`: this lane has two LPs to answer at this stage.  The cooperative fallback below
         // needs the whole wave, so the stage body is wave-uniform and lanes are masked by flags.
@@ -564,32 +508,19 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         S.publish_special(lim + tid);
         double nmax;
         const bool nok = S.norms(nmax);
-        TPR_TICK(2);
         // lane level: is the previous active pair still the verified optimum?  (straight-line code)
         Lp2dOut su, sl;
-#ifdef TPR_NO_PROPOSE  // development: certify the previous pair only
-        bool need_u = solve & !cert_pair<D, BS, false>(S, -1e-9, 1.0, dn0, dn1, dn0 != dn1, dn0, dn1, nok, nmax, su);
-#else
         int up_p, up_q;
         bool up_ok;
         double up_prow[3], up_qrow[3];
-#ifdef TPR_DEBUG_PREDICT
-        int dbg_rows[6];
-        TPR_PROPOSE<D, BS>(S, -1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow, dbg_rows);
-#else
+        // (cert_pair_rows' TRACE mode skips the role derivation and the violation bound: cert_propose_sound has established them)
         if constexpr (SOUND) cert_propose_sound<D, BS, 0, kSignBits>(S, -1e-9, 1.0, dn0, dn1, dn0 != dn1, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
-        else TPR_PROPOSE<D, BS>(S, -1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
-#endif
-        bool need_u = solve & !cert_pair_rows<D, BS, false, kTraceProposal<SOUND>>(S, -1e-9, 1.0, up_p, up_q, nok & up_ok, up_prow[0], up_prow[1], up_prow[2],
+        else cert_propose2<D, BS>(S, -1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
+        bool need_u = solve & !cert_pair_rows<D, BS, false, SOUND>(S, -1e-9, 1.0, up_p, up_q, nok & up_ok, up_prow[0], up_prow[1], up_prow[2],
                                                             up_qrow[0], up_qrow[1], up_qrow[2], dn0, dn1, nmax, su);
-#endif
-#ifdef TPR_DEBUG_PREDICT
-        const int su_why = su.why;
-#endif
         bool need_l;
         if constexpr (SOUND) need_l = solve & !cert_lower_sound<D, BS, true, kSignBits>(S, nok, nmax, up0, up1, sl);
         else need_l = solve & !cert_lower<D, BS>(S, nok, nmax, sl);
-#ifndef TPR_NO_EQ_CERT
         // x_next rows forming an equality (the first stage: K[N] is a single point): neither check above
         // can succeed (both rows are active), a dedicated certificate answers both LPs
         if (__builtin_amdgcn_ballot_w64(solve & (kn0 == kn1)) != 0) {
@@ -600,44 +531,11 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
             if (eq & need_u & eu.ok) { su = eu; need_u = false; }
             if (eq & need_l & el.ok) { sl = el; need_l = false; }
         }
-#endif
-        TPR_TICK(3);
         // the rest goes through family 2's walk / full iteration, 8 LPs at a time
-#ifdef TPR_EXPERIMENT_NO_BATCH  // timing experiment only (wrong results): what the kernel costs when no LP needs the batches
-        need_u = need_l = false;
-#endif
         if (__builtin_amdgcn_ballot_w64(need_u | need_l) != 0) {
-#ifdef TPR_CERT_TIMING
-            batch_entries += 1;
-            batch_lps += __builtin_popcountll(__builtin_amdgcn_ballot_w64(need_u)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(need_l));
-#endif
-            cert_needy_batch<D, BS, INTERP, 0, SOUND>(S, qt, i & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, need_u, need_l, dn0, dn1, up0, up1, su, sl TPR_TACC_ARG TPR_DBG_ARG, i);
+            cert_needy_batch<D, BS, INTERP, 0, SOUND>(S, qt, i & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, need_u, need_l, dn0, dn1, up0, up1, su, sl);
         }
-        TPR_TICK(5);
-#ifdef TPR_DEBUG_PREDICT
-        if (need_u) dbg += 1 << 10;
-        if (need_l) dbg += 1;
-#endif
         if (!solve) { su.ok = sl.ok = false; su.x = sl.x = qnan(); }
-#ifdef TPR_DEBUG_PREDICT
-        if (alive && need_u) atomicAdd(&g_walk_hist[4][100 + (su_why & 7)], 1u);
-        if (alive && need_u && (su_why & 7) == 5) atomicAdd(&g_walk_hist[3][416 + ((su_why >> 3) & 31)], 1u);
-#ifndef TPR_NO_PROPOSE
-        if (alive && need_u && su.ok) {  // the batches' answer against the search's candidates: bits = has p, q, rp, rq; by why-code
-            auto has = [&](int r) { return (r >= 0) & ((su.ac0 == r) | (su.ac1 == r)); };
-            const int code = (has(dbg_rows[0]) ? 1 : 0) | (has(dbg_rows[1]) ? 2 : 0) | (has(dbg_rows[2]) ? 4 : 0) | (has(dbg_rows[3]) ? 8 : 0);
-            atomicAdd(&g_walk_hist[4][128 + (su_why & 7) * 16 + code], 1u);
-        }
-#endif
-        if (alive && solve && su.ok) {  // regime transitions of the upper-bound LP's active pair (row id 1 = x_next upper, -4 = box high1)
-            auto cls = [](int a, int b) { return (a == 1 || b == 1) ? 0 : ((a == -4 || b == -4) ? 1 : 2); };
-            const int same = ((su.ac0 == dn0 && su.ac1 == dn1) || (su.ac0 == dn1 && su.ac1 == dn0)) ? 1 : 0;
-            atomicAdd(&g_walk_hist[3][256 + (need_u ? 32 : 0) + same * 16 + cls(C::id_of(dn0), C::id_of(dn1)) * 4 + cls(C::id_of(su.ac0), C::id_of(su.ac1))], 1u);
-        }
-#endif
-#ifdef TPR_DEBUG_STAGE  // development (-DTPR_DEBUG_STAGE=<i>): the lower-bound LP's answer at stage i, returned in sd2[b][0], u[b][0..1] instead of the forward scan
-        if (i == TPR_DEBUG_STAGE) { dbg_stage_u = sl.u; dbg_stage_code = (double)(sl.ac0 + 1000 * (need_l ? 1 : 0)); dbg_stage_low1 = S.low1; }
-#endif
         if (su.ok) { dn0 = su.ac0; dn1 = su.ac1; } else su.x = qnan();
         if (sl.ok) { up0 = sl.ac0; up1 = sl.ac1; } else sl.x = qnan();
         if (!failed) {
@@ -652,11 +550,6 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         s_n = s_i;
     }
 
-#ifdef TPR_DEBUG_STAGE
-    TPR_WAVE_SYNC();
-    if (alive) { A.sd2[(size_t)bb * (N + 1) + 0] = dbg_stage_u; A.u[(size_t)bb * N + 0] = dbg_stage_code; A.u[(size_t)bb * N + 1] = dbg_stage_low1; }
-    if (alive) return;
-#endif
     const double x_start = boundary_x(A.flags, sd_start);
     // FailUncontrollable: the lane stays (the staged stores are cooperative) and writes NaN everywhere
     const bool dead = failed || x_start + kPySmall < kn0 || kn1 + kPySmall < x_start;
@@ -846,11 +739,6 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
             }
         }
     };
-#ifdef TPR_CERT_TIMING
-    __shared__ int fwd_passes;  // passes of the wave over the forward LP (it pays for the slowest lane of every stage)
-    fwd_passes = 0;
-    int fwd_tries = 0;          // this lane's retries
-#endif
     double s_cur = s_n;  // grid[0]; its q', q'' sit in parity slot 0 and in S.rc1 / S.rc2
     double s_pf = grid(1), k0_pf = K[2], k1_pf = K[3];  // software prefetch of the next stage's inputs
     for (int i = 0; i < N; ++i) {
@@ -868,21 +756,16 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
             TPR_WAVE_SYNC();
         }
         const double delta = s_nx - s_cur;
-        TPR_TICK(7);
         double nx1[D], nx2[D];  // q', q'' at s_{i+1}: the stage's interpolation rows (INTERP) and the next stage's own rows
         eval(s_nx, -1, false, nx1, nx2, dummy0, dummy1);
 #pragma unroll
         for (int k = 0; k < D; ++k) { S.rn1[k] = INTERP ? nx1[k] : 0.0; S.rn2[k] = INTERP ? nx2[k] : 0.0; }
         S.two_delta = 2 * delta; S.n0 = k0; S.n1 = k1;
         s_cur = s_nx;
-        TPR_TICK(8);
         // 1-D LP in u at fixed x: max 2 delta u over the structural rows, u in [-1e8, 1e8]
         double uu = 0.0;
         bool ok = false;
         for (;;) {
-#ifdef TPR_CERT_TIMING
-            if (tid == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) fwd_passes += 1;  // one count per pass of the wave
-#endif
             if (!isnan(x)) {
                 // max 2 delta u: the answer is tmax, the smallest upper bound -(b x + c)/a over the rows
                 // with a > 0 (of a +- pair that is the twin with a > 0).  The lower bounds only decide
@@ -946,12 +829,8 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
             const double t1 = x - kPyTiny, t2 = 0.999 * x;
             x = t2 > t1 ? t2 : t1;
             tries += 1;
-#ifdef TPR_CERT_TIMING
-            fwd_tries += 1;
-#endif
             sq = root(x);
         }
-        TPR_TICK(9);
         {
             fst[(0 * 8 + (i & 7)) * BS + tid] = x;
             fst[(1 * 8 + (i & 7)) * BS + tid] = dead ? qnan() : (ok ? uu : 0.0);
@@ -987,17 +866,6 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         if (WANT_SD) sdv[N] = sq;
         A.status[bb] = dead ? TPR_STATUS_FAIL_UNCONTROLLABLE : (any_nan ? TPR_STATUS_ERR_UNKNOWN : TPR_STATUS_OK);
     }
-#ifdef TPR_CERT_TIMING
-    for (int k = 0; k < 12; ++k) A.u[(size_t)bb * N + k] = (double)t_acc[k];
-    TPR_WAVE_SYNC();
-    A.u[(size_t)bb * N + 12] = (double)fwd_passes;
-    A.u[(size_t)bb * N + 13] = (double)fwd_tries;
-    A.u[(size_t)bb * N + 14] = (double)batch_entries;
-    A.u[(size_t)bb * N + 15] = (double)batch_lps;
-#endif
-#ifdef TPR_DEBUG_PREDICT
-    if (alive) A.status[bb] = dbg;  // debug builds only: needy LPs (lower | upper << 10), of which full iterations (lower << 20 | upper << 26)
-#endif
 }
 
 
@@ -1206,10 +1074,6 @@ __global__ void __launch_bounds__(BS) cert_feasible_kernel(GroupArgs A, double *
         TPR_WAVE_SYNC();
     };
 
-    TPR_T0();
-#ifdef TPR_DEBUG_PREDICT
-    int dbg = 0;
-#endif
     int up0 = 4, up1 = 4, dn0 = 4, dn1 = 4;  // a fresh wrapper object's state, internal row numbering
 
     double low1, high1;
@@ -1230,20 +1094,15 @@ __global__ void __launch_bounds__(BS) cert_feasible_kernel(GroupArgs A, double *
         int up_p, up_q;
         bool up_ok;
         double up_prow[3], up_qrow[3];
-#ifdef TPR_DEBUG_PREDICT
-        int dbg_rows[6];
-        TPR_PROPOSE<D, BS>(S, 1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow, dbg_rows);
-#else
         if constexpr (SOUND) cert_propose_sound<D, BS, 0, kSignBitsF>(S, 1e-9, 1.0, dn0, dn1, dn0 != dn1, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
-        else TPR_PROPOSE<D, BS>(S, 1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
-#endif
-        bool need_u = !cert_pair_rows<D, BS, false, kTraceProposal<SOUND>>(S, 1e-9, 1.0, up_p, up_q, nok & up_ok, up_prow[0], up_prow[1], up_prow[2],
+        else cert_propose2<D, BS>(S, 1e-9, 1.0, dn0, dn1, dn0 != dn1, false, nmax, up_p, up_q, up_ok, up_prow, up_qrow);
+        bool need_u = !cert_pair_rows<D, BS, false, SOUND>(S, 1e-9, 1.0, up_p, up_q, nok & up_ok, up_prow[0], up_prow[1], up_prow[2],
                                                     up_qrow[0], up_qrow[1], up_qrow[2], dn0, dn1, nmax, su);
         bool need_l;
         if constexpr (SOUND) need_l = !cert_lower_sound<D, BS, false, kSignBitsF>(S, nok, nmax, up0, up1, sl);
         else need_l = !cert_lower<D, BS, false>(S, nok, nmax, sl);
         if (__builtin_amdgcn_ballot_w64(need_u | need_l) != 0)
-            cert_needy_batch<D, BS, INTERP, 1, SOUND>(S, qt, i & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, need_u, need_l, dn0, dn1, up0, up1, su, sl TPR_TACC_ARG TPR_DBG_ARG, i);
+            cert_needy_batch<D, BS, INTERP, 1, SOUND>(S, qt, i & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, need_u, need_l, dn0, dn1, up0, up1, su, sl);
         if (su.ok) { dn0 = su.ac0; dn1 = su.ac1; } else su.x = qnan();
         if (sl.ok) { up0 = sl.ac0; up1 = sl.ac1; } else sl.x = qnan();
         double lo = sl.x;
@@ -1261,7 +1120,7 @@ __global__ void __launch_bounds__(BS) cert_feasible_kernel(GroupArgs A, double *
         S.publish_special(lim + tid);
         Lp2dOut su, sl;
         su.ok = sl.ok = false; su.u = sl.u = su.x = sl.x = qnan(); su.ac0 = su.ac1 = sl.ac0 = sl.ac1 = 4;
-        cert_needy_batch<D, BS, INTERP, 2, SOUND>(S, qt, N & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, true, true, dn0, dn1, up0, up1, su, sl TPR_TACC_ARG TPR_DBG_ARG, N);
+        cert_needy_batch<D, BS, INTERP, 2, SOUND>(S, qt, N & 1, lim, alim_blk, ntraj, xch, needy_queue, rowbufs, true, true, dn0, dn1, up0, up1, su, sl);
         if (!su.ok) su.x = qnan();
         if (!sl.ok) sl.x = qnan();
         double lo = sl.x;

@@ -14,11 +14,6 @@
 #endif
 namespace tpr {
 
-#ifdef TPR_PROPOSE_V1  // development: the two-line search of the first version
-#define TPR_PROPOSE cert_propose
-#else
-#define TPR_PROPOSE cert_propose2
-#endif
 constexpr double kCertSlack = TPR_SLACK_ABS;    // absolute margin on row residuals (solver tolerances: 1e-10, 1e-8)
 constexpr double kCertRelSlack = TPR_SLACK_REL; // relative margin against rounding of the residuals
 constexpr double kCertMinNorm = 5e-2;   // rows are null or at least this long (keeps |t| < 1e10 on every pivot line)
@@ -37,13 +32,8 @@ constexpr int kCertBatchLanes = 16;     // lanes per LP in the cooperative batch
 // hold four blocks, one wave per SIMD.  Up to round 6's first session: four up to 7 dof, two at 8..12, one at 13; with the exchange
 // area 2 KB smaller (cert_needy_batch: n0, n1, low1, high1 from the column of row constants) all four fit up to 12 dof (40.0 KB
 // there), two at 13 / 14 (39.6 / 39.8 KB), one at 15 (40.5 KB).
-#ifndef TPR_BATCH_GROUPS_OVERRIDE
 template <int D>
 constexpr int cert_batch_groups() { return D >= 15 ? 1 : (D >= 13 ? 2 : 64 / kCertBatchLanes); }
-#else  // (timing experiments: -DTPR_BATCH_GROUPS_OVERRIDE=<n>)
-template <int D>
-constexpr int cert_batch_groups() { return TPR_BATCH_GROUPS_OVERRIDE; }
-#endif
 
 template <int D, int BS>
 struct CertStage {
@@ -287,10 +277,6 @@ __device__ __forceinline__ bool cert_pair_rows(const CertStage<D, BS> &S, double
     const double u = (pb * qc - qb * pc) * rD;
     const double x = (qa * pc - pa * qc) * rD;
     const double lamp = (v0 * qb - v1 * qa) * rD, lamq = (pa * v1 - pb * v0) * rD;  // v = lamp n_p + lamq n_q
-#ifdef TPR_DEBUG_PREDICT
-    const bool dbg_pair = ok;                      // the pair was usable
-    const bool dbg_dual = (lamp > 0) & (EQ || lamq > 0);
-#endif
     ok &= (lamp > 0) & (EQ || lamq > 0);
     // largest residual + tolerance over the rows other than p, q
     const double au = fabs(u), ax = fabs(x);
@@ -354,11 +340,6 @@ __device__ __forceinline__ bool cert_pair_rows(const CertStage<D, BS> &S, double
         }
         mx = fmax(mx, ms + tol_s);
     }
-#ifdef TPR_DEBUG_PREDICT
-    // why a certificate failed: 1 unusable pair / tiny determinant, 2 dual infeasible, 3 a row violated (> +1e-9),
-    // 4 a row inside the tolerance band, 5 the guards that follow
-    o.why = !dbg_pair ? 1 : (!dbg_dual ? 2 : (!(mx < 0) ? ((mx - tol_s > 1e-9) ? 3 : 4) : 5));
-#endif
     // a usable, dual feasible pair whose vertex violates no row but has one inside the tolerance band (concurrent
     // rows): the batches' walk would arrive at the same vertex and refuse it too, so it is skipped for this LP
     o.hint_full = ok & !(mx - tol_s > 1e-9);
@@ -402,9 +383,6 @@ __device__ __forceinline__ bool cert_pair_rows(const CertStage<D, BS> &S, double
     // |D| m / (max|n| |n_l|), m = smallest margin of the other rows at z* (>= -mx)
     const bool g_viol = (TRACE && !EQ) ? true : fabs(Dm) * (-mx) > 1e-8 * (nmax * (fabs(la) + fabs(lb)));
     ok &= g_viol;
-#ifdef TPR_DEBUG_PREDICT  // which guard refused a verified vertex: 8 parallel row, 16 |v1d|, 32 violation bound, 64 row 5 in the band
-    if ((o.why & 7) == 5) o.why |= (g_cross ? 0 : 8) | (fabs(v1d) > 1e-6 ? 0 : 16) | (g_viol ? 0 : 32) | (band5 ? 64 : 0) | (S.min_range > tol_s ? 0 : 128);
-#endif
     cert_last_pivot(ka, kb, kc, la, lb, lc, o.u, o.x);
     if (!EQ) {
         // cy_seidel_solverwrapper.pyx:274 for row 5 = (2 delta, 1, -K_hi[i+1]):  a u + b x + c < TINY  <=>  satisfied
@@ -445,9 +423,6 @@ __device__ __forceinline__ bool cert_pair(const CertStage<D, BS> &S, double v0, 
 template <int D, int BS>
 __device__ __forceinline__ void cert_propose(const CertStage<D, BS> &S, double v0, double v1, int p0, int q0, bool pair_ok,
                                              int &p2, int &q2, bool &ok2, double (&prow)[3], double (&qrow)[3]
-#ifdef TPR_DEBUG_PREDICT
-                                             , int (&dbg_rows)[6]
-#endif
                                              ) {
     using C = CertStage<D, BS>;
     bool ok = pair_ok & (p0 != q0) & (p0 >= 0) & (q0 >= 0) & (p0 < C::nV) & (q0 < C::nV);
@@ -548,11 +523,6 @@ __device__ __forceinline__ void cert_propose(const CertStage<D, BS> &S, double v
     q2 = both ? ro : qA;
     prow[0] = both ? ra : (from_q ? qa : pa); prow[1] = both ? rb : (from_q ? qb : pb); prow[2] = both ? rc : (from_q ? qc : pc);
     qrow[0] = both ? oa : ra; qrow[1] = both ? ob : rb; qrow[2] = both ? oc : rc;
-#ifdef TPR_DEBUG_PREDICT
-    dbg_rows[0] = p; dbg_rows[1] = q; dbg_rows[2] = rp; dbg_rows[3] = rq;
-    dbg_rows[4] = (viol ? 1 : 0) | (okp ? 2 : 0) | (okq ? 4 : 0) | (cp ? 8 : 0) | (cq ? 16 : 0) | (use_p ? 32 : 0) | (use_q ? 64 : 0) | (both ? 128 : 0);
-    dbg_rows[5] = (res_o > 1e-9 ? 1 : 0) | (res_o > -1e-9 ? 2 : 0);
-#endif
     ok2 = ok & (keep | (r >= 0)) & (p2 != q2) & !((p2 < 4) & (q2 < 4));
 }
 
@@ -586,9 +556,6 @@ __device__ __forceinline__ void cert_propose(const CertStage<D, BS> &S, double v
 template <int D, int BS>
 __device__ __forceinline__ void cert_propose2(const CertStage<D, BS> &S, double v0, double v1, int p0, int q0, bool pair_ok,
                                               bool sound, double nmax, int &p2, int &q2, bool &ok2, double (&prow)[3], double (&qrow)[3]
-#ifdef TPR_DEBUG_PREDICT
-                                              , int (&dbg_rows)[6]
-#endif
                                               ) {
     using C = CertStage<D, BS>;
     bool ok = pair_ok & (p0 != q0) & (p0 >= 0) & (q0 >= 0) & (p0 < C::nV) & (q0 < C::nV);
@@ -694,10 +661,6 @@ __device__ __forceinline__ void cert_propose2(const CertStage<D, BS> &S, double 
     const bool from_l = moved & !alt;
     prow[0] = from_l ? la : (alt_q ? qa : pa); prow[1] = from_l ? lb : (alt_q ? qb : pb); prow[2] = from_l ? lc : (alt_q ? qc : pc);
     qrow[0] = wa; qrow[1] = wb; qrow[2] = wc;
-#ifdef TPR_DEBUG_PREDICT
-    dbg_rows[0] = p; dbg_rows[1] = q; dbg_rows[2] = L; dbg_rows[3] = w;
-    dbg_rows[4] = (viol ? 1 : 0) | (okp ? 2 : 0) | (okq ? 4 : 0); dbg_rows[5] = 0;
-#endif
     // sound mode: "one violated row at a dual feasible warm vertex, partner inside its 1-D problem" (see above)
     const bool partner_first = (L < 4) ? ((q2 == p) | (q2 == q)) : (cert_pos(q2, p, q) < cert_pos(L, p, q));
     const bool predictable = okp & okq & (loose == 3) & partner_first;

@@ -3,9 +3,7 @@
 // The certified lane kernels are instantiated per dof and per (sd output, grid in LDS, discretisation, certificate mode):
 // 8 x 16 heavy kernels, most of the library's compile time.  build.py compiles this file once per dof
 // (-DTPR_TU_D=<dof>), in parallel with tpr_kernels.hip, and links the objects into libtoppra_hip.so; the entry points
-// below are the only interface (declared in tpr_kernels.hip).  Development builds with instrumentation defines
-// (-DTPR_DEBUG_PREDICT ..., whose counters are device globals of ONE translation unit) include this file from
-// tpr_kernels.hip instead (TPR_SINGLE_TU).
+// below are the only interface (declared in tpr_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include "../../include/toppra_hip.h"
@@ -14,9 +12,9 @@
 #include "tpr_cert.hip.inc"
 
 #ifndef TPR_TU_D
-#error "compile with -DTPR_TU_D=<dof 1..14>"
+#error "compile with -DTPR_TU_D=<dof 1..15>"
 #endif
-// A dof's unit can be split by entry point (build.py::CERT_UNIT_PARTS): 1 = the fused solve / backward scan, 2 = feasible sets,
+// A dof's unit can be split by entry point (build.py::CERT_UNITS): 1 = the fused solve / backward scan, 2 = feasible sets,
 // 3 = TOPPRAsd; 0 = all three in one unit.  Above 8 dof the three kernels want DIFFERENT scheduler flags (the switch that takes
 // the 13-dof solve from 8.0 to 5.2 ms takes its feasible-sets kernel from 9.3 to 10.8), and flags are per translation unit.
 #ifndef TPR_TU_PART
@@ -24,7 +22,7 @@
 #endif
 
 // The certificates follow the reference's whole pivot trace (tpr_cert_lane.hip.inc: cert_propose_sound & co) -- the only mode
-// of the product at every dof this file is compiled for (1..13; slim blocks above 8 dof); TPR_SOUND_CERTIFICATES is accepted
+// of the product at every dof this file is compiled for (1..15; slim blocks above 8 dof); TPR_SOUND_CERTIFICATES is accepted
 // and changes nothing.  The round-2/3 "fast" certificates (last pivot only) survive in the opt-in tolerance measurement
 // build.  History of the 9..13-dof instantiations (round 3: not shipped sound; round 4: one conditionally-needed load in
 // CertStage::fetch): DESIGN.md sections 3.2 and 9; tests/test_kernel_resources.py pins their scratch and branch counts.
@@ -56,6 +54,25 @@ struct TwsScope {
     ~TwsScope() { if (ws) (void)hipFreeAsync(ws, stream); }
 };
 
+// Dynamic LDS of a launch: the shared grid, or nothing.  min_cols: the front columns' minimum in doubles per lane (the forward
+// output staging: 3 arrays x 8 stages, TOPPRAsd 4).  The grid goes to LDS only while that does not cost a block per CU (160 KB:
+// four blocks up to 8 dof -- one wave per SIMD --, three at 9..11 dof, two above): a fifth of the 1024 blocks of a
+// 65536-trajectory batch would otherwise wait for a second round.
+// ... and only up to 8 dof (round 3: the <9 dof, grid in LDS, sound certificates> instantiation returned lower bounds that
+// were off in the last bits on 0.9 % of an irregular batch while value-identical spellings were bit-exact -- the signature of
+// the register allocator's copy above the exec restore, profiles/r06_miscompile_root_cause.md, which the build now checks
+// for); above 8 dof the grid is read from global memory, and those instantiations are not compiled (TPR_IF_GRID_LDS).
+template <int D, int BS>
+static size_t cert_grid_lds(const tpr::GroupArgs &G, int min_cols) {
+    using CS = tpr::CertStage<D, BS>;
+    const size_t grid_bytes = (size_t)(G.N + 1) * sizeof(double);
+    const size_t cols = (size_t)((4 * D + CS::kLimCols) > min_cols ? (4 * D + CS::kLimCols) : min_cols) * BS;
+    const size_t static_lds = (cols + tpr::kCertXch * BS + tpr::cert_batch_groups<D>() * tpr::GroupCfg<D, tpr::kCertBatchLanes>::kRowBuf +
+                               CS::kRing * 2 * BS) * sizeof(double);
+    const bool grid_lds = D <= 8 && !(G.flags & TPR_GRID_PER_TRAJ) && (160 * 1024) / (static_lds + grid_bytes) == (160 * 1024) / static_lds;
+    return grid_lds ? grid_bytes : 0;
+}
+
 #define TPR_TU_CAT2(a, b) a##b
 #define TPR_TU_CAT(a, b) TPR_TU_CAT2(a, b)
 
@@ -68,20 +85,8 @@ extern "C" __attribute__((visibility("hidden"))) int TPR_TU_CAT(tpr_tu_cert_laun
     const dim3 grid((G.B + BS - 1) / BS), block(BS);
     TwsScope tws(G, D, (int)grid.x, stream);
     if (tws.err != hipSuccess) return -1;
-    // the shared grid goes to LDS only while four blocks still fit a CU (160 KB): a fifth of the
-    // 1024 blocks of a 65536-trajectory batch would otherwise wait for a second round
-    const size_t grid_bytes = (size_t)(G.N + 1) * sizeof(double);
-    using CS = tpr::CertStage<D, BS>;
-    const size_t static_lds = (((4 * D + CS::kLimCols) > 24 ? (4 * D + CS::kLimCols) : 24) * BS + tpr::kCertXch * BS +
-                               tpr::cert_batch_groups<D>() * tpr::GroupCfg<D, tpr::kCertBatchLanes>::kRowBuf + CS::kRing * 2 * BS) * sizeof(double);
-    // the shared grid goes to LDS only while that does not cost a block per CU (160 KB: four blocks up to 8 dof -- one
-    // wave per SIMD --, three at 9..11 dof, two above)
-    // ... and only up to 8 dof (round 3: the <9 dof, grid in LDS, sound certificates> instantiation returned lower bounds that
-    // were off in the last bits on 0.9 % of an irregular batch while value-identical spellings were bit-exact -- the signature of
-    // the register allocator's copy above the exec restore, profiles/r06_miscompile_root_cause.md, which the build now checks
-    // for); above 8 dof the grid is read from global memory, and those instantiations are not compiled (TPR_IF_GRID_LDS).
-    const bool grid_lds = D <= 8 && !(G.flags & TPR_GRID_PER_TRAJ) && (160 * 1024) / (static_lds + grid_bytes) == (160 * 1024) / static_lds;
-    const size_t lds = grid_lds ? grid_bytes : 0;
+    const size_t lds = cert_grid_lds<D, BS>(G, 24);
+    const bool grid_lds = lds != 0;
     // One 64-lane block per wave; ~39 KB of LDS per block leaves one wave per SIMD, which the kernel
     // is written for (the whole register file, stalls covered by unrolled independent row work).
 #define TPR_LAUNCH_CERT(SD, GL, IN, SO) hipLaunchKernelGGL((tpr::cert_solve_kernel<D, BS, SD, GL, IN, SO>), grid, block, lds, stream, G)
@@ -107,18 +112,8 @@ extern "C" __attribute__((visibility("hidden"))) int TPR_TU_CAT(tpr_tu_cert_feas
     const dim3 grid((G.B + BS - 1) / BS), block(BS);
     TwsScope tws(G, D, (int)grid.x, stream);
     if (tws.err != hipSuccess) return -1;
-    const size_t grid_bytes = (size_t)(G.N + 1) * sizeof(double);
-    using CS = tpr::CertStage<D, BS>;
-    const size_t static_lds = (((4 * D + CS::kLimCols) > 24 ? (4 * D + CS::kLimCols) : 24) * BS + tpr::kCertXch * BS +
-                               tpr::cert_batch_groups<D>() * tpr::GroupCfg<D, tpr::kCertBatchLanes>::kRowBuf + CS::kRing * 2 * BS) * sizeof(double);
-    // the shared grid goes to LDS only while that does not cost a block per CU (160 KB: four blocks up to 8 dof -- one
-    // wave per SIMD --, three at 9..11 dof, two above)
-    // ... and only up to 8 dof (round 3: the <9 dof, grid in LDS, sound certificates> instantiation returned lower bounds that
-    // were off in the last bits on 0.9 % of an irregular batch while value-identical spellings were bit-exact -- the signature of
-    // the register allocator's copy above the exec restore, profiles/r06_miscompile_root_cause.md, which the build now checks
-    // for); above 8 dof the grid is read from global memory, and those instantiations are not compiled (TPR_IF_GRID_LDS).
-    const bool grid_lds = D <= 8 && !(G.flags & TPR_GRID_PER_TRAJ) && (160 * 1024) / (static_lds + grid_bytes) == (160 * 1024) / static_lds;
-    const size_t lds = grid_lds ? grid_bytes : 0;
+    const size_t lds = cert_grid_lds<D, BS>(G, 24);
+    const bool grid_lds = lds != 0;
     const bool interp = (G.flags & TPR_ACC_INTERPOLATION) != 0;
 #define TPR_LAUNCH_FEAS(GL, IN, SO) hipLaunchKernelGGL((tpr::cert_feasible_kernel<D, BS, GL, IN, SO>), grid, block, lds, stream, G, X)
 #define TPR_LAUNCH_FEAS2(GL, IN) TPR_LAUNCH_FEAS(GL, IN, kSoundKernels)
@@ -138,18 +133,8 @@ extern "C" __attribute__((visibility("hidden"))) int TPR_TU_CAT(tpr_tu_cert_sd_l
     const dim3 grid((G.B + BS - 1) / BS), block(BS);
     TwsScope tws(G, D, (int)grid.x, stream);
     if (tws.err != hipSuccess) return -1;
-    const size_t grid_bytes = (size_t)(G.N + 1) * sizeof(double);
-    using CS = tpr::CertStage<D, BS>;
-    const size_t cols = ((4 * D + CS::kLimCols) > 32 ? (4 * D + CS::kLimCols) : 32) * BS;
-    const size_t static_lds = (cols + tpr::kCertXch * BS + tpr::cert_batch_groups<D>() * tpr::GroupCfg<D, tpr::kCertBatchLanes>::kRowBuf + CS::kRing * 2 * BS) * sizeof(double);
-    // the shared grid goes to LDS only while that does not cost a block per CU (160 KB: four blocks up to 8 dof -- one
-    // wave per SIMD --, three at 9..11 dof, two above)
-    // ... and only up to 8 dof (round 3: the <9 dof, grid in LDS, sound certificates> instantiation returned lower bounds that
-    // were off in the last bits on 0.9 % of an irregular batch while value-identical spellings were bit-exact -- the signature of
-    // the register allocator's copy above the exec restore, profiles/r06_miscompile_root_cause.md, which the build now checks
-    // for); above 8 dof the grid is read from global memory, and those instantiations are not compiled (TPR_IF_GRID_LDS).
-    const bool grid_lds = D <= 8 && !(G.flags & TPR_GRID_PER_TRAJ) && (160 * 1024) / (static_lds + grid_bytes) == (160 * 1024) / static_lds;
-    const size_t lds = grid_lds ? grid_bytes : 0;
+    const size_t lds = cert_grid_lds<D, BS>(G, 32);  // (TOPPRAsd: 4 arrays of forward output staging)
+    const bool grid_lds = lds != 0;
     const bool interp = (G.flags & TPR_ACC_INTERPOLATION) != 0;
 #define TPR_LAUNCH_SD(GL, IN, SO) hipLaunchKernelGGL((tpr::cert_solve_kernel<D, BS, false, GL, IN, SO, true>), grid, block, lds, stream, G)
 #define TPR_LAUNCH_SD2(GL, IN) TPR_LAUNCH_SD(GL, IN, kSoundKernels)

@@ -148,9 +148,6 @@ struct Lp2dOut {
     double u, x;
     int ac0, ac1;
     bool hint_full = false;  // family 3: the vertex looked optimal but could not be certified -- skip the walk, iterate
-#ifdef TPR_DEBUG_PREDICT
-    int why = 0;  // debug builds: why a certificate failed (tpr_cert.hip.inc)
-#endif
 };
 
 // Incremental (Seidel) 2-variable LP in the reference's deterministic order.

@@ -39,13 +39,7 @@
 #pragma once
 namespace tpr {
 
-#ifdef TPR_DEBUG_PREDICT  // why predict_upper_lp gave up (debug builds only; read with hipMemcpyFromSymbol)
-__device__ unsigned long long g_walk_fail[16];
-__device__ unsigned int g_walk_hist[5][512];  // [0] third row, [1] p, [2] q, [3] stage -- of the "tolerance band" give-ups
-#define TPR_WALK_FAIL(code) do { if (gl == 0 && live_) atomicAdd(&g_walk_fail[code], 1ull); return false; } while (0)
-#else
 #define TPR_WALK_FAIL(code) return false
-#endif
 
 // ---- cross-lane helpers -------------------------------------------------------------------
 constexpr int kDppXor1 = 0xB1;        // quad_perm [1,0,3,2]
@@ -444,8 +438,7 @@ __device__ inline bool predict_lower_lp(const Slots<D, L> &R, const double *rowb
 // argument: only then is the reference's own run predictable up to its last pivot.
 template <int D, int L>
 __device__ inline bool predict_upper_lp(const Slots<D, L> &R, const double *rowbuf, int gl, double v0, double v1,
-                                        double low1, double high1, int wac0, int wac1, GroupLp &o, bool sound = false,
-                                        bool live_ = true, int dbg_stage = 0) {
+                                        double low1, double high1, int wac0, int wac1, GroupLp &o, bool sound = false) {
     using C = GroupCfg<D, L>;
     const int kMaxIt = sound ? 1 : 6;
     int entered = -1;
@@ -517,19 +510,6 @@ __device__ inline bool predict_upper_lp(const Slots<D, L> &R, const double *rowb
         const double gsc = group_max_f64<L>(lsc);
         maxres = group_max_f64<L>(lmax);
         if (gsc < 0) break;  // primal feasible with margins, dual feasible: optimal
-#ifdef TPR_DEBUG_PREDICT
-        if (!(maxres > 0) && live_) {
-#pragma unroll
-            for (int s = 0; s < C::S; ++s) {
-                const int vi = s * L + gl;
-                const bool row = (vi < C::nV) & (vi != p) & (vi != q);
-                const double au = R.a[s] * u, bx = R.b[s] * x;
-                const double sc = (au + bx + R.c[s]) + (kSlack + kRelSlack * (fabs(au) + fabs(bx) + fabs(R.c[s])));
-                if (row && sc == gsc) { atomicAdd(&g_walk_hist[0][vi], 1u); const double r_ = fabs(au + bx + R.c[s]); atomicAdd(&g_walk_hist[4][r_ == 0 ? 0 : (int)fmin(fmax(-log10(r_), 1.0), 30.0)], 1u); }
-            }
-            if (gl == 0) { atomicAdd(&g_walk_hist[1][p], 1u); atomicAdd(&g_walk_hist[2][q], 1u); atomicAdd(&g_walk_hist[3][dbg_stage & 511], 1u); }
-        }
-#endif
         if (!(maxres > 0)) TPR_WALK_FAIL(6);
         if (++it > kMaxIt) TPR_WALK_FAIL(7);
         // dual pivot: the most violated row enters, the ratio test picks the row that leaves
@@ -581,12 +561,6 @@ __device__ inline bool predict_upper_lp(const Slots<D, L> &R, const double *rowb
     // violation of the pivot row at the optimum of the rows before it: >= |D| m / (max|n| |n_l|),
     // m = smallest margin of the other rows at z*
     const bool bad_viol = !(fabs(Dm) * (-maxres) > 1e-8 * (nmax * (fabs(la) + fabs(lb))));
-#ifdef TPR_DEBUG_PREDICT
-    if (group_or_i32<L>(bad ? 1 : 0) != 0) TPR_WALK_FAIL(10);
-    if (group_or_i32<L>(bad_norm ? 1 : 0) != 0) TPR_WALK_FAIL(11);
-    if (bad_v1d) TPR_WALK_FAIL(12);
-    if (bad_viol) TPR_WALK_FAIL(13);
-#endif
     if (group_or_i32<L>((bad | bad_norm | bad_v1d | bad_viol) ? 1 : 0) != 0) return false;
     // the reference's arithmetic for (pivot k, limiter l)
     const double den = ka * ka + kb * kb;
@@ -885,9 +859,6 @@ __global__ void __launch_bounds__(256, TPR_GROUP_WAVES) group_solve_kernel(Group
     // ---- backward scan: controllable sets ------------------------------------------------
     int up0 = 0, up1 = 0, dn0 = 0, dn1 = 0;  // warm-start state (active_c_up / active_c_down)
     const bool use_shortcut = TPR_PREDICT_LOWER && !(A.flags & TPR_STRICT_SEIDEL);
-#ifdef TPR_DEBUG_PREDICT
-    int dbg_predicted = 0;
-#endif
     double kn0 = boundary_x(A.flags, sd_end), kn1 = A.sd_end_hi ? boundary_x(A.flags, A.sd_end_hi[bb]) : kn0;
     if (writer) { K[2 * N] = kn0; K[2 * N + 1] = kn1; }
     bool failed = false;
@@ -914,19 +885,12 @@ __global__ void __launch_bounds__(256, TPR_GROUP_WAVES) group_solve_kernel(Group
                                                            true);  // round 4: the sound mode is the only mode (a moved pair: one predictable pivot, else the iteration)
 #endif
                 if (!up_hit) su = group_lp2d<D, L>(R, T.rowbuf, gl, -1e-9, 1.0, kVarMin, kVarMax, low1, high1, dn0, dn1);
-#ifdef TPR_DEBUG_PREDICT
-                if (up_hit) dbg_predicted += 1 << 10;
-                if (__builtin_amdgcn_ballot_w64(!up_hit) == 0) dbg_predicted += 1 << 20;  // whole wave answered
-#endif
                 if (su.ok) { dn0 = su.ac0; dn1 = su.ac1; }
                 hi = su.x;
                 {
                     GroupLp sl;
                     if (!(use_shortcut && predict_lower_lp<D, L>(R, T.rowbuf, gl, kVarMin, kVarMax, low1, high1, sl, up0, up1, T.limit_min)))
                         sl = group_lp2d<D, L>(R, T.rowbuf, gl, 1e-9, -1.0, kVarMin, kVarMax, low1, high1, up0, up1);
-#ifdef TPR_DEBUG_PREDICT
-                    else dbg_predicted += 1;
-#endif
                     if (sl.ok) { up0 = sl.ac0; up1 = sl.ac1; }
                     lo = sl.x;
                 }
@@ -1019,9 +983,6 @@ __global__ void __launch_bounds__(256, TPR_GROUP_WAVES) group_solve_kernel(Group
         }
     }
     if (writer && A.status) A.status[bb] = any_nan ? TPR_STATUS_ERR_UNKNOWN : TPR_STATUS_OK;
-#ifdef TPR_DEBUG_PREDICT
-    if (writer && A.status) A.status[bb] = dbg_predicted;  // debug builds only: shortcut hit count
-#endif
 }
 
 // ---- compute_feasible_sets: reachability_algorithm.py:131-164 -------------------------------------

@@ -22,95 +22,31 @@
 #include "tpr_robust_args.hpp"
 #include "tpr_dense_args.hpp"
 
-#define TPR_TU_CAT3_(a, b) a##b
-#define TPR_TU_CAT3(a, b) TPR_TU_CAT3_(a, b)
-// kernel family 3, one translation unit per dof (tpr_cert_tu.hip): 1..TPR_CERT_MAX_DOF (build.py: 15)
+// kernel family 3, one translation unit per dof (tpr_cert_tu.hip): 1..TPR_CERT_MAX_DOF (build.py: 15; the measurement builds: 8).
+// TPR_CERT_DOFS(X) expands X(d) for every dof linked; it spells the entry points' declarations and the launchers' cases.
 #ifndef TPR_CERT_MAX_DOF
 #define TPR_CERT_MAX_DOF 15
 #endif
-#ifdef TPR_SINGLE_TU  // development builds with instrumentation: everything in this translation unit, ONE dof for family 3 (7; -DTPR_SINGLE_TU_D=<dof>)
-#ifndef TPR_SINGLE_TU_D
-#define TPR_SINGLE_TU_D 7
-#endif
-#define TPR_TU_D TPR_SINGLE_TU_D
-#include "tpr_cert_tu.hip"
-#undef TPR_TU_D
-#define TPR_TU_HALF 2
-#include "tpr_robust_tu.hip"
-#undef TPR_TU_HALF
-#include "tpr_dense_tu.hip"
+#if TPR_CERT_MAX_DOF == 15
+#define TPR_CERT_DOFS_ABOVE_8(X) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+#elif TPR_CERT_MAX_DOF == 8
+#define TPR_CERT_DOFS_ABOVE_8(X)
 #else
+#error "TPR_CERT_MAX_DOF: 15 (the product) or 8 (the measurement builds)"
+#endif
+#define TPR_CERT_DOFS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) TPR_CERT_DOFS_ABOVE_8(X)
+#define TPR_CERT_DECLARE(d) \
+    __attribute__((visibility("hidden"))) int tpr_tu_cert_launch_##d(const tpr::GroupArgs *, hipStream_t); \
+    __attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_##d(const tpr::GroupArgs *, double *, hipStream_t); \
+    __attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_##d(const tpr::GroupArgs *, hipStream_t);
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_dense_launch(const tpr::DenseArgs *, int, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_robust_launch_lo(const tpr::RobustArgs *, size_t, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_robust_launch_hi(const tpr::RobustArgs *, size_t, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_robust_lane_launch(const tpr::RobustArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_1(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_1(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_1(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_2(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_2(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_2(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_3(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_3(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_3(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_4(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_4(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_4(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_5(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_5(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_5(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_6(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_6(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_6(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_7(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_7(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_7(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_8(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_8(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_8(const tpr::GroupArgs *, hipStream_t);
-#if TPR_CERT_MAX_DOF >= 9
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_9(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_9(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_9(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 10
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_10(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_10(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_10(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 11
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_11(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_11(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_11(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 12
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_12(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_12(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_12(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 13
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_13(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_13(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_13(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 14
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_14(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_14(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_14(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 15
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_15(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_15(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_15(const tpr::GroupArgs *, hipStream_t);
-#endif
-#if TPR_CERT_MAX_DOF >= 16
-__attribute__((visibility("hidden"))) int tpr_tu_cert_launch_16(const tpr::GroupArgs *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_feasible_launch_16(const tpr::GroupArgs *, double *, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_cert_sd_launch_16(const tpr::GroupArgs *, hipStream_t);
-#endif
+TPR_CERT_DOFS(TPR_CERT_DECLARE)
+#undef TPR_CERT_DECLARE
 }
-#endif
 
 namespace {
 
@@ -273,9 +209,6 @@ int launch_group(const tpr::BatchArgs &A, hipStream_t stream) {
                      A.sd_start, A.sd_end, A.sd2, A.sd, A.u, A.K, A.status, A.sd_end_hi, A.backward_only};
     const int groups = threads / L;
     size_t lds = group_lds_bytes<D, L>(A.nseg, threads, table_in_lds);
-#ifdef TPR_LDS_PAD_EXPERIMENT  // occupancy experiments (development builds only)
-    if (const char *pad = std::getenv("TPR_LDS_PAD")) lds += (size_t)std::atoi(pad);
-#endif
     const dim3 grid((A.B + groups - 1) / groups), block(threads);
     if (table_in_lds) hipLaunchKernelGGL((tpr::group_solve_kernel<D, L, true>), grid, block, lds, stream, G);
     else hipLaunchKernelGGL((tpr::group_solve_kernel<D, L, false>), grid, block, lds, stream, G);
@@ -348,44 +281,9 @@ int cert_tu_rc(int rc) {
 int launch_cert(const tpr::BatchArgs &A, hipStream_t stream) {
     tpr::GroupArgs G{A.B, A.nseg, A.N, A.flags, A.coef, A.breaks, A.grid, A.vlim, A.alim,
                      A.sd_start, A.sd_end, A.sd2, A.sd, A.u, A.K, A.status, A.sd_end_hi, A.backward_only};
-    switch (A.d) {
-#ifndef TPR_CERT_DEV  // development builds instantiate 7 dof only
-        case 1: return cert_tu_rc(tpr_tu_cert_launch_1(&G, stream));
-        case 2: return cert_tu_rc(tpr_tu_cert_launch_2(&G, stream));
-        case 3: return cert_tu_rc(tpr_tu_cert_launch_3(&G, stream));
-        case 4: return cert_tu_rc(tpr_tu_cert_launch_4(&G, stream));
-        case 5: return cert_tu_rc(tpr_tu_cert_launch_5(&G, stream));
-        case 6: return cert_tu_rc(tpr_tu_cert_launch_6(&G, stream));
-        case 8: return cert_tu_rc(tpr_tu_cert_launch_8(&G, stream));
-#if TPR_CERT_MAX_DOF >= 9
-        case 9: return cert_tu_rc(tpr_tu_cert_launch_9(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 10
-        case 10: return cert_tu_rc(tpr_tu_cert_launch_10(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 11
-        case 11: return cert_tu_rc(tpr_tu_cert_launch_11(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 12
-        case 12: return cert_tu_rc(tpr_tu_cert_launch_12(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 13
-        case 13: return cert_tu_rc(tpr_tu_cert_launch_13(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 14
-        case 14: return cert_tu_rc(tpr_tu_cert_launch_14(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 15
-        case 15: return cert_tu_rc(tpr_tu_cert_launch_15(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 16
-        case 16: return cert_tu_rc(tpr_tu_cert_launch_16(&G, stream));
-#endif
-        case 7: return cert_tu_rc(tpr_tu_cert_launch_7(&G, stream));
-#else
-        case TPR_SINGLE_TU_D: return TPR_TU_CAT3(tpr_tu_cert_launch_, TPR_SINGLE_TU_D)(&G, stream);
-#endif
-    }
+#define TPR_CERT_CASE(d) case d: return cert_tu_rc(tpr_tu_cert_launch_##d(&G, stream));
+    switch (A.d) { TPR_CERT_DOFS(TPR_CERT_CASE) }
+#undef TPR_CERT_CASE
     return fail(TPR_E_UNSUPPORTED, "variant 3: dof not instantiated");
 }
 
@@ -398,44 +296,9 @@ bool cert_feasible_supported(const tpr::BatchArgs &A) {
 int launch_cert_feasible(const tpr::BatchArgs &A, double *X, hipStream_t stream) {
     tpr::GroupArgs G{A.B, A.nseg, A.N, A.flags, A.coef, A.breaks, A.grid, A.vlim, A.alim,
                      A.sd_start, A.sd_end, A.sd2, A.sd, A.u, A.K, A.status};
-    switch (A.d) {
-#ifndef TPR_CERT_DEV
-        case 1: return cert_tu_rc(tpr_tu_cert_feasible_launch_1(&G, X, stream));
-        case 2: return cert_tu_rc(tpr_tu_cert_feasible_launch_2(&G, X, stream));
-        case 3: return cert_tu_rc(tpr_tu_cert_feasible_launch_3(&G, X, stream));
-        case 4: return cert_tu_rc(tpr_tu_cert_feasible_launch_4(&G, X, stream));
-        case 5: return cert_tu_rc(tpr_tu_cert_feasible_launch_5(&G, X, stream));
-        case 6: return cert_tu_rc(tpr_tu_cert_feasible_launch_6(&G, X, stream));
-        case 8: return cert_tu_rc(tpr_tu_cert_feasible_launch_8(&G, X, stream));
-#if TPR_CERT_MAX_DOF >= 9
-        case 9: return cert_tu_rc(tpr_tu_cert_feasible_launch_9(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 10
-        case 10: return cert_tu_rc(tpr_tu_cert_feasible_launch_10(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 11
-        case 11: return cert_tu_rc(tpr_tu_cert_feasible_launch_11(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 12
-        case 12: return cert_tu_rc(tpr_tu_cert_feasible_launch_12(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 13
-        case 13: return cert_tu_rc(tpr_tu_cert_feasible_launch_13(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 14
-        case 14: return cert_tu_rc(tpr_tu_cert_feasible_launch_14(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 15
-        case 15: return cert_tu_rc(tpr_tu_cert_feasible_launch_15(&G, X, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 16
-        case 16: return cert_tu_rc(tpr_tu_cert_feasible_launch_16(&G, X, stream));
-#endif
-        case 7: return cert_tu_rc(tpr_tu_cert_feasible_launch_7(&G, X, stream));
-#else
-        case TPR_SINGLE_TU_D: return TPR_TU_CAT3(tpr_tu_cert_feasible_launch_, TPR_SINGLE_TU_D)(&G, X, stream);
-#endif
-    }
+#define TPR_CERT_CASE(d) case d: return cert_tu_rc(tpr_tu_cert_feasible_launch_##d(&G, X, stream));
+    switch (A.d) { TPR_CERT_DOFS(TPR_CERT_CASE) }
+#undef TPR_CERT_CASE
     return fail(TPR_E_UNSUPPORTED, "variant 3: dof not instantiated");
 }
 
@@ -444,44 +307,9 @@ int launch_cert_sd(const tpr::BatchArgs &A, double *xf, double *uf, double *xl, 
     tpr::GroupArgs G{A.B, A.nseg, A.N, A.flags, A.coef, A.breaks, A.grid, A.vlim, A.alim,
                      A.sd_start, A.sd_end, A.sd2, nullptr, A.u, A.K, A.status, nullptr, 0, xf, uf, xl, ul};
     G.sd_dur = dur;
-    switch (A.d) {
-#ifndef TPR_CERT_DEV
-        case 1: return cert_tu_rc(tpr_tu_cert_sd_launch_1(&G, stream));
-        case 2: return cert_tu_rc(tpr_tu_cert_sd_launch_2(&G, stream));
-        case 3: return cert_tu_rc(tpr_tu_cert_sd_launch_3(&G, stream));
-        case 4: return cert_tu_rc(tpr_tu_cert_sd_launch_4(&G, stream));
-        case 5: return cert_tu_rc(tpr_tu_cert_sd_launch_5(&G, stream));
-        case 6: return cert_tu_rc(tpr_tu_cert_sd_launch_6(&G, stream));
-        case 8: return cert_tu_rc(tpr_tu_cert_sd_launch_8(&G, stream));
-#if TPR_CERT_MAX_DOF >= 9
-        case 9: return cert_tu_rc(tpr_tu_cert_sd_launch_9(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 10
-        case 10: return cert_tu_rc(tpr_tu_cert_sd_launch_10(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 11
-        case 11: return cert_tu_rc(tpr_tu_cert_sd_launch_11(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 12
-        case 12: return cert_tu_rc(tpr_tu_cert_sd_launch_12(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 13
-        case 13: return cert_tu_rc(tpr_tu_cert_sd_launch_13(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 14
-        case 14: return cert_tu_rc(tpr_tu_cert_sd_launch_14(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 15
-        case 15: return cert_tu_rc(tpr_tu_cert_sd_launch_15(&G, stream));
-#endif
-#if TPR_CERT_MAX_DOF >= 16
-        case 16: return cert_tu_rc(tpr_tu_cert_sd_launch_16(&G, stream));
-#endif
-        case 7: return cert_tu_rc(tpr_tu_cert_sd_launch_7(&G, stream));
-#else
-        case TPR_SINGLE_TU_D: return TPR_TU_CAT3(tpr_tu_cert_sd_launch_, TPR_SINGLE_TU_D)(&G, stream);
-#endif
-    }
+#define TPR_CERT_CASE(d) case d: return cert_tu_rc(tpr_tu_cert_sd_launch_##d(&G, stream));
+    switch (A.d) { TPR_CERT_DOFS(TPR_CERT_CASE) }
+#undef TPR_CERT_CASE
     return fail(TPR_E_UNSUPPORTED, "variant 3: dof not instantiated");
 }
 
@@ -640,13 +468,6 @@ int launch_solve(const tpr_problem *p, const tpr::BatchArgs &A, hipStream_t stre
             // up to 8 dof a trajectory fits 8 lanes; batches that leave most SIMDs idle at that width
             // (<= 8192 trajectories = 1024 waves) run 16 lanes per trajectory: 1.42 -> 1.15 ms at 4096 x 7 x 200
             const bool wide = A.B <= 8192;
-#ifdef TPR_WIDE_EXPERIMENT  // lanes per trajectory for small batches (development builds): TPR_LANES=32|64
-            if (const char *e = std::getenv("TPR_LANES")) {
-                const int L = std::atoi(e);
-                if (A.d == 7 && L == 32) return launch_group<7, 32>(A, stream);
-                if (A.d == 7 && L == 64) return launch_group<7, 64>(A, stream);
-            }
-#endif
             switch (A.d) {
 #define TPR_GROUP_CASE(DD) case DD: return wide ? launch_group<DD, 16>(A, stream) : launch_group<DD, 8>(A, stream)
                 TPR_GROUP_CASE(1);
@@ -792,20 +613,6 @@ int tpr_init(int device) {
     return TPR_E_OK;
 }
 
-#ifdef TPR_DEBUG_PREDICT  // debug builds only: read and clear the walk's give-up counters
-int tpr_debug_walk_fail(unsigned long long *out16) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(tpr::g_walk_fail), 16 * sizeof(unsigned long long)));
-    unsigned long long zero[16] = {0};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(tpr::g_walk_fail), zero, sizeof(zero)));
-    return TPR_E_OK;
-}
-int tpr_debug_walk_hist(unsigned int *out4x512) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out4x512, HIP_SYMBOL(tpr::g_walk_hist), 5 * 512 * sizeof(unsigned int)));
-    return TPR_E_OK;
-}
-#endif
 
 int tpr_solve_batch(const tpr_problem *p, const tpr_result *r, void *stream_) {
     if (int rc = check_problem(p)) return rc;
@@ -1471,16 +1278,12 @@ int tpr_param_spline_batch(const tpr_problem *p, const double *sd, double *knot_
         return fail(TPR_E_UNSUPPORTED, "spline parametrizer variant 3 needs d <= 16 and about 2 (d + 1) (N + 1) doubles of LDS (<= 64 KB)");
     if (B > 0 && pcr_fits && (p->variant == 0 || p->variant == 3)) {
         const int kpt = N + 1 <= 256 ? 1 : (N + 1 <= 512 ? 2 : 4);
-        int pcr_debug = 0;
-#if TPR_PS_EXPERIMENT
-        if (const char *e = getenv("TPR_PS_DEBUG")) pcr_debug = atoi(e);
-#endif
         const dim3 grid((unsigned)B), block(256);
 #define TPR_PCR_CASE(DD) \
         case DD: \
-            if (kpt == 1) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 1>), grid, block, pcr_lds, stream, K, dcoef, pcr_debug); \
-            else if (kpt == 2) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 2>), grid, block, pcr_lds, stream, K, dcoef, pcr_debug); \
-            else hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 4>), grid, block, pcr_lds, stream, K, dcoef, pcr_debug); \
+            if (kpt == 1) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 1>), grid, block, pcr_lds, stream, K, dcoef); \
+            else if (kpt == 2) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 2>), grid, block, pcr_lds, stream, K, dcoef); \
+            else hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 4>), grid, block, pcr_lds, stream, K, dcoef); \
             break
         switch (p->d) {
             TPR_PCR_CASE(1); TPR_PCR_CASE(2); TPR_PCR_CASE(3); TPR_PCR_CASE(4);
@@ -1505,15 +1308,8 @@ int tpr_param_spline_batch(const tpr_problem *p, const double *sd, double *knot_
         F.rhs = static_cast<double *>(ws);
         F.rows = F.rhs + rhs_n;
         F.sk = F.rows + rows_n;
-        int tile = tpr::kPsTile;
-#if TPR_PS_EXPERIMENT
-        if (const char *e = getenv("TPR_PS_TILE")) tile = atoi(e);
-        if (const char *e = getenv("TPR_PS_DEBUG")) F.debug = atoi(e);
-#endif
-        const size_t lds = ((size_t)(tile + 1) * (128 + 5 * F.tpw) + 64) * sizeof(double) + (size_t)F.tpw * sizeof(int);
-        if (tile == 4) hipLaunchKernelGGL(tpr::param_spline_fused_kernel<4>, dim3((unsigned)tasks), dim3(64), lds, stream, F);
-        else if (tile == 16) hipLaunchKernelGGL(tpr::param_spline_fused_kernel<16>, dim3((unsigned)tasks), dim3(64), lds, stream, F);
-        else hipLaunchKernelGGL(tpr::param_spline_fused_kernel<tpr::kPsTile>, dim3((unsigned)tasks), dim3(64), lds, stream, F);
+        const size_t lds = ((size_t)(tpr::kPsTile + 1) * (128 + 5 * F.tpw) + 64) * sizeof(double) + (size_t)F.tpw * sizeof(int);
+        hipLaunchKernelGGL(tpr::param_spline_fused_kernel<tpr::kPsTile>, dim3((unsigned)tasks), dim3(64), lds, stream, F);
         HIP_TRY(S.finish());
         return TPR_E_OK;
     }
@@ -1568,9 +1364,9 @@ int tpr_param_spline_sample_batch(const tpr_problem *p, const double *sd, int T,
         const dim3 grid((unsigned)B), block(256);
 #define TPR_PCRS_CASE(DD) \
         case DD: \
-            if (kpt == 1) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 1, true>), grid, block, lds, stream, K, (double *)nullptr, 0, Q); \
-            else if (kpt == 2) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 2, true>), grid, block, lds, stream, K, (double *)nullptr, 0, Q); \
-            else hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 4, true>), grid, block, lds, stream, K, (double *)nullptr, 0, Q); \
+            if (kpt == 1) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 1, true>), grid, block, lds, stream, K, (double *)nullptr, Q); \
+            else if (kpt == 2) hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 2, true>), grid, block, lds, stream, K, (double *)nullptr, Q); \
+            else hipLaunchKernelGGL((tpr::param_spline_pcr_kernel<DD, 4, true>), grid, block, lds, stream, K, (double *)nullptr, Q); \
             break
         switch (p->d) {
             TPR_PCRS_CASE(1); TPR_PCRS_CASE(2); TPR_PCRS_CASE(3); TPR_PCRS_CASE(4);

@@ -1,8 +1,7 @@
 // tpr_robust_tu.hip -- translation unit of the robust (conic) kernels (tpr_robust.hip.inc).
 //
 // build.py compiles this file twice (-DTPR_TU_HALF=0: the generic lane kernel and 1..8 dof on 8 lanes per trajectory;
-// =1: 9..16 dof on 16 lanes), in parallel with the other units; instrumented single-unit builds include it from
-// tpr_kernels.hip with TPR_TU_HALF = 2 (both halves).  One entry point per half, declared in tpr_kernels.hip.
+// =1: 9..16 dof on 16 lanes), in parallel with the other units.  One entry point per half, declared in tpr_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "../../include/toppra_hip.h"
@@ -32,7 +31,7 @@ int robust_launch_group(const tpr::RobustArgs &P, size_t max_lds, hipStream_t st
 }
 }  // namespace
 
-#if TPR_TU_HALF == 0 || TPR_TU_HALF == 2
+#if TPR_TU_HALF == 0
 // 0 = launched; 1 = this shape needs the lane kernel (tpr_tu_robust_lane_launch); -1 = dof not served here
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_robust_launch_lo(const tpr::RobustArgs *P, size_t max_lds, hipStream_t stream) {
     switch (P->A.d) {
@@ -52,7 +51,7 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_robust_lane_launch(c
     return 0;
 }
 #endif
-#if TPR_TU_HALF == 1 || TPR_TU_HALF == 2
+#if TPR_TU_HALF == 1
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_robust_launch_hi(const tpr::RobustArgs *P, size_t max_lds, hipStream_t stream) {
     switch (P->A.d) {
         case 9: return robust_launch_group<9, 16>(*P, max_lds, stream);

@@ -277,9 +277,6 @@ __global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs 
 // ends (tests/test_gpu_param.py compares the two bit for bit, ragged knot counts and row exchanges included).
 constexpr int kPsTile = 8;
 constexpr int kPsMaxTpw = 16;   // bounds the per-lane share of a tile's per-trajectory loads
-#ifndef TPR_PS_EXPERIMENT
-#define TPR_PS_EXPERIMENT 0
-#endif
 #ifndef TPR_PS_WAVES
 #define TPR_PS_WAVES 2   // waves per SIMD the register allocation aims at (3 spills: slower)
 #endif
@@ -291,7 +288,6 @@ struct ParamFusedArgs {
     double *rows;       // [tasks][N+1][3][tpw] eliminated matrix rows: diagonal, first and second super-diagonal
     double *sk;         // [B][N+1] path position of each knot
     int tpw;            // trajectories per wave
-    int debug;
 };
 
 // The path segment holding s (find_segment's answer) with its coefficients of dof k in registers.  Gridpoints ascend
@@ -425,7 +421,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TPR_PS_
         }
     }
     __syncthreads();
-    if (TPR_PS_EXPERIMENT && (A.debug & 1)) return;
     int nmax = 1;
     for (int t2 = 0; t2 < ntraj; ++t2) nmax = sN[t2] > nmax ? sN[t2] : nmax;
     if (act) n = sN[tl];
@@ -547,7 +542,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TPR_PS_
         }
     }
     __syncthreads();
-    if (TPR_PS_EXPERIMENT && (A.debug & 2)) return;
 
     // (3) back substitution, a tile of T segments at a time from the top; the tile's coefficient rows
     // (CubicHermiteSpline's formulas) are computed lane-parallel over (trajectory, segment, dof) in the table's own
@@ -630,7 +624,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TPR_PS_
                 const double t = (si + sn - 2 * sl) / dxi;
                 c0 = t / dxi; c1 = (sl - si) / dxi - t; c2 = si; c3 = y0;
             }
-            if (TPR_PS_EXPERIMENT && (A.debug & 4) && c0 != 1.2345) continue;
             double *o = A.coef_t + (size_t)(b0 + t2) * 4 * cs + (size_t)i0 * d + item;
             o[0] = c0; o[cs] = c1; o[2 * cs] = c2; o[3 * cs] = c3;
         }
@@ -709,7 +702,7 @@ struct ParamSampleArgs {
 };
 
 template <int D, int KPT, bool SAMPLE = false>
-__global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A, double *__restrict__ coef_t, int debug,
+__global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A, double *__restrict__ coef_t,
                                                                ParamSampleArgs Q = ParamSampleArgs{}) {
     extern __shared__ double pcr_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -824,7 +817,6 @@ __global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A
         }
         if (tid == 0 && A.counts) A.counts[b] = n;
     }
-    if (TPR_PS_EXPERIMENT && (debug & 1)) return;
     if (!SAMPLE || A.tk) for (int i = tid; i <= N; i += 256) A.tk[b * NS + i] = tkS[i];
 
     // (2) the rows of the clamped system, normalised to a unit diagonal: (a, c, r_1..r_d) of knot i.  Chord slopes are formed
@@ -871,7 +863,6 @@ __global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A
         }
         __syncthreads();
     }
-    if (TPR_PS_EXPERIMENT && (debug & 2)) return;
 
     // (3) the solve.  row i <- row i combined with rows i - s and i + s so that it couples i - 2s and i + 2s instead:
     auto reduce_row = [&](int i, int s, double &a2, double &c2, double (&r2)[D]) {
@@ -936,7 +927,6 @@ __global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A
         }
         __syncthreads();
     }
-    if (TPR_PS_EXPERIMENT && (debug & 4)) return;
 
     // (4) coefficient rows (CubicHermiteSpline's formulas) lane-parallel over (segment, dof), in the table's own order.
     // The waypoints return to LDS (the rows' a, c and the knot times are dead: the steps come from the knot times this block
@@ -1001,7 +991,6 @@ __global__ void __launch_bounds__(256) param_spline_pcr_kernel(ParamSplineArgs A
             const double t = (si + sn - 2 * sl) * rd;
             c0 = t * rd; c1 = (sl - si) * rd - t; c2 = si; c3 = y0;
         }
-        if (TPR_PS_EXPERIMENT && (debug & 8) && c0 != 1.2345) continue;
         o[idx] = c0; o[cs + idx] = c1; o[2 * cs + idx] = c2; o[3 * cs + idx] = c3;
     }
 }

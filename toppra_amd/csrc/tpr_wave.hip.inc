@@ -637,18 +637,6 @@ __host__ __device__ inline size_t wave_lds_doubles(int N, int nseg, int d, bool 
     return (size_t)kWaveRec * (N + 1) + 2 * d + (size_t)(2 * (N + 1) + 3) / 4 + (table_in_lds ? (size_t)3 * nseg * d + (nseg + 1) : 0);
 }
 
-#ifdef TPR_WAVE_STATS  // development builds: full iterations / proposals per trajectory returned in `status`
-#define TPR_WSTAT(expr) expr
-#else
-#define TPR_WSTAT(expr)
-#endif
-#ifdef TPR_WAVE_TIMING  // development builds: cycles per phase, dumped into u[b][0..15] (tools/gpu_wave_phases.py)
-#define TPR_WT0() unsigned long long wt_prev = __builtin_readcyclecounter(), wt_acc[16] = {0}
-#define TPR_WTICK(k) { const unsigned long long wt_now = __builtin_readcyclecounter(); wt_acc[k] += wt_now - wt_prev; wt_prev = wt_now; }
-#else
-#define TPR_WT0()
-#define TPR_WTICK(k)
-#endif
 
 // SPLIT (round 6): TWO waves per trajectory for a handful of trajectories (BASELINE config 1) -- the two LPs of a backward stage
 // (reachability_algorithm.py:229-236) depend only on K[i+1], so wave 0 answers the upper-bound LP and wave 1 the lower-bound LP
@@ -692,7 +680,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
     const double sd_end = A.sd_end ? A.sd_end[bb] : 0.0;
     const double sd_end_hi = A.sd_end_hi ? A.sd_end_hi[bb] : sd_end;
     __syncthreads();
-    TPR_WT0();
 
     // ---- prologue: everything that does not depend on the scans, one gridpoint per lane -----------------
     double dmax = 0.0;
@@ -759,7 +746,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
         nchg += __builtin_popcountll(m);
     }
     __syncthreads();
-    TPR_WTICK(11);
 
     // ---- per-lane row constants --------------------------------------------------------------------------
     // Every row is produced by ONE formula, whatever its kind (no selects on the row type):
@@ -859,7 +845,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
     };
 
     const bool use_cert = !(A.flags & TPR_STRICT_SEIDEL);
-    TPR_WSTAT(int n_full = 0; int n_prop = 0;)
 
     // warm-start state of the reference's wrapper object (active_c_up / active_c_down, reference row ids): zeros for a
     // fresh object, or what an earlier pass on the same object left behind (tpr_problem.active)
@@ -958,7 +943,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
             if (ca == i - 1) ca = chg_at(--ka);
             if (cb == i) cb = chg_at(--kb);
         }
-        TPR_WTICK(7);
         // One straight-line block per stage whether or not the scan is still live (a dead scan computes and discards):
         // the next stage's rows, and both LPs of this one from their warm certificates -- two independent chains of
         // fetches, divisions and ballots that fill each other's latencies: the previous stage's active pair (upper
@@ -981,27 +965,21 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
         // which is left to the iteration (cy_seidel_solverwrapper.pyx:253-264; as families 2 and 3 do: ADVICE r4).
         const bool lcold = !(up0 >= 0 && up0 < nC && up1 >= 0 && up1 < nC && up0 != up1);
         if (do_l) got_l = wave_cert_lower<S>(R, G, wr, lvalid & lcold, kVarMin, kVarMax, sl);
-        TPR_WTICK(1);
         if (live && !(got_u && got_l)) {  // rare: a certificate did not hold
             if (!got_u) {
                 // A moved active pair runs the reference's iteration: conditions (A)-(C) bound its LAST pivot only, and
                 // on the way to a moved pair the reference passes through intermediate optima whose 1-D problems they say
                 // nothing about (tpr_cert.hip.inc, cert_propose2).  A full iteration costs this kernel about what a
                 // proposal and a second certificate did.
-                TPR_WSTAT(n_full += 1;)
                 su = wave_lp2d<S>(R, nC, lane, -1e-9, 1.0, kVarMin, kVarMax, low1, high1, dn0, dn1);
-                TPR_WTICK(3);
             }
             if (!got_l) {
                 if (use_cert) {
                     const int r1 = wave_lower_search<S>(R, G);
                     if (lcold && r1 >= 0 && !(lvalid && r1 == wr)) got_l = wave_cert_lower<S>(R, G, r1, true, kVarMin, kVarMax, sl);
-                    TPR_WTICK(5);
                 }
                 if (!got_l) {
-                    TPR_WSTAT(n_full += 1 << 12;)
                     sl = wave_lp2d<S>(R, nC, lane, 1e-9, -1.0, kVarMin, kVarMax, low1, high1, up0, up1);
-                    TPR_WTICK(6);
                 }
             }
         }
@@ -1039,7 +1017,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
     }
     const bool failed = !live;
     __syncthreads();  // K rows written by lane 0 are read by the whole wave below
-    TPR_WTICK(7);
 
     // the controllable sets leave for HBM only when the caller wants them (SPLIT: wave 1's last job, with its half of the
     // warm-start state; the rest is wave 0's)
@@ -1094,7 +1071,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
             if (ca == i) ca = chg_at(++fa);
             if (cb == i + 1) cb = chg_at(++fb);
         }
-        TPR_WTICK(10);
         WaveRows<S> Rp;
         bool norms_ok_p;
         rows_c(R, k0, k1, 0.0, 0.0);  // (the x box rows have a = 0: no part in the 1-D LP)
@@ -1113,7 +1089,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
             ok = !wave_any(isnan(x)) && ok;
         }
         if (ok && want_state) dn0 = act1d;  // the 1-D path's write into active_c_down (cy_seidel_solverwrapper.pyx:646-649)
-        TPR_WTICK(9);
         if (!ok) {
             nan_from = i + 1; zero_from = i;
             any_nan = true;
@@ -1144,13 +1119,6 @@ __global__ void __launch_bounds__(SPLIT ? 128 : 64) wave_solve_kernel(BatchArgs 
     for (int e = lane; e < N; e += 64) if (us) us[e] = e >= zero_from ? 0.0 : P[kWaveRec * e + 2];
     if (lane == 0 && A.status) A.status[bb] = any_nan ? TPR_STATUS_ERR_UNKNOWN : TPR_STATUS_OK;
     put_state();
-#ifdef TPR_WAVE_STATS
-    if (lane == 0 && A.status) A.status[bb] = n_full | (n_prop << 24);
-#endif
-#ifdef TPR_WAVE_TIMING
-    TPR_WTICK(12);
-    if (lane == 0 && us && N >= 16) for (int k = 0; k < 16; ++k) us[k] = (double)wt_acc[k];
-#endif
 }
 
 }  // namespace tpr
