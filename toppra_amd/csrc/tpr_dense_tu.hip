@@ -1,6 +1,6 @@
 // tpr_dense_tu.hip -- translation unit of the dense-row kernels (tpr_dense.hip.inc): the reference's seidelWrapper contract
-// for ANY canonical-linear constraint set.  build.py compiles it in parallel with the other units; instrumented
-// single-unit builds include it from tpr_kernels.hip.  One entry point, declared in tpr_kernels.hip.
+// for ANY canonical-linear constraint set.  build.py compiles it in parallel with the other units.  One entry point,
+// declared in tpr_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "../../include/toppra_hip.h"
@@ -13,8 +13,7 @@ namespace {
 template <int D, int L>
 int dense_launch(const tpr::DenseArgs &A, int feasible /* 0 solve, 1 feasible sets, 2 TOPPRAsd forward scans */, hipStream_t stream) {
     using C = tpr::GroupCfg<D, L>;
-    int threads = 256;
-    while (threads > 64 && (long long)A.B * L / threads < 4 * 256) threads /= 2;  // small batches: more, smaller blocks
+    const int threads = tpr::shrink_block_to_batch(256, A.B, L);  // small batches: more, smaller blocks
     const int groups = threads / L;
     const size_t lds = (size_t)groups * C::kRowBuf * sizeof(double);
     const dim3 grid((A.B + groups - 1) / groups), block(threads);

@@ -37,6 +37,7 @@
 #endif
 
 #pragma once
+#include <type_traits>
 namespace tpr {
 
 #define TPR_WALK_FAIL(code) return false
@@ -102,6 +103,57 @@ struct GroupCfg {
         return kRowBuf + (table_in_lds ? 3 * nseg * D + (nseg + 1) : 0);
     }
 };
+
+// ---- host side: launch geometry and dof dispatch, shared by every unit that launches these kernels -----------------
+constexpr size_t kMaxDynamicLds = 64 * 1024;
+
+// Block size for B trajectories on L lanes each: `threads`, halved while the batch would leave CUs idle (256 CUs; small
+// batches such as BASELINE config 2's 4096 trajectories only make 128 blocks of 256 threads).
+static inline int shrink_block_to_batch(int threads, int B, int L) {
+    while (threads > 64 && (long long)B * L / threads < 4 * 256) threads /= 2;
+    return threads;
+}
+
+// Launch geometry of a rows-across-lanes kernel.  The spline table is staged in LDS when a 64-thread block's worth fits
+// in 64 KB (always for ordinary waypoint counts); otherwise it stays in global memory.  Block size: the largest of
+// 256 / 128 / 64 threads that fits, then shrink_block_to_batch.
+struct GroupLaunch {
+    int threads;
+    unsigned blocks;
+    size_t lds;
+    bool table_in_lds;
+};
+template <int D, int L>
+static GroupLaunch group_launch_geometry(int B, int nseg) {
+    auto lds_bytes = [&](int threads, bool table) {
+        return (size_t)(threads / L) * GroupCfg<D, L>::lds_doubles(nseg, table) * sizeof(double);
+    };
+    GroupLaunch g{64, 0, 0, lds_bytes(64, true) <= kMaxDynamicLds};
+    for (int t = 256; t > 64; t /= 2)
+        if (lds_bytes(t, g.table_in_lds) <= kMaxDynamicLds) { g.threads = t; break; }
+    g.threads = shrink_block_to_batch(g.threads, B, L);
+    const int groups = g.threads / L;
+    g.blocks = (B + groups - 1) / groups;
+    g.lds = lds_bytes(g.threads, g.table_in_lds);
+    return g;
+}
+
+// Runtime dof -> the compile-time <D, L> of these kernels: 8 lanes per trajectory up to 8 dof, 16 above.  Calls
+// f(integral_constant<int, D>, integral_constant<int, L>) and returns its result; `none` for a dof outside LO..HI
+// (a unit that holds only part of the range instantiates only that part).
+template <int LO = 1, int HI = TPR_MAX_DOF_FAST, class F>
+static int for_dof(int d, int none, F &&f) {
+    switch (d) {
+#define TPR_DOF_CASE(DD)                                                                                              \
+    case DD:                                                                                                          \
+        if constexpr (DD >= LO && DD <= HI) return f(std::integral_constant<int, DD>{}, std::integral_constant<int, (DD <= 8 ? 8 : 16)>{}); \
+        break;
+        TPR_DOF_CASE(1) TPR_DOF_CASE(2) TPR_DOF_CASE(3) TPR_DOF_CASE(4) TPR_DOF_CASE(5) TPR_DOF_CASE(6) TPR_DOF_CASE(7) TPR_DOF_CASE(8)
+        TPR_DOF_CASE(9) TPR_DOF_CASE(10) TPR_DOF_CASE(11) TPR_DOF_CASE(12) TPR_DOF_CASE(13) TPR_DOF_CASE(14) TPR_DOF_CASE(15) TPR_DOF_CASE(16)
+#undef TPR_DOF_CASE
+    }
+    return none;
+}
 
 // Per-lane register state of the LP rows.
 template <int D, int L>
