@@ -257,7 +257,8 @@ def feasible_sets_batch(coef, breaks, grid, vlim, alim, interpolation=True, acti
     """compute_feasible_sets for B trajectories -> X[B,N+1,2] (``active``: see solve_batch).
 
     ``variant``: 0 = auto (one trajectory per wave for a handful of trajectories or with ``active``; the certified lane
-    kernel from 8192 trajectories up to 8 dof; rows across lanes otherwise), 2 / 3 / 4 force a kernel family.
+    kernel from 8192 trajectories up to 8 dof, 14336 .. 36864 at 9 .. 15 dof; rows across lanes otherwise), 2 / 3 / 4 force a
+    kernel family.
     ``strict`` (TPR_STRICT_SEIDEL): the reference's full iteration for every LP; ``sound``: see solve_batch."""
     _prepare(coef)
     p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation, active=active, variant=variant,

@@ -38,11 +38,9 @@ namespace tpr {
 
 // From which dof on the certified lane kernels re-read the velocity limits / the spline segment's coefficients from global
 // memory instead of holding them in registers (cert_solve_kernel; measured per dof, DESIGN.md section 3.2).
+// (TPR_LEAN_COEF_FROM: tpr_group.hip.inc, beside cert_tws_fields, which sizes the workspace by it.)
 #ifndef TPR_LEAN_VEL_FROM
 #define TPR_LEAN_VEL_FROM 10
-#endif
-#ifndef TPR_LEAN_COEF_FROM
-#define TPR_LEAN_COEF_FROM 11
 #endif
 
 // The LPs the lane-level certificates could not answer, handed to family 2's code: up to 8 of them
@@ -298,10 +296,12 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         const double *vl = has_vel ? A.vlim + (size_t)bb * 2 * D : nullptr;
 #pragma unroll
         for (int j = 0; j < 2 * D; ++j) w[(2 * D + j) * BS] = has_vel ? vl[j] : 0.0;
-        if (nseg <= kTwsMaxSeg) {
-            for (int e = 0; e < 3 * nseg * D; ++e) w[(size_t)(4 * D + e) * BS] = gcf[e];
-            cbase = w + (size_t)4 * D * BS;
-            cstride = BS;
+        if constexpr (D >= TPR_LEAN_COEF_FROM) {  // (below, the coefficients live in registers: nothing would read a copy)
+            if (nseg <= kTwsMaxSeg) {
+                for (int e = 0; e < 3 * nseg * D; ++e) w[(size_t)(4 * D + e) * BS] = gcf[e];
+                cbase = w + (size_t)4 * D * BS;
+                cstride = BS;
+            }
         }
         tw = w; tw_blk = wb;
         TPR_WAVE_SYNC();  // (the cooperative batches read other lanes' columns)
@@ -927,10 +927,12 @@ __global__ void __launch_bounds__(BS) cert_feasible_kernel(GroupArgs A, double *
         const double *vl = has_vel ? A.vlim + (size_t)bb * 2 * D : nullptr;
 #pragma unroll
         for (int j = 0; j < 2 * D; ++j) w[(2 * D + j) * BS] = has_vel ? vl[j] : 0.0;
-        if (nseg <= kTwsMaxSeg) {
-            for (int e = 0; e < 3 * nseg * D; ++e) w[(size_t)(4 * D + e) * BS] = gcf[e];
-            cbase = w + (size_t)4 * D * BS;
-            cstride = BS;
+        if constexpr (D >= TPR_LEAN_COEF_FROM) {  // (below, the coefficients live in registers: nothing would read a copy)
+            if (nseg <= kTwsMaxSeg) {
+                for (int e = 0; e < 3 * nseg * D; ++e) w[(size_t)(4 * D + e) * BS] = gcf[e];
+                cbase = w + (size_t)4 * D * BS;
+                cstride = BS;
+            }
         }
         tw = w; tw_blk = wb;
         TPR_WAVE_SYNC();  // (the cooperative batches read other lanes' columns)

@@ -715,9 +715,17 @@ struct GroupArgs {
     // reference's order (desired_duration_algorithm.py:11-18) -- sd_finish_kernel then starts from them instead of two passes
     double *sd_dur = nullptr;
 };
-// fields of the transposed workspace per lane: alim [2 d], vlim [2 d], then c0, c1, c2 [nseg][d] when the table is short enough
+// From which dof on the certified lane kernels re-read the spline segment's coefficients per stage instead of holding them in
+// registers (tpr_cert.hip.inc: kLeanCoef).
+#ifndef TPR_LEAN_COEF_FROM
+#define TPR_LEAN_COEF_FROM 11
+#endif
+// fields of the transposed workspace per lane: alim [2 d], vlim [2 d], then -- where the kernel re-reads them -- c0, c1, c2 [nseg][d]
+// when the table is short enough
 constexpr int kTwsMaxSeg = 16;
-__host__ __device__ inline size_t cert_tws_fields(int d, int nseg) { return (size_t)4 * d + (nseg <= kTwsMaxSeg ? (size_t)3 * nseg * d : 0); }
+__host__ __device__ inline size_t cert_tws_fields(int d, int nseg) {
+    return (size_t)4 * d + (d >= TPR_LEAN_COEF_FROM && nseg <= kTwsMaxSeg ? (size_t)3 * nseg * d : 0);
+}
 
 // A gridpoint located on the spline: segment index and local parameter.
 struct GridPt {
