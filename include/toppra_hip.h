@@ -235,6 +235,52 @@ int tpr_reachable_sets_dense_batch(const tpr_dense_problem *p, const double *sdm
 int tpr_constraint_params_batch(const tpr_problem *p, double *a, double *b, double *c, double *low,
                                 double *high, double *xbound, double *qs, double *qss, void *stream);
 
+/* ---- dense rows of second-order / torque constraints, built on the GPU --------------------------------------
+ * Replaces SplineInterpolator.__call__(gridpoints, order) for order 0, 1, 2 (interpolator.py:423-430), the path samples
+ * SecondOrderConstraint / JointTorqueConstraint hand to the user's inverse dynamics (linear_second_order.py:146-152,
+ * joint_torque.py): q, qs, qss [B][N+1][d] (any may be NULL).  q is scipy PPoly's evaluation of the cubic, qs and qss those of
+ * the differentiated coefficient tables (cspl.derivative()): the bits of tpr_constraint_params_batch's qs, qss.  Uses
+ * coef / breaks / grid and the flags TPR_DEVICE_PTRS, TPR_BREAKS_PER_TRAJ, TPR_GRID_PER_TRAJ of p.                     */
+int tpr_path_eval_batch(const tpr_problem *p, double *q, double *qs, double *qss, void *stream);
+
+/* tpr_second_order_block.flags */
+#define TPR_SO_INTERPOLATION 1 /* DiscretizationType.Interpolation for this block, else Collocation                */
+#define TPR_SO_F_SHARED 2      /* F [m][p], one for the batch; no F bit = the signed identity [I; -I] (F NULL, m = 2 p) */
+#define TPR_SO_F_PER_TRAJ 4    /* F [B][m][p]                                                                       */
+#define TPR_SO_F_PER_POINT 8   /* F [B][N+1][m][p]                                                                  */
+#define TPR_SO_G_PER_TRAJ 16   /* g [B][m]; no g bit = g [m], one for the batch                                     */
+#define TPR_SO_G_PER_POINT 32  /* g [B][N+1][m]                                                                     */
+#define TPR_SO_MAX_BLOCKS 8
+
+/* One second-order constraint F w <= g on w = tau(q, qd, qdd) (linear_second_order.py:11-173; JointTorqueConstraint,
+ * joint_torque.py:10-116, is the signed identity with g = [tau_max; -tau_min]) as the three inverse-dynamics evaluations
+ * that the reference's substitution needs (linear_second_order.py:154-162): w0 = tau(q, 0, 0), wa = tau(q, 0, q'),
+ * wb = tau(q, q', q''), each [B][N+1][p].  friction [B][p] (NULL = none; needs p == d): dry friction, friction * sign(q')
+ * is added to c.  Pointers follow TPR_DEVICE_PTRS of the problem they are passed with.                              */
+typedef struct tpr_second_order_block {
+    int32_t p, m, flags, reserved;
+    const double *w0, *wa, *wb;
+    const double *F, *g;
+    const double *friction;
+} tpr_second_order_block;
+/* ABI guard, as tpr_abi_sizes: bytes of tpr_second_order_block in the library; a binding compares it with its own
+ * declaration before its first call of tpr_second_order_rows_batch.                                          */
+int tpr_second_order_block_bytes(void);
+
+/* Replaces, for B trajectories, SecondOrderConstraint / JointTorqueConstraint.compute_constraint_params
+ * (linear_second_order.py:142-173, joint_torque.py), canonical_to_interpolate (linear_constraint.py:84-192) and the dense
+ * row build of seidelWrapper.__init__ (cy_seidel_solverwrapper.pyx:455-520) for the constraint list
+ * [velocity (p->vlim), acceleration (p->alim, TPR_ACC_INTERPOLATION), blocks[0], ..., blocks[nblocks-1]]: it writes the
+ * complete tpr_dense_problem -- a, b, c [B][N+1][nC] (rows 0, 1 zero, the acceleration block of
+ * tpr_constraint_params_batch, then F a, F b, F c - g of each block: m rows under Collocation, 2 m under Interpolation,
+ * where stage i holds [a_i | a_{i+1} + (2 delta_i) b_{i+1}] against blkdiag(F_i, F_{i+1}) and the last stage repeats
+ * itself), low, high [B][N+1][2] (the +-1e8 box with the velocity constraint's x bound: the values of
+ * tpr_constraint_params_batch) and deltas [B][N] (may be NULL).  a = wa - w0, b = wb - w0, c = w0 + friction sign(q'); every
+ * operation rounded on its own; a dense F row is summed in index order k = 0 .. p-1, then g is subtracted.
+ * nC = 2 + acceleration rows + block rows <= 122; 0 <= nblocks <= TPR_SO_MAX_BLOCKS.                                   */
+int tpr_second_order_rows_batch(const tpr_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a,
+                                double *b, double *c, double *low, double *high, double *deltas, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -54,6 +54,18 @@ class tpr_dense_problem(C.Structure):
                 ("sd_start", C.c_void_p), ("sd_end", C.c_void_p), ("active", C.c_void_p)]
 
 
+class tpr_second_order_block(C.Structure):
+    _fields_ = [("p", C.c_int32), ("m", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("w0", C.c_void_p), ("wa", C.c_void_p), ("wb", C.c_void_p),
+                ("F", C.c_void_p), ("g", C.c_void_p), ("friction", C.c_void_p)]
+
+
+# tpr_second_order_block.flags
+SO_INTERPOLATION, SO_F_SHARED, SO_F_PER_TRAJ, SO_F_PER_POINT, SO_G_PER_TRAJ, SO_G_PER_POINT = 1, 2, 4, 8, 16, 32
+SO_MAX_BLOCKS = 8
+MAX_DENSE_ROWS = 122  # rows per stage of the dense-row kernels, the two x_next rows included
+
+
 EXPORTS = (
     "tpr_init", "tpr_device_count", "tpr_last_error", "tpr_version", "tpr_abi_sizes", "tpr_solve_batch",
     "tpr_controllable_sets_batch", "tpr_feasible_sets_batch", "tpr_constraint_params_batch",
@@ -62,6 +74,7 @@ EXPORTS = (
     "tpr_solve_desired_duration_batch", "tpr_robust_solve_batch", "tpr_param_spline_batch", "tpr_ppoly_eval_batch",
     "tpr_reachable_sets_batch", "tpr_solve_dense_batch", "tpr_controllable_sets_dense_batch", "tpr_feasible_sets_dense_batch",
     "tpr_solve_desired_duration_dense_batch", "tpr_reachable_sets_dense_batch", "tpr_param_spline_sample_batch",
+    "tpr_path_eval_batch", "tpr_second_order_rows_batch", "tpr_second_order_block_bytes",
 )
 
 _lib = None
@@ -151,6 +164,15 @@ def load():
         L.tpr_controllable_sets_dense_batch.argtypes = [DP, V, V, V, V]
         L.tpr_feasible_sets_dense_batch.restype = C.c_int
         L.tpr_feasible_sets_dense_batch.argtypes = [DP, V, V]
+        L.tpr_second_order_block_bytes.restype = C.c_int
+        L.tpr_second_order_block_bytes.argtypes = []
+        if L.tpr_second_order_block_bytes() != C.sizeof(tpr_second_order_block):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_second_order_block takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_second_order_block_bytes(), C.sizeof(tpr_second_order_block)))
+        L.tpr_path_eval_batch.restype = C.c_int
+        L.tpr_path_eval_batch.argtypes = [P, V, V, V, V]
+        L.tpr_second_order_rows_batch.restype = C.c_int
+        L.tpr_second_order_rows_batch.argtypes = [P, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

@@ -12,6 +12,7 @@ import time
 
 import numpy as np
 
+from . import _capi
 from . import batch as _batch
 from . import exceptions
 from . import interpolator as _interp
@@ -239,11 +240,76 @@ class BatchTOPPRA(object):
         (``batch.spline_coefficients`` builds them from waypoints), numpy or torch-ROCm tensors.
     gridpoints : [N+1] shared or [B, N+1] per trajectory.
     vlim, alim : [B, d, 2] joint velocity / acceleration limits (either may be None).
+    constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
+        ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback.  Their rows are built on the GPU
+        once per object and every pass runs on the dense-row entries; without them nothing changes.
     """
 
-    def __init__(self, coef, breaks, gridpoints, vlim, alim, interpolation=True):
+    def __init__(self, coef, breaks, gridpoints, vlim, alim, interpolation=True, constraints=None):
         self.coef, self.breaks, self.gridpoints = coef, breaks, gridpoints
         self.vlim, self.alim, self.interpolation = vlim, alim, interpolation
+        self.constraints = list(constraints) if constraints else []
+        self._rows = self._rows_dev = None
+        if self.constraints:
+            self._check_constraints()
+
+    # -- constraint lists beyond velocity + acceleration limits ------------------------------------------------------
+    # ``constraints``: BatchJointTorqueConstraint / BatchSecondOrderConstraint objects (toppra_amd.constraint), after the
+    # velocity and acceleration limits in the reference's list order.  Their dense rows are built ONCE per object, on first
+    # use (the reference builds them in the wrapper's constructor), by tpr_second_order_rows_batch from the path at the
+    # gridpoints and three batched inverse-dynamics calls per constraint, and stay on the device (for numpy inputs: a device
+    # copy beside the host arrays that dense_rows() returns); every
+    # pass then runs on the dense-row entries (tpr_*_dense_batch: the reference's full Seidel iteration), each from a fresh
+    # warm-start state like a fresh reference object.
+    def _check_constraints(self):
+        """Everything that can be refused from shapes alone, before any launch."""
+        if getattr(self.coef, "ndim", 0) != 4:
+            raise ValueError("coef must have shape [B, 4, nseg, d]")
+        B, d, N = int(self.coef.shape[0]), int(self.coef.shape[3]), int(self.gridpoints.shape[-1]) - 1
+        if len(self.constraints) > _capi.SO_MAX_BLOCKS:
+            raise NotImplementedError("%d second-order constraints in one list: the row kernel takes %d"
+                                      % (len(self.constraints), _capi.SO_MAX_BLOCKS))
+        nC = 2 + ((4 if self.interpolation else 2) * d if self.alim is not None else 0)
+        for con in self.constraints:
+            if not (hasattr(con, "block") and hasattr(con, "rows_per_stage")):
+                raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint and BatchSecondOrderConstraint "
+                                          "are supported)" % type(con).__name__)
+            con.check(B, N, d)
+            nC += con.rows_per_stage(d) or 0
+        if nC > _capi.MAX_DENSE_ROWS:
+            raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
+                                      % (nC, _capi.MAX_DENSE_ROWS))
+
+    def dense_rows(self):
+        """(a, b, c, low, high, deltas) of the constraint list, as arrays of the kind the problem was given in: the arguments
+        of the ``batch.*_dense_batch`` calls.  Built on first use.  A constraint whose F and g are both callables has no
+        row count before its callbacks have run: for such a list the 122-row limit is checked here, after the path
+        evaluation and the callbacks and before the row kernel is launched, not in the constructor."""
+        if self._rows is None:
+            pe = _batch.path_eval_batch(self.coef, self.breaks, self.gridpoints)
+            blocks = [con.block(pe["q"], pe["qs"], pe["qss"]) for con in self.constraints]
+            rows = _batch.second_order_rows_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, blocks,
+                                                  self.interpolation)
+            self._rows = tuple(rows[k] for k in ("a", "b", "c", "low", "high", "deltas"))
+            self._rows_dev = self._rows
+            if not _capi.is_torch_cuda(self.coef):
+                # numpy problem: the passes read a device copy made once (3 B (N+1) nC doubles would otherwise be uploaded by
+                # every pass); results come back as numpy arrays
+                import torch
+                dev = torch.device("cuda", _capi.init())
+                self._rows_dev = tuple(torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in self._rows)
+        return self._rows
+
+    def _dense_pass(self, fn, *args, **kw):
+        """One pass on the device-resident rows; outputs in the kind of the inputs."""
+        self.dense_rows()
+        out = fn(*self._rows_dev, *args, **kw)
+        if self._rows_dev is self._rows:
+            return out
+        host = lambda v: v.cpu().numpy()  # noqa: E731
+        if isinstance(out, dict):
+            return {k: host(v) for k, v in out.items()}
+        return tuple(host(v) for v in out) if isinstance(out, tuple) else host(out)
 
     @classmethod
     def from_waypoints(cls, knots, waypoints, gridpoints, vlim, alim, bc_type="not-a-knot", gpu_fit=True, **kw):
@@ -261,13 +327,18 @@ class BatchTOPPRA(object):
     def compute_parameterization(self, sd_start=None, sd_end=None, want_sd=True, variant=0, want_K=True, want_u=True):
         """dict(sd2, sd, u, K, status): per-trajectory results; status 0/1/2 = Ok /
         FailUncontrollable / ErrUnknown, failed rows NaN-filled.  ``want_K`` / ``want_u`` = False leave the
-        controllable sets / path accelerations in a device workspace (fewer bytes back to a host caller)."""
+        controllable sets / path accelerations in a device workspace (fewer bytes back to a host caller).
+        With ``constraints`` the dense-row entry serves the call (``variant`` does not apply; K and u are always returned)."""
+        if self.constraints:
+            return self._dense_pass(_batch.solve_dense_batch, sd_start, sd_end, want_sd=want_sd)
         return _batch.solve_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
                                   sd_start, sd_end, self.interpolation, want_sd=want_sd, variant=variant,
                                   want_K=want_K, want_u=want_u)
 
     def compute_parameterization_sd(self, desired_duration, sd_start=None, sd_end=None, atol=1e-5):
         """TOPPRAsd for the batch: dict(sd2, sd, u, K, status, alpha)."""
+        if self.constraints:
+            return self._dense_pass(_batch.solve_desired_duration_dense_batch, desired_duration, sd_start, sd_end, atol)
         return _batch.solve_desired_duration_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
                                                    desired_duration, sd_start, sd_end, atol)
 
@@ -301,15 +372,21 @@ class BatchTOPPRA(object):
         return out
 
     def compute_controllable_sets(self, sdmin, sdmax):
+        if self.constraints:
+            return self._dense_pass(_batch.controllable_sets_dense_batch, sdmin, sdmax)
         return _batch.controllable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
                                               self.alim, sdmin, sdmax, self.interpolation)
 
     def compute_feasible_sets(self):
+        if self.constraints:
+            return self._dense_pass(_batch.feasible_sets_dense_batch)
         return _batch.feasible_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
                                           self.alim, self.interpolation)
 
     def compute_reachable_sets(self, sdmin, sdmax):
         """L[B, N+1, 2] (reachability_algorithm.py:409-431 per trajectory)."""
+        if self.constraints:
+            return self._dense_pass(_batch.reachable_sets_dense_batch, sdmin, sdmax)
         return _batch.reachable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, sdmin, sdmax,
                                            self.interpolation)
 

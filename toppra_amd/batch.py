@@ -16,7 +16,8 @@ from . import _capi
 __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "reachable_sets_batch",
            "constraint_params_batch", "make_synthetic_batch", "spline_coefficients",
            "spline_fit_batch", "solve_batch_timed", "const_accel_times_batch", "const_accel_eval_batch",
-           "solve_desired_duration_batch", "robust_solve_batch", "param_spline_batch", "ppoly_eval_batch"]
+           "solve_desired_duration_batch", "robust_solve_batch", "param_spline_batch", "ppoly_eval_batch",
+           "path_eval_batch", "second_order_rows_batch"]
 
 
 def _stream_ptr(like):
@@ -282,6 +283,103 @@ def constraint_params_batch(coef, breaks, grid, vlim, alim, interpolation=True):
     _capi.check(_capi.load().tpr_constraint_params_batch(
         C.byref(p), *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "xbound", "qs", "qss")],
         _stream_ptr(coef)))
+    return out
+
+
+def path_eval_batch(coef, breaks, grid, orders=(0, 1, 2)):
+    """``SplineInterpolator.__call__(gridpoints, order)`` for B paths at their gridpoints: dict(q / qs / qss [B, N+1, d] for the
+    requested ``orders``) -- q in scipy PPoly's evaluation order, qs and qss from the differentiated coefficient tables, the
+    bits the reference hands to a constraint's inverse dynamics (linear_second_order.py:146-152)."""
+    _prepare(coef)
+    p, keep = _capi.make_problem(coef, breaks, grid, None, None)
+    names = {0: "q", 1: "qs", 2: "qss"}
+    out = {names[o]: _empty(coef, (p.B, p.N + 1, p.d)) for o in orders}
+    _capi.check(_capi.load().tpr_path_eval_batch(C.byref(p), _capi.ptr(out.get("q")), _capi.ptr(out.get("qs")),
+                                                 _capi.ptr(out.get("qss")), _stream_ptr(coef)))
+    return out
+
+
+def second_order_rows_per_stage(d, alim, interpolation, blocks):
+    """nC of the dense problem :func:`second_order_rows_batch` writes: the two x_next rows, the acceleration block, the blocks."""
+    nC = 2 + ((4 if interpolation else 2) * d if alim is not None else 0)
+    for blk in blocks:
+        m = 2 * int(blk["w0"].shape[-1]) if blk.get("F") is None else int(blk["F"].shape[-2])
+        nC += (2 if blk.get("interpolation", True) else 1) * m
+    return nC
+
+
+def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolation=True):
+    """The dense problem of the constraint list [velocity, acceleration, second-order blocks ...] for B trajectories, built on
+    the GPU: dict(a, b, c [B, N+1, nC], low, high [B, N+1, 2], deltas [B, N]) -- the arguments of :func:`solve_dense_batch` and
+    its siblings, the bits of ``seidelWrapper.__init__`` on the reference's ``SecondOrderConstraint`` /
+    ``JointTorqueConstraint`` objects (include/toppra_hip.h: tpr_second_order_rows_batch).
+
+    ``blocks``: one dict per second-order constraint, in list order, with
+      ``w0, wa, wb`` [B, N+1, p]: the inverse dynamics tau(q, 0, 0), tau(q, 0, q'), tau(q, q', q'') at the gridpoints
+      (:func:`path_eval_batch` gives q, q', q'');
+      ``F``: None (the signed identity [I; -I]: joint torque limits), [m, p], [B, m, p] or [B, N+1, m, p];
+      ``g``: [m], [B, m] or [B, N+1, m] (m = 2 p for the signed identity: [tau_max; -tau_min]);
+      ``friction``: None or [B, p] (dry friction, p == d);  ``interpolation``: the block's discretisation (default True).
+    ``interpolation`` is the acceleration constraint's.  All arrays numpy, or all torch tensors on coef's device.  Shapes are
+    checked, and more than 122 rows per stage refused (NotImplementedError), before anything is launched."""
+    dev = _capi.is_torch_cuda(coef)
+    if dev:
+        def conv(name, x):
+            if not (hasattr(x, "is_cuda") and x.is_cuda):
+                raise ValueError("%s must be a CUDA tensor like coef (mixing host and device arrays is not supported)" % name)
+            _capi.check_tensor(name, x, coef)
+            return x.contiguous()
+    else:
+        def conv(name, x):
+            return _capi.f64(x)
+    if coef.ndim != 4:
+        raise ValueError("coef must have shape [B, 4, nseg, d]")
+    B, d, N = int(coef.shape[0]), int(coef.shape[3]), int(grid.shape[-1]) - 1
+    blocks = list(blocks)
+    if len(blocks) > _capi.SO_MAX_BLOCKS:
+        raise NotImplementedError("%d second-order constraints in one list: the row kernel takes %d" % (len(blocks), _capi.SO_MAX_BLOCKS))
+    structs = (_capi.tpr_second_order_block * max(len(blocks), 1))()
+    keep, staged = [], []
+    for j, blk in enumerate(blocks):
+        w0, wa, wb = (conv("blocks[%d].%s" % (j, k), blk[k]) for k in ("w0", "wa", "wb"))
+        if w0.ndim != 3 or tuple(w0.shape[:2]) != (B, N + 1) or tuple(wa.shape) != tuple(w0.shape) or tuple(wb.shape) != tuple(w0.shape):
+            raise ValueError("blocks[%d]: w0, wa, wb must have shape [B, N+1, p] = [%d, %d, p], got %s, %s, %s"
+                             % (j, B, N + 1, tuple(w0.shape), tuple(wa.shape), tuple(wb.shape)))
+        pw = int(w0.shape[2])
+        flags = _capi.SO_INTERPOLATION if blk.get("interpolation", True) else 0
+        F = blk.get("F")
+        if F is None:
+            m = 2 * pw
+        else:
+            F = conv("blocks[%d].F" % j, F)
+            if F.ndim not in (2, 3, 4) or int(F.shape[-1]) != pw or tuple(F.shape[:-2]) != ((), (B,), (B, N + 1))[F.ndim - 2]:
+                raise ValueError("blocks[%d].F must have shape [m, p], [B, m, p] or [B, N+1, m, p] with p = %d, got %s" % (j, pw, tuple(F.shape)))
+            m = int(F.shape[-2])
+            flags |= (_capi.SO_F_SHARED, _capi.SO_F_PER_TRAJ, _capi.SO_F_PER_POINT)[F.ndim - 2]
+        g = conv("blocks[%d].g" % j, blk["g"])
+        if g.ndim not in (1, 2, 3) or int(g.shape[-1]) != m or tuple(g.shape[:-1]) != ((), (B,), (B, N + 1))[g.ndim - 1]:
+            raise ValueError("blocks[%d].g must have shape [m], [B, m] or [B, N+1, m] with m = %d, got %s" % (j, m, tuple(g.shape)))
+        flags |= (0, _capi.SO_G_PER_TRAJ, _capi.SO_G_PER_POINT)[g.ndim - 1]
+        fr = blk.get("friction")
+        if fr is not None:
+            fr = conv("blocks[%d].friction" % j, fr)
+            if tuple(fr.shape) != (B, pw) or pw != d:
+                raise ValueError("blocks[%d].friction must have shape [B, d] = [%d, %d] (and p == d), got %s" % (j, B, d, tuple(fr.shape)))
+        staged.append({"w0": w0, "F": F, "interpolation": bool(flags & _capi.SO_INTERPOLATION)})
+        keep += [w0, wa, wb, F, g, fr]
+        structs[j] = _capi.tpr_second_order_block(p=pw, m=m, flags=flags, w0=_capi.ptr(w0), wa=_capi.ptr(wa), wb=_capi.ptr(wb),
+                                                  F=_capi.ptr(F), g=_capi.ptr(g), friction=_capi.ptr(fr))
+    nC = second_order_rows_per_stage(d, alim, interpolation, staged)
+    if nC > _capi.MAX_DENSE_ROWS:
+        raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
+                                  % (nC, _capi.MAX_DENSE_ROWS))
+    _prepare(coef)
+    p, keep2 = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation)
+    out = {k: _empty(coef, (B, N + 1, nC)) for k in ("a", "b", "c")}
+    out.update({k: _empty(coef, (B, N + 1, 2)) for k in ("low", "high")})
+    out["deltas"] = _empty(coef, (B, N))
+    _capi.check(_capi.load().tpr_second_order_rows_batch(
+        C.byref(p), len(blocks), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas")], _stream_ptr(coef)))
     return out
 
 

@@ -9,6 +9,7 @@ from enum import Enum
 
 import numpy as np
 
+from . import _capi
 from . import batch as _batch
 from .interpolator import spline_tables
 
@@ -296,6 +297,202 @@ class JointTorqueConstraint(LinearConstraint):
         if self.discretization_type == DiscretizationType.Collocation:
             return a, b, c, F, g, None, None
         return colloc_to_interpolate(a, b, c, F, g, None, None, gridpoints, identical=True)
+
+
+# ---- batched second-order / torque constraints: rows built on the GPU (BatchTOPPRA(..., constraints=[...])) ----------------
+
+def _like(x, like):
+    """`x` as a float64 array of the kind of `like`: numpy, or a torch tensor on like's device."""
+    if _capi.is_torch_cuda(like):
+        import torch
+        return torch.as_tensor(x, dtype=torch.float64, device=like.device)
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=np.float64)
+
+
+def _zeros_like(x):
+    return np.zeros_like(x) if isinstance(x, np.ndarray) else x.new_zeros(tuple(x.shape))
+
+
+class _BatchSecondOrder(LinearConstraint):
+    """Shared part of the batched second-order constraints: the three batched inverse-dynamics evaluations of the
+    reference's substitution (linear_second_order.py:154-162) and the block description that
+    :func:`toppra_amd.batch.second_order_rows_batch` takes."""
+
+    def _evaluate(self, q, qs, qss):
+        """w0 = tau(q, 0, 0), wa = tau(q, 0, q'), wb = tau(q, q', q''): exactly three calls, each checked."""
+        zero = _zeros_like(q)
+        out = []
+        for what, args in (("(q, 0, 0)", (q, zero, zero)), ("(q, 0, q')", (q, zero, qs)), ("(q, q', q'')", (q, qs, qss))):
+            w = self.inv_dyn(*args)
+            if type(w) is not type(q) and not (isinstance(w, np.ndarray) and isinstance(q, np.ndarray)):
+                raise ValueError("inv_dyn%s must return %s like its arguments, got %s" % (what, type(q).__name__, type(w).__name__))
+            if w.ndim != 3 or tuple(w.shape[:2]) != tuple(q.shape[:2]) or (out and tuple(w.shape) != tuple(out[0].shape)):
+                raise ValueError("inv_dyn%s must return an array [B, N+1, p] = [%d, %d, p], got %s"
+                                 % (what, q.shape[0], q.shape[1], tuple(w.shape)))
+            out.append(w)
+        return out
+
+    def _interp(self):
+        return self.discretization_type == DiscretizationType.Interpolation
+
+    def rows_per_stage(self, d):
+        """Rows this constraint adds to a stage (None while they depend on a callback's output)."""
+        raise NotImplementedError
+
+    def check(self, B, N, d):
+        """Shape errors that can be told from the problem's sizes alone (ValueError), before any launch."""
+        raise NotImplementedError
+
+    def block(self, q, qs, qss):
+        raise NotImplementedError
+
+    def compute_constraint_params(self, path, gridpoints, *args, **kwargs):
+        raise NotImplementedError("%s serves BatchTOPPRA(..., constraints=[...]); the single-path classes take %s"
+                                  % (type(self).__name__, type(self).__name__.replace("Batch", "")))
+
+
+class BatchJointTorqueConstraint(_BatchSecondOrder):
+    """``JointTorqueConstraint`` (joint_torque.py:10-116) for a batch:  tau_lim[..., 0] <= inv_dyn(q, qd, qdd) + fs_coef *
+    sign(qd) <= tau_lim[..., 1].
+
+    ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, d] out -- numpy arrays when the problem was
+    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  ``tau_lim``:
+    [d, 2] or [B, d, 2]; ``fs_coef``: [d] or [B, d].  Defaults are the reference's (Collocation)."""
+
+    def __init__(self, inv_dyn, tau_lim, fs_coef, discretization_scheme=DiscretizationType.Collocation):
+        super(BatchJointTorqueConstraint, self).__init__()
+        self.inv_dyn = inv_dyn
+        self.tau_lim, self.fs_coef = tau_lim, fs_coef
+        shape = tuple(tau_lim.shape) if hasattr(tau_lim, "shape") else np.shape(tau_lim)
+        if len(shape) not in (2, 3) or shape[-1] != 2:
+            raise ValueError("tau_lim must have shape [d, 2] or [B, d, 2], got %s" % (shape,))
+        self.dof = int(shape[-2])
+        fshape = tuple(fs_coef.shape) if hasattr(fs_coef, "shape") else np.shape(fs_coef)
+        if len(fshape) not in (1, 2) or fshape[-1] != self.dof:
+            raise ValueError("fs_coef must have shape [d] or [B, d] with d = %d, got %s" % (self.dof, fshape))
+        self._tau_batch = shape[0] if len(shape) == 3 else None
+        self._fs_batch = fshape[0] if len(fshape) == 2 else None
+        self.set_discretization_type(discretization_scheme)
+        self.identical = True
+        self._format_string = "    Batched torque limit, %d dof\n" % self.dof
+
+    def rows_per_stage(self, d):
+        return (2 if self._interp() else 1) * 2 * self.dof
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: constraint dof ({:d}) not equal to path dof ({:d})".format(self.dof, d))
+        for name, n in (("tau_lim", self._tau_batch), ("fs_coef", self._fs_batch)):
+            if n is not None and n != B:
+                raise ValueError("%s is given per trajectory for %d trajectories, the problem has %d" % (name, n, B))
+
+    def block(self, q, qs, qss):
+        B, d = int(q.shape[0]), int(q.shape[2])
+        self.check(B, int(q.shape[1]) - 1, d)
+        w0, wa, wb = self._evaluate(q, qs, qss)
+        if int(w0.shape[2]) != d:
+            raise ValueError("inv_dyn must return joint torques [B, N+1, d] = [%d, %d, %d], got %s" % (B, q.shape[1], d, tuple(w0.shape)))
+        lim, fs = _like(self.tau_lim, q), _like(self.fs_coef, q)
+        cat = np.concatenate if isinstance(lim, np.ndarray) else __import__("torch").cat
+        g = cat((lim[..., 1], -lim[..., 0]), -1)  # [tau_max; -tau_min]
+        if fs.ndim == 1:
+            fs = np.broadcast_to(fs, (B, d)) if isinstance(fs, np.ndarray) else fs.expand(B, d)
+        return {"w0": w0, "wa": wa, "wb": wb, "F": None, "g": g, "friction": fs, "interpolation": self._interp()}
+
+
+class BatchSecondOrderConstraint(_BatchSecondOrder):
+    """``SecondOrderConstraint`` (linear_second_order.py:11-173) for a batch:  F w <= g  on  w = inv_dyn(q, qd, qdd).
+
+    ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, p] out -- numpy arrays when the problem was
+    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  ``F``: [m, p],
+    [B, m, p], [B, N+1, m, p], a batched callable of q returning [B, N+1, m, p], or None for the signed identity [I; -I]
+    (what :meth:`joint_torque_constraint` builds: m = 2 p); ``g``: [m], [B, m], [B, N+1, m] or a batched callable of q.
+    ``friction``: dry friction [d] or [B, d], friction * sign(q') is added to c (the ``custom_term`` of the reference's
+    ``joint_torque_constraint``; needs p == d).  A general ``custom_term(path, s)`` beyond dry friction is out of scope: the
+    reference evaluates it through a Python callback per gridpoint.  A dense F row is summed in index order k = 0 .. p-1
+    (include/toppra_hip.h).  Defaults are the reference's (Interpolation)."""
+
+    def __init__(self, inv_dyn, F, g, friction=None, discretization_scheme=DiscretizationType.Interpolation):
+        super(BatchSecondOrderConstraint, self).__init__()
+        self.inv_dyn = inv_dyn
+        self.F, self.g, self.friction = F, g, friction
+        self.set_discretization_type(discretization_scheme)
+        if F is not None and not callable(F):
+            shape = tuple(F.shape) if hasattr(F, "shape") else np.shape(F)
+            if len(shape) not in (2, 3, 4):
+                raise ValueError("F must have shape [m, p], [B, m, p] or [B, N+1, m, p], got %s" % (shape,))
+        if not callable(g):
+            gshape = tuple(g.shape) if hasattr(g, "shape") else np.shape(g)
+            if len(gshape) not in (1, 2, 3):
+                raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (gshape,))
+            if F is not None and not callable(F) and gshape[-1] != shape[-2]:
+                raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], shape[-2]))
+        if friction is not None:
+            fshape = tuple(friction.shape) if hasattr(friction, "shape") else np.shape(friction)
+            if len(fshape) not in (1, 2):
+                raise ValueError("friction must have shape [d] or [B, d], got %s" % (fshape,))
+        self._format_string = "    Kind: Batched generalized second-order constraint\n"
+
+    @classmethod
+    def joint_torque_constraint(cls, inv_dyn, taulim, joint_friction, **kwargs):
+        """Joint torque bounds taulim [d, 2] or [B, d, 2] with dry friction joint_friction [d] or [B, d]
+        (linear_second_order.py:100-140): the signed identity with g = [tau_max; -tau_min]."""
+        shape = tuple(taulim.shape) if hasattr(taulim, "shape") else np.shape(taulim)
+        if len(shape) not in (2, 3) or shape[-1] != 2:
+            raise ValueError("taulim must have shape [d, 2] or [B, d, 2], got %s" % (shape,))
+        if hasattr(taulim, "detach"):
+            import torch
+            g = torch.cat((taulim[..., 1], -taulim[..., 0]), -1)
+        else:
+            taulim = np.asarray(taulim, dtype=np.float64)
+            g = np.concatenate((taulim[..., 1], -taulim[..., 0]), -1)
+        return cls(inv_dyn, None, g, friction=joint_friction, **kwargs)
+
+    def _shape(self, x):
+        return None if x is None or callable(x) else (tuple(x.shape) if hasattr(x, "shape") else np.shape(x))
+
+    def rows_per_stage(self, d):
+        F, g = self._shape(self.F), self._shape(self.g)
+        m = F[-2] if F is not None else (g[-1] if g is not None else None)
+        return None if m is None else (2 if self._interp() else 1) * int(m)
+
+    def check(self, B, N, d):
+        for name, shape, tail in (("F", self._shape(self.F), 2), ("g", self._shape(self.g), 1)):
+            if shape is not None and tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
+                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
+                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+        fr = self._shape(self.friction)
+        if fr is not None and (fr[-1] != d or (len(fr) == 2 and fr[0] != B)):
+            raise ValueError("friction must have shape [d] or [B, d] = [%d, %d], got %s" % (B, d, fr))
+
+    def block(self, q, qs, qss):
+        B, n1, d = (int(v) for v in q.shape)
+        self.check(B, n1 - 1, d)
+        w0, wa, wb = self._evaluate(q, qs, qss)
+        p = int(w0.shape[2])
+        F = self.F(q) if callable(self.F) else self.F
+        g = self.g(q) if callable(self.g) else self.g
+        F = None if F is None else _like(F, q)
+        g = _like(g, q)
+        if callable(self.F) and (F.ndim != 4 or tuple(F.shape[:2]) != (B, n1)):
+            raise ValueError("the F callback must return [B, N+1, m, p] = [%d, %d, m, %d], got %s" % (B, n1, p, tuple(F.shape)))
+        if callable(self.g) and (g.ndim != 3 or tuple(g.shape[:2]) != (B, n1)):
+            raise ValueError("the g callback must return [B, N+1, m] = [%d, %d, m], got %s" % (B, n1, tuple(g.shape)))
+        if F is not None and int(F.shape[-1]) != p:
+            raise ValueError("F has %d columns, inv_dyn returns p = %d" % (int(F.shape[-1]), p))
+        m = 2 * p if F is None else int(F.shape[-2])
+        if int(g.shape[-1]) != m:
+            raise ValueError("g has %d entries per gridpoint, F has %d rows" % (int(g.shape[-1]), m))
+        fr = self.friction
+        if fr is not None:
+            if p != d:
+                raise ValueError("dry friction needs inv_dyn to return joint torques (p == d = %d), got p = %d" % (d, p))
+            fr = _like(fr, q)
+            if fr.ndim == 1:
+                fr = np.broadcast_to(fr, (B, d)) if isinstance(fr, np.ndarray) else fr.expand(B, d)
+        return {"w0": w0, "wa": wa, "wb": wb, "F": F, "g": g, "friction": fr, "interpolation": self._interp()}
 
 
 class ConicConstraint(Constraint):

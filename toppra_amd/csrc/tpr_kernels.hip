@@ -1228,3 +1228,75 @@ int tpr_lp2d_batch(int n, int nrows, const double *v, const double *a, const dou
 }
 
 }  // extern "C"
+
+// ---- dense rows of second-order / torque constraints built on the GPU: tpr_rows.hip.inc (host side only here; the kernels
+// are a unit of their own, csrc/tpr_rows_tu.hip) -------------------------------------------------------------------------
+#include "tpr_rows_args.hpp"
+extern "C" {
+__attribute__((visibility("hidden"))) int tpr_tu_rows_launch(const tpr::RowsArgs *, double *, double *, double *, double *, double *,
+                                                             double *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_path_eval_launch(const tpr::PathEvalArgs *, hipStream_t);
+
+int tpr_second_order_block_bytes(void) { return (int)sizeof(tpr_second_order_block); }
+
+int tpr_path_eval_batch(const tpr_problem *p, double *q, double *qs, double *qss, void *stream_) {
+    if (int rc = check_problem(p)) return rc;
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->coef, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::PathEvalArgs A{};
+    A.B = p->B; A.d = p->d; A.nseg = p->nseg; A.N = p->N; A.flags = p->flags;
+    stage_path(p, S, A);
+    const size_t n = (size_t)p->B * (p->N + 1) * p->d;
+    A.q = S.out(q, n); A.qs = S.out(qs, n); A.qss = S.out(qss, n);
+    if (int rc = S.failed()) return rc;
+    if (n > 0 && tpr_tu_path_eval_launch(&A, S.stream) != 0) return fail(TPR_E_BADARG, "tpr_path_eval_batch: B (N + 1) d too large for one launch");
+    return S.finish();
+}
+
+int tpr_second_order_rows_batch(const tpr_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a, double *b,
+                                double *c, double *low, double *high, double *deltas, void *stream_) {
+    if (int rc = check_problem(p)) return rc;
+    if (nblocks < 0 || nblocks > TPR_SO_MAX_BLOCKS || (nblocks > 0 && !blocks))
+        return fail(TPR_E_BADARG, "tpr_second_order_rows_batch: 0 <= nblocks <= TPR_SO_MAX_BLOCKS");
+    if (!a || !b || !c || !low || !high) return fail(TPR_E_BADARG, "tpr_second_order_rows_batch: a, b, c, low, high are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->coef, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t B = (size_t)p->B, d = (size_t)p->d, pts = B * ((size_t)p->N + 1);
+    tpr::RowsArgs A{};
+    A.B = p->B; A.d = p->d; A.nseg = p->nseg; A.N = p->N; A.flags = p->flags;
+    stage_path(p, S, A);
+    A.vlim = S.in(p->vlim, B * d * 2);
+    A.alim = S.in(p->alim, B * d * 2);
+    A.nC = rows_per_lp(p);
+    A.nblocks = nblocks;
+    for (int j = 0; j < nblocks; ++j) {
+        const tpr_second_order_block &U = blocks[j];
+        tpr::RowsBlock &K = A.blk[j];
+        const int fkind = U.flags & (TPR_SO_F_SHARED | TPR_SO_F_PER_TRAJ | TPR_SO_F_PER_POINT);
+        const int gkind = U.flags & (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT);
+        if (U.p < 1 || !U.w0 || !U.wa || !U.wb || !U.g) return fail(TPR_E_BADARG, "second-order block: p >= 1 and w0, wa, wb, g are required");
+        if ((fkind & (fkind - 1)) || gkind == (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT)) return fail(TPR_E_BADARG, "second-order block: one F layout and one g layout");
+        if (fkind ? (!U.F || U.m < 1) : (U.F != nullptr)) return fail(TPR_E_BADARG, "second-order block: F [m][p] with an F flag, NULL for the signed identity");
+        if (U.friction && U.p != p->d) return fail(TPR_E_BADARG, "second-order block: dry friction needs p == d");
+        K.p = U.p; K.m = fkind ? U.m : 2 * U.p; K.flags = U.flags; K.col0 = A.nC; K.lds0 = A.wsum;
+        const size_t m = (size_t)K.m, w = (size_t)U.p;
+        if (m > 122) return fail(TPR_E_UNSUPPORTED, "second-order block: more than 122 rows per stage");
+        A.nC += ((U.flags & TPR_SO_INTERPOLATION) ? 2 : 1) * K.m;
+        A.wsum += 3 * U.p;
+        if (A.nC > 122 || A.wsum > 3 * 1024) return fail(TPR_E_UNSUPPORTED, "tpr_second_order_rows_batch: more than 122 rows per stage (incl. the two x_next rows), or blocks wider than 1024 in all");
+        K.w0 = S.in(U.w0, pts * w); K.wa = S.in(U.wa, pts * w); K.wb = S.in(U.wb, pts * w);
+        K.F = S.in(U.F, (fkind == TPR_SO_F_PER_POINT ? pts : fkind == TPR_SO_F_PER_TRAJ ? B : 1) * m * w);
+        K.g = S.in(U.g, (gkind == TPR_SO_G_PER_POINT ? pts : gkind == TPR_SO_G_PER_TRAJ ? B : 1) * m);
+        K.friction = S.in(U.friction, B * w);
+    }
+    const size_t nC = (size_t)A.nC;
+    double *da = S.out(a, pts * nC), *db = S.out(b, pts * nC), *dc = S.out(c, pts * nC);
+    double *dlow = S.out(low, pts * 2), *dhigh = S.out(high, pts * 2), *ddel = S.out(deltas, B * (size_t)p->N);
+    if (int rc = S.failed()) return rc;
+    if (pts > 0) {
+        const int rc = tpr_tu_rows_launch(&A, da, db, dc, dlow, dhigh, ddel, S.stream);
+        if (rc != 0) return fail(TPR_E_UNSUPPORTED, rc == -1 ? "tpr_second_order_rows_batch: one gridpoint's coefficients do not fit the LDS" : "tpr_second_order_rows_batch: more than 65535 tiles of gridpoints");
+    }
+    return S.finish();
+}
+}  // extern "C"
