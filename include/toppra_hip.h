@@ -15,6 +15,9 @@
  *   grid   [N+1]             path discretisation; [B][N+1] with TPR_GRID_PER_TRAJ
  *   vlim   [B][d][2]         JointVelocityConstraint.vlim      (linear_joint_velocity.py:19-28)
  *   alim   [B][d][2]         JointAccelerationConstraint.alim  (linear_joint_acceleration.py:46-52)
+ *                            Infinite and arbitrarily large or small limits are valid inputs; NaN limits are the caller's
+ *                            error (the reference rejects them); the velocity bound is computed in fp32 as the reference
+ *                            computes it, fp32 overflow and gradual underflow (subnormal squares, exact zeros) included.
  *   sd_start, sd_end [B]     boundary path velocities (NULL = 0)
  *
  * Buffers belong to the caller.  Pointers are host pointers unless TPR_DEVICE_PTRS is set, in

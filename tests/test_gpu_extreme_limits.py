@@ -1,0 +1,346 @@
+"""Limits at the edge of the number range on every kernel family: infinite, 1e38 / 1e300, subnormal-squared, one-sided and
+inverted limits, standing joints, shifted path parameters (tests/test_oracle_vs_reference.py::extreme_limit_problems -- the
+generator whose problems the real reference solved for tests/golden/oracle_vs_reference_extreme.npz, and to whose outputs the
+CPU oracle is pinned bit for bit there).
+
+The fp32 velocity bound exists in six restatements on the device (tpr_device.hpp, tpr_group / tpr_wave / tpr_pair / tpr_cert
+twice), four of them restructured around a running fp64 minimum, a wave-level ballot and a positive-lower-limit shortcut; the
+certificates of families 2 .. 5 meet rows with c = -inf or 1e300 here and refuse most stages, so that the fallback iteration runs
+in bulk; and family 3 holds 64 trajectories per wave, each kind next to ordinary ones.  Batches: trajectory b is of kind
+b % 13 (twelve kinds and the `plain` control), odd sizes 64 k + 37, breakpoints and grids per trajectory.
+
+Everything is bit for bit -- np.array_equal(..., equal_nan=True) on K, sd2, sd, u, status, and on the sets and rows -- against
+the oracle on EVERY trajectory of every batch; part e goes past the oracle to the reference's stored bits.  No NaN is ever fed
+in, and no tolerance appears anywhere in this module.
+"""
+import csv
+import functools
+import glob
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+from tests import test_oracle_vs_reference as T
+from toppra_amd import batch
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+B_SMALL = 64 * 3 + 37
+ACC_KINDS = ("ainf", "ainf_one", "ahuge", "inverted")
+# pick_variant (toppra_amd/csrc/tpr_kernels.hip): family 3 solves from 9216 trajectories up to 8 dof, computes feasible sets from
+# 8192, and family 5 serves 2560 .. 9215 trajectories up to 7 dof.  A change there must be copied here.
+CERT_SOLVE_FROM, CERT_FEASIBLE_FROM, PAIR_FROM = 9216, 8192, 2560
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# shared setup
+
+@functools.lru_cache(maxsize=8)
+def extreme(B, d, N, seed=0, kinds=T.EXTREME_KINDS):
+    return T.extreme_limit_batch(B, d, N, seed, kinds=kinds)
+
+
+def problem(data, vel=True):
+    return (data["coef"], data["breaks"], data["grid"], data["vlim"] if vel else None, data["alim"])
+
+
+def oracle_flags(oracle, vel, interp):
+    return oracle.FLAG_ACC | (oracle.FLAG_VEL if vel else 0) | (oracle.FLAG_INTERP if interp else 0)
+
+
+def oracle_solve(oracle, data, interp, vel=True):
+    ref = oracle.solve_batch(*problem(data, vel), data["sd0"], data["sd1"], flags=oracle_flags(oracle, vel, interp), nthreads=0)
+    with np.errstate(invalid="ignore"):
+        ref["sd"] = np.sqrt(ref["sd2"])  # (the wrapper's own sd = sqrt(x): IEEE, correctly rounded on either side)
+    return ref
+
+
+def wrappers(oracle, data, interp, vel=True):
+    """A fresh oracle wrapper object per trajectory."""
+    coef, breaks, grid, vlim, alim = problem(data, vel)
+    for b in range(coef.shape[0]):
+        yield oracle.Wrapper(coef[b], breaks[b], grid[b], None if vlim is None else vlim[b], alim[b], flags=oracle_flags(oracle, vel, interp))
+
+
+def same(got, want, keys, what):
+    """Bit for bit on every key (NaNs must coincide), exact on status; names the first trajectories that differ and their kinds."""
+    kinds = what[0]["kinds"] if isinstance(what[0], dict) else None
+    what = what[1:] if kinds is not None else what
+    for k in ("status",) + tuple(keys):
+        if k == "status" and "status" not in want:
+            continue
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape, (what, k, g.shape, w.shape)
+        if not np.array_equal(g, w, equal_nan=(k != "status")):
+            differs = ~((g == w) | ((g != g) & (w != w))).reshape(g.shape[0], -1).all(axis=1)
+            where = np.flatnonzero(differs)
+            raise AssertionError((what, k, int(differs.sum()), where[:8], None if kinds is None else sorted(set(kinds[where]))))
+
+
+def same_array(got, want, what):
+    same({"x": got}, {"x": want}, ("x",), what)
+
+
+def not_vacuous(ref, data, kinds=T.EXTREME_KINDS):
+    """On the ORACLE's output: every kind but `inverted` and `vneg` has solved trajectories, and the batch holds failures too."""
+    for kind in kinds:
+        ok = ref["status"][data["kinds"] == kind] == 0
+        assert len(ok) and (ok.any() or kind in ("inverted", "vneg")), kind
+    assert (ref["status"][data["kinds"] == "inverted"] == 1).all()
+    assert (ref["status"][data["kinds"] == "plain"] == 0).any()
+    assert {0, 1} <= set(np.unique(ref["status"]).tolist())
+
+
+def solve_variants(d):
+    if d <= 8:
+        return [dict(variant=v) for v in (1, 2, 3, 4) + ((5,) if d <= 7 else ())] + [dict(), dict(strict=True), dict(variant=2, strict=True),
+                                                                                      dict(variant=4, strict=True)]
+    return [dict(variant=v) for v in ((1, 2, 3, 4) if d <= 15 else (1, 2, 4) if d == 16 else (1, 4))] + [dict()]
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# a. solve, every family
+
+@pytest.mark.parametrize("interp", [True, False], ids=["interpolation", "collocation"])
+@pytest.mark.parametrize("d,N", [(1, 33), (3, 40), (7, 50), (8, 36), (9, 30), (12, 40), (15, 24), (16, 24), (20, 20)])
+def test_solve_on_every_family(gpu, oracle, d, N, interp):
+    data = extreme(B_SMALL, d, N)
+    ref = oracle_solve(oracle, data, interp)
+    not_vacuous(ref, data)
+    for kw in solve_variants(d):
+        got = batch.solve_batch(*problem(data), data["sd0"], data["sd1"], interp, want_sd=True, **kw)
+        same(got, ref, ("K", "sd2", "sd", "u"), (data, d, interp, kw))
+
+
+@pytest.mark.parametrize("d,N", [(3, 40), (7, 50), (12, 30)])
+def test_solve_with_acceleration_limits_alone(gpu, oracle, d, N):
+    """vlim = None: no box on x but the solver's own, so that infinite and 1e300 acceleration rows are all there is."""
+    data = extreme(B_SMALL, d, N, 1, ACC_KINDS)
+    for interp in (True, False):
+        ref = oracle_solve(oracle, data, interp, vel=False)
+        not_vacuous(ref, data, ACC_KINDS)
+        for kw in solve_variants(d):
+            got = batch.solve_batch(*problem(data, False), data["sd0"], data["sd1"], interp, want_sd=True, **kw)
+            same(got, ref, ("K", "sd2", "sd", "u"), (data, d, interp, kw))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# b. the batch sizes at which the automatic choice picks the throughput kernels
+
+_TRACED_CHILD = """
+import sys
+import numpy as np
+from tests import test_oracle_vs_reference as T
+from toppra_amd import batch
+out = {}
+for name, B, N in (("solve3", %d, 24), ("feasible3", %d, 24), ("solve5", %d, 24)):
+    data = T.extreme_limit_batch(B + 37, 7, N, 2)
+    args = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    if name == "feasible3":
+        out[name + "_X"] = batch.feasible_sets_batch(*args)
+    else:
+        got = batch.solve_batch(*args, data["sd0"], data["sd1"], want_sd=True)
+        out.update({name + "_" + k: got[k] for k in ("K", "sd2", "sd", "u", "status")})
+np.savez(sys.argv[1], **out)
+print("traced child done")
+""" % (CERT_SOLVE_FROM, CERT_FEASIBLE_FROM, PAIR_FROM)
+
+
+def test_the_sizes_at_which_the_throughput_kernels_are_chosen(gpu, oracle):
+    """The automatic choice at 7 dof: 9216 + 37 trajectories (family 3 solves), 8192 + 37 (family 3 computes the feasible sets),
+    2560 + 37 (family 5 solves) -- made in a fresh child process under the kernel tracer (no counters), whose statistics say that
+    the certified lane kernels and the two-trajectories-per-wave kernel are what ran, and whose outputs are compared with the oracle
+    on every trajectory here."""
+    rp = shutil.which("rocprofv3")
+    assert rp, "rocprofv3 is not on PATH: the dispatch of the automatic choice cannot be traced (GPU tests do not skip here)"
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    with tempfile.TemporaryDirectory(prefix="tpr_trace_") as tmp:
+        npz = os.path.join(tmp, "out.npz")
+        cmd = ["timeout", "-k", "10", "240", rp, "--kernel-trace", "--stats", "-d", tmp, "-o", "run", "--output-format", "csv", "--",
+               sys.executable, "-c", _TRACED_CHILD, npz]
+        run = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert run.returncode == 0, (run.returncode, run.stdout[-3000:])
+        assert "traced child done" in run.stdout, run.stdout[-3000:]
+        stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats*.csv"), recursive=True)
+        assert stats, ([os.path.join(r, f) for r, _, fs in os.walk(tmp) for f in fs], run.stdout[-2000:])
+        calls = []  # (kernel name, dispatches)
+        for path in stats:
+            with open(path, newline="") as fh:
+                calls += [(r["Name"], int(r["Calls"])) for r in csv.DictReader(fh)]
+        with np.load(npz) as z:
+            out = {k: z[k] for k in z.files}
+
+    def ran(kernel, d=None):  # demangled names, or ...<kernel>ILi<d>E...: the dof is the first template argument where there is one
+        return sum(c for n, c in calls if (kernel in n if d is None else (kernel + "<%d," % d in n or kernel + "ILi%dE" % d in n)))
+    seen = {k: ran(k, 7) for k in ("cert_solve_kernel", "cert_feasible_kernel", "group_solve_kernel", "group_feasible_kernel")}
+    seen.update({k: ran(k) for k in ("pair_solve_kernel", "wave_solve_kernel", "lane_solve_kernel")})
+    assert seen["cert_solve_kernel"] >= 1 and seen["cert_feasible_kernel"] >= 1 and seen["pair_solve_kernel"] >= 1, seen
+    assert not (seen["group_solve_kernel"] or seen["group_feasible_kernel"] or seen["wave_solve_kernel"] or seen["lane_solve_kernel"]), seen
+    for name, B in (("solve3", CERT_SOLVE_FROM), ("solve5", PAIR_FROM)):
+        data = T.extreme_limit_batch(B + 37, 7, 24, 2)
+        ref = oracle_solve(oracle, data, True)
+        not_vacuous(ref, data)
+        same({k: out[name + "_" + k] for k in ("K", "sd2", "sd", "u", "status")}, ref, ("K", "sd2", "sd", "u"), (data, name))
+    data = T.extreme_limit_batch(CERT_FEASIBLE_FROM + 37, 7, 24, 2)
+    want = np.stack([w.compute_feasible_sets() for w in wrappers(oracle, data, True)])
+    same_array(out["feasible3_X"], want, (data, "feasible3"))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# c. the other entries that read vlim / alim
+
+SET_SHAPES = [(3, 40), (7, 50), (12, 30)]
+
+
+def lattice_interval(B, seed):
+    rng = np.random.default_rng(seed)
+    lo = np.round(0.1 * rng.random(B) * 1024) / 1024
+    return lo, lo + np.round((0.01 + 0.3 * rng.random(B)) * 1024) / 1024
+
+
+@pytest.mark.parametrize("d,N", SET_SHAPES)
+def test_controllable_sets(gpu, oracle, d, N):
+    data = extreme(B_SMALL, d, N)
+    lo, hi = lattice_interval(B_SMALL, d)
+    zero = np.zeros(B_SMALL)
+    for interp in (True, False):
+        for sdmin, sdmax in ((lo, hi), (zero, zero)):
+            want = np.stack([w.compute_controllable_sets(float(sdmin[b]), float(sdmax[b])) for b, w in enumerate(wrappers(oracle, data, interp))])
+            assert np.isnan(want).any() and not np.isnan(want[data["kinds"] == "plain"]).all()
+            for kw in (dict(), dict(variant=1), dict(variant=2), dict(variant=3), dict(variant=4), dict(variant=2, strict=True)):
+                K = batch.controllable_sets_batch(*problem(data), sdmin, sdmax, interp, **kw)
+                same_array(K, want, (data, d, interp, bool(sdmax.any()), kw))
+
+
+@pytest.mark.parametrize("d,N", SET_SHAPES)
+def test_feasible_sets(gpu, oracle, d, N):
+    data = extreme(B_SMALL, d, N)
+    for interp in (True, False):
+        want = np.stack([w.compute_feasible_sets() for w in wrappers(oracle, data, interp)])
+        kws = [dict(), dict(variant=1), dict(variant=2), dict(variant=3), dict(variant=4), dict(variant=2, strict=True)]
+        for kw in kws + ([dict(variant=3, sound=True)] if interp else []):
+            same_array(batch.feasible_sets_batch(*problem(data), interp, **kw), want, (data, d, interp, kw))
+
+
+@pytest.mark.parametrize("d,N", SET_SHAPES)
+def test_reachable_sets(gpu, oracle, d, N):
+    data = extreme(B_SMALL, d, N)
+    lo, hi = lattice_interval(B_SMALL, 10 + d)
+    zero = np.zeros(B_SMALL)
+    for interp in (True, False):
+        for sdmin, sdmax in ((lo, hi), (zero, zero)):
+            want = [w.compute_reachable_sets(float(sdmin[b]), float(sdmax[b])) for b, w in enumerate(wrappers(oracle, data, interp))]
+            L, X = batch.reachable_sets_batch(*problem(data), sdmin, sdmax, interp, want_X=True)
+            same_array(L, np.stack([w[0] for w in want]), (data, d, interp, "L"))
+            same_array(X, np.stack([w[1] for w in want]), (data, d, interp, "X"))
+
+
+@pytest.mark.parametrize("d,N", SET_SHAPES)
+def test_desired_duration(gpu, oracle, d, N):
+    """TOPPRAsd with desired durations on both sides of each trajectory's optimum: 0.6 and 1.7 times the duration of the oracle's
+    own time-optimal profile (1e20 s under subnormal velocity bounds, where an absolute number of seconds would sit on one side
+    only; 3 s where that duration is not finite or there is no profile).  alpha included."""
+    data = extreme(B_SMALL, d, N)
+    for interp in (True, False):
+        opt = oracle_solve(oracle, data, interp)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            duration = np.sum(2.0 * np.diff(data["grid"], axis=1) / (opt["sd"][:, :-1] + opt["sd"][:, 1:]), axis=1)
+        factor = np.where((np.arange(B_SMALL) // 13) % 2 == 0, 0.6, 1.7)
+        desired = np.where(np.isfinite(duration) & (duration > 0), factor * duration, 3.0)
+        assert (desired[data["kinds"] == "vsub"] > 1e15).any()
+        ref = oracle.solve_batch_sd(*problem(data), desired, data["sd0"], data["sd1"], flags=oracle_flags(oracle, True, interp), nthreads=0)
+        ok = ref["status"] == 0
+        assert (ok & (ref["alpha"] > 0) & (ref["alpha"] < 1)).any() and (ref["alpha"] == 1).any() and (~ok).any()
+        with np.errstate(invalid="ignore"):
+            ref["sd"] = np.sqrt(ref["sd2"])
+        for variant in (0, 2, 3):
+            got = batch.solve_desired_duration_batch(*problem(data), desired, data["sd0"], data["sd1"], variant=variant, interpolation=interp)
+            same(got, ref, ("K", "sd2", "sd", "u", "alpha"), (data, d, interp, variant))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# d. rows
+
+@pytest.mark.parametrize("interp", [True, False], ids=["interpolation", "collocation"])
+@pytest.mark.parametrize("d,N", SET_SHAPES)
+def test_rows(gpu, oracle, d, N, interp):
+    """constraint_params_batch against the oracle's wrapper arrays and its velocity bound at every gridpoint; second_order_rows_batch
+    without blocks; and the rows as a dense problem against the fused kernels, which never materialise them."""
+    data = extreme(B_SMALL, d, N)
+    rows = batch.constraint_params_batch(*problem(data), interp)
+    for b, w in enumerate(wrappers(oracle, data, interp)):
+        for k, want in (("a", w.a_arr), ("b", w.b_arr), ("c", w.c_arr), ("low", w.low_arr), ("high", w.high_arr)):
+            assert np.array_equal(rows[k][b], want, equal_nan=True), (d, interp, k, b, data["kinds"][b])
+        xb = np.array([oracle.velocity_xbound(oracle.path_eval(data["coef"][b], data["breaks"][b], float(s))[0], data["vlim"][b])
+                       for s in data["grid"][b]])
+        assert np.array_equal(rows["xbound"][b], xb, equal_nan=True), (d, interp, "xbound", b, data["kinds"][b])
+    assert not any(np.isnan(rows[k]).any() for k in ("a", "b", "c", "low", "high", "xbound"))
+    assert np.isinf(rows["c"]).any() and (rows["xbound"][..., 1] == 0).any() and (rows["xbound"][..., 0] > 0).any()
+    hi = rows["xbound"][data["kinds"] == "vsub"][..., 1]
+    assert ((hi > 0) & (hi < T.FLT_MIN_NORMAL)).any()  # fp32 subnormals, as the reference's fixture holds them
+    so = batch.second_order_rows_batch(*problem(data), [], interp)
+    for k in ("a", "b", "c", "low", "high"):
+        same_array(so[k], rows[k], (data, d, interp, "second_order_rows_batch", k))
+    same_array(so["deltas"], np.diff(data["grid"], axis=1), (data, d, interp, "deltas"))
+    dense = (rows["a"], rows["b"], rows["c"], rows["low"], rows["high"], so["deltas"])
+    fused = batch.solve_batch(*problem(data), data["sd0"], data["sd1"], interp, want_sd=True)
+    got = batch.solve_dense_batch(*dense, data["sd0"], data["sd1"], want_sd=True)
+    same(got, fused, ("K", "sd2", "sd", "u"), (data, d, interp, "dense rows vs fused"))
+    same_array(batch.feasible_sets_dense_batch(*dense), batch.feasible_sets_batch(*problem(data), interp), (data, d, interp, "dense X"))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# e. the reference's stored bits, not via the oracle
+
+@pytest.mark.parametrize("d,N,seed", T.EXTREME_CASES)
+def test_against_the_references_stored_outputs(gpu, d, N, seed):
+    """tests/golden/oracle_vs_reference_extreme.npz -- what the real reference computed on these problems, on its own spline tables
+    -- through every solve family and through feasible_sets_batch: K, sd, u, X and the failures."""
+    ref = T.reference_outputs("extreme", T.case_id(d, N, seed), "all")
+    probs = list(T.extreme_limit_problems(d, N, seed))
+    grid, vlim, alim = (np.array([p[i] for p in probs]) for i in (2, 4, 5))
+    sd0, sd1 = (np.array([p[i] for p in probs]) for i in (6, 7))
+    args = (np.ascontiguousarray(ref["c"]), np.ascontiguousarray(ref["x"]), grid, vlim, alim)
+    failed = ref["failed"].astype(bool)
+    assert failed.any() and not failed.all()
+    for kw in solve_variants(d):
+        got = batch.solve_batch(*args, sd0, sd1, want_sd=True, **kw)
+        assert np.array_equal(got["status"] != 0, failed), (kw, np.flatnonzero((got["status"] != 0) != failed))
+        same_array(got["K"], ref["K"], (d, kw, "K"))
+        same_array(got["sd"][~failed], ref["sd"][~failed], (d, kw, "sd"))
+        same_array(got["u"][~failed], ref["sdd"][~failed], (d, kw, "u"))
+        assert np.isnan(got["sd"][failed]).all()
+    for kw in (dict(), dict(variant=1), dict(variant=2), dict(variant=3), dict(variant=4), dict(variant=2, strict=True)):
+        same_array(batch.feasible_sets_batch(*args, **kw), ref["X"], (d, kw, "X"))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# f. neighbours
+
+@pytest.mark.parametrize("d,N,variants", [(3, 40, (2, 3, 5)), (7, 50, (2, 3, 5)), (12, 30, (2, 3))])
+def test_extreme_trajectories_leave_their_neighbours_bits_alone(gpu, oracle, d, N, variants):
+    """The batch as built, and once more with every extreme trajectory replaced by the ordinary problem it was made from: the
+    `plain` controls -- in every wave, next to every kind -- give the same bits in both runs (and the oracle's)."""
+    data = extreme(64 * 6 + 37, d, N, 3)
+    base = data["base"]
+    plain = data["kinds"] == "plain"
+    assert plain.sum() >= 28 and all(plain[w * 64:(w + 1) * 64].any() and (~plain[w * 64:(w + 1) * 64]).any() for w in range(6))
+    ordinary = (base["coef"], base["breaks"], base["grid"], base["vlim"], base["alim"])
+    assert all(np.array_equal(x[plain], y[plain]) for x, y in zip(problem(data), ordinary))
+    assert not any(np.array_equal(x[~plain], y[~plain]) for x, y in zip(problem(data)[3:], ordinary[3:]))
+    ref = oracle_solve(oracle, data, True)
+    quiet = oracle.solve_batch(*ordinary, data["sd0"], data["sd1"], nthreads=0)
+    assert (quiet["status"] == 0).mean() > (ref["status"] == 0).mean() and (ref["status"][plain] == 0).any()
+    for variant in variants:
+        with_extremes = batch.solve_batch(*problem(data), data["sd0"], data["sd1"], want_sd=True, variant=variant)
+        without = batch.solve_batch(*ordinary, data["sd0"], data["sd1"], want_sd=True, variant=variant)
+        for k in ("status", "K", "sd2", "sd", "u"):
+            assert np.array_equal(with_extremes[k][plain], without[k][plain], equal_nan=True), (d, variant, k)
+            assert np.array_equal(with_extremes[k][plain], ref[k][plain], equal_nan=True), (d, variant, k, "oracle")
+        same(without, quiet, ("K", "sd2", "u"), (d, variant, "ordinary batch vs oracle"))

@@ -39,6 +39,21 @@ def test_certificates_return_the_references_bits(harness, family, seed, B, min_u
         assert res["eq_upper_cert"] + res["eq_lower_cert"] >= 1.8 * res["eq_upper"], res
 
 
+@pytest.mark.parametrize("minform", [False, True])
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("seed,B", [(0, 39), (9, 52), (1, 65)])  # 7 dof N = 200, 12 dof N = 40, 3 dof N = 60
+def test_certificates_on_limits_at_the_edge_of_the_number_range(harness, seed, B, mode, minform):
+    """Infinite, 1e300, subnormal-squared, one-sided and inverted limits (family `extreme`: every kind of
+    tests/test_oracle_vs_reference.py::extreme_limit_problems, round-robin, beside ordinary trajectories): rows with c = -inf or
+    1e300 in every stage LP.  Whatever a certificate answers is the reference's bits, and it answers no LP the reference fails
+    on -- in the solve and in the feasible-set mode, in both forms of the slides.  No acceptance floor: refusing is the right
+    answer on infinite rows (0 .. 99 % of the LPs are certified, depending on the kind)."""
+    (coef, breaks, grid, vlim, alim, sd_end, flags, _), _ = hunt.workloads("extreme", B, seed)
+    res, rc = hunt.run(coef, breaks, grid, vlim, alim, sd_end, flags, mode, minform=minform)
+    assert res["mismatch"] == 0 and res["ref_failed_cert_answered"] == 0 and rc == 0, res
+    assert (res["feas_upper"] + res["feas_lower"] if mode else res["upper"] + res["lower"]) > 0, res  # LPs were compared
+
+
 @pytest.mark.parametrize("family,seed,B", [("natural", 0, 24), ("sliver", 0, 64), ("lower_ties", 5, 48), ("feasible", 0, 24)])
 def test_the_minimum_form_of_the_slides(harness, family, seed, B):
     """The slides fold their verdicts into sign bits (every kernel but TOPPRAsd's) or into a running minimum (TOPPRAsd's

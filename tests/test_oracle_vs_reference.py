@@ -57,6 +57,122 @@ def irregular_problems(d, N, nway, seed):
         yield knots, grid, way, vl, al, sd0, sd1
 
 
+EXTREME_KINDS = ("vinf", "ainf", "ainf_one", "vhuge", "ahuge", "vsub", "vtiny", "vneg", "inverted", "still", "shifted", "mix")
+EXTREME_CASES = [(1, 30, 1), (3, 40, 2), (7, 60, 3), (12, 36, 4)]
+EXTREME_TRIALS = 3
+FLT_MAX = float(np.finfo(np.float32).max)
+FLT_MIN_NORMAL = float(np.finfo(np.float32).tiny)  # 2^-126: fp32 values below it are subnormal
+
+
+def extreme_limit_problem(rng, kind, d, N, with_sd):
+    """One problem whose limits sit at the edge of the number range (the table of kinds: extreme_limit_problems), and the
+    ordinary problem it was made from: (knots, grid, waypoints, vlim, alim, sd_start, sd_end), (base waypoints, vlim, alim).
+    Kind 'plain' is the base problem itself, drawn from the same stream; with_sd: non-zero boundary velocities.  No NaN
+    anywhere."""
+    way, vl, al = _problem(rng, d)
+    base = (way.copy(), vl.copy(), al.copy())
+    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
+    hit = rng.random(d) < 0.35
+    hit[rng.integers(d)] = True                      # 30 - 40 % of the joints, at least one
+    one = int(rng.choice(np.flatnonzero(hit)))       # the joint of the one-joint kinds
+    # (every draw below is made for every kind, so that a kind's problem does not depend on the kinds before it)
+    expo = rng.uniform(-23, -19, size=d)
+    huge = np.where(rng.random(d) < 0.5, 1e38, 1e300)
+    side, frac, s0 = rng.random() < 0.5, 0.01 + 0.05 * rng.random(), (5.0, -3.0, 1e3)[int(rng.integers(3))]
+    order = rng.permutation(d)
+    lattice = [np.round(0.2 * rng.random() * 1024) / 1024 for _ in range(2)]  # 2^-10 lattice: the squares are exact
+    if kind == "vinf":
+        vl[hit] = [-np.inf, np.inf]
+    elif kind == "ainf":
+        al[hit] = [-np.inf, np.inf]
+    elif kind == "ainf_one":
+        al[hit, 1] = np.inf
+    elif kind == "vhuge":
+        vl[hit] *= huge[hit, None]
+    elif kind == "ahuge":
+        al[hit] *= 1e300
+    elif kind == "vsub":
+        vl *= 10.0 ** expo[:, None]
+    elif kind == "vtiny":
+        vl[hit] *= 1e-30
+    elif kind == "vneg":
+        vl[one] = [frac * vl[one, 1], vl[one, 1]] if side else [vl[one, 0], frac * vl[one, 0]]
+    elif kind == "inverted":
+        al[one] = al[one, ::-1]
+    elif kind == "still":
+        way[:, hit] = way[:1, hit]
+    elif kind == "shifted":
+        knots, grid = s0 + knots, s0 + grid
+    elif kind == "mix":
+        j = [int(order[i % d]) for i in range(4)]
+        vl[j[0]] = [-np.inf, np.inf]
+        al[j[1], 1] = np.inf
+        vl[j[2]] = base[1][j[2]] * 10.0 ** expo[j[2]]
+        al[j[3]] = al[j[3]] * 1e300
+    else:
+        assert kind == "plain", kind
+    sd0, sd1 = lattice if with_sd else (0.0, 0.0)
+    return (knots, grid, way, vl, al, float(sd0), float(sd1)), base
+
+
+def extreme_limit_problems(d, N, seed, trials=EXTREME_TRIALS):
+    """Limits at the edge of the number range, on the ordinary problem _problem(rng, d) with 30 - 40 % of the joints (at
+    least one) modified: `trials` x (kind, knots, grid, waypoints, vlim, alim, sd_start, sd_end) for every kind of
+
+      vinf      vlim = (-inf, +inf)                       ainf      alim = (-inf, +inf)
+      ainf_one  alim_hi = +inf only                       ahuge     alim x 1e300
+      vhuge     vlim x 1e38 and x 1e300: quotients vlim / q' beyond FLT_MAX
+      vsub      ALL vlim x 10^U(-23, -19): the fp32 square of sdmax is subnormal or underflows to 0
+      vtiny     vlim x 1e-30: the square underflows to 0, x is pinned to 0
+      vneg      vlim_hi < 0 or vlim_lo > 0 on one joint: a positive lower bound on sd, mostly infeasible
+      inverted  alim_lo and alim_hi swapped on one joint: every stage infeasible
+      still     the modified joints do not move (q' = q'' = 0: zero-normal rows, skipped in the velocity bound)
+      shifted   knots and grid on [s0, s0 + 1], s0 in {5, -3, 1e3}
+      mix       one joint each of vinf, ainf_one, vsub, ahuge in one trajectory
+
+    Every third trial of a kind carries non-zero boundary velocities on the 2^-10 lattice."""
+    rng = np.random.default_rng(31000 + seed)
+    for kind in EXTREME_KINDS:
+        for t in range(trials):
+            yield (kind,) + extreme_limit_problem(rng, kind, d, N, t % 3 == 2)[0]
+
+
+def extreme_limit_batch(B, d, N, seed, kinds=EXTREME_KINDS, shared_s0=None):
+    """The same problems as one batch, for the batched entries and for tools/host_cert_hunt.py: trajectory b is of kind
+    (kinds + ('plain',))[b % (len(kinds) + 1)] -- every 64-trajectory wave holds every kind next to ordinary trajectories, the
+    `plain` controls at a fixed stride -- and every third round of kinds carries non-zero boundary velocities.
+    dict(coef [B, 4, 4, d], breaks [B, 5], grid [B, N+1], vlim, alim [B, d, 2], sd0, sd1 [B], kinds [B], base): `base` holds
+    the unmodified problems (coef, breaks, grid, vlim, alim) in the same layout.  With shared_s0 (a number) breaks [5] and grid
+    [N+1] are one shifted set for the whole batch, and kind 'shifted' is an ordinary problem on it."""
+    from toppra_amd.batch import spline_coefficients
+    rng = np.random.default_rng(47000 + seed)
+    names = tuple(kinds) + ("plain",)
+    unit_k, unit_g = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
+    kind = [names[b % len(names)] for b in range(B)]
+    out = {k: [] for k in ("knots", "grid", "way", "vlim", "alim", "sd0", "sd1")}
+    base = {k: [] for k in ("way", "vlim", "alim")}
+    for b in range(B):
+        prob, (bw, bv, ba) = extreme_limit_problem(rng, kind[b], d, N, (b // len(names)) % 3 == 2)
+        for k, v in zip(("knots", "grid", "way", "vlim", "alim", "sd0", "sd1"), prob):
+            out[k].append(v)
+        base["way"].append(bw); base["vlim"].append(bv); base["alim"].append(ba)
+    out = {k: np.array(v) for k, v in out.items()}
+    base = {k: np.array(v) for k, v in base.items()}
+    if shared_s0 is not None:
+        out["knots"], out["grid"] = shared_s0 + unit_k, shared_s0 + unit_g
+        out["coef"], _ = spline_coefficients(out["knots"], out["way"])
+        base.update(coef=spline_coefficients(out["knots"], base["way"])[0], breaks=out["knots"], grid=out["grid"])
+    else:
+        out["coef"] = np.empty((B, 4, 4, d))
+        for k0 in np.unique(out["knots"][:, 0]):   # one batched fit per set of knots
+            m = out["knots"][:, 0] == k0
+            out["coef"][m], _ = spline_coefficients(out["knots"][m][0], out["way"][m])
+        base.update(coef=spline_coefficients(unit_k, base["way"])[0], breaks=np.tile(unit_k, (B, 1)), grid=np.tile(unit_g, (B, 1)))
+    out["breaks"] = out.pop("knots")
+    out.update(kinds=np.array(kind), base=base)
+    return out
+
+
 def lp2d_problems():
     """300 x (v, a, b, c, low, high, active_c)."""
     for seed in range(300):
@@ -198,6 +314,62 @@ def test_irregular_problems_match_reference(oracle, d, N, nway, seed):
             assert_same(osd, ref["sd"], "sd")
             assert_same(osdd, ref["sdd"], "sdd")
     assert 0 in seen
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_fixture_census():
+    """What the REFERENCE's stored outputs hold, over the whole fixture: (non-zero fp32 subnormal upper bounds of `vsub`, its
+    exact zeros, quotients |vlim / q'| beyond FLT_MAX of `vhuge`, gridpoints of `vneg` with a positive lower bound)."""
+    from scipy.interpolate import PPoly
+    sub = zero = beyond = pos_lower = 0
+    for d, N, seed in EXTREME_CASES:
+        ref = reference_outputs("extreme", case_id(d, N, seed), "all")
+        for t, (kind, knots, grid, way, vl, al, sd0, sd1) in enumerate(extreme_limit_problems(d, N, seed)):
+            lo, hi = ref["xbound"][t][:, 0], ref["xbound"][t][:, 1]
+            if kind == "vsub":
+                sub += int(np.sum((hi > 0) & (hi < FLT_MIN_NORMAL)))
+                zero += int(np.sum(hi == 0))
+            elif kind == "vhuge":
+                qs = PPoly(ref["c"][t], ref["x"][t]).derivative()(grid)  # the reference's path(grid, 1): scipy on its own table
+                with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+                    beyond += int(np.sum(np.abs(vl[None, :, :] / qs[:, :, None]) > FLT_MAX))
+            elif kind == "vneg":
+                pos_lower += int(np.sum(lo > 0))
+    return sub, zero, beyond, pos_lower
+
+
+@pytest.mark.parametrize("d,N,seed", EXTREME_CASES)
+def test_extreme_limits_match_reference(oracle, d, N, seed):
+    """Infinite, huge, subnormal-squared, one-sided and inverted limits, standing joints, shifted path parameters: the
+    oracle against the reference bit for bit -- K, the feasible sets, sd, sdd, failures, and the fp32 velocity bound against
+    the reference's own _create_velocity_constraint at every gridpoint.  The conditions at the end are on the REFERENCE's
+    stored outputs: every kind but `inverted` and `vneg` is solved at least once in every case, `inverted` never, and the
+    fixture does hold subnormal and underflowed bounds, quotients beyond FLT_MAX and positive lower bounds."""
+    ref = reference_outputs("extreme", case_id(d, N, seed), "all")
+    solved = {}
+    for t, (kind, knots, grid, way, vl, al, sd0, sd1) in enumerate(extreme_limit_problems(d, N, seed)):
+        c, x, what = ref["c"][t], ref["x"][t], " (%s, trial %d)" % (kind, t)
+        assert not any(np.isnan(v).any() for v in (c, x, grid, vl, al))
+        st, osdd, osd, oxs, oK = oracle.Wrapper(c, x, grid, vl, al).compute_parameterization(sd0, sd1)
+        assert_same(oK, ref["K"][t], "K" + what)
+        if ref["failed"][t]:
+            assert st == 1, what
+        else:
+            assert st == 0, what
+            assert_same(osd, ref["sd"][t], "sd" + what)
+            assert_same(osdd, ref["sdd"][t], "sdd" + what)
+        assert_same(oracle.Wrapper(c, x, grid, vl, al).compute_feasible_sets(), ref["X"][t], "X" + what)
+        xb = np.array([oracle.velocity_xbound(oracle.path_eval(c, x, float(s))[0], vl) for s in grid])
+        assert_same(xb, ref["xbound"][t], "xbound" + what)
+        solved.setdefault(kind, []).append(not ref["failed"][t])
+    assert set(solved) == set(EXTREME_KINDS)
+    for kind, ok in solved.items():
+        if kind == "inverted":
+            assert not any(ok), kind
+        elif kind != "vneg":
+            assert any(ok), kind
+    sub, zero, beyond, pos_lower = extreme_fixture_census()
+    assert sub > 0 and zero > 0 and beyond > 0 and pos_lower > 0, (sub, zero, beyond, pos_lower)
 
 
 def test_lp2d_matches_reference(oracle):

@@ -5,7 +5,9 @@ restatement of the reference) over workload families -- TEST INFRASTRUCTURE, CPU
 
 Families: natural, scaled, tight (velocity limits that bind), boundary (non-zero end velocities), collocation,
 acc_only, sliver (three rows through one point to 1e-9 .. 1e-13: the family of tools/gpu_sliver_hunt.py), parallel (near-parallel
-joints), feasible (compute_feasible_sets).  Prints one JSON line per workload; exit code 1 on any mismatch.
+joints), feasible (compute_feasible_sets), extreme (limits at the edge of the number range -- infinite, huge, subnormal-squared,
+one-sided, inverted: tests/test_oracle_vs_reference.py::extreme_limit_batch, the kinds round-robin over the batch; the certificates
+refuse most stages with infinite rows, which is the right answer: no acceptance rate is expected of it).  Prints one JSON line per workload; exit code 1 on any mismatch.
 """
 import json
 import os
@@ -146,6 +148,10 @@ def workloads(family, B, seed):
                 alim[b, m, 1] = val
             else:
                 alim[b, m, 0] = -val
+    elif family == "extreme":
+        from tests import test_oracle_vs_reference as T  # the generator shared with the fixtures and the GPU tests
+        data = T.extreme_limit_batch(B, d, N, seed, shared_s0=(0.0, 5.0, -3.0, 1e3)[seed % 4])
+        coef, breaks, grid, vlim, alim, sd_end = data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd1"]
     elif family == "feasible":
         mode = 1
         if seed % 2:

@@ -7,6 +7,10 @@ its outputs on those problems are committed as fixtures; this script is their pr
 
 Keys are '<case>__<trial>__<name>' (tests/test_oracle_vs_reference.py::reference_outputs).  A trajectory the reference
 declares FailUncontrollable (it returns None) is stored with failed = 1 and no sd / sdd.
+
+Fixtures: parameterization, irregular, lp2d, velocity_bound, reachable, host_glue, general, and extreme (limits at the edge of
+the number range: tests/test_oracle_vs_reference.py::extreme_limit_problems; one stacked array per name and case, trial
+'all', failed trajectories NaN-filled, and the reference's own velocity bound at every gridpoint beside K, X, sd, sdd).
 """
 import os
 import sys
@@ -129,9 +133,33 @@ def general():
     return out
 
 
+def extreme():
+    from toppra._CythonUtils import _create_velocity_constraint
+    out = {}
+    for d, N, seed in T.EXTREME_CASES:
+        recs = []
+        for kind, knots, grid, way, vl, al, sd0, sd1 in T.extreme_limit_problems(d, N, seed):
+            path = reference.SplineInterpolator(knots, way)
+            cons = [constraint.JointVelocityConstraint(vl), constraint.JointAccelerationConstraint(al)]
+            inst = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel")
+            sdd, sdv, _, K = inst.compute_parameterization(sd0, sd1, return_data=True)
+            X = algo.TOPPRA(cons, path, gridpoints=grid, solver_wrapper="seidel").compute_feasible_sets()
+            _, _, cc = _create_velocity_constraint(path(grid, 1).reshape(N + 1, d), vl)
+            failed = sdv is None
+            recs.append({"c": path.cspl.c, "x": path.cspl.x, "K": K, "X": X, "failed": int(failed),
+                         "sd": np.full(N + 1, np.nan) if failed else sdv, "sdd": np.full(N, np.nan) if failed else sdd,
+                         "xbound": np.stack([cc[:, 1], -cc[:, 0]], 1)})
+        put(out, T.case_id(d, N, seed), "all", **{k: np.stack([np.asarray(r[k]) for r in recs]) for k in recs[0]})
+    return out
+
+
 if __name__ == "__main__":
+    only = sys.argv[1:]
     for name, fn in (("parameterization", parameterization), ("irregular", irregular), ("lp2d", lp2d),
-                     ("velocity_bound", velocity_bound), ("reachable", reachable), ("host_glue", host_glue), ("general", general)):
+                     ("velocity_bound", velocity_bound), ("reachable", reachable), ("host_glue", host_glue), ("general", general),
+                     ("extreme", extreme)):
+        if only and name not in only:
+            continue
         arrays = fn()
         np.savez_compressed(T.golden_path(name), **arrays)
         print("%s: %d arrays, %d bytes" % (T.golden_path(name), len(arrays), os.path.getsize(T.golden_path(name))))
