@@ -12,6 +12,9 @@ b % 13 (twelve kinds and the `plain` control), odd sizes 64 k + 37, breakpoints 
 Everything is bit for bit -- np.array_equal(..., equal_nan=True) on K, sd2, sd, u, status, and on the sets and rows -- against
 the oracle on EVERY trajectory of every batch; part e goes past the oracle to the reference's stored bits.  No NaN is ever fed
 in, and no tolerance appears anywhere in this module.
+
+Every entry that reads vlim / alim runs this family, including the robust one: robust_solve_batch has its own restatement in the
+oracle and takes it in tests/test_gpu_robust_shapes.py, part 9.
 """
 import csv
 import functools

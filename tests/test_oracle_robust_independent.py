@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import robust_independent as ri
+from tests import robust_shapes as S
 from toppra_amd import batch
 
 ELL = [1e-3, 5e-2, 9e-3]  # examples/plot_robust_kinematics.py:26-28
@@ -40,6 +41,36 @@ def test_oracle_robust_matches_independent_solver(oracle, B, d, N, interp, ell, 
     agg = ri.check_batch(d2, ell, out, interp, stride=3, tol_x=1e-9)
     assert agg["stages"] >= N // 3 * int((out["status"] == 0).sum()) - B
     assert agg["K"] <= 1e-9 and agg["X"] <= 1e-9
+
+
+@pytest.mark.parametrize("name", S.PARITY_CASES)
+def test_new_shape_classes_match_independent_solver(oracle, name):
+    """The shape classes tests/test_gpu_robust_shapes.py adds -- a non-uniform grid per trajectory with non-zero sd_start, a
+    42-segment spline on non-uniform knots (the kernels' long-table path), 20 dof under Collocation -- with the restatement
+    standing in for the kernels: every fifth stage, K and X at this file's 1e-9."""
+    prob, interp = S.parity_cases()[name]
+    out = S.restatement(oracle, prob, interp, True)
+    assert (out["status"] == 0).sum() >= 4
+    agg = ri.check_batch(S.as_checker_data(prob), S.ELL, out, interp, stride=5, tol_x=1e-9)
+    assert agg["stages"] >= (prob[2].shape[-1] - 1) // 5 * int((out["status"] == 0).sum())
+    assert agg["K"] <= 1e-9 and agg["X"] <= 1e-9
+
+
+@pytest.mark.parametrize("d,slow", S.RELAXED_CASES)
+def test_limits_written_as_1e300_are_limits_written_as_inf(oracle, d, slow):
+    """Acceleration limits of a third of the joints written as +-inf and as 1e300 x the ordinary ones: identical bits in every
+    output, solved wherever the ordinary problem is.  slow: |q'| < ru on those joints (rob_row_interval's A < 0 branch).
+    (Until rob_row_interval stopped squaring m = b x + c beyond 1.3e154, the 1e300 form was uncontrollable everywhere.)"""
+    S.check_relaxed_twins(lambda prob, interp, want_X: S.restatement(oracle, prob, interp, want_X), d, slow)
+
+
+@pytest.mark.parametrize("d,N", S.EXTREME_SHAPES)
+def test_huge_acceleration_limits_are_solved_where_infinite_ones_are(oracle, d, N):
+    """extreme_limit_batch on the robust entry: kind `ahuge` (limits x 1e300) is solved wherever the same problem with those limits
+    written as +-inf is; `inverted` never, the `plain` controls mostly."""
+    data, prob = S.extreme_case(d, N)
+    for interp in (True, False):
+        S.check_extreme_counts(S.restatement(oracle, prob, interp, True), S.restatement(oracle, S.inf_twin(data, prob), interp, True), data["kinds"])
 
 
 def test_uncontrollable_trajectories_are_infeasible_for_the_independent_solver_too(oracle):

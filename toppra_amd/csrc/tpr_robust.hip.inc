@@ -80,7 +80,10 @@ __device__ inline void rob_row_interval(double a, double b, double c, double ru,
     if (A > 0) {
         // one quotient for both signs of a (the +- twin rows of a joint sit in neighbouring lanes: as two branches half of
         // the lanes idled through each division); x - s == x + (-s) exactly
-        const double s = sqrt(kap * A + (ru * ru) * (m * m));
+        // limits written as 1e300: m * m overflows, the root would be +inf and a row that is slack by 1e300 would bound u
+        // at -+inf.  There |m| > 1.3e154 and the root is |m| ru (kap A, at most ~1e8 a^2, is far below an ulp of ru^2 m^2)
+        const double mm = m * m, root = sqrt(kap * A + (ru * ru) * mm);
+        const double s = mm == pinf() ? fabs(m) * ru : root;
         const bool up = a > 0;
         const double val = (-a * m + (up ? -s : s)) / A;
         hi = up ? val : hi; lo = up ? lo : val;
