@@ -284,6 +284,62 @@ int tpr_second_order_block_bytes(void);
 int tpr_second_order_rows_batch(const tpr_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a,
                                 double *b, double *c, double *low, double *high, double *deltas, void *stream);
 
+/* ---- any geometric path: the path given as SAMPLES at the gridpoints -------------------------------------------------
+ * The reference's constraints see a path only through path(gridpoints, 1) and path(gridpoints, 2)
+ * (linear_joint_velocity.py:48, linear_joint_acceleration.py:72-73, linear_second_order.py:146-152), ParametrizeSpline
+ * additionally through path(gridpoints) and the first derivative at the two ends (parametrizer.py:161-196).  A solver fed
+ * with these samples therefore returns the reference's bits for ANY AbstractGeometricPath (SimplePath, PolynomialPath,
+ * UnivariateSplineInterpolator, a user's own class): nothing of the path's arithmetic is reproduced on the GPU.
+ *   grid        [N+1], or [B][N+1] with TPR_GRID_PER_TRAJ
+ *   q, qs, qss  [B][N+1][d]: path(grid), path(grid, 1), path(grid, 2); q may be NULL where only the solver is asked.
+ *               Samples must be finite: NaN samples are the caller's error, like NaN limits.
+ *   vlim, alim, sd_start, sd_end, active: as in tpr_problem.
+ * flags: TPR_HAS_VELOCITY, TPR_HAS_ACCELERATION, TPR_ACC_INTERPOLATION, TPR_DEVICE_PTRS, TPR_GRID_PER_TRAJ,
+ * TPR_BOUNDARY_SQUARED, with their meanings above.
+ * These entries are the dense-row family with the rows generated from the samples.  The fused families 1-5 of
+ * tpr_solve_batch (certificates, the cubic evaluated in registers) read a spline table and do not take samples. */
+typedef struct tpr_sampled_problem {
+    int32_t B, d, N, flags;
+    const double *grid;
+    const double *q, *qs, *qss;
+    const double *vlim, *alim;
+    const double *sd_start, *sd_end;
+    int32_t *active;
+} tpr_sampled_problem;
+/* ABI guard, as tpr_second_order_block_bytes: bytes of tpr_sampled_problem in the library.                       */
+int tpr_sampled_problem_bytes(void);
+
+/* The counterpart of tpr_constraint_params_batch / tpr_second_order_rows_batch with the samples in place of the spline
+ * evaluation (replaces the same reference code: linear_joint_velocity.py:43-53, linear_joint_acceleration.py:63-104,
+ * linear_second_order.py:142-173, linear_constraint.py:84-192, cy_seidel_solverwrapper.pyx:455-520): the complete
+ * tpr_dense_problem of [velocity, acceleration, blocks[0], ...] -- a, b, c [B][N+1][nC], low, high [B][N+1][2], deltas
+ * [B][N] (may be NULL), xbound [B][N+1][2] (may be NULL: the velocity constraint's own x bound, before the +-1e8 box).
+ * Every expression after the evaluation of q', q'' is that of the spline entries; same limits (nC <= 122).       */
+int tpr_sampled_rows_batch(const tpr_sampled_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a,
+                           double *b, double *c, double *low, double *high, double *deltas, double *xbound, void *stream);
+
+/* The passes of the dense family WITHOUT materialised rows: each takes the arguments of its *_dense_batch twin and
+ * replaces the same reference code, with a stage's rows produced in registers from qs / qss at gridpoints i and i+1, alim
+ * and the velocity box from vlim (4 d doubles read per stage in place of 3 nC).  Results are the bits of the dense pass
+ * on the rows tpr_sampled_rows_batch writes (nblocks = 0), warm-start state in and out included.  Limits of the dense
+ * family: nC = 2 + 4 d <= 122 under Interpolation (d <= 30), d <= 32 under Collocation or without an acceleration
+ * constraint; beyond that TPR_E_UNSUPPORTED.                                                                      */
+int tpr_solve_sampled_batch(const tpr_sampled_problem *p, const tpr_result *r, void *stream);
+int tpr_solve_desired_duration_sampled_batch(const tpr_sampled_problem *p, const double *desired, double atol,
+                                             const tpr_result *r, double *alpha, void *stream);
+int tpr_controllable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *K,
+                                        void *stream);
+int tpr_feasible_sets_sampled_batch(const tpr_sampled_problem *p, double *X, void *stream);
+int tpr_reachable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *L,
+                                     double *X, void *stream);
+
+/* ParametrizeSpline (toppra/parametrizer.py:161-196) for a sampled path: as tpr_param_spline_batch's generic variant
+ * (1) with the kept samples p->q copied where that variant evaluates the cubic, and the end derivatives p->qs[:, 0] and
+ * p->qs[:, N] (the gridpoints must span the path interval, as the reference's do).  sd [B][N+1] -> knot_times
+ * [B][N+1], counts [B], coef_t [B][4][N][d]; tpr_ppoly_eval_batch evaluates the result.  p->q and p->qs are required. */
+int tpr_param_spline_samples_batch(const tpr_sampled_problem *p, const double *sd, double *knot_times, int32_t *counts,
+                                   double *coef_t, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -15,11 +15,13 @@ gfx950 behind the C-ABI of ``include/toppra_hip.h``); there is no CPU fallback.
 """
 import logging
 
-from . import algorithm, batch, constants, constraint, exceptions, interpolator, parametrizer, solverwrapper
-from .interpolator import SplineInterpolator
+from . import algorithm, batch, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
+from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
+from .simplepath import SimplePath
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 
 __all__ = ["algorithm", "batch", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
-           "solverwrapper", "SplineInterpolator", "ParametrizeConstAccel", "ParametrizeSpline"]
+           "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
+           "ParametrizeConstAccel", "ParametrizeSpline"]

@@ -60,6 +60,13 @@ class tpr_second_order_block(C.Structure):
                 ("F", C.c_void_p), ("g", C.c_void_p), ("friction", C.c_void_p)]
 
 
+class tpr_sampled_problem(C.Structure):
+    _fields_ = [("B", C.c_int32), ("d", C.c_int32), ("N", C.c_int32), ("flags", C.c_int32),
+                ("grid", C.c_void_p), ("q", C.c_void_p), ("qs", C.c_void_p), ("qss", C.c_void_p),
+                ("vlim", C.c_void_p), ("alim", C.c_void_p),
+                ("sd_start", C.c_void_p), ("sd_end", C.c_void_p), ("active", C.c_void_p)]
+
+
 # tpr_second_order_block.flags
 SO_INTERPOLATION, SO_F_SHARED, SO_F_PER_TRAJ, SO_F_PER_POINT, SO_G_PER_TRAJ, SO_G_PER_POINT = 1, 2, 4, 8, 16, 32
 SO_MAX_BLOCKS = 8
@@ -75,6 +82,9 @@ EXPORTS = (
     "tpr_reachable_sets_batch", "tpr_solve_dense_batch", "tpr_controllable_sets_dense_batch", "tpr_feasible_sets_dense_batch",
     "tpr_solve_desired_duration_dense_batch", "tpr_reachable_sets_dense_batch", "tpr_param_spline_sample_batch",
     "tpr_path_eval_batch", "tpr_second_order_rows_batch", "tpr_second_order_block_bytes",
+    "tpr_sampled_problem_bytes", "tpr_sampled_rows_batch", "tpr_solve_sampled_batch", "tpr_controllable_sets_sampled_batch",
+    "tpr_feasible_sets_sampled_batch", "tpr_reachable_sets_sampled_batch", "tpr_solve_desired_duration_sampled_batch",
+    "tpr_param_spline_samples_batch",
 )
 
 _lib = None
@@ -173,6 +183,26 @@ def load():
         L.tpr_path_eval_batch.argtypes = [P, V, V, V, V]
         L.tpr_second_order_rows_batch.restype = C.c_int
         L.tpr_second_order_rows_batch.argtypes = [P, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V]
+        L.tpr_sampled_problem_bytes.restype = C.c_int
+        L.tpr_sampled_problem_bytes.argtypes = []
+        if L.tpr_sampled_problem_bytes() != C.sizeof(tpr_sampled_problem):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_sampled_problem takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_sampled_problem_bytes(), C.sizeof(tpr_sampled_problem)))
+        SP = C.POINTER(tpr_sampled_problem)
+        L.tpr_sampled_rows_batch.restype = C.c_int
+        L.tpr_sampled_rows_batch.argtypes = [SP, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V, V]
+        L.tpr_solve_sampled_batch.restype = C.c_int
+        L.tpr_solve_sampled_batch.argtypes = [SP, R, V]
+        L.tpr_solve_desired_duration_sampled_batch.restype = C.c_int
+        L.tpr_solve_desired_duration_sampled_batch.argtypes = [SP, V, C.c_double, R, V, V]
+        L.tpr_reachable_sets_sampled_batch.restype = C.c_int
+        L.tpr_reachable_sets_sampled_batch.argtypes = [SP, V, V, V, V, V]
+        L.tpr_controllable_sets_sampled_batch.restype = C.c_int
+        L.tpr_controllable_sets_sampled_batch.argtypes = [SP, V, V, V, V]
+        L.tpr_feasible_sets_sampled_batch.restype = C.c_int
+        L.tpr_feasible_sets_sampled_batch.argtypes = [SP, V, V]
+        L.tpr_param_spline_samples_batch.restype = C.c_int
+        L.tpr_param_spline_samples_batch.argtypes = [SP, V, V, V, V, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int
@@ -297,16 +327,101 @@ def make_dense_problem(a, b, c, low, high, deltas, sd_start=None, sd_end=None, s
             keep.append(arr)
             setattr(p, name, ptr(arr))
     if active is not None:  # [B, 4] int32 warm-start state of the reference's wrapper object, updated in place
-        if dev:
-            import torch
-            if not (hasattr(active, "is_cuda") and active.is_cuda) or active.device != a.device or \
-                    active.dtype != torch.int32 or tuple(active.shape) != (B, 4) or not active.is_contiguous():
-                raise ValueError("active must be a contiguous int32 tensor [B, 4] on a's device")
-        elif not (isinstance(active, np.ndarray) and active.dtype == np.int32 and active.shape == (B, 4)
-                  and active.flags["C_CONTIGUOUS"]):
-            raise ValueError("active must be a C-contiguous int32 array [B, 4] (it is updated in place)")
-        keep.append(active)
+        keep.append(_check_active(active, B, a, dev))
         p.active = ptr(active)
+    return p, keep
+
+
+def converter(like, like_name):
+    """``conv(name, x)`` for the arrays of one call: a contiguous fp64 numpy array when ``like`` is a host array; when it is a
+    torch CUDA tensor, ``x`` checked to be an fp64 tensor on like's device, made contiguous."""
+    if is_torch_cuda(like):
+        def conv(name, x):
+            if not (hasattr(x, "is_cuda") and x.is_cuda):
+                raise ValueError("%s must be a CUDA tensor like %s (mixing host and device arrays is not supported)" % (name, like_name))
+            check_tensor(name, x, like)
+            return x.contiguous()
+        return conv
+    return lambda name, x: f64(x)
+
+
+def _check_active(active, B, like, dev):
+    """[B, 4] int32 warm-start state of the reference's wrapper object, updated in place."""
+    if dev:
+        import torch
+        if not (hasattr(active, "is_cuda") and active.is_cuda) or active.device != like.device or \
+                active.dtype != torch.int32 or tuple(active.shape) != (B, 4) or not active.is_contiguous():
+            raise ValueError("active must be a contiguous int32 tensor [B, 4] on the problem's device")
+    elif not (isinstance(active, np.ndarray) and active.dtype == np.int32 and active.shape == (B, 4)
+              and active.flags["C_CONTIGUOUS"]):
+        raise ValueError("active must be a C-contiguous int32 array [B, 4] (it is updated in place)")
+    return active
+
+
+def sampled_rows_per_stage(d, alim, interpolation):
+    """nC of a sampled problem without second-order blocks: the two x_next rows and the acceleration block."""
+    return 2 + ((4 if interpolation else 2) * d if alim is not None else 0)
+
+
+def make_sampled_problem(grid, q, qs, qss, vlim, alim, sd_start=None, sd_end=None, interpolation=True, keep=None,
+                         active=None, squared=False, solver=True):
+    """Build a tpr_sampled_problem -- a geometric path given as samples at the gridpoints -- from arrays (all numpy or all
+    torch-CUDA): grid [N+1] or [B, N+1] (strictly increasing); q (may be None), qs, qss [B, N+1, d]: path(grid),
+    path(grid, 1), path(grid, 2) (qss may be None too with ``solver=False``: the spline
+    parametrizer reads q and qs only); vlim / alim [B, d, 2] or None; sd_start / sd_end scalars or [B]; active [B, 4] int32
+    (in / out).  Everything that can be refused from shapes alone is refused here, before any launch: ``solver`` (the fused
+    passes) holds 122 rows per stage -- d <= 30 under Interpolation, d <= 32 otherwise."""
+    dev = is_torch_cuda(qs)
+    keep = keep if keep is not None else []
+    conv = converter(qs, "qs")
+    qs = conv("qs", qs)
+    if qs.ndim != 3:
+        raise ValueError("qs must have shape [B, N+1, d], got %s" % (tuple(qs.shape),))
+    B, N1, d = (int(v) for v in qs.shape)
+    N = N1 - 1
+    if N < 1:
+        raise ValueError("a sampled path needs at least two gridpoints")
+    if not 1 <= d <= MAX_DOF:
+        raise NotImplementedError("dof %d is outside 1..%d" % (d, MAX_DOF))
+    if qss is None and solver:
+        raise ValueError("the solver passes need qss = path(grid, 2)")
+    qss = None if qss is None else conv("qss", qss)
+    q = None if q is None else conv("q", q)
+    for name, arr in (("qss", qss), ("q", q)):
+        if arr is not None and tuple(arr.shape) != (B, N1, d):
+            raise ValueError("%s must have the shape of qs, [B, N+1, d] = [%d, %d, %d], got %s" % (name, B, N1, d, tuple(arr.shape)))
+    grid = conv("grid", grid)
+    if tuple(grid.shape) not in ((N1,), (B, N1)):
+        raise ValueError("grid must have shape [N+1] or [B, N+1] = [%d, %d], got %s" % (B, N1, tuple(grid.shape)))
+    if not dev and not np.all(np.diff(grid, axis=-1) > 0):  # device grids are the caller's responsibility
+        raise ValueError("grid must be strictly increasing")
+    if solver and sampled_rows_per_stage(d, alim, interpolation) > MAX_DENSE_ROWS:
+        raise NotImplementedError("%d dof under Interpolation: %d constraint rows per stage (incl. the two x_next rows), the "
+                                  "sampled passes hold %d (30 dof; 32 under Collocation)"
+                                  % (d, sampled_rows_per_stage(d, alim, interpolation), MAX_DENSE_ROWS))
+    flags = (DEVICE_PTRS if dev else 0) | (BOUNDARY_SQUARED if squared else 0) | (GRID_PER_TRAJ if grid.ndim == 2 else 0)
+    p = tpr_sampled_problem(B=B, d=d, N=N, flags=0)
+    keep += [grid, q, qs, qss]
+    p.grid, p.q, p.qs, p.qss = ptr(grid), ptr(q), ptr(qs), ptr(qss)
+    for name, arr, flag in (("vlim", vlim, HAS_VELOCITY), ("alim", alim, HAS_ACCELERATION)):
+        if arr is not None:
+            arr = conv(name, arr)
+            if tuple(arr.shape) != (B, d, 2):
+                raise ValueError("%s must have shape [B, d, 2] = [%d, %d, 2], got %s" % (name, B, d, tuple(arr.shape)))
+            keep.append(arr)
+            setattr(p, name, ptr(arr))
+            flags |= flag
+    if alim is not None and interpolation:
+        flags |= ACC_INTERPOLATION
+    for name, arr in (("sd_start", sd_start), ("sd_end", sd_end)):
+        if arr is not None:
+            arr = _per_traj(name, arr, B, qs, dev)
+            keep.append(arr)
+            setattr(p, name, ptr(arr))
+    if active is not None:
+        keep.append(_check_active(active, B, qs, dev))
+        p.active = ptr(active)
+    p.flags = flags
     return p, keep
 
 
@@ -388,15 +503,7 @@ def make_problem(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, int
             keep.append(arr)
             setattr(p, name, ptr(arr))
     if active is not None:  # [B, 4] int32 warm-start state of the reference's wrapper object, updated in place
-        if dev:
-            import torch
-            if not (hasattr(active, "is_cuda") and active.is_cuda) or active.device != coef.device or \
-                    active.dtype != torch.int32 or tuple(active.shape) != (B, 4) or not active.is_contiguous():
-                raise ValueError("active must be a contiguous int32 tensor [B, 4] on coef's device")
-        elif not (isinstance(active, np.ndarray) and active.dtype == np.int32 and active.shape == (B, 4)
-                  and active.flags["C_CONTIGUOUS"]):
-            raise ValueError("active must be a C-contiguous int32 array [B, 4] (it is updated in place)")
-        keep.append(active)
+        keep.append(_check_active(active, B, coef, dev))
         p.active = ptr(active)
     p.flags = flags
     return p, keep

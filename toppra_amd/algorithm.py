@@ -17,7 +17,7 @@ from . import batch as _batch
 from . import exceptions
 from . import interpolator as _interp
 from .constants import SMALL
-from .solverwrapper import hipDenseSeidelWrapper, hipRobustWrapper, hipSeidelWrapper
+from .solverwrapper import hipDenseSeidelWrapper, hipRobustWrapper, hipSampledSeidelWrapper, hipSeidelWrapper
 
 logger = logging.getLogger(__name__)
 
@@ -131,10 +131,14 @@ class ReachabilityAlgorithm(ParameterizationAlgorithm):
                 self.solver_wrapper = hipSeidelWrapper(self.constraints, self.path, self.gridpoints,
                                                        solve_lp1d=True)
             except NotImplementedError:
-                # any other canonical-linear list (second-order / torque constraints, the reference's own or hand-written
-                # constraint objects): parameters from the constraints' callbacks, the scans on the dense-row entries
-                self.solver_wrapper = hipDenseSeidelWrapper(self.constraints, self.path, self.gridpoints,
-                                                            solve_lp1d=True)
+                try:  # velocity + acceleration limits on a path without a cubic-spline table: the fused passes on its samples
+                    self.solver_wrapper = hipSampledSeidelWrapper(self.constraints, self.path, self.gridpoints,
+                                                                  solve_lp1d=True)
+                except NotImplementedError:
+                    # any other canonical-linear list (second-order / torque constraints, the reference's own or hand-written
+                    # constraint objects): parameters from the constraints' callbacks, the scans on the dense-row entries
+                    self.solver_wrapper = hipDenseSeidelWrapper(self.constraints, self.path, self.gridpoints,
+                                                                solve_lp1d=True)
 
     def compute_feasible_sets(self):
         """X[N+1, 2]: feasible squared velocities per gridpoint (NaN where infeasible)."""
@@ -250,8 +254,33 @@ class BatchTOPPRA(object):
         self.vlim, self.alim, self.interpolation = vlim, alim, interpolation
         self.constraints = list(constraints) if constraints else []
         self._rows = self._rows_dev = None
+        self._samples = None  # (q, qs, qss) of from_path_samples: the path as samples at the gridpoints, no spline table
         if self.constraints:
             self._check_constraints()
+
+    @classmethod
+    def from_path_samples(cls, gridpoints, q, qs, qss, vlim, alim, interpolation=True, constraints=None):
+        """The batch for ANY geometric paths, given as samples at the gridpoints: ``q = path(grid)`` (may be None where no
+        trajectory and no second-order constraint is asked for), ``qs = path(grid, 1)``, ``qss = path(grid, 2)``, each
+        [B, N+1, d], numpy or torch-ROCm tensors; ``gridpoints`` [N+1] or [B, N+1].  The reference's constraints and its
+        default parametrizer read nothing else of a path, so every pass returns the reference's bits for the path class that
+        produced the samples.  The passes run on the fused sampled entries (``batch.solve_sampled_batch`` ...); with
+        ``constraints`` their rows come from ``batch.sampled_rows_batch`` and ``inv_dyn`` receives the given samples.
+        ``compute_trajectory("ParametrizeSpline")`` works; "ParametrizeConstAccel" and ``compute_trajectory_samples`` need
+        the path between the gridpoints and raise NotImplementedError.  Shapes and the row limit (d <= 30 under
+        Interpolation, 32 under Collocation) are checked here, before anything is launched."""
+        self = cls(None, None, gridpoints, vlim, alim, interpolation=interpolation)
+        self.constraints = list(constraints) if constraints else []
+        _capi.make_sampled_problem(gridpoints, q, qs, qss, vlim, alim, interpolation=interpolation, solver=not self.constraints)
+        self._samples = (q, qs, qss)
+        if self.constraints:
+            if q is None:
+                raise ValueError("second-order constraints evaluate their inverse dynamics at q: give the path positions")
+            self._check_constraints()
+        return self
+
+    def _sampled_args(self):
+        return (self.gridpoints, self._samples[1], self._samples[2], self.vlim, self.alim)
 
     # -- constraint lists beyond velocity + acceleration limits ------------------------------------------------------
     # ``constraints``: BatchJointTorqueConstraint / BatchSecondOrderConstraint objects (toppra_amd.constraint), after the
@@ -263,9 +292,12 @@ class BatchTOPPRA(object):
     # warm-start state like a fresh reference object.
     def _check_constraints(self):
         """Everything that can be refused from shapes alone, before any launch."""
-        if getattr(self.coef, "ndim", 0) != 4:
-            raise ValueError("coef must have shape [B, 4, nseg, d]")
-        B, d, N = int(self.coef.shape[0]), int(self.coef.shape[3]), int(self.gridpoints.shape[-1]) - 1
+        if self._samples is not None:
+            B, N, d = int(self._samples[1].shape[0]), int(self._samples[1].shape[1]) - 1, int(self._samples[1].shape[2])
+        else:
+            if getattr(self.coef, "ndim", 0) != 4:
+                raise ValueError("coef must have shape [B, 4, nseg, d]")
+            B, d, N = int(self.coef.shape[0]), int(self.coef.shape[3]), int(self.gridpoints.shape[-1]) - 1
         if len(self.constraints) > _capi.SO_MAX_BLOCKS:
             raise NotImplementedError("%d second-order constraints in one list: the row kernel takes %d"
                                       % (len(self.constraints), _capi.SO_MAX_BLOCKS))
@@ -286,13 +318,17 @@ class BatchTOPPRA(object):
         row count before its callbacks have run: for such a list the 122-row limit is checked here, after the path
         evaluation and the callbacks and before the row kernel is launched, not in the constructor."""
         if self._rows is None:
-            pe = _batch.path_eval_batch(self.coef, self.breaks, self.gridpoints)
-            blocks = [con.block(pe["q"], pe["qs"], pe["qss"]) for con in self.constraints]
-            rows = _batch.second_order_rows_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, blocks,
-                                                  self.interpolation)
+            if self._samples is not None:
+                blocks = [con.block(*self._samples) for con in self.constraints]
+                rows = _batch.sampled_rows_batch(*self._sampled_args(), blocks, self.interpolation)
+            else:
+                pe = _batch.path_eval_batch(self.coef, self.breaks, self.gridpoints)
+                blocks = [con.block(pe["q"], pe["qs"], pe["qss"]) for con in self.constraints]
+                rows = _batch.second_order_rows_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, blocks,
+                                                      self.interpolation)
             self._rows = tuple(rows[k] for k in ("a", "b", "c", "low", "high", "deltas"))
             self._rows_dev = self._rows
-            if not _capi.is_torch_cuda(self.coef):
+            if not _capi.is_torch_cuda(rows["a"]):
                 # numpy problem: the passes read a device copy made once (3 B (N+1) nC doubles would otherwise be uploaded by
                 # every pass); results come back as numpy arrays
                 import torch
@@ -331,6 +367,8 @@ class BatchTOPPRA(object):
         With ``constraints`` the dense-row entry serves the call (``variant`` does not apply; K and u are always returned)."""
         if self.constraints:
             return self._dense_pass(_batch.solve_dense_batch, sd_start, sd_end, want_sd=want_sd)
+        if self._samples is not None:  # (the sampled entry always returns K and u; ``variant`` does not apply)
+            return _batch.solve_sampled_batch(*self._sampled_args(), sd_start, sd_end, self.interpolation, want_sd=want_sd)
         return _batch.solve_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
                                   sd_start, sd_end, self.interpolation, want_sd=want_sd, variant=variant,
                                   want_K=want_K, want_u=want_u)
@@ -339,6 +377,9 @@ class BatchTOPPRA(object):
         """TOPPRAsd for the batch: dict(sd2, sd, u, K, status, alpha)."""
         if self.constraints:
             return self._dense_pass(_batch.solve_desired_duration_dense_batch, desired_duration, sd_start, sd_end, atol)
+        if self._samples is not None:
+            return _batch.solve_desired_duration_sampled_batch(*self._sampled_args(), desired_duration, sd_start, sd_end, atol,
+                                                               self.interpolation)
         return _batch.solve_desired_duration_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
                                                    desired_duration, sd_start, sd_end, atol)
 
@@ -348,7 +389,16 @@ class BatchTOPPRA(object):
         "ParametrizeSpline" (its default) or "ParametrizeConstAccel" -- entirely on the GPU.  Returns a
         :class:`BatchTrajectory`; trajectories that could not be parameterized have ``status != 0`` and
         NaN durations (the reference returns None for them)."""
+        if self._samples is not None:
+            if parametrizer == "ParametrizeConstAccel":
+                raise NotImplementedError("ParametrizeConstAccel evaluates the path between the gridpoints: a batch given as "
+                                          "samples at the gridpoints has ParametrizeSpline only")
+            if parametrizer == "ParametrizeSpline" and self._samples[0] is None:
+                raise ValueError("ParametrizeSpline needs the path positions q at the gridpoints")
         res = self.compute_parameterization(sd_start, sd_end, want_sd=True, want_K=False, want_u=False)  # retiming reads sd only
+        if parametrizer == "ParametrizeSpline" and self._samples is not None:
+            sp = _batch.param_spline_samples_batch(self.gridpoints, self._samples[0], self._samples[1], res["sd"])
+            return BatchTrajectory("spline", res, self, spline=sp)
         if parametrizer == "ParametrizeSpline":
             sp = _batch.param_spline_batch(self.coef, self.breaks, self.gridpoints, res["sd"])
             return BatchTrajectory("spline", res, self, spline=sp)
@@ -365,6 +415,9 @@ class BatchTOPPRA(object):
         (``np.linspace(0, 1, T)``) or [B, T] (fractions, or absolute times with ``fractions=False``).  Returns
         dict(q / qd / qdd [B, T, d] for the requested orders, duration [B], status [B]); the same bits as
         ``compute_trajectory()`` followed by its evaluation.  Up to 16 dof."""
+        if self._samples is not None:
+            raise NotImplementedError("compute_trajectory_samples fits and evaluates from the spline table: a batch given as "
+                                      "samples at the gridpoints has compute_trajectory('ParametrizeSpline')")
         res = self.compute_parameterization(sd_start, sd_end, want_sd=True, want_K=False, want_u=False)
         out = _batch.param_spline_sample_batch(self.coef, self.breaks, self.gridpoints, res["sd"], times, fractions=fractions,
                                                orders=orders)
@@ -374,12 +427,16 @@ class BatchTOPPRA(object):
     def compute_controllable_sets(self, sdmin, sdmax):
         if self.constraints:
             return self._dense_pass(_batch.controllable_sets_dense_batch, sdmin, sdmax)
+        if self._samples is not None:
+            return _batch.controllable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
         return _batch.controllable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
                                               self.alim, sdmin, sdmax, self.interpolation)
 
     def compute_feasible_sets(self):
         if self.constraints:
             return self._dense_pass(_batch.feasible_sets_dense_batch)
+        if self._samples is not None:
+            return _batch.feasible_sets_sampled_batch(*self._sampled_args(), self.interpolation)
         return _batch.feasible_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
                                           self.alim, self.interpolation)
 
@@ -387,6 +444,8 @@ class BatchTOPPRA(object):
         """L[B, N+1, 2] (reachability_algorithm.py:409-431 per trajectory)."""
         if self.constraints:
             return self._dense_pass(_batch.reachable_sets_dense_batch, sdmin, sdmax)
+        if self._samples is not None:
+            return _batch.reachable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
         return _batch.reachable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, sdmin, sdmax,
                                            self.interpolation)
 

@@ -17,7 +17,9 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "constraint_params_batch", "make_synthetic_batch", "spline_coefficients",
            "spline_fit_batch", "solve_batch_timed", "const_accel_times_batch", "const_accel_eval_batch",
            "solve_desired_duration_batch", "robust_solve_batch", "param_spline_batch", "ppoly_eval_batch",
-           "path_eval_batch", "second_order_rows_batch"]
+           "path_eval_batch", "second_order_rows_batch", "sampled_rows_batch", "solve_sampled_batch",
+           "controllable_sets_sampled_batch", "feasible_sets_sampled_batch", "reachable_sets_sampled_batch",
+           "solve_desired_duration_sampled_batch", "param_spline_samples_batch"]
 
 
 def _stream_ptr(like):
@@ -308,33 +310,9 @@ def second_order_rows_per_stage(d, alim, interpolation, blocks):
     return nC
 
 
-def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolation=True):
-    """The dense problem of the constraint list [velocity, acceleration, second-order blocks ...] for B trajectories, built on
-    the GPU: dict(a, b, c [B, N+1, nC], low, high [B, N+1, 2], deltas [B, N]) -- the arguments of :func:`solve_dense_batch` and
-    its siblings, the bits of ``seidelWrapper.__init__`` on the reference's ``SecondOrderConstraint`` /
-    ``JointTorqueConstraint`` objects (include/toppra_hip.h: tpr_second_order_rows_batch).
-
-    ``blocks``: one dict per second-order constraint, in list order, with
-      ``w0, wa, wb`` [B, N+1, p]: the inverse dynamics tau(q, 0, 0), tau(q, 0, q'), tau(q, q', q'') at the gridpoints
-      (:func:`path_eval_batch` gives q, q', q'');
-      ``F``: None (the signed identity [I; -I]: joint torque limits), [m, p], [B, m, p] or [B, N+1, m, p];
-      ``g``: [m], [B, m] or [B, N+1, m] (m = 2 p for the signed identity: [tau_max; -tau_min]);
-      ``friction``: None or [B, p] (dry friction, p == d);  ``interpolation``: the block's discretisation (default True).
-    ``interpolation`` is the acceleration constraint's.  All arrays numpy, or all torch tensors on coef's device.  Shapes are
-    checked, and more than 122 rows per stage refused (NotImplementedError), before anything is launched."""
-    dev = _capi.is_torch_cuda(coef)
-    if dev:
-        def conv(name, x):
-            if not (hasattr(x, "is_cuda") and x.is_cuda):
-                raise ValueError("%s must be a CUDA tensor like coef (mixing host and device arrays is not supported)" % name)
-            _capi.check_tensor(name, x, coef)
-            return x.contiguous()
-    else:
-        def conv(name, x):
-            return _capi.f64(x)
-    if coef.ndim != 4:
-        raise ValueError("coef must have shape [B, 4, nseg, d]")
-    B, d, N = int(coef.shape[0]), int(coef.shape[3]), int(grid.shape[-1]) - 1
+def _stage_blocks(blocks, B, N, d, conv):
+    """The ``blocks`` of :func:`second_order_rows_batch` / :func:`sampled_rows_batch` as tpr_second_order_block structures:
+    (structs, the converted arrays they point to, what :func:`second_order_rows_per_stage` needs).  Shapes are checked here."""
     blocks = list(blocks)
     if len(blocks) > _capi.SO_MAX_BLOCKS:
         raise NotImplementedError("%d second-order constraints in one list: the row kernel takes %d" % (len(blocks), _capi.SO_MAX_BLOCKS))
@@ -369,6 +347,28 @@ def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolatio
         keep += [w0, wa, wb, F, g, fr]
         structs[j] = _capi.tpr_second_order_block(p=pw, m=m, flags=flags, w0=_capi.ptr(w0), wa=_capi.ptr(wa), wb=_capi.ptr(wb),
                                                   F=_capi.ptr(F), g=_capi.ptr(g), friction=_capi.ptr(fr))
+    return structs, keep, staged
+
+
+def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolation=True):
+    """The dense problem of the constraint list [velocity, acceleration, second-order blocks ...] for B trajectories, built on
+    the GPU: dict(a, b, c [B, N+1, nC], low, high [B, N+1, 2], deltas [B, N]) -- the arguments of :func:`solve_dense_batch` and
+    its siblings, the bits of ``seidelWrapper.__init__`` on the reference's ``SecondOrderConstraint`` /
+    ``JointTorqueConstraint`` objects (include/toppra_hip.h: tpr_second_order_rows_batch).
+
+    ``blocks``: one dict per second-order constraint, in list order, with
+      ``w0, wa, wb`` [B, N+1, p]: the inverse dynamics tau(q, 0, 0), tau(q, 0, q'), tau(q, q', q'') at the gridpoints
+      (:func:`path_eval_batch` gives q, q', q'');
+      ``F``: None (the signed identity [I; -I]: joint torque limits), [m, p], [B, m, p] or [B, N+1, m, p];
+      ``g``: [m], [B, m] or [B, N+1, m] (m = 2 p for the signed identity: [tau_max; -tau_min]);
+      ``friction``: None or [B, p] (dry friction, p == d);  ``interpolation``: the block's discretisation (default True).
+    ``interpolation`` is the acceleration constraint's.  All arrays numpy, or all torch tensors on coef's device.  Shapes are
+    checked, and more than 122 rows per stage refused (NotImplementedError), before anything is launched."""
+    conv = _capi.converter(coef, "coef")
+    if coef.ndim != 4:
+        raise ValueError("coef must have shape [B, 4, nseg, d]")
+    B, d, N = int(coef.shape[0]), int(coef.shape[3]), int(grid.shape[-1]) - 1
+    structs, keep, staged = _stage_blocks(blocks, B, N, d, conv)
     nC = second_order_rows_per_stage(d, alim, interpolation, staged)
     if nC > _capi.MAX_DENSE_ROWS:
         raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
@@ -379,7 +379,140 @@ def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolatio
     out.update({k: _empty(coef, (B, N + 1, 2)) for k in ("low", "high")})
     out["deltas"] = _empty(coef, (B, N))
     _capi.check(_capi.load().tpr_second_order_rows_batch(
-        C.byref(p), len(blocks), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas")], _stream_ptr(coef)))
+        C.byref(p), len(staged), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas")], _stream_ptr(coef)))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
+# any geometric path: the path given as samples at the gridpoints (include/toppra_hip.h: tpr_sampled_problem)
+
+def sampled_rows_batch(grid, qs, qss, vlim, alim, blocks=(), interpolation=True):
+    """The dense problem of [velocity, acceleration, second-order blocks ...] for B paths given as samples ``qs = path(grid, 1)``,
+    ``qss = path(grid, 2)`` [B, N+1, d] -- :func:`constraint_params_batch` / :func:`second_order_rows_batch` with the samples
+    in place of the spline evaluation, for any geometric path: dict(a, b, c [B, N+1, nC], low, high, xbound [B, N+1, 2],
+    deltas [B, N]).  ``blocks`` as in :func:`second_order_rows_batch`.  numpy in -> numpy out, tensors in -> tensors out."""
+    if qss is None:
+        raise ValueError("the rows need qss = path(grid, 2)")
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, solver=False)
+    like = keep[2]
+    conv = _capi.converter(like, "qs")
+    B, N, d = p.B, p.N, p.d
+    structs, keep2, staged = _stage_blocks(blocks, B, N, d, conv)
+    nC = second_order_rows_per_stage(d, alim, interpolation, staged)
+    if nC > _capi.MAX_DENSE_ROWS:
+        raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
+                                  % (nC, _capi.MAX_DENSE_ROWS))
+    _prepare(like)
+    out = {k: _empty(like, (B, N + 1, nC)) for k in ("a", "b", "c")}
+    out.update({k: _empty(like, (B, N + 1, 2)) for k in ("low", "high", "xbound")})
+    out["deltas"] = _empty(like, (B, N))
+    _capi.check(_capi.load().tpr_sampled_rows_batch(
+        C.byref(p), len(staged), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas", "xbound")],
+        _stream_ptr(like)))
+    return out
+
+
+def solve_sampled_batch(grid, qs, qss, vlim, alim, sd_start=None, sd_end=None, interpolation=True, want_sd=False,
+                        squared=False, active=None):
+    """compute_parameterization for B paths given as samples (see :func:`sampled_rows_batch`): the dict of
+    :func:`solve_dense_batch`, and its bits on the rows :func:`sampled_rows_batch` writes -- without materialising them (a
+    stage's rows are produced in registers from qs / qss at gridpoints i and i+1).  d <= 30 under Interpolation, <= 32 under
+    Collocation (NotImplementedError beyond, before any launch).  ``active`` / ``squared``: as the dense entries."""
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, sd_start, sd_end, interpolation, active=active,
+                                         squared=squared)
+    like = keep[2]
+    _prepare(like)
+    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
+           "status": _empty(like, (p.B,), "i32")}
+    if want_sd:
+        out["sd"] = _empty(like, (p.B, p.N + 1))
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
+                         status=_capi.ptr(out["status"]))
+    _capi.check(_capi.load().tpr_solve_sampled_batch(C.byref(p), C.byref(r), _stream_ptr(like)))
+    return out
+
+
+def solve_desired_duration_sampled_batch(grid, qs, qss, vlim, alim, desired_duration, sd_start=None, sd_end=None, atol=1e-5,
+                                         interpolation=True, active=None, squared=False):
+    """TOPPRAsd.compute_parameterization for B sampled paths (see :func:`solve_sampled_batch`,
+    :func:`solve_desired_duration_dense_batch`): dict(sd2, sd, u, K, status, alpha)."""
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, sd_start, sd_end, interpolation, active=active,
+                                         squared=squared)
+    like = keep[2]
+    _prepare(like)
+    B, N = p.B, p.N
+    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
+    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
+           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
+                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
+    _capi.check(_capi.load().tpr_solve_desired_duration_sampled_batch(C.byref(p), _capi.ptr(desired), float(atol), C.byref(r),
+                                                                      _capi.ptr(out["alpha"]), _stream_ptr(like)))
+    return out
+
+
+def controllable_sets_sampled_batch(grid, qs, qss, vlim, alim, sdmin, sdmax, interpolation=True, squared=False, active=None):
+    """compute_controllable_sets(sdmin, sdmax) for B sampled paths (see :func:`solve_sampled_batch`) -> K [B, N+1, 2]."""
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active,
+                                         squared=squared)
+    like = keep[2]
+    _prepare(like)
+    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
+    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
+    K = _empty(like, (p.B, p.N + 1, 2))
+    _capi.check(_capi.load().tpr_controllable_sets_sampled_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(K),
+                                                                 _stream_ptr(like)))
+    return K
+
+
+def feasible_sets_sampled_batch(grid, qs, qss, vlim, alim, interpolation=True, active=None):
+    """compute_feasible_sets for B sampled paths (see :func:`solve_sampled_batch`) -> X [B, N+1, 2]."""
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active)
+    like = keep[2]
+    _prepare(like)
+    X = _empty(like, (p.B, p.N + 1, 2))
+    _capi.check(_capi.load().tpr_feasible_sets_sampled_batch(C.byref(p), _capi.ptr(X), _stream_ptr(like)))
+    return X
+
+
+def reachable_sets_sampled_batch(grid, qs, qss, vlim, alim, sdmin, sdmax, interpolation=True, want_X=False, active=None,
+                                 squared=False):
+    """compute_reachable_sets(sdmin, sdmax) for B sampled paths (see :func:`solve_sampled_batch`) -> L [B, N+1, 2] (and the
+    feasible sets X with ``want_X``)."""
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active,
+                                         squared=squared)
+    like = keep[2]
+    _prepare(like)
+    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
+    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
+    L = _empty(like, (p.B, p.N + 1, 2))
+    X = _empty(like, (p.B, p.N + 1, 2)) if want_X else None
+    _capi.check(_capi.load().tpr_reachable_sets_sampled_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L),
+                                                              _capi.ptr(X), _stream_ptr(like)))
+    return (L, X) if want_X else L
+
+
+def param_spline_samples_batch(grid, q, qs, sd):
+    """ParametrizeSpline for B sampled paths: ``q = path(grid)``, ``qs = path(grid, 1)`` [B, N+1, d] (the gridpoints span the
+    path interval: the end derivatives are qs[:, 0] and qs[:, N]), sd [B, N+1] -> the dict of :func:`param_spline_batch`
+    (its generic variant's arithmetic, the kept samples copied where that variant evaluates the cubic).  Evaluate with
+    :func:`ppoly_eval_batch`."""
+    if q is None:
+        raise ValueError("the spline parametrizer needs the path positions q at the gridpoints")
+    p, keep = _capi.make_sampled_problem(grid, q, qs, None, None, None, solver=False)
+    like = keep[2]
+    if _capi.is_torch_cuda(like):
+        _capi.check_tensor("sd", sd, like)
+        sd = sd.contiguous()
+    else:
+        sd = _capi.f64(sd)
+    if tuple(sd.shape) != (p.B, p.N + 1):
+        raise ValueError("sd must have shape [B, N+1] = [%d, %d]" % (p.B, p.N + 1))
+    _prepare(like)
+    out = {"knot_times": _empty(like, (p.B, p.N + 1)), "counts": _empty(like, (p.B,), "i32"),
+           "coef": _empty(like, (p.B, 4, p.N, p.d))}
+    _capi.check(_capi.load().tpr_param_spline_samples_batch(C.byref(p), _capi.ptr(sd), _capi.ptr(out["knot_times"]),
+                                                            _capi.ptr(out["counts"]), _capi.ptr(out["coef"]), _stream_ptr(like)))
     return out
 
 

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtoppra_hip.so")
-SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_rows_tu.hip"]
+SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_sampled_tu.hip", "tpr_rows_tu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-Wno-unused-variable"]
 
@@ -97,6 +97,7 @@ def compile_jobs(measurement=False):
     jobs = [("main", "tpr_kernels.hip", ["-DTPR_CERT_MAX_DOF=%d" % max_dof])]
     jobs += [("robust%d" % half, "tpr_robust_tu.hip", ["-DTPR_TU_HALF=%d" % half]) for half in (0, 1)]  # 1..8 dof + lane kernel; 9..16
     jobs.append(("dense", "tpr_dense_tu.hip", []))  # dense rows: any constraint list
+    jobs.append(("sampled", "tpr_sampled_tu.hip", []))  # the dense-row passes on path samples: any geometric path
     jobs.append(("rows", "tpr_rows_tu.hip", []))  # the dense rows of second-order / torque constraints, built on the GPU
     for d in range(1, max_dof + 1):
         for part, flags in sorted(({0: []} if measurement else CERT_UNITS[d]).items()):

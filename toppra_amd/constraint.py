@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .interpolator import spline_tables
+from .interpolator import path_samples, spline_tables
 
 
 class ConstraintType(Enum):
@@ -92,10 +92,16 @@ def _check_dof(constraint, path):
 
 
 def _params_on_device(path, gridpoints, vlim=None, alim=None, interpolation=True):
-    coef, breaks = spline_tables(path)
-    return _batch.constraint_params_batch(
-        coef[None], breaks, np.asarray(gridpoints, dtype=np.float64),
-        None if vlim is None else vlim[None], None if alim is None else alim[None], interpolation)
+    vlim, alim = None if vlim is None else vlim[None], None if alim is None else alim[None]
+    try:
+        coef, breaks = spline_tables(path)
+    except NotImplementedError:
+        # any other geometric path: path(gridpoints, 1) and path(gridpoints, 2) evaluated on the host, as the reference
+        # evaluates them (linear_joint_velocity.py:48, linear_joint_acceleration.py:72-73), and the same rows from the samples
+        qs, qss = path_samples(path, gridpoints)
+        return _batch.sampled_rows_batch(np.asarray(gridpoints, dtype=np.float64), qs[None], qss[None], vlim, alim,
+                                         interpolation=interpolation)
+    return _batch.constraint_params_batch(coef[None], breaks, np.asarray(gridpoints, dtype=np.float64), vlim, alim, interpolation)
 
 
 class JointVelocityConstraint(LinearConstraint):

@@ -11,8 +11,9 @@
 // through the reference's full Seidel iteration (group_lp2d / group_lp1d: its decisions and arithmetic, warm-start state
 // carried along as the wrapper object carries it) -- no certificates: they lean on the structure of the generated rows.
 // Missing rows of the last slots hold the disabled row (0, 0, -1), which Seidel never pivots on and never projects.
-// The row traffic is what bounds it: 24 (nC + 2) bytes per stage and pass, 8 consecutive rows per group load.
-// Included by tpr_dense_tu.hip (after tpr_dense_args.hpp).
+// Row traffic: 24 (nC + 2) bytes per stage and pass, 8 consecutive rows per group load; it hides behind the iteration's
+// instruction count, which is what bounds these kernels (DESIGN.md section 3.5).
+// Included by tpr_dense_tu.hip and tpr_sampled_tu.hip (after tpr_dense_args.hpp).
 
 namespace tpr {
 
@@ -20,9 +21,20 @@ namespace tpr {
 template <int D, int L>
 struct DenseStage {
     using C = GroupCfg<D, L>;
-    const double *a, *b, *c, *low, *high;
+    using Args = DenseArgs;
+    const double *a, *b, *c, *low, *high, *deltas;
     int nC;
     double *rowbuf;
+    // trajectory bb of the batch; rb: the group's LDS row mirror
+    __device__ inline void init(const DenseArgs &A, int bb, int gl, double *rb) {
+        const int N = A.N;
+        nC = A.nC;
+        a = A.a + (size_t)bb * (N + 1) * nC; b = A.b + (size_t)bb * (N + 1) * nC; c = A.c + (size_t)bb * (N + 1) * nC;
+        low = A.low + (size_t)bb * 2 * (N + 1); high = A.high + (size_t)bb * 2 * (N + 1);
+        deltas = A.deltas + (size_t)bb * N;
+        rowbuf = rb;
+    }
+    __device__ inline double delta(int i) const { return deltas[i]; }
     template <bool MIRROR>
     __device__ inline void build(Slots<D, L> &R, int gl, int i, double delta, double n0, double n1, double &low0,
                                  double &high0, double &low1, double &high1, bool last, double xcap) const {
@@ -63,12 +75,121 @@ struct DenseStage {
     }
 };
 
+// The same contract with the stage's rows GENERATED from path samples (tpr_sampled_problem): the velocity + acceleration
+// rows of any geometric path, given as q', q'' [N+1][d] at the gridpoints.  The slots hold what second_order_rows_kernel
+// (nblocks = 0) writes into the dense arrays, expression for expression -- [q'_i, -q'_i (| q'_{i+1} + (2 delta) q''_{i+1},
+// -...)], [q'', ...], c = -amax / amin, the +-1e8 box with velocity_xbound's fp32 running bounds, the last stage
+// repeating itself -- so every pass returns the bits of the dense pass on those rows.  Here D is the slot layout
+// (2 + 4 D >= nC) and d the path's dof: under Collocation 2 d rows take the place of 4 D.
+// Loads: a slot reads its q', q'' straight from global memory, consecutive lanes consecutive dofs -- per stage the group
+// touches the 4 d doubles of gridpoints i and i + 1, two short runs of 8 d bytes in each of the two arrays.  No LDS
+// staging: the run of gridpoint i + 1 is the run of gridpoint i one stage later (and the whole trajectory is read again
+// by the forward scan), so three of the four runs of a stage are cache hits either way, and staging would put a second
+// wave barrier and 4 d more LDS doubles per group (q', q'' of both gridpoints) in front of every stage for a load that is already one instruction per
+// slot (DESIGN.md section 3.5).
+template <int D, int L>
+struct SampledStage {
+    using C = GroupCfg<D, L>;
+    using Args = SampledArgs;
+    int dof[C::S];      // dof of an acceleration row, -1 otherwise
+    bool neg[C::S];     // row is the negated half of its +- pair
+    bool nextpt[C::S];  // row is evaluated at s_{i+1} (the Interpolation block)
+    double climit[C::S];
+    const double *qs, *qss, *grid, *vlim;
+    int d;
+    double *rowbuf;
+    __device__ inline void init(const SampledArgs &A, int bb, int gl, double *rb) {
+        d = A.d;
+        const int N = A.N;
+        qs = A.qs + (size_t)bb * (N + 1) * d; qss = A.qss + (size_t)bb * (N + 1) * d;
+        grid = A.grid + ((A.flags & TPR_GRID_PER_TRAJ) ? (size_t)bb * (N + 1) : 0);
+        vlim = (A.flags & TPR_HAS_VELOCITY) ? A.vlim + (size_t)bb * 2 * d : nullptr;
+        const double *alim = (A.flags & TPR_HAS_ACCELERATION) ? A.alim + (size_t)bb * 2 * d : nullptr;
+        const int nacc = A.nC - 2;  // (4 | 2 | 0) d
+        rowbuf = rb;
+#pragma unroll
+        for (int s = 0; s < C::S; ++s) {
+            const int m = s * L + gl - 6;
+            const bool acc = m >= 0 && m < nacc;
+            const int blk = acc ? m / d : 0;
+            dof[s] = acc ? m - blk * d : -1;
+            neg[s] = blk & 1;
+            nextpt[s] = blk >> 1;
+            climit[s] = acc ? ((blk & 1) ? alim[2 * dof[s]] : -alim[2 * dof[s] + 1]) : 0.0;
+        }
+    }
+    __device__ inline double delta(int i) const { return grid[i + 1] - grid[i]; }
+    template <bool MIRROR>
+    __device__ inline void build(Slots<D, L> &R, int gl, int i, double delta, double n0, double n1, double &low0,
+                                 double &high0, double &low1, double &high1, bool last, double xcap) const {
+        const double *q1i = qs + (size_t)i * d, *q2i = qss + (size_t)i * d;
+        low0 = kVarMin; high0 = kVarMax;
+        low1 = kVarMin; high1 = kVarMax;
+        if (vlim) {  // velocity_xbound with the dofs across the group's lanes: min / max of fp32-rounded quotients in any order
+            float sdmin = -kJvelMaxSd, sdmax = kJvelMaxSd;
+            for (int k = gl; k < d; k += L) {
+                const double q1 = q1i[k], vlo = vlim[2 * k], vhi = vlim[2 * k + 1];
+                const double rmax = (q1 > 0 ? vhi : vlo) / q1, rmin = (q1 > 0 ? vlo : vhi) / q1;
+                if (q1 != 0) {
+                    sdmax = (float)(rmax <= (double)sdmax ? rmax : (double)sdmax);
+                    sdmin = (float)(rmin >= (double)sdmin ? rmin : (double)sdmin);
+                }
+            }
+            sdmax = group_min_f32<L>(sdmax);
+            sdmin = group_max_f32<L>(sdmin);
+            const float up = sdmax * sdmax;
+            const double lo = (double)sdmin >= 0.0 ? (double)sdmin : 0.0;
+            const double xlo = lo * lo, xhi = (double)up;
+            low1 = low1 > xlo ? low1 : xlo;
+            high1 = high1 < xhi ? high1 : xhi;
+        }
+        low1 = low1 > -xcap ? low1 : -xcap;
+        high1 = high1 < xcap ? high1 : xcap;
+#pragma unroll
+        for (int s = 0; s < C::S; ++s) {
+            const int vi = s * L + gl;
+            double ra = 0, rb = 0, rc = -1;
+            if (s == 0) {  // the box rows and the x_next pair live in slot 0 (L >= 8)
+                const double ta[6] = {-1.0, 1.0, 0.0, 0.0, last ? 0.0 : -2 * delta, last ? 0.0 : 2 * delta};
+                const double tb[6] = {0.0, 0.0, -1.0, 1.0, last ? 0.0 : -1.0, last ? 0.0 : 1.0};
+                const double tc[6] = {low0, -high0, low1, -high1, last ? -1.0 : n0, last ? -1.0 : -n1};
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    const bool hit = vi == j;
+                    ra = hit ? ta[j] : ra;
+                    rb = hit ? tb[j] : rb;
+                    rc = hit ? tc[j] : rc;
+                }
+            }
+            {
+                const bool acc = dof[s] >= 0;
+                const bool nx = nextpt[s] & !last;  // (the last stage repeats itself: linear_constraint.py:172,177)
+                const int at = (acc ? dof[s] : 0) + (nx ? d : 0);
+                const double q1 = q1i[at], q2 = q2i[at];
+                const double av = nx ? q1 + (2 * delta) * q2 : q1;
+                ra = acc ? (neg[s] ? -av : av) : ra;
+                rb = acc ? (neg[s] ? -q2 : q2) : rb;
+                rc = acc ? climit[s] : rc;
+            }
+            R.a[s] = ra; R.b[s] = rb; R.c[s] = rc;
+            if (MIRROR && vi < C::nV) {
+                rowbuf[vi] = ra; rowbuf[C::nV + vi] = rb; rowbuf[2 * C::nV + vi] = rc;
+            }
+        }
+        if (MIRROR) {  // rows are read back by other lanes of the wave: stores before, loads after, in the memory model too
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+};
+
 constexpr double kDenseNoCap = 1e300;  // "no x box beyond the wrapper's own"
 
 // compute_controllable_sets + compute_parameterization (backward_only: the first alone) -- group_solve_kernel's scans
 // with every LP through the full iteration.
-template <int D, int L>
-__global__ void __launch_bounds__(256) dense_solve_kernel(DenseArgs A) {
+template <int D, int L, class Stage = DenseStage<D, L>>
+__global__ void __launch_bounds__(256) dense_solve_kernel(typename Stage::Args A) {
     using C = GroupCfg<D, L>;
     const int kGroupsPerBlock = blockDim.x / L;
     extern __shared__ double lds[];
@@ -76,13 +197,9 @@ __global__ void __launch_bounds__(256) dense_solve_kernel(DenseArgs A) {
     const int b = blockIdx.x * kGroupsPerBlock + gidx;
     const bool alive0 = b < A.B;
     const int bb = alive0 ? b : A.B - 1;  // idle groups shadow the last trajectory, never store
-    const int N = A.N, nC = A.nC;
-    DenseStage<D, L> T;
-    T.nC = nC;
-    T.a = A.a + (size_t)bb * (N + 1) * nC; T.b = A.b + (size_t)bb * (N + 1) * nC; T.c = A.c + (size_t)bb * (N + 1) * nC;
-    T.low = A.low + (size_t)bb * 2 * (N + 1); T.high = A.high + (size_t)bb * 2 * (N + 1);
-    T.rowbuf = lds + (size_t)gidx * C::kRowBuf;
-    const double *deltas = A.deltas + (size_t)bb * N;
+    const int N = A.N;
+    Stage T;
+    T.init(A, bb, gl, lds + (size_t)gidx * C::kRowBuf);
 
     Slots<D, L> R;
     double *K = A.K + (size_t)bb * 2 * (N + 1);
@@ -105,7 +222,7 @@ __global__ void __launch_bounds__(256) dense_solve_kernel(DenseArgs A) {
     if (writer) { K[2 * N] = kn0; K[2 * N + 1] = kn1; }
     bool failed = false;
     for (int i = N - 1; i >= 0; --i) {
-        const double delta = deltas[i];
+        const double delta = T.delta(i);
         double lo = 0, hi = 0;
         if (!failed) {
             if (isnan(kn0) || isnan(kn1)) { lo = qnan(); hi = qnan(); }
@@ -154,7 +271,7 @@ __global__ void __launch_bounds__(256) dense_solve_kernel(DenseArgs A) {
     while (i < N) {
         if (!rows_ready) {
             k0 = K[2 * (i + 1)]; k1 = K[2 * (i + 1) + 1];
-            delta = deltas[i];
+            delta = T.delta(i);
             double low1, high1;
             T.template build<false>(R, gl, i, delta, k0, k1, low0, high0, low1, high1, false, kDenseNoCap);
             rows_ready = true;
@@ -201,8 +318,8 @@ __global__ void __launch_bounds__(256) dense_solve_kernel(DenseArgs A) {
 }
 
 // compute_feasible_sets (reachability_algorithm.py:131-164): group_feasible_kernel on dense rows.
-template <int D, int L>
-__global__ void __launch_bounds__(256) dense_feasible_kernel(DenseArgs A) {
+template <int D, int L, class Stage = DenseStage<D, L>>
+__global__ void __launch_bounds__(256) dense_feasible_kernel(typename Stage::Args A) {
     using C = GroupCfg<D, L>;
     const int kGroupsPerBlock = blockDim.x / L;
     extern __shared__ double lds[];
@@ -210,13 +327,9 @@ __global__ void __launch_bounds__(256) dense_feasible_kernel(DenseArgs A) {
     const int b = blockIdx.x * kGroupsPerBlock + gidx;
     const bool alive0 = b < A.B;
     const int bb = alive0 ? b : A.B - 1;
-    const int N = A.N, nC = A.nC;
-    DenseStage<D, L> T;
-    T.nC = nC;
-    T.a = A.a + (size_t)bb * (N + 1) * nC; T.b = A.b + (size_t)bb * (N + 1) * nC; T.c = A.c + (size_t)bb * (N + 1) * nC;
-    T.low = A.low + (size_t)bb * 2 * (N + 1); T.high = A.high + (size_t)bb * 2 * (N + 1);
-    T.rowbuf = lds + (size_t)gidx * C::kRowBuf;
-    const double *deltas = A.deltas + (size_t)bb * N;
+    const int N = A.N;
+    Stage T;
+    T.init(A, bb, gl, lds + (size_t)gidx * C::kRowBuf);
     Slots<D, L> R;
     double *Xb = A.X + (size_t)bb * 2 * (N + 1);
     const bool writer = alive0 && gl == 0;
@@ -224,7 +337,7 @@ __global__ void __launch_bounds__(256) dense_feasible_kernel(DenseArgs A) {
     if (A.active) { const int32_t *st = A.active + (size_t)bb * 4; up0 = st[0]; up1 = st[1]; dn0 = st[2]; dn1 = st[3]; }
     for (int i = 0; i <= N; ++i) {
         const bool last = i == N;
-        const double delta = last ? 0.0 : deltas[i];
+        const double delta = last ? 0.0 : T.delta(i);
         double low0, high0, low1, high1;
         T.template build<true>(R, gl, i, delta, -kFeasMaxX, kFeasMaxX, low0, high0, low1, high1, last, kFeasMaxX);
         GroupLp sl = group_lp2d<D, L>(R, T.rowbuf, gl, -1e-9, -1.0, low0, high0, low1, high1, up0, up1);
@@ -240,8 +353,8 @@ __global__ void __launch_bounds__(256) dense_feasible_kernel(DenseArgs A) {
 
 // The two forward scans of TOPPRAsd (desired_duration_algorithm.py:93-142,219-226) on dense rows: group_sd_forward_kernel
 // with the stage rows loaded.  Reads K and the controllability verdict (status) of the backward scan.
-template <int D, int L>
-__global__ void __launch_bounds__(256) dense_sd_forward_kernel(DenseArgs A) {
+template <int D, int L, class Stage = DenseStage<D, L>>
+__global__ void __launch_bounds__(256) dense_sd_forward_kernel(typename Stage::Args A) {
     using C = GroupCfg<D, L>;
     const int kGroupsPerBlock = blockDim.x / L;
     extern __shared__ double lds[];
@@ -249,13 +362,9 @@ __global__ void __launch_bounds__(256) dense_sd_forward_kernel(DenseArgs A) {
     const int b = blockIdx.x * kGroupsPerBlock + gidx;
     const bool alive0 = b < A.B;
     const int bb = alive0 ? b : A.B - 1;
-    const int N = A.N, nC = A.nC;
-    DenseStage<D, L> T;
-    T.nC = nC;
-    T.a = A.a + (size_t)bb * (N + 1) * nC; T.b = A.b + (size_t)bb * (N + 1) * nC; T.c = A.c + (size_t)bb * (N + 1) * nC;
-    T.low = A.low + (size_t)bb * 2 * (N + 1); T.high = A.high + (size_t)bb * 2 * (N + 1);
-    T.rowbuf = lds + (size_t)gidx * C::kRowBuf;
-    const double *deltas = A.deltas + (size_t)bb * N;
+    const int N = A.N;
+    Stage T;
+    T.init(A, bb, gl, lds + (size_t)gidx * C::kRowBuf);
     const double *K = A.K + (size_t)bb * 2 * (N + 1);
     double *xf = A.sd_xf + (size_t)bb * (N + 1), *xl = A.sd_xl + (size_t)bb * (N + 1);
     double *uf = A.sd_uf + (size_t)bb * N, *ul = A.sd_ul + (size_t)bb * N;
@@ -268,7 +377,7 @@ __global__ void __launch_bounds__(256) dense_sd_forward_kernel(DenseArgs A) {
     int st_up0 = 0, st_dn0 = 0;  // (the backward scan of the same call left the state in A.active)
     if (A.active) { st_up0 = A.active[(size_t)bb * 4]; st_dn0 = A.active[(size_t)bb * 4 + 2]; }
     for (int i = 0; i < N; ++i) {
-        const double delta = deltas[i];
+        const double delta = T.delta(i);
         const double k0 = K[2 * (i + 1)], k1 = K[2 * (i + 1) + 1];
         double low0, high0, low1, high1;
         T.template build<false>(R, gl, i, delta, k0, k1, low0, high0, low1, high1, false, kDenseNoCap);
@@ -294,6 +403,20 @@ __global__ void __launch_bounds__(256) dense_sd_forward_kernel(DenseArgs A) {
         if (writer) { uf[i] = u_fast; xf[i + 1] = x_fast; ul[i] = u_slow; xl[i + 1] = x_slow; }
     }
     if (A.active && writer) { A.active[(size_t)bb * 4] = st_up0; A.active[(size_t)bb * 4 + 2] = st_dn0; }
+}
+
+// Host side: launch geometry of one pass, shared by the units that instantiate these kernels.
+template <int D, int L, class Stage = DenseStage<D, L>>
+static int dense_launch(const typename Stage::Args &A, int feasible /* 0 solve, 1 feasible sets, 2 TOPPRAsd forward scans */, hipStream_t stream) {
+    using C = GroupCfg<D, L>;
+    const int threads = shrink_block_to_batch(256, A.B, L);  // small batches: more, smaller blocks
+    const int groups = threads / L;
+    const size_t lds = (size_t)groups * C::kRowBuf * sizeof(double);
+    const dim3 grid((A.B + groups - 1) / groups), block(threads);
+    if (feasible == 1) hipLaunchKernelGGL((dense_feasible_kernel<D, L, Stage>), grid, block, lds, stream, A);
+    else if (feasible == 2) hipLaunchKernelGGL((dense_sd_forward_kernel<D, L, Stage>), grid, block, lds, stream, A);
+    else hipLaunchKernelGGL((dense_solve_kernel<D, L, Stage>), grid, block, lds, stream, A);
+    return 0;
 }
 
 }  // namespace tpr

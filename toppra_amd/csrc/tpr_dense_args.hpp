@@ -16,4 +16,13 @@ struct DenseArgs {
     // TOPPRAsd: the fastest / slowest forward profiles x [B][N+1], u [B][N] (dense_sd_forward_kernel reads K and status)
     double *sd_xf, *sd_uf, *sd_xl, *sd_ul;
 };
+
+// The same passes with the rows generated from path samples (tpr_sampled_problem): a, b, c, low, high, deltas stay null,
+// nC = 2 + (4 | 2 | 0) d by flags.
+struct SampledArgs : DenseArgs {
+    int d;
+    const double *grid;        // [N+1], or [B][N+1] with TPR_GRID_PER_TRAJ
+    const double *qs, *qss;    // [B][N+1][d]
+    const double *vlim, *alim; // [B][d][2] (null without the constraint)
+};
 }  // namespace tpr

@@ -867,7 +867,7 @@ int tpr_reachable_sets_dense_batch(const tpr_dense_problem *p, const double *sdm
     Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
     if (int rc = S.failed()) return rc;
     tpr::DenseArgs A = stage_dense(p, S);
-    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel, sdmin, sdmax, L, X);
+    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::DenseArgs>, sdmin, sdmax, L, X);
 }
 
 int tpr_controllable_sets_dense_batch(const tpr_dense_problem *p, const double *sdmin, const double *sdmax, double *K,
@@ -1124,7 +1124,7 @@ int tpr_param_spline_batch(const tpr_problem *p, const double *sd, double *knot_
     if (B > 0) {
         K.bcv0 = K.way + B * (N + 1) * d;
         K.bcv1 = K.bcv0 + B * d;
-        hipLaunchKernelGGL(tpr::param_spline_knots_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, S.stream, K);
+        hipLaunchKernelGGL(tpr::param_spline_knots_kernel<tpr::ParamSplineArgs>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, S.stream, K);
         tpr::SplineArgs A{};
         A.B = p->B; A.m = p->N + 1; A.d = p->d; A.knots_per_path = 1; A.bc0 = tpr::kBcFirst; A.bc1 = tpr::kBcFirst;
         A.knots = K.tk; A.way = K.way; A.bcv0 = K.bcv0; A.bcv1 = K.bcv1; A.coef = dcoef;
@@ -1232,6 +1232,36 @@ int tpr_lp2d_batch(int n, int nrows, const double *v, const double *a, const dou
 // ---- dense rows of second-order / torque constraints built on the GPU: tpr_rows.hip.inc (host side only here; the kernels
 // are a unit of their own, csrc/tpr_rows_tu.hip) -------------------------------------------------------------------------
 #include "tpr_rows_args.hpp"
+namespace {
+// The second-order blocks of a row entry staged into its argument block (A.nC holds the rows before them on entry, the
+// stage's rows on return): shared by tpr_second_order_rows_batch and tpr_sampled_rows_batch.
+int stage_row_blocks(tpr::RowsArgs &A, Staging &S, int nblocks, const tpr_second_order_block *blocks, int dof, const char *who) {
+    const size_t B = (size_t)A.B, pts = B * ((size_t)A.N + 1);
+    A.nblocks = nblocks;
+    for (int j = 0; j < nblocks; ++j) {
+        const tpr_second_order_block &U = blocks[j];
+        tpr::RowsBlock &K = A.blk[j];
+        const int fkind = U.flags & (TPR_SO_F_SHARED | TPR_SO_F_PER_TRAJ | TPR_SO_F_PER_POINT);
+        const int gkind = U.flags & (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT);
+        if (U.p < 1 || !U.w0 || !U.wa || !U.wb || !U.g) return fail(TPR_E_BADARG, "second-order block: p >= 1 and w0, wa, wb, g are required");
+        if ((fkind & (fkind - 1)) || gkind == (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT)) return fail(TPR_E_BADARG, "second-order block: one F layout and one g layout");
+        if (fkind ? (!U.F || U.m < 1) : (U.F != nullptr)) return fail(TPR_E_BADARG, "second-order block: F [m][p] with an F flag, NULL for the signed identity");
+        if (U.friction && U.p != dof) return fail(TPR_E_BADARG, "second-order block: dry friction needs p == d");
+        K.p = U.p; K.m = fkind ? U.m : 2 * U.p; K.flags = U.flags; K.col0 = A.nC; K.lds0 = A.wsum;
+        const size_t m = (size_t)K.m, w = (size_t)U.p;
+        if (m > 122) return fail(TPR_E_UNSUPPORTED, "second-order block: more than 122 rows per stage");
+        A.nC += ((U.flags & TPR_SO_INTERPOLATION) ? 2 : 1) * K.m;
+        A.wsum += 3 * U.p;
+        if (A.nC > 122 || A.wsum > 3 * 1024) return fail(TPR_E_UNSUPPORTED, std::string(who) + ": more than 122 rows per stage (incl. the two x_next rows), or blocks wider than 1024 in all");
+        K.w0 = S.in(U.w0, pts * w); K.wa = S.in(U.wa, pts * w); K.wb = S.in(U.wb, pts * w);
+        K.F = S.in(U.F, (fkind == TPR_SO_F_PER_POINT ? pts : fkind == TPR_SO_F_PER_TRAJ ? B : 1) * m * w);
+        K.g = S.in(U.g, (gkind == TPR_SO_G_PER_POINT ? pts : gkind == TPR_SO_G_PER_TRAJ ? B : 1) * m);
+        K.friction = S.in(U.friction, B * w);
+    }
+    return TPR_E_OK;
+}
+}  // namespace
+
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_rows_launch(const tpr::RowsArgs *, double *, double *, double *, double *, double *,
                                                              double *, hipStream_t);
@@ -1268,27 +1298,7 @@ int tpr_second_order_rows_batch(const tpr_problem *p, int nblocks, const tpr_sec
     A.vlim = S.in(p->vlim, B * d * 2);
     A.alim = S.in(p->alim, B * d * 2);
     A.nC = rows_per_lp(p);
-    A.nblocks = nblocks;
-    for (int j = 0; j < nblocks; ++j) {
-        const tpr_second_order_block &U = blocks[j];
-        tpr::RowsBlock &K = A.blk[j];
-        const int fkind = U.flags & (TPR_SO_F_SHARED | TPR_SO_F_PER_TRAJ | TPR_SO_F_PER_POINT);
-        const int gkind = U.flags & (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT);
-        if (U.p < 1 || !U.w0 || !U.wa || !U.wb || !U.g) return fail(TPR_E_BADARG, "second-order block: p >= 1 and w0, wa, wb, g are required");
-        if ((fkind & (fkind - 1)) || gkind == (TPR_SO_G_PER_TRAJ | TPR_SO_G_PER_POINT)) return fail(TPR_E_BADARG, "second-order block: one F layout and one g layout");
-        if (fkind ? (!U.F || U.m < 1) : (U.F != nullptr)) return fail(TPR_E_BADARG, "second-order block: F [m][p] with an F flag, NULL for the signed identity");
-        if (U.friction && U.p != p->d) return fail(TPR_E_BADARG, "second-order block: dry friction needs p == d");
-        K.p = U.p; K.m = fkind ? U.m : 2 * U.p; K.flags = U.flags; K.col0 = A.nC; K.lds0 = A.wsum;
-        const size_t m = (size_t)K.m, w = (size_t)U.p;
-        if (m > 122) return fail(TPR_E_UNSUPPORTED, "second-order block: more than 122 rows per stage");
-        A.nC += ((U.flags & TPR_SO_INTERPOLATION) ? 2 : 1) * K.m;
-        A.wsum += 3 * U.p;
-        if (A.nC > 122 || A.wsum > 3 * 1024) return fail(TPR_E_UNSUPPORTED, "tpr_second_order_rows_batch: more than 122 rows per stage (incl. the two x_next rows), or blocks wider than 1024 in all");
-        K.w0 = S.in(U.w0, pts * w); K.wa = S.in(U.wa, pts * w); K.wb = S.in(U.wb, pts * w);
-        K.F = S.in(U.F, (fkind == TPR_SO_F_PER_POINT ? pts : fkind == TPR_SO_F_PER_TRAJ ? B : 1) * m * w);
-        K.g = S.in(U.g, (gkind == TPR_SO_G_PER_POINT ? pts : gkind == TPR_SO_G_PER_TRAJ ? B : 1) * m);
-        K.friction = S.in(U.friction, B * w);
-    }
+    if (int rc = stage_row_blocks(A, S, nblocks, blocks, p->d, "tpr_second_order_rows_batch")) return rc;
     const size_t nC = (size_t)A.nC;
     double *da = S.out(a, pts * nC), *db = S.out(b, pts * nC), *dc = S.out(c, pts * nC);
     double *dlow = S.out(low, pts * 2), *dhigh = S.out(high, pts * 2), *ddel = S.out(deltas, B * (size_t)p->N);
@@ -1296,6 +1306,185 @@ int tpr_second_order_rows_batch(const tpr_problem *p, int nblocks, const tpr_sec
     if (pts > 0) {
         const int rc = tpr_tu_rows_launch(&A, da, db, dc, dlow, dhigh, ddel, S.stream);
         if (rc != 0) return fail(TPR_E_UNSUPPORTED, rc == -1 ? "tpr_second_order_rows_batch: one gridpoint's coefficients do not fit the LDS" : "tpr_second_order_rows_batch: more than 65535 tiles of gridpoints");
+    }
+    return S.finish();
+}
+}  // extern "C"
+
+// ---- any geometric path: the path given as samples at the gridpoints (tpr_sampled_problem) -------------------------------
+// The dense-row passes with SampledStage in place of DenseStage (csrc/tpr_sampled_tu.hip), the row kernel and the spline
+// parametrizer's knot kernel with a sample source.
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_sampled_launch(const tpr::SampledArgs *, int, hipStream_t);
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_sampled_rows_launch(const tpr::SampledRowsArgs *, double *, double *, double *,
+                                                                                double *, double *, double *, hipStream_t);
+namespace {
+int sampled_rows_per_lp(const tpr_sampled_problem *p) {
+    return 2 + ((p->flags & TPR_HAS_ACCELERATION) ? ((p->flags & TPR_ACC_INTERPOLATION) ? 4 : 2) * p->d : 0);
+}
+// solver: the fused passes (rows across lanes: nC <= 122), else the row / parametrizer entries
+int check_sampled(const tpr_sampled_problem *p, bool solver) {
+    if (default_device() < 0) return fail(TPR_E_HIP, "tpr_init() has not succeeded");
+    if (!p) return fail(TPR_E_BADARG, "null sampled problem");
+    if (p->B < 0 || p->N < 1) return fail(TPR_E_BADARG, "sampled problem: B >= 0, N >= 1");
+    if (p->d < 1 || p->d > TPR_MAX_DOF) return fail(TPR_E_UNSUPPORTED, "sampled problem: dof must be in [1, TPR_MAX_DOF]");
+    if (!p->grid || !p->qs || !p->qss) return fail(TPR_E_BADARG, "sampled problem: grid, qs, qss are required");
+    if ((p->flags & TPR_HAS_VELOCITY) && !p->vlim) return fail(TPR_E_BADARG, "TPR_HAS_VELOCITY without vlim");
+    if ((p->flags & TPR_HAS_ACCELERATION) && !p->alim) return fail(TPR_E_BADARG, "TPR_HAS_ACCELERATION without alim");
+    if (solver && sampled_rows_per_lp(p) > 122)
+        return fail(TPR_E_UNSUPPORTED, "sampled problem: more than 122 rows per stage (2 + 4 d under Interpolation: d <= 30; Collocation: d <= 32)");
+    return TPR_E_OK;
+}
+tpr::SampledArgs stage_sampled(const tpr_sampled_problem *p, Staging &S) {
+    tpr::SampledArgs A{};
+    const size_t B = (size_t)p->B, N = (size_t)p->N, d = (size_t)p->d;
+    A.B = p->B; A.N = p->N; A.d = p->d; A.flags = p->flags; A.nC = sampled_rows_per_lp(p);
+    A.grid = S.in(p->grid, ((p->flags & TPR_GRID_PER_TRAJ) ? B : 1) * (N + 1));
+    A.qs = S.in(p->qs, B * (N + 1) * d); A.qss = S.in(p->qss, B * (N + 1) * d);
+    A.vlim = S.in(p->vlim, B * d * 2); A.alim = S.in(p->alim, B * d * 2);
+    A.active = S.out(p->active, B * 4, true);
+    return A;
+}
+}  // namespace
+
+extern "C" {
+int tpr_sampled_problem_bytes(void) { return (int)sizeof(tpr_sampled_problem); }
+
+int tpr_solve_sampled_batch(const tpr_sampled_problem *p, const tpr_result *r, void *stream_) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (!r || !r->K) return fail(TPR_E_BADARG, "sampled solve: r->K is required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::SampledArgs A = stage_sampled(p, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
+    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_sampled_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled solve: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_solve_desired_duration_sampled_batch(const tpr_sampled_problem *p, const double *desired, double atol, const tpr_result *r,
+                                             double *alpha, void *stream_) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::SampledArgs A = stage_sampled(p, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    const double *ddes = S.in(desired, B);
+    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
+    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    double *dalpha = S.out(alpha, B);
+    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
+    if (int rc = S.failed()) return rc;
+    if (!dalpha) dalpha = W.extra;
+    if (A.B > 0) {
+        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
+        A.backward_only = 1;
+        if (tpr_tu_sampled_launch(&A, 0, S.stream) != 0 || tpr_tu_sampled_launch(&A, 2, S.stream) != 0)
+            return fail(TPR_E_UNSUPPORTED, "sampled TOPPRAsd: no kernel for this row count");
+        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, A.grid, ddes, nullptr, nullptr, nullptr, nullptr, A.status,
+                           dsd2, dsd, du, dalpha, A.status};
+        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
+    }
+    return S.finish();
+}
+
+int tpr_controllable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *K,
+                                        void *stream_) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::SampledArgs A = stage_sampled(p, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
+    A.K = S.out(K, B * (N + 1) * 2);
+    A.backward_only = 1;
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_sampled_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled controllable sets: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_feasible_sets_sampled_batch(const tpr_sampled_problem *p, double *X, void *stream_) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (!X) return fail(TPR_E_BADARG, "X is required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::SampledArgs A = stage_sampled(p, S);
+    A.X = S.out(X, (size_t)p->B * ((size_t)p->N + 1) * 2);
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_sampled_launch(&A, 1, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled feasible sets: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_reachable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *L, double *X,
+                                     void *stream_) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::SampledArgs A = stage_sampled(p, S);
+    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::SampledArgs>, sdmin, sdmax, L, X);
+}
+
+int tpr_sampled_rows_batch(const tpr_sampled_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a, double *b,
+                           double *c, double *low, double *high, double *deltas, double *xbound, void *stream_) {
+    if (int rc = check_sampled(p, false)) return rc;
+    if (nblocks < 0 || nblocks > TPR_SO_MAX_BLOCKS || (nblocks > 0 && !blocks))
+        return fail(TPR_E_BADARG, "tpr_sampled_rows_batch: 0 <= nblocks <= TPR_SO_MAX_BLOCKS");
+    if (!a || !b || !c || !low || !high) return fail(TPR_E_BADARG, "tpr_sampled_rows_batch: a, b, c, low, high are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t B = (size_t)p->B, d = (size_t)p->d, pts = B * ((size_t)p->N + 1);
+    tpr::SampledRowsArgs A{};
+    A.B = p->B; A.d = p->d; A.nseg = 0; A.N = p->N; A.flags = p->flags;
+    A.grid = S.in(p->grid, ((p->flags & TPR_GRID_PER_TRAJ) ? B : 1) * ((size_t)p->N + 1));
+    A.qs = S.in(p->qs, pts * d); A.qss = S.in(p->qss, pts * d);
+    A.vlim = S.in(p->vlim, B * d * 2);
+    A.alim = S.in(p->alim, B * d * 2);
+    A.nC = sampled_rows_per_lp(p);
+    if (int rc = stage_row_blocks(A, S, nblocks, blocks, p->d, "tpr_sampled_rows_batch")) return rc;
+    const size_t nC = (size_t)A.nC;
+    double *da = S.out(a, pts * nC), *db = S.out(b, pts * nC), *dc = S.out(c, pts * nC);
+    double *dlow = S.out(low, pts * 2), *dhigh = S.out(high, pts * 2), *ddel = S.out(deltas, B * (size_t)p->N);
+    A.xbound = S.out(xbound, pts * 2);
+    if (int rc = S.failed()) return rc;
+    if (pts > 0) {
+        const int rc = tpr_tu_sampled_rows_launch(&A, da, db, dc, dlow, dhigh, ddel, S.stream);
+        if (rc != 0) return fail(TPR_E_UNSUPPORTED, rc == -1 ? "tpr_sampled_rows_batch: one gridpoint's coefficients do not fit the LDS" : "tpr_sampled_rows_batch: more than 65535 tiles of gridpoints");
+    }
+    return S.finish();
+}
+
+int tpr_param_spline_samples_batch(const tpr_sampled_problem *p, const double *sd, double *knot_times, int32_t *counts,
+                                   double *coef_t, void *stream_) {
+    if (default_device() < 0) return fail(TPR_E_HIP, "tpr_init() has not succeeded");
+    if (!p || p->B < 0 || p->N < 1 || p->d < 1 || !p->grid || !p->q || !p->qs || !sd || !knot_times || !counts || !coef_t)
+        return fail(TPR_E_BADARG, "bad sampled spline-parametrizer arguments (grid, q, qs, sd and the outputs are required)");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->q, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t B = (size_t)p->B, N = (size_t)p->N, d = (size_t)p->d;
+    tpr::ParamSamplesArgs K{};
+    K.B = p->B; K.N = p->N; K.d = p->d; K.nseg = 0; K.flags = p->flags;
+    K.grid = S.in(p->grid, ((p->flags & TPR_GRID_PER_TRAJ) ? B : 1) * (N + 1));
+    K.q = S.in(p->q, B * (N + 1) * d); K.qs = S.in(p->qs, B * (N + 1) * d);
+    K.sd = S.in(sd, B * (N + 1));
+    K.tk = S.out(knot_times, B * (N + 1));
+    K.counts = S.out(counts, B);
+    double *dcoef = S.out(coef_t, B * 4 * N * d);
+    K.way = S.scratch<double>(B * (N + 1) * d + 2 * B * d);
+    if (int rc = S.failed()) return rc;
+    if (B > 0) {
+        K.bcv0 = K.way + B * (N + 1) * d;
+        K.bcv1 = K.bcv0 + B * d;
+        hipLaunchKernelGGL(tpr::param_spline_knots_kernel<tpr::ParamSamplesArgs>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, S.stream, K);
+        tpr::SplineArgs A{};
+        A.B = p->B; A.m = p->N + 1; A.d = p->d; A.knots_per_path = 1; A.bc0 = tpr::kBcFirst; A.bc1 = tpr::kBcFirst;
+        A.knots = K.tk; A.way = K.way; A.bcv0 = K.bcv0; A.bcv1 = K.bcv1; A.coef = dcoef;
+        if (int rc = launch_spline_fit(A, K.counts, S)) return rc;
     }
     return S.finish();
 }

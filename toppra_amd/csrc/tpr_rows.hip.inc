@@ -26,6 +26,7 @@
 // once) and walks the tile's gridpoints, so consecutive threads store consecutive addresses -- 256 / nC whole stages, up to
 // 2 KB contiguous, per store instruction.
 #pragma once
+#include <type_traits>
 #include "tpr_device.hpp"
 #include "tpr_rows_args.hpp"
 
@@ -50,8 +51,12 @@ __device__ __forceinline__ Traj rows_traj(const RowsArgs &A, int b) {
 // np.sign
 __device__ __forceinline__ double sign_of(double v) { return v > 0 ? 1.0 : (v < 0 ? -1.0 : (v == 0 ? 0.0 : v)); }
 
-static __global__ void __launch_bounds__(256)
-second_order_rows_kernel(RowsArgs A, int tile, int cap, double *a, double *b, double *c, double *low, double *high, double *deltas) {
+// The body of the row kernels.  Args = RowsArgs: q', q'' from the spline table (second_order_rows_kernel); Args = SampledRowsArgs:
+// q', q'' are the caller's samples of any geometric path, which phase 1 copies (sampled_rows_kernel) -- everything after phase 1
+// is shared.
+template <class Args>
+__device__ __forceinline__ void
+rows_tile(const Args &A, int tile, int cap, double *a, double *b, double *c, double *low, double *high, double *deltas) {
     // q1 [(cap + 1) d], q2 [(cap + 1) d], delta [cap], alim [2 d], w [(cap + 1) wsum]; cap = the tile the LDS was sized for
     extern __shared__ double rows_lds[];
     const int bt = blockIdx.x, tid = threadIdx.x;
@@ -60,10 +65,16 @@ second_order_rows_kernel(RowsArgs A, int tile, int cap, double *a, double *b, do
     const int i0 = blockIdx.y * tile;
     const int npts = N + 1 - i0 < tile ? N + 1 - i0 : tile;
     double *q1s = rows_lds, *q2s = q1s + (cap + 1) * d, *dl = q2s + (cap + 1) * d, *al = dl + cap, *ws = al + 2 * d;
+    constexpr bool kSampled = std::is_same<Args, SampledRowsArgs>::value;
     // phase 1: q', q'' (tpr_device.hpp::cubic_d1_d2, the expressions of params_tile_kernel)
     for (int idx = tid; idx < (npts + 1) * d; idx += blockDim.x) {
         const int pp = idx / d, k = idx - pp * d, i = i0 + pp;
-        if (i <= N) {
+        if constexpr (kSampled) {
+            if (i <= N) {
+                const size_t at = ((size_t)bt * (N + 1) + i0) * d + idx;
+                q1s[idx] = A.qs[at]; q2s[idx] = A.qss[at];
+            }
+        } else if (i <= N) {
             const double s = T.grid[i];
             const int j = find_segment(T.breaks, T.nseg, s);
             const double t = s - T.breaks[j];
@@ -179,8 +190,22 @@ second_order_rows_kernel(RowsArgs A, int tile, int cap, double *a, double *b, do
         const size_t g = pt0 + tid;
         low[2 * g] = kVarMin; low[2 * g + 1] = low1;
         high[2 * g] = kVarMax; high[2 * g + 1] = high1;
+        if constexpr (kSampled) {
+            // the constraint's own bound (None without a velocity constraint: the box is written in its place)
+            if (A.xbound) { A.xbound[2 * g] = T.has_vel ? xlo : kVarMin; A.xbound[2 * g + 1] = T.has_vel ? xhi : kVarMax; }
+        }
         if (deltas && i0 + tid < N) deltas[(size_t)bt * N + i0 + tid] = dl[tid];
     }
+}
+
+static __global__ void __launch_bounds__(256)
+second_order_rows_kernel(RowsArgs A, int tile, int cap, double *a, double *b, double *c, double *low, double *high, double *deltas) {
+    rows_tile(A, tile, cap, a, b, c, low, high, deltas);
+}
+// ... for a path given as samples at the gridpoints (tpr_sampled_rows_batch)
+static __global__ void __launch_bounds__(256)
+sampled_rows_kernel(SampledRowsArgs A, int tile, int cap, double *a, double *b, double *c, double *low, double *high, double *deltas) {
+    rows_tile(A, tile, cap, a, b, c, low, high, deltas);
 }
 
 // SplineInterpolator.__call__(grid, order) for order 0, 1, 2 (interpolator.py:423-430): q in scipy PPoly's evaluation order

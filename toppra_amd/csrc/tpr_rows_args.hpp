@@ -23,6 +23,12 @@ struct RowsArgs {
     RowsBlock blk[kRowsMaxBlocks];
 };
 
+// The same rows for a path given as samples at the gridpoints (tpr_sampled_rows_batch): coef / breaks stay null, nseg 0.
+struct SampledRowsArgs : RowsArgs {
+    const double *qs, *qss;  // [B][N+1][d]
+    double *xbound;          // [B][N+1][2] or null: the velocity constraint's own x bound
+};
+
 struct PathEvalArgs {
     int B, d, nseg, N, flags;
     const double *coef, *breaks, *grid;

@@ -193,6 +193,11 @@ struct ParamSplineArgs {
     int32_t *counts;   // [B] kept gridpoints
 };
 
+// The same for a path given as samples at the gridpoints (tpr_param_spline_samples_batch): coef / breaks stay null.
+struct ParamSamplesArgs : ParamSplineArgs {
+    const double *q, *qs;  // [B][N+1][d]: path(grid), path(grid, 1)
+};
+
 // q(s) in scipy's power-basis order (PPoly.__call__)
 __device__ __forceinline__ double cubic_d0(double c0, double c1, double c2, double c3, double x) {
     return ((c3 + c2 * x) + c1 * (x * x)) + c0 * ((x * x) * x);
@@ -200,7 +205,10 @@ __device__ __forceinline__ double cubic_d0(double c0, double c1, double c2, doub
 
 // One thread per trajectory: the time stamps of :176-186 (a sequential sum; a gridpoint reached in less
 // than TINY seconds is dropped), then the waypoints and the clamped-end derivatives.
-__global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs A) {
+// Args = ParamSamplesArgs: the kept samples are copied where the cubic is evaluated, the end derivatives are the samples'.
+template <class Args>
+__global__ void __launch_bounds__(64) param_spline_knots_kernel(Args A) {
+    constexpr bool kSampled = std::is_same<Args, ParamSamplesArgs>::value;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= A.B) return;
     const int N = A.N, d = A.d, nseg = A.nseg;
@@ -210,7 +218,12 @@ __global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs 
     const double *cf = A.coef + (size_t)b * 4 * nseg * d;
     double *tk = A.tk + (size_t)b * (N + 1);
     double *way = A.way + (size_t)b * (N + 1) * d;
-    auto put = [&](int slot, double s) {
+    auto put = [&](int slot, int i) {
+        if constexpr (kSampled) {
+            for (int k = 0; k < d; ++k) way[(size_t)slot * d + k] = A.q[((size_t)b * (N + 1) + i) * d + k];
+            return;
+        }
+        const double s = ss[i];
         const int j = find_segment(breaks, nseg, s);
         const double x = s - breaks[j];
         for (int k = 0; k < d; ++k)
@@ -220,7 +233,7 @@ __global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs 
     int cnt = 1;
     double t = 0.0;
     tk[0] = 0.0;
-    put(0, ss[0]);
+    put(0, 0);
     for (int i = 1; i <= N; ++i) {
         const double sd_avg = (v[i - 1] + v[i]) / 2;
         // (a trajectory that could not be parameterized has NaN velocities: its time stamps -- and with them its
@@ -229,7 +242,7 @@ __global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs 
         t = t + delta_t;
         if (delta_t < kPyTiny) continue;  // np.delete(t_grid, skip): the running time keeps the skipped step
         tk[cnt] = t;
-        put(cnt, ss[i]);
+        put(cnt, i);
         cnt += 1;
     }
     for (int i = cnt; i <= N; ++i) {  // rectangular padding (never evaluated: counts says so)
@@ -238,6 +251,13 @@ __global__ void __launch_bounds__(64) param_spline_knots_kernel(ParamSplineArgs 
     }
     A.counts[b] = cnt;
     // clamped ends: path(path_interval[0/1], 1) * velocities[0/-1]; the path interval is the spline's own
+    if constexpr (kSampled) {  // (the gridpoints span the path interval)
+        for (int k = 0; k < d; ++k) {
+            A.bcv0[(size_t)b * d + k] = A.qs[(size_t)b * (N + 1) * d + k] * v[0];
+            A.bcv1[(size_t)b * d + k] = A.qs[((size_t)b * (N + 1) + N) * d + k] * v[N];
+        }
+        return;
+    }
     const double s0 = breaks[0], s1 = breaks[nseg];
     for (int e = 0; e < 2; ++e) {
         const double s = e ? s1 : s0;

@@ -1,11 +1,11 @@
-"""Geometric paths: the subset of toppra/interpolator.py the hot path consumes.
+"""Geometric paths: the path classes of toppra/interpolator.py (``SimplePath`` lives in simplepath.py, as in the reference).
 
 ``SplineInterpolator`` keeps the reference's constructor and call signature
 (interpolator.py:360-430); the fit is scipy's ``CubicSpline`` on the host (a "next" row of
 SURVEY.md section 8f), and the kernels read its coefficient tensor ``cspl.c`` / ``cspl.x``.
 """
 import numpy as np
-from scipy.interpolate import CubicSpline
+from scipy.interpolate import CubicSpline, UnivariateSpline
 
 
 class AbstractGeometricPath(object):
@@ -72,6 +72,101 @@ class SplineInterpolator(AbstractGeometricPath):
         if np.isscalar(self._q_waypoints[0]):
             return 1
         return self._q_waypoints[0].shape[0]
+
+
+class UnivariateSplineInterpolator(AbstractGeometricPath):
+    """Smoothing cubic spline through the waypoints: one scipy ``UnivariateSpline`` per joint, in the public lists ``uspl``,
+    ``uspld``, ``uspldd`` (the spline and its first two derivatives), as the reference's class of this name has them.  The
+    path positions must start at 0.  A host-side interface mirror; the solver reads the path through its samples."""
+
+    def __init__(self, ss_waypoints, waypoints):
+        self.ss_waypoints = np.array(ss_waypoints)
+        points = np.array(waypoints)
+        if self.ss_waypoints[0] != 0:
+            raise AssertionError("First index must equals zero.")
+        if len(points) != len(self.ss_waypoints):
+            raise AssertionError("%d path positions for %d waypoints" % (len(self.ss_waypoints), len(points)))
+        columns = [points] if points.ndim == 1 else list(points.T)  # a flat list of waypoints is one joint
+        self._points = points
+        self.uspl = [UnivariateSpline(self.ss_waypoints, column) for column in columns]
+        self.uspld = [spl.derivative() for spl in self.uspl]
+        self.uspldd = [spl.derivative() for spl in self.uspld]
+
+    @property
+    def dof(self):
+        return len(self.uspl)
+
+    @property
+    def path_interval(self):
+        return [self.ss_waypoints[0], self.ss_waypoints[-1]]
+
+    def __call__(self, ss_sam, order=0):
+        splines = (self.uspl, self.uspld, self.uspldd)[order] if order in (0, 1, 2) else []  # (another order: an empty array)
+        return np.array([spl(ss_sam) for spl in splines]).T
+
+    def eval(self, ss_sam):
+        return self(ss_sam, 0)
+
+    def evald(self, ss_sam):
+        return self(ss_sam, 1)
+
+    def evaldd(self, ss_sam):
+        return self(ss_sam, 2)
+
+
+class PolynomialPath(AbstractGeometricPath):
+    """Polynomial path: joint i is ``coeff[i, 0] + coeff[i, 1] s + coeff[i, 2] s^2 + ...`` on [s_start, s_end]; a 1-d
+    ``coeff`` is a single joint; the samples of a single joint come back flat, [n], also for a 2-d ``coeff`` of one row.  The public surface of the reference's class of this name
+    (``coeff``, ``s_start``, ``s_end``, ``__call__``, ``eval`` / ``evald`` / ``evaldd``, ``dof``, ``duration``,
+    ``path_interval``), evaluated by ``numpy.polynomial.Polynomial`` and its ``deriv()`` so the samples are the reference's."""
+
+    def __init__(self, coeff, s_start=0.0, s_end=1.0):
+        self.s_start, self.s_end = s_start, s_end
+        self.coeff = np.atleast_2d(coeff)
+        # _tables[order][joint]
+        self._tables = [[np.polynomial.Polynomial(row) for row in self.coeff]]
+        for _ in range(2):
+            self._tables.append([poly.deriv() for poly in self._tables[-1]])
+        self.poly, self.polyd, self.polydd = self._tables
+
+    def __call__(self, path_positions, order=0):
+        if order not in (0, 1, 2):
+            raise ValueError("Invalid order %s" % order)
+        values = np.array([poly(np.array(path_positions)) for poly in self._tables[order]])
+        return values.flatten() if self.dof == 1 else values.T
+
+    def eval(self, ss_sam):
+        return self(ss_sam, 0)
+
+    def evald(self, ss_sam):
+        return self(ss_sam, 1)
+
+    def evaldd(self, ss_sam):
+        return self(ss_sam, 2)
+
+    @property
+    def dof(self):
+        return len(self._tables[0])
+
+    @property
+    def duration(self):
+        return self.s_end - self.s_start
+
+    @property
+    def path_interval(self):
+        return np.array([self.s_start, self.s_end])
+
+    # the reference's deprecated accessors
+    get_dof = lambda self: self.dof  # noqa: E731
+    get_duration = lambda self: self.duration  # noqa: E731
+    get_path_interval = lambda self: self.path_interval  # noqa: E731
+
+
+def path_samples(path, gridpoints, orders=(1, 2)):
+    """``path(gridpoints, order)`` as [N+1, dof] fp64 arrays for the requested orders: what the sampled entries of the library
+    take for a path without a cubic-spline table (a single joint's flat result becomes one column)."""
+    grid = np.asarray(gridpoints, dtype=np.float64)
+    return [np.ascontiguousarray(np.asarray(path(grid, o), dtype=np.float64).reshape(len(grid), -1)) for o in orders]
 
 
 def spline_tables(path):

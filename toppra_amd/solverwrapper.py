@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi, batch
-from .interpolator import spline_tables
+from .interpolator import path_samples, spline_tables
 
 
 def available_solvers(output_msg=True):
@@ -229,7 +229,9 @@ class hipDenseSeidelWrapper(SolverWrapper):
     from pass to pass as the reference object carries it.
     TOPPRAsd and reachable sets run here too."""
 
-    def __init__(self, constraint_list, path, path_discretization, solve_lp1d=1):
+    def __init__(self, constraint_list, path, path_discretization, solve_lp1d=1, active=None):
+        """``active``: an int32 [1, 4] warm-start state to share with another wrapper of the same problem (updated in place);
+        None = this object's own, zero like a fresh reference object's."""
         self.constraints = constraint_list
         self.path = path
         self.path_discretization = np.array(path_discretization, dtype=np.float64)
@@ -249,7 +251,7 @@ class hipDenseSeidelWrapper(SolverWrapper):
         self._solve_lp1d = int(solve_lp1d)
         # warm-start state of the two LP "solvers", as in the reference object: every pass and every per-stage call reads
         # and updates it (tpr_dense_problem.active), so a sequence of calls on ONE instance pivots in the reference's order
-        self._active = np.zeros((1, 4), dtype=np.int32)
+        self._active = np.zeros((1, 4), dtype=np.int32) if active is None else active
         self._active_up, self._active_down = self._active[0, 0:2], self._active[0, 2:4]
 
     def controllable_sets(self, sdmin, sdmax):
@@ -320,6 +322,79 @@ class hipDenseSeidelWrapper(SolverWrapper):
                                                        np.array([sd_end ** 2], dtype=np.float64), atol, active=self._active,
                                                        squared=True)
         return {k: v[0] for k, v in out.items()}
+
+
+class hipSampledSeidelWrapper(SolverWrapper):
+    """seidelWrapper for velocity + acceleration limits on ANY geometric path (SimplePath, PolynomialPath,
+    UnivariateSplineInterpolator, a user's own ``AbstractGeometricPath``): the path is evaluated on the host at the gridpoints,
+    as the reference's constraints evaluate it -- ``path(gridpoints, 1)`` and ``path(gridpoints, 2)`` are all they read --
+    and every pass runs on the fused sampled entries of the library (tpr_*_sampled_batch: a stage's rows produced in
+    registers from the samples, the reference's full Seidel iteration).  The object's warm-start state is carried from pass to
+    pass as in :class:`hipDenseSeidelWrapper`.  Other constraint lists on such a path go through that class."""
+
+    def __init__(self, constraint_list, path, path_discretization, solve_lp1d=1):
+        self.constraints = constraint_list
+        self.path = path
+        self.path_discretization = np.array(path_discretization, dtype=np.float64)
+        self.N = len(self.path_discretization) - 1
+        self.deltas = self.path_discretization[1:] - self.path_discretization[:-1]
+        self.nV = 2
+        self.dof = path.dof
+        vlim, alim, self._interp = extract_limits(constraint_list, self.dof)
+        self.nC = _capi.sampled_rows_per_stage(self.dof, alim, self._interp)
+        if self.nC > _capi.MAX_DENSE_ROWS:
+            raise NotImplementedError("%d constraint rows per stage: the sampled passes hold %d" % (self.nC, _capi.MAX_DENSE_ROWS))
+        qs, qss = path_samples(path, self.path_discretization)
+        if qs.shape != (self.N + 1, self.dof) or qss.shape != qs.shape:
+            raise ValueError("path(gridpoints, order) must have shape [N+1, dof] = [%d, %d], got %s and %s"
+                             % (self.N + 1, self.dof, qs.shape, qss.shape))
+        self._args = (self.path_discretization, qs[None], qss[None], None if vlim is None else vlim[None],
+                      None if alim is None else alim[None])
+        self._solve_lp1d = int(solve_lp1d)
+        self._active = np.zeros((1, 4), dtype=np.int32)
+        self._params = self._dense = None
+
+    @property
+    def params(self):
+        if self._params is None:
+            self._params = [c.compute_constraint_params(self.path, self.path_discretization) for c in self.constraints]
+        return self._params
+
+    def controllable_sets(self, sdmin, sdmax):
+        return batch.controllable_sets_sampled_batch(*self._args, np.array([sdmin ** 2], dtype=np.float64),
+                                                     np.array([sdmax ** 2], dtype=np.float64), self._interp, squared=True,
+                                                     active=self._active)[0]
+
+    def feasible_sets(self):
+        return batch.feasible_sets_sampled_batch(*self._args, self._interp, active=self._active)[0]
+
+    def reachable_sets(self, sdmin, sdmax):
+        L, X = batch.reachable_sets_sampled_batch(*self._args, np.array([sdmin ** 2], dtype=np.float64),
+                                                  np.array([sdmax ** 2], dtype=np.float64), self._interp, want_X=True,
+                                                  active=self._active, squared=True)
+        return L[0], X[0]
+
+    def parameterization(self, sd_start, sd_end):
+        out = batch.solve_sampled_batch(*self._args, np.array([sd_start ** 2], dtype=np.float64),
+                                        np.array([sd_end ** 2], dtype=np.float64), self._interp, want_sd=True, squared=True,
+                                        active=self._active)
+        res = {k: v[0] for k, v in out.items() if k != "status"}
+        res["status"] = int(out["status"][0])
+        return res
+
+    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
+        out = batch.solve_desired_duration_sampled_batch(*self._args, desired_duration, np.array([sd_start ** 2], dtype=np.float64),
+                                                         np.array([sd_end ** 2], dtype=np.float64), atol, self._interp,
+                                                         active=self._active, squared=True)
+        return {k: v[0] for k, v in out.items()}
+
+    def solve_stagewise_optim(self, i, H, g, x_min, x_max, x_next_min, x_next_max):
+        """The single-LP compatibility entry: served by a :class:`hipDenseSeidelWrapper` on the same constraints (its rows are
+        these rows, materialised), sharing this object's warm-start state."""
+        if self._dense is None:
+            self._dense = hipDenseSeidelWrapper(self.constraints, self.path, self.path_discretization, self._solve_lp1d,
+                                                active=self._active)
+        return self._dense.solve_stagewise_optim(i, H, g, x_min, x_max, x_next_min, x_next_max)
 
 
 class hipRobustWrapper(SolverWrapper):
