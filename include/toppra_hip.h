@@ -340,6 +340,58 @@ int tpr_reachable_sets_sampled_batch(const tpr_sampled_problem *p, const double 
 int tpr_param_spline_samples_batch(const tpr_sampled_problem *p, const double *sd, double *knot_times, int32_t *counts,
                                    double *coef_t, void *stream);
 
+/* ---- first-order constraints of any kind: per-stage variable boxes ------------------------------------------------
+ * Constraints that only tighten the box of a stage's variables (u, x) = (sdd, sd^2): the `ubound` / `xbound` outputs of
+ * compute_constraint_params, which seidelWrapper.__init__ folds into low_arr / high_arr
+ * (cy_seidel_solverwrapper.pyx:477-478, 512-520).  A bound source is one such output for the whole batch:               */
+#define TPR_BOUND_VLIM      1   /* [B][d][2]        JointVelocityConstraint                      */
+#define TPR_BOUND_VLIM_GRID 2   /* [B][N+1][d][2]   JointVelocityConstraintVarying: vlim_func(s_i) */
+#define TPR_BOUND_X         3   /* [B][N+1][2]      a constraint's xbound                        */
+#define TPR_BOUND_U         4   /* [B][N+1][2]      a constraint's ubound                        */
+#define TPR_BOUND_SHARED    1   /* flags: one array for the whole batch (no leading [B])         */
+#define TPR_BOUND_MAX_SOURCES 8
+typedef struct tpr_bound_source {
+    int32_t kind, flags;
+    const double *data;
+} tpr_bound_source;
+/* ABI guard, as tpr_second_order_block_bytes: bytes of tpr_bound_source in the library.                          */
+int tpr_bound_source_bytes(void);
+
+/* Replaces the box part of seidelWrapper.__init__ (cy_seidel_solverwrapper.pyx:477-478, 512-520) together with
+ * JointVelocityConstraint.compute_constraint_params (linear_joint_velocity.py:43-53, _CythonUtils.pyx:16-59) and
+ * JointVelocityConstraintVarying.compute_constraint_params (linear_joint_velocity.py:76-87, _CythonUtils.pyx:61-100) for B
+ * trajectories: low, high [B][N+1][2] start at -+1e8 and take the sources IN LIST ORDER with the reference's
+ * dbl_max(a, b) = a > b ? a : b / dbl_min(a, b) = a < b ? a : b (a: the running value); a VLIM* source first becomes an
+ * xbound from qs = path(grid, 1) [B][N+1][d] with the reference's fp32 running bounds.  qs may be NULL without a VLIM*
+ * source (d is ignored then).  flags: TPR_DEVICE_PTRS.  Refused before any launch: nsrc outside 0..TPR_BOUND_MAX_SOURCES,
+ * an unknown kind, a NULL source array, a VLIM* source without qs (TPR_E_BADARG); B (N+1) > 2^31 - 1, or d > TPR_MAX_DOF with a
+ * VLIM* source (TPR_E_UNSUPPORTED).
+ * NaN bounds are the caller's error, as NaN samples are.                                                           */
+int tpr_stage_boxes_batch(int B, int N, int d, const double *qs, int nsrc, const tpr_bound_source *src, int flags,
+                          double *low, double *high, void *stream);
+
+/* The passes of the sampled family with the boxes of tpr_stage_boxes_batch in place of the velocity limits: each takes the
+ * arguments of its *_sampled_batch twin plus low, high [B][N+1][2], and replaces the same reference code as that twin --
+ * compute_parameterization (reachability_algorithm.py:166-376, time_optimal_algorithm.py:55-92), TOPPRAsd
+ * (desired_duration_algorithm.py:93-234), compute_controllable_sets (reachability_algorithm.py:166-238),
+ * compute_feasible_sets (:131-164), compute_reachable_sets (:378-431) -- on a wrapper whose constraint list holds an
+ * acceleration constraint and any number of first-order ones (JointVelocityConstraint, JointVelocityConstraintVarying,
+ * bound-only LinearConstraints).  A stage reads its box (four doubles) and generates the acceleration rows from qs / qss;
+ * results are the bits of the dense pass on the rows tpr_sampled_rows_batch writes without a velocity constraint and
+ * these boxes.  p->vlim must be NULL and TPR_HAS_VELOCITY clear -- the box carries every first-order constraint --
+ * otherwise TPR_E_UNSUPPORTED.  Limits of the sampled family: nC = 2 + 4 d <= 122 under Interpolation, d <= 32 otherwise. */
+int tpr_solve_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, const tpr_result *r,
+                                  void *stream);
+int tpr_solve_desired_duration_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                                   const double *desired, double atol, const tpr_result *r, double *alpha,
+                                                   void *stream);
+int tpr_controllable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                              const double *sdmin, const double *sdmax, double *K, void *stream);
+int tpr_feasible_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, double *X,
+                                          void *stream);
+int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                           const double *sdmin, const double *sdmax, double *L, double *X, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -67,6 +67,16 @@ class tpr_sampled_problem(C.Structure):
                 ("sd_start", C.c_void_p), ("sd_end", C.c_void_p), ("active", C.c_void_p)]
 
 
+class tpr_bound_source(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("data", C.c_void_p)]
+
+
+# tpr_bound_source.kind / .flags
+BOUND_VLIM, BOUND_VLIM_GRID, BOUND_X, BOUND_U = 1, 2, 3, 4
+BOUND_SHARED = 1
+BOUND_MAX_SOURCES = 8
+BOUND_KINDS = {"vlim": BOUND_VLIM, "vlim_grid": BOUND_VLIM_GRID, "xbound": BOUND_X, "ubound": BOUND_U}
+
 # tpr_second_order_block.flags
 SO_INTERPOLATION, SO_F_SHARED, SO_F_PER_TRAJ, SO_F_PER_POINT, SO_G_PER_TRAJ, SO_G_PER_POINT = 1, 2, 4, 8, 16, 32
 SO_MAX_BLOCKS = 8
@@ -85,6 +95,9 @@ EXPORTS = (
     "tpr_sampled_problem_bytes", "tpr_sampled_rows_batch", "tpr_solve_sampled_batch", "tpr_controllable_sets_sampled_batch",
     "tpr_feasible_sets_sampled_batch", "tpr_reachable_sets_sampled_batch", "tpr_solve_desired_duration_sampled_batch",
     "tpr_param_spline_samples_batch",
+    "tpr_bound_source_bytes", "tpr_stage_boxes_batch", "tpr_solve_sampled_boxed_batch",
+    "tpr_solve_desired_duration_sampled_boxed_batch", "tpr_controllable_sets_sampled_boxed_batch",
+    "tpr_feasible_sets_sampled_boxed_batch", "tpr_reachable_sets_sampled_boxed_batch",
 )
 
 _lib = None
@@ -203,6 +216,23 @@ def load():
         L.tpr_feasible_sets_sampled_batch.argtypes = [SP, V, V]
         L.tpr_param_spline_samples_batch.restype = C.c_int
         L.tpr_param_spline_samples_batch.argtypes = [SP, V, V, V, V, V]
+        L.tpr_bound_source_bytes.restype = C.c_int
+        L.tpr_bound_source_bytes.argtypes = []
+        if L.tpr_bound_source_bytes() != C.sizeof(tpr_bound_source):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_bound_source takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_bound_source_bytes(), C.sizeof(tpr_bound_source)))
+        L.tpr_stage_boxes_batch.restype = C.c_int
+        L.tpr_stage_boxes_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, C.c_int, C.POINTER(tpr_bound_source), C.c_int, V, V, V]
+        L.tpr_solve_sampled_boxed_batch.restype = C.c_int
+        L.tpr_solve_sampled_boxed_batch.argtypes = [SP, V, V, R, V]
+        L.tpr_solve_desired_duration_sampled_boxed_batch.restype = C.c_int
+        L.tpr_solve_desired_duration_sampled_boxed_batch.argtypes = [SP, V, V, V, C.c_double, R, V, V]
+        L.tpr_controllable_sets_sampled_boxed_batch.restype = C.c_int
+        L.tpr_controllable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V]
+        L.tpr_feasible_sets_sampled_boxed_batch.restype = C.c_int
+        L.tpr_feasible_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V]
+        L.tpr_reachable_sets_sampled_boxed_batch.restype = C.c_int
+        L.tpr_reachable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int
@@ -423,6 +453,68 @@ def make_sampled_problem(grid, q, qs, qss, vlim, alim, sd_start=None, sd_end=Non
         p.active = ptr(active)
     p.flags = flags
     return p, keep
+
+
+def _no_nan(name, arr):
+    """Host bounds are checked for NaN (a NaN loses every comparison of the fold and would silently drop the bound); device
+    tensors are not read back: NaN bounds there are the caller's error, as NaN samples are."""
+    if isinstance(arr, np.ndarray) and np.isnan(arr).any():
+        raise ValueError("%s holds NaN (use +-inf for 'no bound')" % name)
+    return arr
+
+
+def make_bound_sources(sources, B, N, d, conv):
+    """The ``sources`` of :func:`toppra_amd.batch.stage_boxes_batch` -- an ordered list of ``(kind, array)`` with kind
+    "vlim" ([B, d, 2] or [d, 2]), "vlim_grid" ([B, N+1, d, 2] or [N+1, d, 2]), "xbound" / "ubound" ([B, N+1, 2] or [N+1, 2]);
+    the shorter shape is one array for the whole batch -- as tpr_bound_source structures: (structs, the converted arrays
+    they point to).  Shapes are checked here, numpy arrays also for NaN (+-inf is allowed).  ``d`` is None without samples:
+    velocity sources are refused then."""
+    sources = list(sources)
+    if len(sources) > BOUND_MAX_SOURCES:
+        raise NotImplementedError("%d bound sources in one list: the box kernel takes %d" % (len(sources), BOUND_MAX_SOURCES))
+    structs = (tpr_bound_source * max(len(sources), 1))()
+    keep = []
+    for j, (kind, arr) in enumerate(sources):
+        if kind not in BOUND_KINDS:
+            raise ValueError("sources[%d]: unknown kind %r (one of %s)" % (j, kind, sorted(BOUND_KINDS)))
+        name = "sources[%d] (%s)" % (j, kind)
+        arr = _no_nan(name, conv(name, arr))
+        if kind in ("vlim", "vlim_grid"):
+            if d is None:
+                raise ValueError("%s needs qs = path(grid, 1)" % name)
+            if d > MAX_DOF:
+                raise NotImplementedError("%s: dof %d is outside 1..%d" % (name, d, MAX_DOF))
+            full = (B, d, 2) if kind == "vlim" else (B, N + 1, d, 2)
+        else:
+            full = (B, N + 1, 2)
+        shape = tuple(int(v) for v in arr.shape)
+        if shape not in (full, full[1:]):
+            raise ValueError("%s must have shape %s or %s, got %s" % (name, list(full), list(full[1:]), shape))
+        keep.append(arr)
+        structs[j] = tpr_bound_source(kind=BOUND_KINDS[kind], flags=BOUND_SHARED if shape == full[1:] and full != full[1:] else 0,
+                                      data=ptr(arr))
+    return structs, keep
+
+
+def make_boxed_problem(grid, qs, qss, alim, low, high, sd_start=None, sd_end=None, interpolation=True, keep=None, active=None,
+                       squared=False, vlim=None):
+    """The tpr_sampled_problem of the boxed passes (no velocity limits: the boxes carry every first-order constraint) and the
+    checked boxes: (problem, keep, low, high).  low, high [B, N+1, 2] as :func:`toppra_amd.batch.stage_boxes_batch` returns
+    them; numpy boxes are checked for NaN.  Everything is refused here, before any launch."""
+    if vlim is not None:
+        raise NotImplementedError("the boxed passes take no vlim: the boxes carry every first-order constraint -- make the "
+                                  "limits a (\"vlim\", vlim) source of stage_boxes_batch")
+    p, keep = make_sampled_problem(grid, None, qs, qss, None, alim, sd_start, sd_end, interpolation, keep=keep, active=active,
+                                   squared=squared)
+    conv = converter(keep[2], "qs")
+    out = []
+    for name, arr in (("low", low), ("high", high)):
+        arr = _no_nan(name, conv(name, arr))
+        if tuple(int(v) for v in arr.shape) != (p.B, p.N + 1, 2):
+            raise ValueError("%s must have shape [B, N+1, 2] = [%d, %d, 2], got %s" % (name, p.B, p.N + 1, tuple(arr.shape)))
+        out.append(arr)
+    keep += out
+    return p, keep, out[0], out[1]
 
 
 def check_tensor(name, t, like):

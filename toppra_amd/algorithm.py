@@ -247,16 +247,23 @@ class BatchTOPPRA(object):
     constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
         ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback.  Their rows are built on the GPU
         once per object and every pass runs on the dense-row entries; without them nothing changes.
+        ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` objects (first-order: they only tighten the box
+        of a stage's variables) may stand anywhere among them: their bounds and vlim are folded into stage boxes on the GPU
+        once per object, in list order, and the passes run on the boxed sampled entries (or, with second-order constraints
+        in the list too, on the dense-row entries with these boxes).
     """
 
     def __init__(self, coef, breaks, gridpoints, vlim, alim, interpolation=True, constraints=None):
         self.coef, self.breaks, self.gridpoints = coef, breaks, gridpoints
         self.vlim, self.alim, self.interpolation = vlim, alim, interpolation
-        self.constraints = list(constraints) if constraints else []
+        self._set_constraints(constraints)
         self._rows = self._rows_dev = None
+        self._pe = self._boxed = self._boxed_dev = None
         self._samples = None  # (q, qs, qss) of from_path_samples: the path as samples at the gridpoints, no spline table
         if self.constraints:
             self._check_constraints()
+        if self.first_order and coef is not None:
+            self._check_first_order()
 
     @classmethod
     def from_path_samples(cls, gridpoints, q, qs, qss, vlim, alim, interpolation=True, constraints=None):
@@ -270,14 +277,23 @@ class BatchTOPPRA(object):
         the path between the gridpoints and raise NotImplementedError.  Shapes and the row limit (d <= 30 under
         Interpolation, 32 under Collocation) are checked here, before anything is launched."""
         self = cls(None, None, gridpoints, vlim, alim, interpolation=interpolation)
-        self.constraints = list(constraints) if constraints else []
+        self._set_constraints(constraints)
         _capi.make_sampled_problem(gridpoints, q, qs, qss, vlim, alim, interpolation=interpolation, solver=not self.constraints)
         self._samples = (q, qs, qss)
         if self.constraints:
             if q is None:
                 raise ValueError("second-order constraints evaluate their inverse dynamics at q: give the path positions")
             self._check_constraints()
+        if self.first_order:
+            self._check_first_order()
         return self
+
+    def _set_constraints(self, constraints):
+        """``constraints`` split by what they produce: the second-order ones (rows; ``self.constraints``, in list order) and
+        the first-order ones (``self.first_order``: they only tighten the stage boxes, in list order after vlim)."""
+        constraints = list(constraints) if constraints else []
+        self.first_order = [c for c in constraints if getattr(c, "first_order", False)]
+        self.constraints = [c for c in constraints if not getattr(c, "first_order", False)]
 
     def _sampled_args(self):
         return (self.gridpoints, self._samples[1], self._samples[2], self.vlim, self.alim)
@@ -312,20 +328,97 @@ class BatchTOPPRA(object):
             raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
                                       % (nC, _capi.MAX_DENSE_ROWS))
 
+    # -- first-order constraints: BatchJointVelocityConstraintVarying / BatchBoundConstraint -------------------------------
+    # They add no rows.  The bound sources [vlim (if given), then the first-order constraints in list order] are folded into
+    # the stage boxes ONCE per object, on first use, by tpr_stage_boxes_batch, and the boxes stay on the device.  Without
+    # second-order constraints the passes run on the boxed sampled entries (tpr_*_sampled_boxed_batch) -- for a spline-table
+    # problem on path_eval_batch's q', q'' at the gridpoints, evaluated once; with them the rows are built WITHOUT vlim and
+    # the dense entries take the boxes as their low / high.
+    def _sizes(self):
+        if self._samples is not None:
+            return int(self._samples[1].shape[0]), int(self._samples[1].shape[1]) - 1, int(self._samples[1].shape[2])
+        if getattr(self.coef, "ndim", 0) != 4:
+            raise ValueError("coef must have shape [B, 4, nseg, d]")
+        return int(self.coef.shape[0]), int(self.gridpoints.shape[-1]) - 1, int(self.coef.shape[3])
+
+    def _check_first_order(self):
+        """Everything that can be refused from shapes alone, before any launch."""
+        B, N, d = self._sizes()
+        nsrc = (self.vlim is not None) + sum(con.source_count() for con in self.first_order)
+        if nsrc > _capi.BOUND_MAX_SOURCES:
+            raise NotImplementedError("%d bound sources (vlim and the first-order constraints' bounds) in one list: the box "
+                                      "kernel takes %d" % (nsrc, _capi.BOUND_MAX_SOURCES))
+        for con in self.first_order:
+            con.check(B, N, d)
+        if not self.constraints:
+            nC = _capi.sampled_rows_per_stage(d, self.alim, self.interpolation)
+            if nC > _capi.MAX_DENSE_ROWS:
+                raise NotImplementedError("%d dof under Interpolation: %d constraint rows per stage (incl. the two x_next rows), "
+                                          "the boxed passes hold %d (30 dof; 32 under Collocation)" % (d, nC, _capi.MAX_DENSE_ROWS))
+
+    def _path_eval(self):
+        """q, q', q'' of a spline-table problem at the gridpoints, evaluated once per object."""
+        if self._pe is None:
+            self._pe = _batch.path_eval_batch(self.coef, self.breaks, self.gridpoints)
+        return self._pe
+
+    def stage_boxes(self):
+        """(low, high) [B, N+1, 2] of [vlim, first-order constraints ...]: the reference wrapper's ``low_arr`` / ``high_arr``,
+        as arrays of the kind the problem was given in.  Built on first use."""
+        return self._boxed_state()[4:]
+
+    def _boxed_state(self):
+        if self._boxed is None:
+            qs, qss = self._samples[1:] if self._samples is not None else (self._path_eval()["qs"], self._path_eval()["qss"])
+            B, N, d = self._sizes()
+            from .constraint import _like
+            grid = _like(self.gridpoints, qs)
+            sources = [("vlim", self.vlim)] if self.vlim is not None else []
+            for con in self.first_order:
+                sources += con.bound_sources(grid, B, N, d, qs)
+            low, high = _batch.stage_boxes_batch(qs, sources)
+            self._boxed = (self.gridpoints, qs, qss, self.alim, low, high)
+        return self._boxed
+
+    @staticmethod
+    def _to_host(out):
+        host = lambda v: v.cpu().numpy()  # noqa: E731
+        if isinstance(out, dict):
+            return {k: host(v) for k, v in out.items()}
+        return tuple(host(v) for v in out) if isinstance(out, tuple) else host(out)
+
+    def _boxed_pass(self, fn, *args, **kw):
+        """One pass on the device-resident samples and boxes; outputs in the kind of the inputs."""
+        if self._boxed_dev is None:
+            self._boxed_dev = self._boxed_state()
+            if not _capi.is_torch_cuda(self._boxed[1]):
+                # numpy problem: the passes read a device copy of the samples and the boxes made once; results come back as
+                # numpy arrays
+                import torch
+                dev = torch.device("cuda", _capi.init())
+                self._boxed_dev = tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
+                                        for v in self._boxed)
+        out = fn(*self._boxed_dev, *args, **kw)
+        return out if self._boxed_dev is self._boxed else self._to_host(out)
+
     def dense_rows(self):
         """(a, b, c, low, high, deltas) of the constraint list, as arrays of the kind the problem was given in: the arguments
         of the ``batch.*_dense_batch`` calls.  Built on first use.  A constraint whose F and g are both callables has no
         row count before its callbacks have run: for such a list the 122-row limit is checked here, after the path
         evaluation and the callbacks and before the row kernel is launched, not in the constructor."""
         if self._rows is None:
+            vlim = None if self.first_order else self.vlim  # (with first-order constraints the boxes carry vlim too)
             if self._samples is not None:
                 blocks = [con.block(*self._samples) for con in self.constraints]
-                rows = _batch.sampled_rows_batch(*self._sampled_args(), blocks, self.interpolation)
+                rows = _batch.sampled_rows_batch(self.gridpoints, self._samples[1], self._samples[2], vlim, self.alim, blocks,
+                                                 self.interpolation)
             else:
-                pe = _batch.path_eval_batch(self.coef, self.breaks, self.gridpoints)
+                pe = self._path_eval()
                 blocks = [con.block(pe["q"], pe["qs"], pe["qss"]) for con in self.constraints]
-                rows = _batch.second_order_rows_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, blocks,
+                rows = _batch.second_order_rows_batch(self.coef, self.breaks, self.gridpoints, vlim, self.alim, blocks,
                                                       self.interpolation)
+            if self.first_order:
+                rows["low"], rows["high"] = self.stage_boxes()
             self._rows = tuple(rows[k] for k in ("a", "b", "c", "low", "high", "deltas"))
             self._rows_dev = self._rows
             if not _capi.is_torch_cuda(rows["a"]):
@@ -367,6 +460,8 @@ class BatchTOPPRA(object):
         With ``constraints`` the dense-row entry serves the call (``variant`` does not apply; K and u are always returned)."""
         if self.constraints:
             return self._dense_pass(_batch.solve_dense_batch, sd_start, sd_end, want_sd=want_sd)
+        if self.first_order:  # (the boxed entry always returns K and u; ``variant`` does not apply)
+            return self._boxed_pass(_batch.solve_sampled_boxed_batch, sd_start, sd_end, self.interpolation, want_sd=want_sd)
         if self._samples is not None:  # (the sampled entry always returns K and u; ``variant`` does not apply)
             return _batch.solve_sampled_batch(*self._sampled_args(), sd_start, sd_end, self.interpolation, want_sd=want_sd)
         return _batch.solve_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
@@ -377,6 +472,9 @@ class BatchTOPPRA(object):
         """TOPPRAsd for the batch: dict(sd2, sd, u, K, status, alpha)."""
         if self.constraints:
             return self._dense_pass(_batch.solve_desired_duration_dense_batch, desired_duration, sd_start, sd_end, atol)
+        if self.first_order:
+            return self._boxed_pass(_batch.solve_desired_duration_sampled_boxed_batch, desired_duration, sd_start, sd_end, atol,
+                                    self.interpolation)
         if self._samples is not None:
             return _batch.solve_desired_duration_sampled_batch(*self._sampled_args(), desired_duration, sd_start, sd_end, atol,
                                                                self.interpolation)
@@ -427,6 +525,8 @@ class BatchTOPPRA(object):
     def compute_controllable_sets(self, sdmin, sdmax):
         if self.constraints:
             return self._dense_pass(_batch.controllable_sets_dense_batch, sdmin, sdmax)
+        if self.first_order:
+            return self._boxed_pass(_batch.controllable_sets_sampled_boxed_batch, sdmin, sdmax, self.interpolation)
         if self._samples is not None:
             return _batch.controllable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
         return _batch.controllable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
@@ -435,6 +535,8 @@ class BatchTOPPRA(object):
     def compute_feasible_sets(self):
         if self.constraints:
             return self._dense_pass(_batch.feasible_sets_dense_batch)
+        if self.first_order:
+            return self._boxed_pass(_batch.feasible_sets_sampled_boxed_batch, self.interpolation)
         if self._samples is not None:
             return _batch.feasible_sets_sampled_batch(*self._sampled_args(), self.interpolation)
         return _batch.feasible_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
@@ -444,6 +546,8 @@ class BatchTOPPRA(object):
         """L[B, N+1, 2] (reachability_algorithm.py:409-431 per trajectory)."""
         if self.constraints:
             return self._dense_pass(_batch.reachable_sets_dense_batch, sdmin, sdmax)
+        if self.first_order:
+            return self._boxed_pass(_batch.reachable_sets_sampled_boxed_batch, sdmin, sdmax, self.interpolation)
         if self._samples is not None:
             return _batch.reachable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
         return _batch.reachable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, sdmin, sdmax,

@@ -19,7 +19,9 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "solve_desired_duration_batch", "robust_solve_batch", "param_spline_batch", "ppoly_eval_batch",
            "path_eval_batch", "second_order_rows_batch", "sampled_rows_batch", "solve_sampled_batch",
            "controllable_sets_sampled_batch", "feasible_sets_sampled_batch", "reachable_sets_sampled_batch",
-           "solve_desired_duration_sampled_batch", "param_spline_samples_batch"]
+           "solve_desired_duration_sampled_batch", "param_spline_samples_batch", "stage_boxes_batch",
+           "solve_sampled_boxed_batch", "solve_desired_duration_sampled_boxed_batch", "controllable_sets_sampled_boxed_batch",
+           "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch"]
 
 
 def _stream_ptr(like):
@@ -514,6 +516,140 @@ def param_spline_samples_batch(grid, q, qs, sd):
     _capi.check(_capi.load().tpr_param_spline_samples_batch(C.byref(p), _capi.ptr(sd), _capi.ptr(out["knot_times"]),
                                                             _capi.ptr(out["counts"]), _capi.ptr(out["coef"]), _stream_ptr(like)))
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# first-order constraints of any kind: per-stage variable boxes (include/toppra_hip.h: tpr_stage_boxes_batch)
+
+def stage_boxes_batch(qs, sources, N=None):
+    """``seidelWrapper.low_arr / high_arr`` for B trajectories, built on the GPU: (low, high) [B, N+1, 2], the (u, x) boxes of a
+    list of first-order constraints.  ``sources``: an ordered list of ``(kind, array)`` --
+      ``("vlim", [B, d, 2] | [d, 2])``: JointVelocityConstraint;
+      ``("vlim_grid", [B, N+1, d, 2] | [N+1, d, 2])``: JointVelocityConstraintVarying, ``vlim_func`` at the gridpoints;
+      ``("xbound" | "ubound", [B, N+1, 2] | [N+1, 2])``: a constraint's bound on x = sd^2 / u = sdd;
+    the shorter shape is one array for the whole batch.  The boxes start at -+1e8 and take the sources in list order with the
+    reference's ``a > b ? a : b`` / ``a < b ? a : b`` (cy_seidel_solverwrapper.pyx:512-520); velocity sources become an
+    xbound from ``qs = path(grid, 1)`` [B, N+1, d] with the reference's fp32 running bounds (_CythonUtils.pyx:16-100).
+    ``qs`` may be None without a velocity source: give ``N`` then, and B comes from the first per-trajectory source.
+    numpy in -> numpy out (NaN refused, +-inf allowed), tensors in -> tensors out (NaN bounds are the caller's error, as NaN
+    samples are: they are not read back, and a NaN silently DROPS its bound, because it loses every comparison of the fold).  At most 8 sources.  Everything is checked before anything is launched."""
+    sources = list(sources)
+    like = qs if qs is not None else (sources[0][1] if sources else None)
+    if like is None:
+        raise ValueError("stage_boxes_batch needs qs or at least one source")
+    conv = _capi.converter(like, "qs" if qs is not None else "sources[0]")
+    d = None
+    if qs is not None:
+        qs = conv("qs", qs)
+        if qs.ndim != 3:
+            raise ValueError("qs must have shape [B, N+1, d], got %s" % (tuple(qs.shape),))
+        B, N1, d = (int(v) for v in qs.shape)
+        if N is not None and int(N) != N1 - 1:
+            raise ValueError("N = %d does not match qs [B, N+1, d] = %s" % (N, tuple(qs.shape)))
+        N = N1 - 1
+    else:
+        if N is None:
+            raise ValueError("without qs, give N")
+        N, B = int(N), None
+        for kind, arr in sources:
+            if kind in ("xbound", "ubound") and getattr(arr, "ndim", np.ndim(arr)) == 3:
+                B = int(arr.shape[0])
+                break
+        if B is None:
+            raise ValueError("without qs, at least one source must be given per trajectory ([B, N+1, 2])")
+    if N < 1:
+        raise ValueError("stage boxes need at least two gridpoints")
+    structs, keep = _capi.make_bound_sources(sources, B, N, d, conv)
+    _prepare(like)
+    low, high = _empty(like, (B, N + 1, 2)), _empty(like, (B, N + 1, 2))
+    _capi.check(_capi.load().tpr_stage_boxes_batch(B, N, d or 1, _capi.ptr(qs), len(sources), structs,
+                                                   _capi.DEVICE_PTRS if _capi.is_torch_cuda(like) else 0,
+                                                   _capi.ptr(low), _capi.ptr(high), _stream_ptr(like)))
+    return low, high
+
+
+def solve_sampled_boxed_batch(grid, qs, qss, alim, low, high, sd_start=None, sd_end=None, interpolation=True, want_sd=False,
+                              squared=False, active=None, vlim=None):
+    """:func:`solve_sampled_batch` with the stage boxes of :func:`stage_boxes_batch` (low, high [B, N+1, 2]) in place of the
+    velocity limits: compute_parameterization for B sampled paths under an acceleration constraint and any list of
+    first-order constraints.  Same keywords and dict; the bits of :func:`solve_dense_batch` on the rows
+    :func:`sampled_rows_batch` writes without vlim, with these boxes.  ``vlim`` must stay None."""
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, sd_start, sd_end, interpolation, active=active,
+                                                  squared=squared, vlim=vlim)
+    like = keep[2]
+    _prepare(like)
+    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
+           "status": _empty(like, (p.B,), "i32")}
+    if want_sd:
+        out["sd"] = _empty(like, (p.B, p.N + 1))
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
+                         status=_capi.ptr(out["status"]))
+    _capi.check(_capi.load().tpr_solve_sampled_boxed_batch(C.byref(p), _capi.ptr(low), _capi.ptr(high), C.byref(r), _stream_ptr(like)))
+    return out
+
+
+def solve_desired_duration_sampled_boxed_batch(grid, qs, qss, alim, low, high, desired_duration, sd_start=None, sd_end=None,
+                                               atol=1e-5, interpolation=True, active=None, squared=False, vlim=None):
+    """:func:`solve_desired_duration_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`)."""
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, sd_start, sd_end, interpolation, active=active,
+                                                  squared=squared, vlim=vlim)
+    like = keep[2]
+    _prepare(like)
+    B, N = p.B, p.N
+    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
+    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
+           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
+                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
+    _capi.check(_capi.load().tpr_solve_desired_duration_sampled_boxed_batch(
+        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(desired), float(atol), C.byref(r), _capi.ptr(out["alpha"]),
+        _stream_ptr(like)))
+    return out
+
+
+def controllable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sdmax, interpolation=True, squared=False,
+                                          active=None, vlim=None):
+    """:func:`controllable_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> K [B, N+1, 2]."""
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
+                                                  squared=squared, vlim=vlim)
+    like = keep[2]
+    _prepare(like)
+    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
+    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
+    K = _empty(like, (p.B, p.N + 1, 2))
+    _capi.check(_capi.load().tpr_controllable_sets_sampled_boxed_batch(
+        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(K), _stream_ptr(like)))
+    return K
+
+
+def feasible_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, interpolation=True, active=None, vlim=None):
+    """:func:`feasible_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> X [B, N+1, 2]."""
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
+                                                  vlim=vlim)
+    like = keep[2]
+    _prepare(like)
+    X = _empty(like, (p.B, p.N + 1, 2))
+    _capi.check(_capi.load().tpr_feasible_sets_sampled_boxed_batch(C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(X),
+                                                                   _stream_ptr(like)))
+    return X
+
+
+def reachable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sdmax, interpolation=True, want_X=False,
+                                       active=None, squared=False, vlim=None):
+    """:func:`reachable_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> L [B, N+1, 2] (and the
+    feasible sets X with ``want_X``)."""
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
+                                                  squared=squared, vlim=vlim)
+    like = keep[2]
+    _prepare(like)
+    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
+    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
+    L = _empty(like, (p.B, p.N + 1, 2))
+    X = _empty(like, (p.B, p.N + 1, 2)) if want_X else None
+    _capi.check(_capi.load().tpr_reachable_sets_sampled_boxed_batch(
+        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L), _capi.ptr(X),
+        _stream_ptr(like)))
+    return (L, X) if want_X else L
 
 
 # --------------------------------------------------------------------------------------------

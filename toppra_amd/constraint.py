@@ -501,6 +501,109 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         return {"w0": w0, "wa": wa, "wb": wb, "F": F, "g": g, "friction": fr, "interpolation": self._interp()}
 
 
+# ---- batched first-order constraints: they only tighten a stage's variable box (BatchTOPPRA(..., constraints=[...])) -------
+
+def _shape_of(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+class _BatchFirstOrder(LinearConstraint):
+    """Shared part of the batched constraints that produce only ``ubound`` / ``xbound``: they become bound sources of
+    :func:`toppra_amd.batch.stage_boxes_batch`, folded into the stage boxes in list order on the GPU."""
+    first_order = True
+
+    def source_count(self):
+        """Bound sources this constraint hands to the box kernel."""
+        raise NotImplementedError
+
+    def check(self, B, N, d):
+        """Shape errors that can be told from the problem's sizes alone (ValueError), before any launch."""
+        raise NotImplementedError
+
+    def bound_sources(self, gridpoints, B, N, d, like):
+        """[(kind, array)] for ``stage_boxes_batch``; arrays of the kind of ``like``."""
+        raise NotImplementedError
+
+    def compute_constraint_params(self, path, gridpoints, *args, **kwargs):
+        raise NotImplementedError("%s serves BatchTOPPRA(..., constraints=[...]); a single path takes "
+                                  "JointVelocityConstraintVarying or a LinearConstraint of its own" % type(self).__name__)
+
+
+class BatchJointVelocityConstraintVarying(_BatchFirstOrder):
+    """``JointVelocityConstraintVarying`` (linear_joint_velocity.py:56-87) for a batch: joint velocity limits that depend on
+    the position along the path.
+
+    ``vlim``: an array [B, N+1, d, 2] -- the limits of every trajectory at its gridpoints -- or a callable ``vlim_func(s)``.
+    The callable is BATCHED, the convention of ``inv_dyn``: it is called ONCE, with the problem's gridpoints ([N+1], or
+    [B, N+1] when they are given per trajectory; a numpy array or a torch tensor like the problem), and returns [..., d, 2].
+    A 3-D array is refused: [B, d, 2] and [N+1, d, 2] cannot be told apart -- constant limits are BatchTOPPRA's ``vlim``, and
+    one grid of limits for the whole batch is given as a callable or broadcast by the caller."""
+
+    def __init__(self, vlim):
+        super(BatchJointVelocityConstraintVarying, self).__init__()
+        self.vlim_func = vlim if callable(vlim) else None
+        self.vlim_grid = None if callable(vlim) else vlim
+        if self.vlim_grid is not None:
+            shape = _shape_of(self.vlim_grid)
+            if len(shape) == 3:
+                raise ValueError("a 3-D vlim %s is ambiguous between [B, d, 2] and [N+1, d, 2]: give [B, N+1, d, 2], or a "
+                                 "callable vlim_func(s)" % (shape,))
+            if len(shape) != 4 or shape[-1] != 2:
+                raise ValueError("vlim must have shape [B, N+1, d, 2] or be a callable, got %s" % (shape,))
+            self.dof = shape[2]
+        self._format_string = "    Batched varying velocity limit\n"
+
+    def source_count(self):
+        return 1
+
+    def check(self, B, N, d):
+        if self.vlim_grid is not None and _shape_of(self.vlim_grid) != (B, N + 1, d, 2):
+            raise ValueError("vlim must have shape [B, N+1, d, 2] = [%d, %d, %d, 2], got %s" % (B, N + 1, d, _shape_of(self.vlim_grid)))
+
+    def bound_sources(self, gridpoints, B, N, d, like):
+        self.check(B, N, d)
+        if self.vlim_func is None:
+            return [("vlim_grid", _like(self.vlim_grid, like))]
+        lim = self.vlim_func(gridpoints)  # once, with every gridpoint
+        want = _shape_of(gridpoints) + (d, 2)
+        if not hasattr(lim, "shape") or _shape_of(lim) != want:
+            raise ValueError("vlim_func(gridpoints) must return an array %s for gridpoints %s, got %s"
+                             % (list(want), list(_shape_of(gridpoints)), _shape_of(lim) if hasattr(lim, "shape") else type(lim).__name__))
+        return [("vlim_grid", _like(lim, like))]
+
+
+class BatchBoundConstraint(_BatchFirstOrder):
+    """A constraint that is only a bound on x = sd^2 and / or u = sdd at every gridpoint -- a ``LinearConstraint`` whose
+    ``compute_constraint_params`` returns ``(None, None, None, None, None, ubound, xbound)``: a Cartesian tool-speed limit
+    x <= v^2 / |J q'|^2, a cap on the path acceleration, a slow zone.  ``xbound``, ``ubound``: [B, N+1, 2] (lower, upper),
+    or [N+1, 2] for the whole batch; either may be None.  +-inf means no bound; NaN is refused for host arrays."""
+
+    def __init__(self, xbound=None, ubound=None):
+        super(BatchBoundConstraint, self).__init__()
+        if xbound is None and ubound is None:
+            raise ValueError("BatchBoundConstraint needs xbound or ubound")
+        for name, arr in (("xbound", xbound), ("ubound", ubound)):
+            if arr is not None:
+                shape = _shape_of(arr)
+                if len(shape) not in (2, 3) or shape[-1] != 2:
+                    raise ValueError("%s must have shape [B, N+1, 2] or [N+1, 2], got %s" % (name, shape))
+        self.xbound, self.ubound = xbound, ubound
+        self._format_string = "    Batched bound on the stage variables\n"
+
+    def source_count(self):
+        return (self.xbound is not None) + (self.ubound is not None)
+
+    def check(self, B, N, d):
+        for name, arr in (("xbound", self.xbound), ("ubound", self.ubound)):
+            if arr is not None and _shape_of(arr) not in ((B, N + 1, 2), (N + 1, 2)):
+                raise ValueError("%s must have shape [B, N+1, 2] = [%d, %d, 2] or [N+1, 2], got %s" % (name, B, N + 1, _shape_of(arr)))
+
+    def bound_sources(self, gridpoints, B, N, d, like):
+        self.check(B, N, d)
+        # (the reference folds a constraint's ubound before its xbound: cy_seidel_solverwrapper.pyx:512-520)
+        return [(kind, _like(arr, like)) for kind, arr in (("ubound", self.ubound), ("xbound", self.xbound)) if arr is not None]
+
+
 class ConicConstraint(Constraint):
     """Base class of canonical conic constraints (conic_constraint.py:6-44)."""
 

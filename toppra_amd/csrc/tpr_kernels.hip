@@ -1489,3 +1489,156 @@ int tpr_param_spline_samples_batch(const tpr_sampled_problem *p, const double *s
     return S.finish();
 }
 }  // extern "C"
+
+// ---- first-order constraints of any kind: stage boxes built on the GPU, the sampled passes reading them -------------------
+// The box kernel and the dense-row passes with BoxedSampledStage live in csrc/tpr_boxed_tu.hip.
+#include "tpr_boxed_args.hpp"
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_boxed_launch(const tpr::BoxedArgs *, int, hipStream_t);
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_stage_boxes_launch(tpr::BoxesArgs *, hipStream_t);
+namespace {
+// the checks of the sampled passes, and: the box carries every first-order constraint
+int check_boxed(const tpr_sampled_problem *p, const double *low, const double *high) {
+    if (int rc = check_sampled(p, true)) return rc;
+    if (p->vlim || (p->flags & TPR_HAS_VELOCITY))
+        return fail(TPR_E_UNSUPPORTED, "boxed sampled problem: vlim must be NULL and TPR_HAS_VELOCITY clear (the boxes carry every first-order constraint: make the limits a source of tpr_stage_boxes_batch)");
+    if (!low || !high) return fail(TPR_E_BADARG, "boxed sampled problem: low, high are required");
+    return TPR_E_OK;
+}
+tpr::BoxedArgs stage_boxed(const tpr_sampled_problem *p, const double *low, const double *high, Staging &S) {
+    tpr::BoxedArgs A{};
+    static_cast<tpr::SampledArgs &>(A) = stage_sampled(p, S);
+    const size_t pts = (size_t)p->B * ((size_t)p->N + 1);
+    A.low = S.in(low, pts * 2); A.high = S.in(high, pts * 2);
+    return A;
+}
+}  // namespace
+
+extern "C" {
+int tpr_bound_source_bytes(void) { return (int)sizeof(tpr_bound_source); }
+
+int tpr_stage_boxes_batch(int B, int N, int d, const double *qs, int nsrc, const tpr_bound_source *src, int flags, double *low,
+                          double *high, void *stream_) {
+    if (default_device() < 0) return fail(TPR_E_HIP, "tpr_init() has not succeeded");
+    if (B < 0 || N < 1) return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: B >= 0, N >= 1");
+    if (nsrc < 0 || nsrc > TPR_BOUND_MAX_SOURCES || (nsrc > 0 && !src))
+        return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: 0 <= nsrc <= TPR_BOUND_MAX_SOURCES");
+    if (!low || !high) return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: low, high are required");
+    bool vel = false;
+    for (int j = 0; j < nsrc; ++j) {
+        if (src[j].kind < TPR_BOUND_VLIM || src[j].kind > TPR_BOUND_U) return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: unknown bound source kind");
+        if (!src[j].data) return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: a bound source without data");
+        vel |= src[j].kind == TPR_BOUND_VLIM || src[j].kind == TPR_BOUND_VLIM_GRID;
+    }
+    if (vel && (!qs || d < 1)) return fail(TPR_E_BADARG, "tpr_stage_boxes_batch: a VLIM* source needs qs and d >= 1");
+    if (vel && d > TPR_MAX_DOF) return fail(TPR_E_UNSUPPORTED, "tpr_stage_boxes_batch: dof must be in [1, TPR_MAX_DOF]");
+    const size_t pts = (size_t)B * ((size_t)N + 1);
+    if (pts > (size_t)0x7fffffff) return fail(TPR_E_UNSUPPORTED, "tpr_stage_boxes_batch: more than 2^31 - 1 gridpoints in the batch");
+    Staging S(flags & TPR_DEVICE_PTRS, low, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxesArgs A{};
+    A.B = B; A.N = N; A.d = vel ? d : 1; A.nsrc = nsrc;
+    A.qs = vel ? S.in(qs, pts * (size_t)d) : nullptr;
+    for (int j = 0; j < nsrc; ++j) {
+        const bool shared = src[j].flags & TPR_BOUND_SHARED;
+        const size_t lead = shared ? 1 : (size_t)B;
+        size_t count = 0;
+        switch (src[j].kind) {
+            case TPR_BOUND_VLIM: count = lead * (size_t)d * 2; break;
+            case TPR_BOUND_VLIM_GRID: count = lead * ((size_t)N + 1) * (size_t)d * 2; break;
+            default: count = lead * ((size_t)N + 1) * 2; break;
+        }
+        A.src[j] = tpr::BoxSource{src[j].kind, src[j].flags, S.in(src[j].data, count)};
+    }
+    A.low = S.out(low, pts * 2); A.high = S.out(high, pts * 2);
+    if (int rc = S.failed()) return rc;
+    if (pts > 0) {
+        const int rc = tpr_tu_stage_boxes_launch(&A, S.stream);
+        if (rc != 0) return fail(TPR_E_UNSUPPORTED, rc == -1 ? "tpr_stage_boxes_batch: one gridpoint's joints do not fit the LDS" : "tpr_stage_boxes_batch: more than 2^31 - 1 gridpoints in the batch");
+    }
+    return S.finish();
+}
+
+int tpr_solve_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, const tpr_result *r,
+                                  void *stream_) {
+    if (int rc = check_boxed(p, low, high)) return rc;
+    if (!r || !r->K) return fail(TPR_E_BADARG, "boxed sampled solve: r->K is required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
+    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_boxed_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled solve: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_solve_desired_duration_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                                   const double *desired, double atol, const tpr_result *r, double *alpha,
+                                                   void *stream_) {
+    if (int rc = check_boxed(p, low, high)) return rc;
+    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    const double *ddes = S.in(desired, B);
+    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
+    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    double *dalpha = S.out(alpha, B);
+    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
+    if (int rc = S.failed()) return rc;
+    if (!dalpha) dalpha = W.extra;
+    if (A.B > 0) {
+        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
+        A.backward_only = 1;
+        if (tpr_tu_boxed_launch(&A, 0, S.stream) != 0 || tpr_tu_boxed_launch(&A, 2, S.stream) != 0)
+            return fail(TPR_E_UNSUPPORTED, "boxed sampled TOPPRAsd: no kernel for this row count");
+        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, A.grid, ddes, nullptr, nullptr, nullptr, nullptr, A.status,
+                           dsd2, dsd, du, dalpha, A.status};
+        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
+    }
+    return S.finish();
+}
+
+int tpr_controllable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                              const double *sdmin, const double *sdmax, double *K, void *stream_) {
+    if (int rc = check_boxed(p, low, high)) return rc;
+    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
+    const size_t B = (size_t)p->B, N = (size_t)p->N;
+    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
+    A.K = S.out(K, B * (N + 1) * 2);
+    A.backward_only = 1;
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_boxed_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled controllable sets: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_feasible_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, double *X,
+                                          void *stream_) {
+    if (int rc = check_boxed(p, low, high)) return rc;
+    if (!X) return fail(TPR_E_BADARG, "X is required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
+    A.X = S.out(X, (size_t)p->B * ((size_t)p->N + 1) * 2);
+    if (int rc = S.failed()) return rc;
+    if (A.B > 0 && tpr_tu_boxed_launch(&A, 1, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled feasible sets: no kernel for this row count");
+    return S.finish();
+}
+
+int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
+                                           const double *sdmin, const double *sdmax, double *L, double *X, void *stream_) {
+    if (int rc = check_boxed(p, low, high)) return rc;
+    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
+    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
+    if (int rc = S.failed()) return rc;
+    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
+    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::BoxedArgs>, sdmin, sdmax, L, X);
+}
+}  // extern "C"

@@ -3,22 +3,24 @@
 
 #pragma once
 #include <type_traits>
-#include "tpr_dense_args.hpp"
+#include "tpr_boxed_args.hpp"
 namespace tpr {
 
 // compute_reachable_sets (reachability_algorithm.py:378-431) on dense rows: lane_reachable_kernel (tpr_lane.hip.inc: one
 // trajectory per lane, the reference's solve_stagewise_optim with its stateful warm start, the deltas[i - 1] quirk of
 // _one_step_forward) with the stage rows copied from the arrays instead of generated.
 // Args = DenseArgs: the rows of tpr_dense_problem; Args = SampledArgs: the rows second_order_rows_kernel (nblocks = 0) would
-// write for the path samples, generated in place.
+// write for the path samples, generated in place; Args = BoxedArgs: those rows without a velocity constraint, the variable
+// box of a stage read from the arrays tpr_stage_boxes_batch writes.
 template <class Args>
 static __global__ void __launch_bounds__(64) lane_dense_reachable_kernel(Args A, const double *sdmin, const double *sdmax,
                                                                   double *L, double *X) {
-    constexpr bool kSampled = std::is_same<Args, SampledArgs>::value;
+    constexpr bool kBoxed = std::is_same<Args, BoxedArgs>::value;
+    constexpr bool kSampled = std::is_same<Args, SampledArgs>::value || kBoxed;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= A.B) return;
     const int N = A.N, nC = A.nC;
-    const size_t row0 = kSampled ? 0 : (size_t)b * (N + 1) * nC, box0 = kSampled ? 0 : (size_t)b * 2 * (N + 1);  // (kSampled: no arrays)
+    const size_t row0 = kSampled ? 0 : (size_t)b * (N + 1) * nC, box0 = kSampled && !kBoxed ? 0 : (size_t)b * 2 * (N + 1);  // (kSampled: no arrays)
     const double *ga = A.a + row0, *gb = A.b + row0, *gc = A.c + row0;
     const double *glow = A.low + box0, *ghigh = A.high + box0;
     const double *deltas = A.deltas + (kSampled ? 0 : (size_t)b * N);
@@ -54,7 +56,9 @@ static __global__ void __launch_bounds__(64) lane_dense_reachable_kernel(Args A,
                 R.a[r] = neg ? -ra : ra; R.b[r] = neg ? -q2 : q2; R.c[r] = neg ? T.alim[2 * k] : -T.alim[2 * k + 1];
             }
             R.low0 = kVarMin; R.high0 = kVarMax; R.low1 = kVarMin; R.high1 = kVarMax;
-            if (T.has_vel) {
+            if constexpr (kBoxed) {
+                R.low0 = glow[2 * i]; R.high0 = ghigh[2 * i]; R.low1 = glow[2 * i + 1]; R.high1 = ghigh[2 * i + 1];
+            } else if (T.has_vel) {
                 double xlo, xhi;
                 velocity_xbound(T, gqs + (size_t)i * d, xlo, xhi);
                 R.low1 = R.low1 > xlo ? R.low1 : xlo;
