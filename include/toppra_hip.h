@@ -392,6 +392,59 @@ int tpr_feasible_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const do
 int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
                                            const double *sdmin, const double *sdmax, double *L, double *X, void *stream);
 
+/* ---- a rigid-body chain evaluated on the GPU: inverse dynamics and tool velocity for a batch --------------------------
+ * The reference's Python side leaves the robot to the caller (JointTorqueConstraint takes an inv_dyn callback,
+ * joint_torque.py:10-116); its C++ twin evaluates a model itself (cpp/src/toppra/constraint/joint_torque/pinocchio.hpp:
+ * recursive Newton-Euler behind JointTorque; constraint/cartesian_velocity_norm/pinocchio.hpp: forward kinematics behind
+ * CartesianVelocityNorm, b = v' S v, g = limit).  These entries are that piece for ONE serial chain shared by the batch:
+ * a fixed base, d = 1 .. TPR_MAX_DOF links, link i's parent is link i-1 (link 0's is the base = the world frame).
+ *   joint_type [d] int32   TPR_JOINT_REVOLUTE / TPR_JOINT_PRISMATIC.  ALWAYS A HOST ARRAY, with or without TPR_DEVICE_PTRS:
+ *                          it is the model's structure, read by the host (validation) and handed to the kernels by value;
+ *                          a device pointer here is refused (TPR_E_BADARG).
+ *   rot   [d][3][3]        row-major; columns = the joint frame's axes in parent coordinates
+ *   trans [d][3]           the joint frame's origin in parent coordinates
+ *   axis  [d][3]           unit vector in the joint frame: a revolute joint rotates by q_i about it (Rodrigues' formula), a
+ *                          prismatic one translates by q_i * axis.  The link frame is the joint frame after that motion.
+ *   mass [d], com [d][3] (link frame), inertia [d][6] = xx, yy, zz, xy, xz, yz about the centre of mass in link-frame axes
+ *   gravity [3]            gravitational acceleration in the world frame, applied as a base acceleration of -gravity
+ *   tool [3]               a point in the last link's frame
+ * The numeric arrays follow TPR_DEVICE_PTRS of the call's flags; every lane reads them through uniform loads.  Not modelled:
+ * rotor inertia, viscous damping, branched trees, floating bases.  fp64, every operation rounded on its own; sine and cosine
+ * are the device library's (1 - 2 ulp), so results agree with a host evaluation to rounding, not in bits.                */
+#define TPR_JOINT_REVOLUTE 0
+#define TPR_JOINT_PRISMATIC 1
+typedef struct tpr_chain {
+    int32_t d, flags; /* flags: reserved, 0 */
+    const int32_t *joint_type;
+    const double *axis, *rot, *trans;
+    const double *mass, *com, *inertia;
+    const double *gravity, *tool;
+} tpr_chain;
+/* ABI guard, as tpr_second_order_block_bytes: bytes of tpr_chain in the library.                                  */
+int tpr_chain_bytes(void);
+
+/* tau = RNEA(q, qd, qdd) at npoints points: q, qd, qdd, tau [npoints][d].  One thread per point; 1 .. 8 dof keep a point's
+ * state in registers, 9 .. 32 dof in LDS.  flags: TPR_DEVICE_PTRS.  Refused before any launch: a NULL chain, array or
+ * buffer, d outside 1 .. TPR_MAX_DOF, an unknown joint type, npoints < 0 (TPR_E_BADARG); npoints > 2^31 - 1
+ * (TPR_E_UNSUPPORTED) -- the same for the two entries below, with B (N + 1) as the point count.                       */
+int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd,
+                                     const double *qdd, double *tau, int flags, void *stream);
+/* The three evaluations of tpr_second_order_block in one pass over the point (linear_second_order.py:154-162):
+ * w0 = tau(q, 0, 0), wa = tau(q, 0, qs), wb = tau(q, qs, qss); q, qs, qss, w0, wa, wb [B][N+1][d].  The recursions share the
+ * sines, cosines and link rotations; each output equals tpr_chain_inverse_dynamics_batch on the same arguments (products
+ * with an exact zero are dropped, no sum is reordered).                                                               */
+int tpr_chain_torque_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
+                                 double *w0, double *wa, double *wb, int flags, void *stream);
+/* The tool point's spatial velocity for qd = qs -- linear v and angular w, both world-aligned -- as vSv = [v; w]' S [v; w]
+ * [B][N+1]; S [6][6] row-major, NULL = the linear speed only (v' v).  With limit [B] it also writes the bound
+ * xbound [B][N+1][2] = (0, limit / vSv) on x = sd^2 (an IEEE division: vSv == 0 gives +inf, which tpr_stage_boxes_batch
+ * folds against its 1e8 box); vSv or xbound may be NULL, not both; xbound needs limit.  The caller's responsibility, as NaN
+ * limits are elsewhere: limit > 0 (limit == 0 at a standstill is 0 / 0 = NaN, and a NaN bound loses every comparison of
+ * tpr_stage_boxes_batch's fold, i.e. silently drops out) and S symmetric positive semi-definite (an indefinite S can give
+ * vSv < 0 and with it a negative upper bound: an empty box).  toppra_amd's host layer checks both.                       */
+int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *S,
+                                  const double *limit, double *vSv, double *xbound, int flags, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -15,13 +15,14 @@ gfx950 behind the C-ABI of ``include/toppra_hip.h``); there is no CPU fallback.
 """
 import logging
 
-from . import algorithm, batch, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
+from . import algorithm, batch, chain, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
+from .chain import SerialChain
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 
-__all__ = ["algorithm", "batch", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
+__all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
-           "ParametrizeConstAccel", "ParametrizeSpline"]
+           "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain"]

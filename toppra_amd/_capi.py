@@ -71,6 +71,17 @@ class tpr_bound_source(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("data", C.c_void_p)]
 
 
+class tpr_chain(C.Structure):
+    _fields_ = [("d", C.c_int32), ("flags", C.c_int32), ("joint_type", C.c_void_p),
+                ("axis", C.c_void_p), ("rot", C.c_void_p), ("trans", C.c_void_p),
+                ("mass", C.c_void_p), ("com", C.c_void_p), ("inertia", C.c_void_p),
+                ("gravity", C.c_void_p), ("tool", C.c_void_p)]
+
+
+JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
+# the numeric arrays of tpr_chain, in the order of one packed upload, with their doubles per link (0: per chain, three)
+CHAIN_ARRAYS = (("axis", 3), ("rot", 9), ("trans", 3), ("mass", 1), ("com", 3), ("inertia", 6), ("gravity", 0), ("tool", 0))
+
 # tpr_bound_source.kind / .flags
 BOUND_VLIM, BOUND_VLIM_GRID, BOUND_X, BOUND_U = 1, 2, 3, 4
 BOUND_SHARED = 1
@@ -98,6 +109,7 @@ EXPORTS = (
     "tpr_bound_source_bytes", "tpr_stage_boxes_batch", "tpr_solve_sampled_boxed_batch",
     "tpr_solve_desired_duration_sampled_boxed_batch", "tpr_controllable_sets_sampled_boxed_batch",
     "tpr_feasible_sets_sampled_boxed_batch", "tpr_reachable_sets_sampled_boxed_batch",
+    "tpr_chain_bytes", "tpr_chain_inverse_dynamics_batch", "tpr_chain_torque_terms_batch", "tpr_chain_tool_velocity_batch",
 )
 
 _lib = None
@@ -233,6 +245,18 @@ def load():
         L.tpr_feasible_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V]
         L.tpr_reachable_sets_sampled_boxed_batch.restype = C.c_int
         L.tpr_reachable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V, V]
+        L.tpr_chain_bytes.restype = C.c_int
+        L.tpr_chain_bytes.argtypes = []
+        if L.tpr_chain_bytes() != C.sizeof(tpr_chain):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_chain takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_chain_bytes(), C.sizeof(tpr_chain)))
+        CP = C.POINTER(tpr_chain)
+        L.tpr_chain_inverse_dynamics_batch.restype = C.c_int
+        L.tpr_chain_inverse_dynamics_batch.argtypes = [CP, C.c_longlong, V, V, V, V, C.c_int, V]
+        L.tpr_chain_torque_terms_batch.restype = C.c_int
+        L.tpr_chain_torque_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
+        L.tpr_chain_tool_velocity_batch.restype = C.c_int
+        L.tpr_chain_tool_velocity_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int
@@ -525,6 +549,17 @@ def check_tensor(name, t, like):
         raise ValueError("%s must be float64 (got %s): the kernels read raw fp64 pointers" % (name, t.dtype))
     if not t.is_cuda or t.device != like.device:
         raise ValueError("%s must live on %s like coef (got %s)" % (name, like.device, t.device))
+
+
+def check_weight(S):
+    """The weight of v' S v must be symmetric positive semi-definite: an indefinite one can make the form negative and its
+    bound limit / v' S v an empty box.  A device tensor is read back (36 doubles)."""
+    host = S.detach().cpu().numpy() if hasattr(S, "detach") else np.asarray(S, dtype=np.float64)
+    if not np.all(np.isfinite(host)) or not np.array_equal(host, host.T):
+        raise ValueError("S must be finite and symmetric")
+    eig = np.linalg.eigvalsh(host)
+    if eig.min() < -1e-12 * max(abs(eig).max(), 1e-300):
+        raise ValueError("S must be positive semi-definite (smallest eigenvalue %g)" % eig.min())
 
 
 def per_traj_vector(name, arr, B, like):

@@ -247,7 +247,8 @@ class BatchTOPPRA(object):
     constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
         ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback.  Their rows are built on the GPU
         once per object and every pass runs on the dense-row entries; without them nothing changes.
-        ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` objects (first-order: they only tighten the box
+        ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` / ``BatchCartesianVelocityNormConstraint`` objects
+        (first-order: they only tighten the box
         of a stage's variables) may stand anywhere among them: their bounds and vlim are folded into stage boxes on the GPU
         once per object, in list order, and the passes run on the boxed sampled entries (or, with second-order constraints
         in the list too, on the dense-row entries with these boxes).
@@ -285,6 +286,8 @@ class BatchTOPPRA(object):
                 raise ValueError("second-order constraints evaluate their inverse dynamics at q: give the path positions")
             self._check_constraints()
         if self.first_order:
+            if q is None and any(getattr(c, "needs_q", False) for c in self.first_order):
+                raise ValueError("a tool velocity limit evaluates the chain at q: give the path positions")
             self._check_first_order()
         return self
 
@@ -375,7 +378,11 @@ class BatchTOPPRA(object):
             grid = _like(self.gridpoints, qs)
             sources = [("vlim", self.vlim)] if self.vlim is not None else []
             for con in self.first_order:
-                sources += con.bound_sources(grid, B, N, d, qs)
+                if getattr(con, "needs_q", False):  # (a constraint on the robot's pose, not only on q')
+                    q = self._samples[0] if self._samples is not None else self._path_eval()["q"]
+                    sources += con.bound_sources(grid, B, N, d, qs, q=q)
+                else:
+                    sources += con.bound_sources(grid, B, N, d, qs)
             low, high = _batch.stage_boxes_batch(qs, sources)
             self._boxed = (self.gridpoints, qs, qss, self.alim, low, high)
         return self._boxed

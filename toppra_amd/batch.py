@@ -21,7 +21,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "controllable_sets_sampled_batch", "feasible_sets_sampled_batch", "reachable_sets_sampled_batch",
            "solve_desired_duration_sampled_batch", "param_spline_samples_batch", "stage_boxes_batch",
            "solve_sampled_boxed_batch", "solve_desired_duration_sampled_boxed_batch", "controllable_sets_sampled_boxed_batch",
-           "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch"]
+           "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch",
+           "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch"]
 
 
 def _stream_ptr(like):
@@ -654,6 +655,94 @@ def reachable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sd
 
 # --------------------------------------------------------------------------------------------
 # host-side input preparation (outside the hot path)
+
+# --------------------------------------------------------------------------------------------
+# a rigid-body chain evaluated on the GPU (include/toppra_hip.h: tpr_chain; the model object is toppra_amd.chain.SerialChain)
+
+def _chain_points(chain, arrays, names):
+    """The arrays of one chain call -- all numpy or all torch-CUDA, one shape [..., d] -- as contiguous fp64 [npoints, d]:
+    (converted arrays, the common shape)."""
+    like = arrays[0]
+    conv = _capi.converter(like, names[0])
+    out, shape = [], None
+    for name, arr in zip(names, arrays):
+        arr = conv(name, arr)
+        if shape is None:
+            shape = tuple(int(v) for v in arr.shape)
+            if len(shape) < 1 or shape[-1] != chain.dof:
+                raise ValueError("%s must have shape [..., d] with d = %d (the chain's dof), got %s" % (name, chain.dof, shape))
+        elif tuple(int(v) for v in arr.shape) != shape:
+            raise ValueError("%s must have the shape of %s, %s, got %s" % (name, names[0], list(shape), tuple(arr.shape)))
+        out.append(arr)
+    npoints = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
+    if npoints > 0x7fffffff:
+        raise NotImplementedError("%d points in one call: the chain kernels take 2^31 - 1" % npoints)
+    return out, shape, npoints
+
+
+def chain_inverse_dynamics_batch(chain, q, qd, qdd):
+    """tau = RNEA(q, qd, qdd) of ``chain`` (a :class:`toppra_amd.chain.SerialChain`) at every point: three arrays [..., d] in,
+    [..., d] out; numpy in -> numpy out, tensors in -> a tensor out on the current stream."""
+    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    tau = _empty(q, shape)
+    _capi.check(_capi.load().tpr_chain_inverse_dynamics_batch(C.byref(model), npoints, _capi.ptr(q), _capi.ptr(qd), _capi.ptr(qdd),
+                                                              _capi.ptr(tau), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
+                                                              _stream_ptr(q)))
+    return tau
+
+
+def chain_torque_terms_batch(chain, q, qs, qss):
+    """(w0, wa, wb) = (tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: what a torque constraint's rows are built
+    from (``second_order_rows_batch``).  Each equals :func:`chain_inverse_dynamics_batch` on the same arguments."""
+    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    w0, wa, wb = _empty(q, shape), _empty(q, shape), _empty(q, shape)
+    _capi.check(_capi.load().tpr_chain_torque_terms_batch(C.byref(model), npoints, 0, _capi.ptr(q), _capi.ptr(qs), _capi.ptr(qss),
+                                                          _capi.ptr(w0), _capi.ptr(wa), _capi.ptr(wb),
+                                                          _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return w0, wa, wb
+
+
+def chain_tool_bound_batch(chain, q, qs, limit=None, S=None):
+    """The tool point's v' S v for qd = qs, [v; w] its linear and angular velocity in world axes: ``vSv`` of the shape of q
+    without its last axis.  ``S``: [6, 6] symmetric positive semi-definite (checked; a device tensor is read back for it: 36
+    doubles), None = the linear speed only (|v|^2).  With ``limit`` (> 0, a scalar or [B]; q must be
+    [B, N+1, d] then) also the bound on x = sd^2 it implies: (vSv, xbound) with xbound [B, N+1, 2] = (0, limit / vSv) --
+    +inf where the tool stands still -- the array a ``("xbound", ...)`` source of :func:`stage_boxes_batch` takes."""
+    (q, qs), shape, npoints = _chain_points(chain, (q, qs), ("q", "qs"))
+    dev = _capi.is_torch_cuda(q)
+    conv = _capi.converter(q, "q")
+    if S is not None:
+        if not dev:
+            S = np.asarray(S, dtype=np.float64)
+        elif not hasattr(S, "is_cuda"):
+            import torch
+            S = torch.as_tensor(np.asarray(S, dtype=np.float64), device=q.device)
+        S = conv("S", S)
+        if tuple(S.shape) != (6, 6):
+            raise ValueError("S must have shape [6, 6], got %s" % (tuple(S.shape),))
+        _capi.check_weight(S)
+    B, N, xbound = npoints, 0, None
+    if limit is not None:
+        if len(shape) != 3:
+            raise ValueError("with a limit, q must have shape [B, N+1, d], got %s" % (list(shape),))
+        B, N = shape[0], shape[1] - 1
+        limit = _capi.per_traj_vector("limit", limit, B, q)
+        if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
+            raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    vSv = _empty(q, shape[:-1])
+    if limit is not None:
+        xbound = _empty(q, shape[:-1] + (2,))
+    _capi.check(_capi.load().tpr_chain_tool_velocity_batch(C.byref(model), B, N, _capi.ptr(q), _capi.ptr(qs), _capi.ptr(S),
+                                                           _capi.ptr(limit), _capi.ptr(vSv), _capi.ptr(xbound),
+                                                           _capi.DEVICE_PTRS if dev else 0, _stream_ptr(q)))
+    return vSv if limit is None else (vSv, xbound)
+
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):
     """Batched cubic-spline fit on the host: waypoints [B, m, d] -> coef [B, 4, m-1, d].

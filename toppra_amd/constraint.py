@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
+from .chain import SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -321,13 +322,21 @@ def _zeros_like(x):
     return np.zeros_like(x) if isinstance(x, np.ndarray) else x.new_zeros(tuple(x.shape))
 
 
+def _check_chain_dof(inv_dyn, d):
+    if isinstance(inv_dyn, SerialChain) and inv_dyn.dof != d:
+        raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(inv_dyn.dof, d))
+
+
 class _BatchSecondOrder(LinearConstraint):
     """Shared part of the batched second-order constraints: the three batched inverse-dynamics evaluations of the
     reference's substitution (linear_second_order.py:154-162) and the block description that
     :func:`toppra_amd.batch.second_order_rows_batch` takes."""
 
     def _evaluate(self, q, qs, qss):
-        """w0 = tau(q, 0, 0), wa = tau(q, 0, q'), wb = tau(q, q', q''): exactly three calls, each checked."""
+        """w0 = tau(q, 0, 0), wa = tau(q, 0, q'), wb = tau(q, q', q''): exactly three calls, each checked -- or, for a
+        :class:`toppra_amd.chain.SerialChain`, one launch that evaluates the three (the values of the three calls)."""
+        if isinstance(self.inv_dyn, SerialChain):
+            return list(self.inv_dyn.torque_terms(q, qs, qss))
         zero = _zeros_like(q)
         out = []
         for what, args in (("(q, 0, 0)", (q, zero, zero)), ("(q, 0, q')", (q, zero, qs)), ("(q, q', q'')", (q, qs, qss))):
@@ -364,7 +373,9 @@ class BatchJointTorqueConstraint(_BatchSecondOrder):
     sign(qd) <= tau_lim[..., 1].
 
     ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, d] out -- numpy arrays when the problem was
-    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  ``tau_lim``:
+    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  A
+    :class:`toppra_amd.chain.SerialChain` may stand in its place: the robot's inverse dynamics then run on the GPU, the
+    three evaluations in one launch (the values of ``inv_dyn=chain.inverse_dynamics``).  ``tau_lim``:
     [d, 2] or [B, d, 2]; ``fs_coef``: [d] or [B, d].  Defaults are the reference's (Collocation)."""
 
     def __init__(self, inv_dyn, tau_lim, fs_coef, discretization_scheme=DiscretizationType.Collocation):
@@ -390,6 +401,7 @@ class BatchJointTorqueConstraint(_BatchSecondOrder):
     def check(self, B, N, d):
         if self.dof != d:
             raise ValueError("Wrong dimension: constraint dof ({:d}) not equal to path dof ({:d})".format(self.dof, d))
+        _check_chain_dof(self.inv_dyn, d)
         for name, n in (("tau_lim", self._tau_batch), ("fs_coef", self._fs_batch)):
             if n is not None and n != B:
                 raise ValueError("%s is given per trajectory for %d trajectories, the problem has %d" % (name, n, B))
@@ -412,7 +424,8 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
     """``SecondOrderConstraint`` (linear_second_order.py:11-173) for a batch:  F w <= g  on  w = inv_dyn(q, qd, qdd).
 
     ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, p] out -- numpy arrays when the problem was
-    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  ``F``: [m, p],
+    given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times; or a
+    :class:`toppra_amd.chain.SerialChain` (p = d: its joint torques, the three evaluations in one launch).  ``F``: [m, p],
     [B, m, p], [B, N+1, m, p], a batched callable of q returning [B, N+1, m, p], or None for the signed identity [I; -I]
     (what :meth:`joint_torque_constraint` builds: m = 2 p); ``g``: [m], [B, m], [B, N+1, m] or a batched callable of q.
     ``friction``: dry friction [d] or [B, d], friction * sign(q') is added to c (the ``custom_term`` of the reference's
@@ -465,6 +478,7 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         return None if m is None else (2 if self._interp() else 1) * int(m)
 
     def check(self, B, N, d):
+        _check_chain_dof(self.inv_dyn, d)
         for name, shape, tail in (("F", self._shape(self.F), 2), ("g", self._shape(self.g), 1)):
             if shape is not None and tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
                 raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
@@ -602,6 +616,55 @@ class BatchBoundConstraint(_BatchFirstOrder):
         self.check(B, N, d)
         # (the reference folds a constraint's ubound before its xbound: cy_seidel_solverwrapper.pyx:512-520)
         return [(kind, _like(arr, like)) for kind, arr in (("ubound", self.ubound), ("xbound", self.xbound)) if arr is not None]
+
+
+class BatchCartesianVelocityNormConstraint(_BatchFirstOrder):
+    """A limit on the tool point's velocity for a batch (the C++ twin's ``CartesianVelocityNorm``,
+    constraint/cartesian_velocity_norm.hpp):  v' S v * x <= limit  at every gridpoint, x = sd^2, where [v; w] are the linear
+    and angular velocity of ``chain``'s tool point per unit of path velocity (qd = q'), in world axes.
+
+    ``chain``: a :class:`toppra_amd.chain.SerialChain`; ``S``: [6, 6] symmetric positive semi-definite, None selects the linear
+    part (v' S v = |v|^2).  ``limit``: > 0, a scalar or [B].  It bounds v' S v * sd^2 -- with the default ``S`` that is the SQUARE of a tool speed: a limit
+    of 0.25 holds the tool to 0.5 length units per second.  The bound (0, limit / v' S v) comes from the chain kernel and is one
+    ``xbound`` source of the stage boxes; where the tool stands still it is +inf and the box keeps its 1e8.  Needs the path
+    positions: a ``from_path_samples`` batch must be given ``q``."""
+    needs_q = True
+
+    def __init__(self, chain, limit, S=None):
+        super(BatchCartesianVelocityNormConstraint, self).__init__()
+        if not isinstance(chain, SerialChain):
+            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+        self.chain, self.limit, self.S = chain, limit, S
+        self.dof = chain.dof
+        lshape = _shape_of(limit)
+        if len(lshape) > 1:
+            raise ValueError("limit must be a scalar or have shape [B], got %s" % (lshape,))
+        self._limit_batch = lshape[0] if lshape else None
+        host_limit = limit.detach().cpu().numpy() if hasattr(limit, "detach") else np.asarray(limit, dtype=np.float64)
+        if not np.all(host_limit > 0):
+            raise ValueError("limit must be > 0 (NaN is refused; 0 / 0 at a standstill would be a NaN bound)")
+        if S is not None:
+            if _shape_of(S) != (6, 6):
+                raise ValueError("S must have shape [6, 6], got %s" % (_shape_of(S),))
+            _capi.check_weight(S)
+        self._format_string = "    Batched tool velocity limit, %d dof\n" % self.dof
+
+    def source_count(self):
+        return 1
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
+        if self._limit_batch is not None and self._limit_batch != B:
+            raise ValueError("limit is given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
+
+    def bound_sources(self, gridpoints, B, N, d, like, q=None):
+        self.check(B, N, d)
+        if q is None:
+            raise ValueError("a tool velocity limit evaluates the chain at q: give the path positions")
+        limit = self.limit if hasattr(self.limit, "is_cuda") and self.limit.is_cuda else _like(self.limit, like)
+        S = None if self.S is None else _like(self.S, like)
+        return [("xbound", _batch.chain_tool_bound_batch(self.chain, q, like, limit, S)[1])]
 
 
 class ConicConstraint(Constraint):

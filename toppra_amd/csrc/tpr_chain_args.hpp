@@ -1,0 +1,42 @@
+// tpr_chain_args.hpp -- argument blocks of the rigid-body chain kernels (tpr_chain.hip.inc), shared with the C-ABI entries.
+#pragma once
+#include <cstdint>
+namespace tpr {
+constexpr int kChainRegMaxDof = 8;   // 1 .. 8 dof: compile-time dof, a point's state in registers; above: runtime dof, LDS
+constexpr int kChainBlock = 64;      // threads per block of every chain kernel: one wave
+// Doubles of LDS one thread keeps per link in the runtime-dof kernels: sine, cosine, and (force, moment) of each evaluation
+// that the backward recursion reads -- 3 doubles for tau(q, 0, 0) (no moment without velocity and acceleration), 6 else.
+constexpr int kChainSlotsSingle = 2 + 6, kChainSlotsFused = 2 + 3 + 6 + 6;
+constexpr int kChainLdsBytes = 160 * 1024;
+
+// tpr_chain with device pointers; the joint types by value as one bit per link (set = prismatic): wave-uniform by construction.
+struct ChainModel {
+    int d;
+    uint32_t prismatic;
+    const double *axis, *rot, *trans, *mass, *com, *inertia, *gravity, *tool;
+};
+
+struct ChainDynArgs {
+    ChainModel M;
+    int npoints;
+    const double *q, *qd, *qdd;  // [npoints][d]
+    double *tau;
+};
+
+struct ChainTermsArgs {
+    ChainModel M;
+    int npoints;
+    const double *q, *qs, *qss;  // [npoints][d]
+    double *w0, *wa, *wb;
+};
+
+struct ChainToolArgs {
+    ChainModel M;
+    int npoints, n1;      // B (N + 1); N + 1
+    const double *q, *qs;  // [npoints][d]
+    const double *S;       // [6][6] or null
+    const double *limit;   // [B] or null
+    double *vSv;           // [npoints] or null
+    double *xbound;        // [npoints][2] or null
+};
+}  // namespace tpr

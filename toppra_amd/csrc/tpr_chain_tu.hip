@@ -1,0 +1,72 @@
+// tpr_chain_tu.hip -- translation unit of the rigid-body chain kernels (tpr_chain.hip.inc): inverse dynamics, the three
+// evaluations of a torque constraint in one pass, the tool point's velocity.  build.py compiles it in parallel with the other
+// units.  Three entry points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "../../include/toppra_hip.h"
+#include "tpr_chain.hip.inc"
+
+namespace {
+inline unsigned chain_blocks(int npoints) { return (unsigned)(((long long)npoints + tpr::kChainBlock - 1) / tpr::kChainBlock); }
+
+// The runtime-dof kernels take up to the whole LDS of a CU; above 64 KB a kernel has to be told so, once per device: `done`
+// is the kernel's bit mask of the devices that have been told (the attribute is raised to the full 160 KB, so one call serves
+// every dof).
+template <class Kernel>
+int chain_allow_lds(Kernel kernel, size_t lds, std::atomic<unsigned long long> &done) {
+    if (lds > (size_t)tpr::kChainLdsBytes) return -1;
+    if (lds <= 64 * 1024) return 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    if (done.load(std::memory_order_relaxed) >> dev & 1ull) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tpr::kChainLdsBytes) != hipSuccess) return -1;
+    done.fetch_or(1ull << dev, std::memory_order_relaxed);
+    return 0;
+}
+std::atomic<unsigned long long> g_dyn_lds{0}, g_terms_fused_lds{0}, g_terms_serial_lds{0};
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *A, hipStream_t stream) {
+    const dim3 grid(chain_blocks(A->npoints)), block(tpr::kChainBlock);
+    switch (A->M.d) {
+#define TPR_CHAIN_CASE(DD) case DD: hipLaunchKernelGGL(tpr::chain_inverse_dynamics_kernel<DD>, grid, block, 0, stream, *A); return 0
+        TPR_CHAIN_CASE(1); TPR_CHAIN_CASE(2); TPR_CHAIN_CASE(3); TPR_CHAIN_CASE(4);
+        TPR_CHAIN_CASE(5); TPR_CHAIN_CASE(6); TPR_CHAIN_CASE(7); TPR_CHAIN_CASE(8);
+#undef TPR_CHAIN_CASE
+    }
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    const size_t lds = (size_t)A->M.d * tpr::kChainSlotsSingle * tpr::kChainBlock * sizeof(double);
+    if (chain_allow_lds(tpr::chain_inverse_dynamics_lds_kernel, lds, g_dyn_lds) != 0) return -1;
+    hipLaunchKernelGGL(tpr::chain_inverse_dynamics_lds_kernel, grid, block, lds, stream, *A);
+    return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *A, hipStream_t stream) {
+    const dim3 grid(chain_blocks(A->npoints)), block(tpr::kChainBlock);
+    switch (A->M.d) {
+#define TPR_CHAIN_CASE(DD) case DD: hipLaunchKernelGGL(tpr::chain_torque_terms_kernel<DD>, grid, block, 0, stream, *A); return 0
+        TPR_CHAIN_CASE(1); TPR_CHAIN_CASE(2); TPR_CHAIN_CASE(3); TPR_CHAIN_CASE(4);
+        TPR_CHAIN_CASE(5); TPR_CHAIN_CASE(6); TPR_CHAIN_CASE(7); TPR_CHAIN_CASE(8);
+#undef TPR_CHAIN_CASE
+    }
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    const size_t per_slot = (size_t)A->M.d * tpr::kChainBlock * sizeof(double);
+    if (per_slot * tpr::kChainSlotsFused <= (size_t)tpr::kChainLdsBytes) {
+        const size_t lds = per_slot * tpr::kChainSlotsFused;
+        if (chain_allow_lds(tpr::chain_torque_terms_lds_kernel<true>, lds, g_terms_fused_lds) != 0) return -1;
+        hipLaunchKernelGGL(tpr::chain_torque_terms_lds_kernel<true>, grid, block, lds, stream, *A);
+    } else {
+        const size_t lds = per_slot * tpr::kChainSlotsSingle;
+        if (chain_allow_lds(tpr::chain_torque_terms_lds_kernel<false>, lds, g_terms_serial_lds) != 0) return -1;
+        hipLaunchKernelGGL(tpr::chain_torque_terms_lds_kernel<false>, grid, block, lds, stream, *A);
+    }
+    return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *A, hipStream_t stream) {
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    hipLaunchKernelGGL(tpr::chain_tool_velocity_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), 0, stream, *A);
+    return 0;
+}

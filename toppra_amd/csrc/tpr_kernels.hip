@@ -1642,3 +1642,111 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
     return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::BoxedArgs>, sdmin, sdmax, L, X);
 }
 }  // extern "C"
+
+// ---- a rigid-body chain evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip) ------------------------------------------
+#include "tpr_chain_args.hpp"
+extern "C" {
+__attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *, hipStream_t);
+}
+namespace {
+// What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
+int check_chain(const tpr_chain *c, long long npoints, const char *who) {
+    if (default_device() < 0) return fail(TPR_E_HIP, "tpr_init() has not succeeded");
+    if (!c) return fail(TPR_E_BADARG, std::string(who) + ": null chain");
+    if (c->d < 1 || c->d > TPR_MAX_DOF) return fail(TPR_E_BADARG, std::string(who) + ": the chain's dof must be in [1, TPR_MAX_DOF]");
+    if (!c->joint_type || !c->axis || !c->rot || !c->trans || !c->mass || !c->com || !c->inertia || !c->gravity || !c->tool)
+        return fail(TPR_E_BADARG, std::string(who) + ": every array of the chain is required");
+    {  // joint_type is read here, on the host: a device pointer in its place is refused, not dereferenced
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, c->joint_type) == hipSuccess) {
+            if (attr.type == hipMemoryTypeDevice) return fail(TPR_E_BADARG, std::string(who) + ": joint_type must be a host array, also with TPR_DEVICE_PTRS");
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    for (int i = 0; i < c->d; ++i)
+        if (c->joint_type[i] != TPR_JOINT_REVOLUTE && c->joint_type[i] != TPR_JOINT_PRISMATIC)
+            return fail(TPR_E_BADARG, std::string(who) + ": unknown joint type");
+    if (npoints < 0) return fail(TPR_E_BADARG, std::string(who) + ": a negative point count");
+    if (npoints > 0x7fffffffLL) return fail(TPR_E_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 points");
+    return TPR_E_OK;
+}
+tpr::ChainModel stage_chain(const tpr_chain *c, Staging &S) {
+    tpr::ChainModel M{};
+    const size_t d = (size_t)c->d;
+    M.d = c->d;
+    for (int i = 0; i < c->d; ++i) M.prismatic |= (uint32_t)(c->joint_type[i] == TPR_JOINT_PRISMATIC) << i;
+    M.axis = S.in(c->axis, 3 * d); M.rot = S.in(c->rot, 9 * d); M.trans = S.in(c->trans, 3 * d);
+    M.mass = S.in(c->mass, d); M.com = S.in(c->com, 3 * d); M.inertia = S.in(c->inertia, 6 * d);
+    M.gravity = S.in(c->gravity, 3); M.tool = S.in(c->tool, 3);
+    return M;
+}
+}  // namespace
+
+extern "C" {
+int tpr_chain_bytes(void) { return (int)sizeof(tpr_chain); }
+
+int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
+                                     double *tau, int flags, void *stream_) {
+    if (int rc = check_chain(chain, npoints, "tpr_chain_inverse_dynamics_batch")) return rc;
+    if (!q || !qd || !qdd || !tau) return fail(TPR_E_BADARG, "tpr_chain_inverse_dynamics_batch: q, qd, qdd, tau are required");
+    Staging S(flags & TPR_DEVICE_PTRS, tau, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainDynArgs A{};
+    A.M = stage_chain(chain, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
+    A.tau = S.out(tau, n);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_dynamics_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_inverse_dynamics_batch: the kernel's LDS could not be reserved");
+    return S.finish();
+}
+
+int tpr_chain_torque_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
+                                 double *w0, double *wa, double *wb, int flags, void *stream_) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_torque_terms_batch: B >= 0, N >= 0");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_torque_terms_batch")) return rc;
+    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_torque_terms_batch: q, qs, qss, w0, wa, wb are required");
+    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainTermsArgs A{};
+    A.M = stage_chain(chain, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
+    A.w0 = S.out(w0, n); A.wa = S.out(wa, n); A.wb = S.out(wb, n);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_terms_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_torque_terms_batch: the kernel's LDS could not be reserved");
+    return S.finish();
+}
+
+int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *Sm,
+                                  const double *limit, double *vSv, double *xbound, int flags, void *stream_) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: B >= 0, N >= 0");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_velocity_batch")) return rc;
+    if (!q || !qs) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: q, qs are required");
+    if (!vSv && !xbound) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: one of vSv, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: xbound needs limit");
+    Staging S(flags & TPR_DEVICE_PTRS, vSv ? vSv : xbound, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainToolArgs A{};
+    A.M = stage_chain(chain, S);
+    A.npoints = (int)npoints; A.n1 = N + 1;
+    A.q = S.in(q, n); A.qs = S.in(qs, n);
+    A.S = S.in(Sm, 36);
+    A.limit = xbound ? S.in(limit, (size_t)B) : nullptr;
+    A.vSv = S.out(vSv, (size_t)npoints); A.xbound = S.out(xbound, 2 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_tool_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_velocity_batch: no kernel for this dof");
+    return S.finish();
+}
+}  // extern "C"
