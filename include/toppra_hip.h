@@ -444,6 +444,22 @@ int tpr_chain_torque_terms_batch(const tpr_chain *chain, int B, int N, const dou
  * vSv < 0 and with it a negative upper bound: an empty box).  toppra_amd's host layer checks both.                       */
 int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *S,
                                   const double *limit, double *vSv, double *xbound, int flags, void *stream);
+/* The tool point's acceleration acc(q, qd, qdd) = [lin; ang], [npoints][6], world axes, from the forward recursion of
+ * tpr_chain_inverse_dynamics_batch with the base at rest (W = the last link's axes in the world; w, wd, a its angular velocity,
+ * angular acceleration and origin acceleration in its own frame):
+ *   lin = W (a + wd x tool + w x (w x tool)),   ang = W wd.
+ * Pure kinematics: gravity is NOT applied (nor masses read).  lin is the CLASSICAL acceleration of the point -- the second time
+ * derivative of its world position, what the reference's example examples-old/cartesian_accel.py reads from
+ * GetLinkAccelerations(...)[:3] -- not the spatial one (which lacks w x v).  q, qd, qdd [npoints][d]; one thread per point,
+ * any dof, state in registers.  A zero result is +0.  Refusals as tpr_chain_inverse_dynamics_batch.                      */
+int tpr_chain_tool_acceleration_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd,
+                                      const double *qdd, double *acc, int flags, void *stream);
+/* The evaluations a second-order constraint on that acceleration needs (tpr_second_order_block with p = 6), in one pass:
+ * wa = acc(q, 0, qs), wb = acc(q, qs, qss), [B][N+1][6]; w0 = acc(q, 0, 0) is an exact zero and is not computed.  Each
+ * output equals tpr_chain_tool_acceleration_batch on the same arguments in every bit (products with an exact zero are
+ * dropped, no sum is reordered).  Refusals as tpr_chain_torque_terms_batch.                                            */
+int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs,
+                                            const double *qss, double *wa, double *wb, int flags, void *stream);
 
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).

@@ -110,6 +110,7 @@ EXPORTS = (
     "tpr_solve_desired_duration_sampled_boxed_batch", "tpr_controllable_sets_sampled_boxed_batch",
     "tpr_feasible_sets_sampled_boxed_batch", "tpr_reachable_sets_sampled_boxed_batch",
     "tpr_chain_bytes", "tpr_chain_inverse_dynamics_batch", "tpr_chain_torque_terms_batch", "tpr_chain_tool_velocity_batch",
+    "tpr_chain_tool_acceleration_batch", "tpr_chain_tool_acceleration_terms_batch",
 )
 
 _lib = None
@@ -257,6 +258,10 @@ def load():
         L.tpr_chain_torque_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
         L.tpr_chain_tool_velocity_batch.restype = C.c_int
         L.tpr_chain_tool_velocity_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
+        L.tpr_chain_tool_acceleration_batch.restype = C.c_int
+        L.tpr_chain_tool_acceleration_batch.argtypes = [CP, C.c_longlong, V, V, V, V, C.c_int, V]
+        L.tpr_chain_tool_acceleration_terms_batch.restype = C.c_int
+        L.tpr_chain_tool_acceleration_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

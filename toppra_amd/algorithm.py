@@ -245,7 +245,8 @@ class BatchTOPPRA(object):
     gridpoints : [N+1] shared or [B, N+1] per trajectory.
     vlim, alim : [B, d, 2] joint velocity / acceleration limits (either may be None).
     constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
-        ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback.  Their rows are built on the GPU
+        ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback, or
+        ``BatchCartesianAccelerationConstraint`` (a limit on a chain's tool acceleration).  Their rows are built on the GPU
         once per object and every pass runs on the dense-row entries; without them nothing changes.
         ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` / ``BatchCartesianVelocityNormConstraint`` objects
         (first-order: they only tighten the box

@@ -22,7 +22,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "solve_desired_duration_sampled_batch", "param_spline_samples_batch", "stage_boxes_batch",
            "solve_sampled_boxed_batch", "solve_desired_duration_sampled_boxed_batch", "controllable_sets_sampled_boxed_batch",
            "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch",
-           "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch"]
+           "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch",
+           "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -742,6 +743,34 @@ def chain_tool_bound_batch(chain, q, qs, limit=None, S=None):
                                                            _capi.ptr(limit), _capi.ptr(vSv), _capi.ptr(xbound),
                                                            _capi.DEVICE_PTRS if dev else 0, _stream_ptr(q)))
     return vSv if limit is None else (vSv, xbound)
+
+
+def chain_tool_acceleration_batch(chain, q, qd, qdd):
+    """The tool point's acceleration acc(q, qd, qdd) = [linear; angular] in world axes at every point: three arrays [..., d]
+    in, [..., 6] out.  Kinematics only (no gravity); the linear part is the classical acceleration of the point, the second
+    time derivative of its world position (include/toppra_hip.h: tpr_chain_tool_acceleration_batch)."""
+    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    acc = _empty(q, shape[:-1] + (6,))
+    _capi.check(_capi.load().tpr_chain_tool_acceleration_batch(C.byref(model), npoints, _capi.ptr(q), _capi.ptr(qd), _capi.ptr(qdd),
+                                                               _capi.ptr(acc), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
+                                                               _stream_ptr(q)))
+    return acc
+
+
+def chain_tool_acceleration_terms_batch(chain, q, qs, qss):
+    """(wa, wb) = (acc(q, 0, qs), acc(q, qs, qss)) [..., 6] in one launch: what a constraint on the tool point's acceleration
+    builds its rows from (w0 = acc(q, 0, 0) is an exact zero).  Each equals :func:`chain_tool_acceleration_batch` on the same
+    arguments in every bit."""
+    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    wa, wb = _empty(q, shape[:-1] + (6,)), _empty(q, shape[:-1] + (6,))
+    _capi.check(_capi.load().tpr_chain_tool_acceleration_terms_batch(C.byref(model), npoints, 0, _capi.ptr(q), _capi.ptr(qs),
+                                                                     _capi.ptr(qss), _capi.ptr(wa), _capi.ptr(wb),
+                                                                     _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return wa, wb
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

@@ -30,7 +30,7 @@ class SerialChain(object):
     masses : [d] (>= 0), coms : [d, 3] centres of mass in the link frames, inertias : [d, 6] = xx, yy, zz, xy, xz, yz about
         the centre of mass in link-frame axes (or [d, 3, 3] symmetric).
     gravity : gravitational acceleration in the world frame (applied as a base acceleration of -gravity).
-    tool : a point in the last link's frame (:meth:`tool_velocity_norm`).
+    tool : a point in the last link's frame (:meth:`tool_velocity_norm`, :meth:`tool_acceleration`).
 
     Not modelled: rotor inertia, viscous damping, branched trees, floating bases; dry friction stays with the constraints
     (``fs_coef`` / ``friction``).  The model is uploaded to a device once per object, on first use there.
@@ -121,3 +121,14 @@ class SerialChain(object):
         """v' S v of the tool point for qd = qs, shape [...]: [v; w] are its linear and angular velocity in world axes, ``S``
         [6, 6] (None: the linear part only, i.e. the squared tool speed per unit of path velocity)."""
         return _batch.chain_tool_bound_batch(self, q, qs, None, S)
+
+    def tool_acceleration(self, q, qd, qdd):
+        """The tool point's acceleration [..., 6] = [linear; angular] in world axes: the classical acceleration of the point
+        (the second time derivative of its world position) and the last link's angular acceleration.  Kinematics only: gravity
+        does not enter.  A valid batched ``inv_dyn`` of :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
+        return _batch.chain_tool_acceleration_batch(self, q, qd, qdd)
+
+    def tool_acceleration_terms(self, q, qs, qss):
+        """(acc(q, 0, qs), acc(q, qs, qss)) in one launch: the evaluations a limit on the tool acceleration needs; acc(q, 0, 0)
+        is an exact zero."""
+        return _batch.chain_tool_acceleration_terms_batch(self, q, qs, qss)

@@ -515,6 +515,108 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         return {"w0": w0, "wa": wa, "wb": wb, "F": F, "g": g, "friction": fr, "interpolation": self._interp()}
 
 
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64)
+
+
+class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
+    """A limit on the tool point's acceleration for a batch (the reference's example examples-old/cartesian_accel.py: a
+    ``SecondOrderConstraint`` whose ``inv_dyn`` returns the link's acceleration):  F acc <= g  on  acc(q, qd, qdd) =
+    [linear; angular] of ``chain``'s tool point in world axes -- the classical acceleration of the point and the last link's
+    angular acceleration (:meth:`toppra_amd.chain.SerialChain.tool_acceleration`; kinematics, no gravity).  The two
+    evaluations the rows need come from one launch of the chain kernel; acc(q, 0, 0) is an exact zero.
+
+    ``chain``: a :class:`toppra_amd.chain.SerialChain`.  The limits are given in one of two spellings:
+
+    ``linear`` / ``angular`` (either or both): a scalar ``amax`` (-amax <= component <= amax on each world axis), [3, 2] or
+    [B, 3, 2] (lower, upper).  Each part given adds six rows, the signed identity on that part with g = [upper; -lower]; with
+    both, the linear part's rows come first: F = [I 0; -I 0; 0 I; 0 -I] (12 rows).
+
+    ``F`` [m, 6], [B, m, 6] or [B, N+1, m, 6] with ``g`` [m], [B, m] or [B, N+1, m], as ``BatchSecondOrderConstraint`` takes
+    them: a polyhedral stand-in for a norm limit, or limits in a tilted frame.
+
+    Defaults are the reference's for ``SecondOrderConstraint`` (Interpolation).  Needs the path positions: a
+    ``from_path_samples`` batch must be given ``q``.  A true norm (conic) limit and a point on another link than the last
+    are out of scope."""
+
+    def __init__(self, chain, linear=None, angular=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
+        super(BatchCartesianAccelerationConstraint, self).__init__()
+        if not isinstance(chain, SerialChain):
+            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+        self.chain = chain
+        self.dof = chain.dof
+        boxes, rows = linear is not None or angular is not None, F is not None or g is not None
+        if boxes and rows:
+            raise ValueError("give the limits either as linear / angular or as F and g, not both")
+        if not boxes and not rows:
+            raise ValueError("no limit given: one of linear, angular, or F with g, is required")
+        self._limit_batch = None
+        if boxes:
+            F_parts, g_parts = [], []
+            for name, lim, first in (("linear", linear, 0), ("angular", angular, 3)):
+                if lim is None:
+                    continue
+                lim = _host(lim)
+                if lim.ndim == 0:
+                    lim = np.stack([np.full(3, -float(lim)), np.full(3, float(lim))], -1)
+                if lim.ndim not in (2, 3) or lim.shape[-2:] != (3, 2):
+                    raise ValueError("%s must be a scalar or have shape [3, 2] or [B, 3, 2], got %s" % (name, list(lim.shape)))
+                if not np.all(np.isfinite(lim)):
+                    raise ValueError("%s holds a limit that is not finite" % name)
+                if np.any(lim[..., 0] > lim[..., 1]):
+                    raise ValueError("%s holds a lower limit above its upper limit" % name)
+                if lim.ndim == 3:
+                    if self._limit_batch not in (None, lim.shape[0]):
+                        raise ValueError("linear and angular are given per trajectory for %d and %d trajectories"
+                                         % (self._limit_batch, lim.shape[0]))
+                    self._limit_batch = int(lim.shape[0])
+                part = np.zeros((6, 6))
+                part[:3, first:first + 3], part[3:, first:first + 3] = np.eye(3), -np.eye(3)
+                F_parts.append(part)
+                g_parts.append(np.concatenate((lim[..., 1], -lim[..., 0]), -1))  # [upper; -lower]
+            if self._limit_batch is not None:
+                g_parts = [np.broadcast_to(p, (self._limit_batch, 6)) for p in g_parts]
+            self.F, self.g = np.concatenate(F_parts, 0), np.ascontiguousarray(np.concatenate(g_parts, -1))
+        else:
+            if F is None or g is None:
+                raise ValueError("F and g are given together")
+            fshape, gshape = _shape_of(F), _shape_of(g)
+            if len(fshape) not in (2, 3, 4) or fshape[-1] != 6:
+                raise ValueError("F must have shape [m, 6], [B, m, 6] or [B, N+1, m, 6], got %s" % (list(fshape),))
+            if len(gshape) not in (1, 2, 3):
+                raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
+            if gshape[-1] != fshape[-2]:
+                raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
+            for name, arr in (("F", F), ("g", g)):
+                if not np.all(np.isfinite(_host(arr))):
+                    raise ValueError("%s holds a value that is not finite" % name)
+            self.F, self.g = F, g
+        self.linear, self.angular = linear, angular
+        self.set_discretization_type(discretization_scheme)
+        self.identical = True
+        self._format_string = "    Batched tool acceleration limit, %d dof, %d rows\n" % (self.dof, _shape_of(self.F)[-2])
+
+    def rows_per_stage(self, d):
+        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
+        if self._limit_batch is not None and self._limit_batch != B:
+            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
+        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
+            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
+                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
+                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+
+    def block(self, q, qs, qss):
+        B, n1, d = (int(v) for v in q.shape)
+        self.check(B, n1 - 1, d)
+        wa, wb = self.chain.tool_acceleration_terms(q, qs, qss)
+        return {"w0": _zeros_like(wa), "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
+                "interpolation": self._interp()}
+
+
 # ---- batched first-order constraints: they only tighten a stage's variable box (BatchTOPPRA(..., constraints=[...])) -------
 
 def _shape_of(x):

@@ -26,7 +26,8 @@
 // consecutive doubles, read back one row per lane at pitch d | 1 -- and so do the outputs.  9 .. 32 dof: runtime dof, the
 // state in LDS as [link][slot][lane] (conflict-free), d * slots * 512 bytes per block; the fused state fits 160 KB up to 18
 // dof, above that the three evaluations run one after another in one launch.  Chain parameters are addressed by the loop
-// index only: uniform loads.
+// index only: uniform loads.  The tool point's velocity and acceleration (at the end of this file) keep nothing per link:
+// runtime dof, registers only, at any dof.
 #pragma once
 #include "tpr_device.hpp"
 #include "tpr_chain_args.hpp"
@@ -100,8 +101,9 @@ __device__ __forceinline__ ChainJoint chain_joint(const ChainLink &L, double sv,
 struct ChainKin { V3 w, wd, a; };  // a link's angular velocity, angular acceleration, origin acceleration, in its own frame
 
 // Level 2: the recursion.  Level 1: velocity zero, its products left out.  Level 0: acceleration zero as well.
+// The kinematic part (the tool point's acceleration needs nothing else): the parent's K becomes this link's.
 template <int Level>
-__device__ __forceinline__ void chain_forward(const ChainLink &L, const ChainJoint &J, ChainKin &K, double qd, double qdd, V3 &F, V3 &Nm) {
+__device__ __forceinline__ void chain_kinematics(const ChainLink &L, const ChainJoint &J, ChainKin &K, double qd, double qdd) {
     const V3 zero{0.0, 0.0, 0.0};
     const V3 zr = L.prismatic ? zero : L.axis, zp = L.prismatic ? L.axis : zero;
     V3 ar = K.a;
@@ -118,6 +120,14 @@ __device__ __forceinline__ void chain_forward(const ChainLink &L, const ChainJoi
         wd = wd + cross(wl, zr) * qd;
         a = a + cross(wl, zp) * (2.0 * qd);
     }
+    K.w = w; K.wd = wd; K.a = a;
+}
+
+template <int Level>
+__device__ __forceinline__ void chain_forward(const ChainLink &L, const ChainJoint &J, ChainKin &K, double qd, double qdd, V3 &F, V3 &Nm) {
+    const V3 zero{0.0, 0.0, 0.0};
+    chain_kinematics<Level>(L, J, K, qd, qdd);
+    const V3 w = K.w, wd = K.wd, a = K.a;
     V3 ac = a;
     if (Level >= 1) ac = ac + cross(wd, L.com);
     if (Level >= 2) ac = ac + cross(w, cross(w, L.com));
@@ -125,7 +135,6 @@ __device__ __forceinline__ void chain_forward(const ChainLink &L, const ChainJoi
     Nm = zero;
     if (Level >= 1) Nm = inertia_mul(L, wd);
     if (Level >= 2) Nm = Nm + cross(w, inertia_mul(L, w));
-    K.w = w; K.wd = wd; K.a = a;
 }
 
 struct ChainWrench { V3 f, n; };  // the child's force and moment in this link's frame, the moment about this link's origin
@@ -336,6 +345,110 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_velocity_kernel
         A.xbound[2 * p] = 0.0;
         A.xbound[2 * p + 1] = A.limit[p / (size_t)A.n1] / vSv;
     }
+}
+
+// ---- the tool point's acceleration: the kinematic recursion with the base at rest, any dof, state in registers ------------
+//   acc(q, qd, qdd) = [W_d (a_d + wd_d x tool + w_d x (w_d x tool)); W_d wd_d]: the classical (point) acceleration and the
+//   angular acceleration, world axes; no gravity.  Per evaluation the state is (w, wd, a) of the current link, W is shared.
+// Every output passes through "+ 0.0": a zero leaves as +0 whatever the signs of the vanishing products were, so the fused
+// outputs equal the single evaluation's in every bit and acc(q, 0, 0) is the +0 a constraint's w0 is given as.
+// A block is one wave of 64 consecutive points.  Their q, q', q'' [64][d] are contiguous in memory and pass through LDS, as
+// in the 1 .. 8-dof torque kernels but with a runtime d: loaded with consecutive lanes on consecutive doubles, read back one
+// row per lane at the odd pitch d | 1 (conflict-free).  Read in place instead, a wave's rows -- 64 lanes x 3 arrays x d doubles,
+// re-read link after link -- outgrow the caches from about 12 dof on and the lines come from memory again and again.  The
+// 6-wide outputs leave through the same LDS at pitch 7.  Dynamic LDS: chain_accel_lds_bytes.
+__host__ __device__ constexpr size_t chain_accel_lds_bytes(int d, int outputs) {
+    const size_t in = 3 * (size_t)kChainBlock * (size_t)(d | 1), out = (size_t)outputs * kChainBlock * 7;
+    return (in > out ? in : out) * sizeof(double);
+}
+
+// The block's rows [npts][d] of three arrays into LDS at `pitch`: (row, column) of element k advance without a division.
+__device__ __forceinline__ void chain_rows_load(double *b0, double *b1, double *b2, const double *s0, const double *s1, const double *s2,
+                                                size_t g0, int npts, int d, int pitch) {
+    const size_t base = g0 * (size_t)d;
+    const int step_r = kChainBlock / d, step_c = kChainBlock % d;
+    int r = (int)threadIdx.x / d, c = (int)threadIdx.x % d;
+    for (int k = threadIdx.x; k < npts * d; k += kChainBlock) {
+        const int at = r * pitch + c;
+        b0[at] = s0[base + k]; b1[at] = s1[base + k]; b2[at] = s2[base + k];
+        r += step_r; c += step_c;
+        if (c >= d) { c -= d; ++r; }
+    }
+}
+// ... and a block's outputs [npts][6] from LDS at pitch 7.
+__device__ __forceinline__ void chain_accel_rows_store(const double *buf, double *dst, size_t g0, int npts) {
+    for (int k = threadIdx.x; k < npts * 6; k += kChainBlock) dst[g0 * 6 + k] = buf[(k / 6) * 7 + (k % 6)];
+}
+
+template <int Level>
+__device__ __forceinline__ void chain_tool_accel_put(const M3 &W, const ChainKin &K, V3 tool, double *o) {
+    V3 al = K.a + cross(K.wd, tool);
+    if (Level >= 2) al = al + cross(K.w, cross(K.w, tool));
+    const V3 lin = mul(W, al), ang = mul(W, K.wd);
+    o[0] = lin.x + 0.0; o[1] = lin.y + 0.0; o[2] = lin.z + 0.0;
+    o[3] = ang.x + 0.0; o[4] = ang.y + 0.0; o[5] = ang.z + 0.0;
+}
+
+// Lanes past the last point of the batch work on the last point's row again and rewrite its LDS row with its values (no lane is
+// masked out); only npts rows leave.
+static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_kernel(ChainAccelArgs A) {
+    extern __shared__ double chain_lds[];
+    const ChainModel &M = A.M;
+    const int d = M.d, pitch = d | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    chain_rows_load(bq, b1, b2, A.q, A.qd, A.qdd, g0, npts, d, pitch);
+    __syncthreads();
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const V3 zero{0.0, 0.0, 0.0};
+    ChainKin K{zero, zero, zero};
+    M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+#pragma nounroll
+    for (int i = 0; i < d; ++i) {
+        const ChainLink L = chain_link(M, i);
+        const double qi = bq[row + i];
+        const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+        chain_kinematics<2>(L, J, K, b1[row + i], b2[row + i]);
+        W = mul(W, J.E);
+    }
+    __syncthreads();
+    chain_tool_accel_put<2>(W, K, load3(M.tool), chain_lds + lane * 7);
+    __syncthreads();
+    chain_accel_rows_store(chain_lds, A.acc, g0, npts);
+}
+
+// wa = acc(q, 0, qs), wb = acc(q, qs, qss) in one pass: level 1 leaves out the products with the zero velocity.
+static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_terms_kernel(ChainAccelTermsArgs A) {
+    extern __shared__ double chain_lds[];
+    const ChainModel &M = A.M;
+    const int d = M.d, pitch = d | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    chain_rows_load(bq, b1, b2, A.q, A.qs, A.qss, g0, npts, d, pitch);
+    __syncthreads();
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const V3 zero{0.0, 0.0, 0.0};
+    ChainKin K1{zero, zero, zero}, K2 = K1;
+    M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+#pragma nounroll
+    for (int i = 0; i < d; ++i) {
+        const ChainLink L = chain_link(M, i);
+        const double qi = bq[row + i], v1 = b1[row + i], v2 = b2[row + i];
+        const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+        chain_kinematics<1>(L, J, K1, 0.0, v1);
+        chain_kinematics<2>(L, J, K2, v1, v2);
+        W = mul(W, J.E);
+    }
+    const V3 tool = load3(M.tool);
+    double *oa = chain_lds, *ob = chain_lds + kChainBlock * 7;
+    __syncthreads();
+    chain_tool_accel_put<1>(W, K1, tool, oa + lane * 7);
+    chain_tool_accel_put<2>(W, K2, tool, ob + lane * 7);
+    __syncthreads();
+    chain_accel_rows_store(oa, A.wa, g0, npts);
+    chain_accel_rows_store(ob, A.wb, g0, npts);
 }
 
 }  // namespace tpr

@@ -39,4 +39,18 @@ struct ChainToolArgs {
     double *vSv;           // [npoints] or null
     double *xbound;        // [npoints][2] or null
 };
+
+struct ChainAccelArgs {
+    ChainModel M;
+    int npoints;
+    const double *q, *qd, *qdd;  // [npoints][d]
+    double *acc;                 // [npoints][6]: linear, angular
+};
+
+struct ChainAccelTermsArgs {
+    ChainModel M;
+    int npoints;
+    const double *q, *qs, *qss;  // [npoints][d]
+    double *wa, *wb;             // [npoints][6]
+};
 }  // namespace tpr

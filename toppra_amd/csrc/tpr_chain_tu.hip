@@ -1,6 +1,6 @@
 // tpr_chain_tu.hip -- translation unit of the rigid-body chain kernels (tpr_chain.hip.inc): inverse dynamics, the three
-// evaluations of a torque constraint in one pass, the tool point's velocity.  build.py compiles it in parallel with the other
-// units.  Three entry points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof.
+// evaluations of a torque constraint in one pass, the tool point's velocity and acceleration.  build.py compiles it in parallel
+// with the other units.  Five entry points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -68,5 +68,18 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(c
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *A, hipStream_t stream) {
     if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
     hipLaunchKernelGGL(tpr::chain_tool_velocity_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), 0, stream, *A);
+    return 0;
+}
+
+// (the tool-acceleration kernels' staging area is at most 3 * 64 * 33 doubles = 50 688 bytes at 32 dof: under the 64 KB any kernel may take)
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(const tpr::ChainAccelArgs *A, hipStream_t stream) {
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    hipLaunchKernelGGL(tpr::chain_tool_accel_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
+    return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *A, hipStream_t stream) {
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    hipLaunchKernelGGL(tpr::chain_tool_accel_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 2), stream, *A);
     return 0;
 }

@@ -1649,6 +1649,8 @@ extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(const tpr::ChainAccelArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *, hipStream_t);
 }
 namespace {
 // What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
@@ -1747,6 +1749,44 @@ int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const do
     if (int rc = S.failed()) return rc;
     if (npoints > 0 && tpr_tu_chain_tool_launch(&A, S.stream) != 0)
         return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_velocity_batch: no kernel for this dof");
+    return S.finish();
+}
+
+int tpr_chain_tool_acceleration_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
+                                      double *acc, int flags, void *stream_) {
+    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_acceleration_batch")) return rc;
+    if (!q || !qd || !qdd || !acc) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_batch: q, qd, qdd, acc are required");
+    Staging S(flags & TPR_DEVICE_PTRS, acc, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainAccelArgs A{};
+    A.M = stage_chain(chain, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
+    A.acc = S.out(acc, 6 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_accel_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_acceleration_batch: no kernel for this dof");
+    return S.finish();
+}
+
+int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
+                                            double *wa, double *wb, int flags, void *stream_) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_terms_batch: B >= 0, N >= 0");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_acceleration_terms_batch")) return rc;
+    if (!q || !qs || !qss || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_terms_batch: q, qs, qss, wa, wb are required");
+    Staging S(flags & TPR_DEVICE_PTRS, wa, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainAccelTermsArgs A{};
+    A.M = stage_chain(chain, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
+    A.wa = S.out(wa, 6 * (size_t)npoints); A.wb = S.out(wb, 6 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_accel_terms_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_acceleration_terms_batch: no kernel for this dof");
     return S.finish();
 }
 }  // extern "C"
