@@ -307,6 +307,12 @@ __global__ void __launch_bounds__(BS) cert_solve_kernel(GroupArgs A) {
         TPR_WAVE_SYNC();  // (the cooperative batches read other lanes' columns)
     }
     C S;
+    if constexpr (C::kPairFetch) {  // rows 0..5 as (q1, q2) pairs for CertStage::fetch: (1, 0), (+0, 1), (-0, 1)
+        __shared__ double spec_rows[C::kSpecDoubles];
+        if (tid < C::kSpecDoubles) spec_rows[tid] = (tid == 0 || (tid & 1)) ? (tid == 1 ? 0.0 : 1.0) : (tid == 4 ? -0.0 : 0.0);
+        S.spec = spec_rows;
+        TPR_WAVE_SYNC();
+    }
     double vlo[D], vhi[D];
     {
         const double *alim = A.alim + (size_t)bb * 2 * D;
@@ -938,6 +944,12 @@ __global__ void __launch_bounds__(BS) cert_feasible_kernel(GroupArgs A, double *
         TPR_WAVE_SYNC();  // (the cooperative batches read other lanes' columns)
     }
     C S;
+    if constexpr (C::kPairFetch) {  // rows 0..5 as (q1, q2) pairs for CertStage::fetch: (1, 0), (+0, 1), (-0, 1)
+        __shared__ double spec_rows[C::kSpecDoubles];
+        if (tid < C::kSpecDoubles) spec_rows[tid] = (tid == 0 || (tid & 1)) ? (tid == 1 ? 0.0 : 1.0) : (tid == 4 ? -0.0 : 0.0);
+        S.spec = spec_rows;
+        TPR_WAVE_SYNC();
+    }
     double vlo[D], vhi[D];
     {
         const double *alim = A.alim + (size_t)bb * 2 * D;

@@ -35,8 +35,15 @@ constexpr int kCertBatchLanes = 16;     // lanes per LP in the cooperative batch
 template <int D>
 constexpr int cert_batch_groups() { return D >= 15 ? 1 : (D >= 13 ? 2 : 64 / kCertBatchLanes); }
 
+// Up to 7 dof CertStage::fetch reads rows 0..5 as (q1, q2) pairs from a six-double LDS table of the block (kSpecRows there); the
+// pointer is a member only where it is used, so that the other dofs' stage objects are what they were.
+template <bool PAIRS>
+struct CertSpecTable { const double *spec = nullptr; };
+template <>
+struct CertSpecTable<false> {};
+
 template <int D, int BS>
-struct CertStage {
+struct CertStage : CertSpecTable<(D <= 7)> {
     static constexpr int nC = 2 + 4 * D;
     // Row numbering INSIDE this kernel family ("vi"): 0..3 box rows, 4,5 the x_next pair, and the acceleration
     // rows at 8 + 8 blk + k (blk 0: +q(s_i), 1: -q(s_i), 2: +q(s_{i+1}), 3: -q(s_{i+1}); k < D <= 8), so that
@@ -76,6 +83,10 @@ struct CertStage {
     static constexpr int kAlimStride = 1;
 #endif
     const double *alim_lane = nullptr;
+    // The pair form of fetch (below): up to 7 dof.  At 8 dof it left the TOPPRAsd instantiation with 12 B of scratch per lane, and
+    // the slim blocks keep their own form (the sunk-load story in fetch).
+    static constexpr bool kPairFetch = D <= 7;
+    static constexpr int kSpecDoubles = kPairFetch ? 6 : 0;
     double rc1[D], rc2[D], rn1[D], rn2[D];    // q', q'' again, in registers for the unrolled scans
     double cpos[D], cneg[D];                  // c of the + rows (-amax) and of the - rows (+amin)
     double cmax;                              // max |c| over the acceleration rows
@@ -84,6 +95,35 @@ struct CertStage {
 
     // One row by (per-lane) index.
     __device__ __forceinline__ void fetch(int vi, double &a, double &b, double &c) const {
+        if constexpr (kPairFetch) {
+            // Every row as "q1 (+ 2 delta q2), q2" of one pair of loads, signed by an XOR on the high words: rows 0..5 take their
+            // pair from a six-double table (`spec`: (1, 0) for the u box, (+0, 1) for the x box, (-0, 1) for the x_next pair,
+            // whose a = -0 + 2 delta * 1 is 2 delta bit for bit, signed zeros included), the acceleration rows from the lane's
+            // columns (cur2 / nxt2 follow cur1 / nxt1 at D * BS).  No select between values, one index for c.
+#if defined(__HIP_DEVICE_COMPILE__)
+            const double *sp = this->spec;
+#else
+            static const double kSpecRows[6] = {1.0, 0.0, 0.0, 1.0, -0.0, 1.0};
+            const double *sp = kSpecRows;
+#endif
+            const bool acc = vi >= ST;
+            const int k = vi & (ST - 1);                                   // (rows 0..5: the row itself)
+            const bool nx = vi >= (acc ? V2 : 4);                          // the row's a is q1 + 2 delta q2
+            // the negated twin: blocks 1 and 3 of the acceleration rows (vi >> SH even), the even rows of 0..5
+            const unsigned sgn = ~((unsigned)(acc ? vi >> SH : vi) << 31) & 0x80000000u;
+            // (both addresses formed before the select between them: an arm with arithmetic in it becomes a divergent region)
+            const double *pa = (nx ? nxt1 : cur1) + k * BS, *ps = sp + (vi & 6);
+            const int st2 = acc ? D * BS : 1;
+            const double *p1 = acc ? pa : ps;
+            const double *p2 = p1 + st2;
+            const double q1 = *p1, q2 = *p2;
+            const double av = nx ? q1 + two_delta * q2 : q1;
+            a = __hiloint2double(__double2hiint(av) ^ (int)sgn, __double2loint(av));
+            b = __hiloint2double(__double2hiint(q2) ^ (int)sgn, __double2loint(q2));
+            // c: rows 0..5 at their own index, the + blocks' (vi >> SH odd) at 6 + k, the - blocks' at 6 + D + k
+            c = lim[(k + (acc ? ((vi >> SH) & 1 ? 6 : 6 + D) : 0)) * BS];
+            return;
+        }
         const bool acc = vi >= ST;
         const int blk = acc ? (vi >> SH) - 1 : 0, k = acc ? (vi & (ST - 1)) : 0;
         const bool nx = blk >> 1;

@@ -68,7 +68,7 @@ static size_t cert_grid_lds(const tpr::GroupArgs &G, int min_cols) {
     const size_t grid_bytes = (size_t)(G.N + 1) * sizeof(double);
     const size_t cols = (size_t)((4 * D + CS::kLimCols) > min_cols ? (4 * D + CS::kLimCols) : min_cols) * BS;
     const size_t static_lds = (cols + tpr::kCertXch * BS + tpr::cert_batch_groups<D>() * tpr::GroupCfg<D, tpr::kCertBatchLanes>::kRowBuf +
-                               CS::kRing * 2 * BS) * sizeof(double);
+                               CS::kRing * 2 * BS + CS::kSpecDoubles) * sizeof(double);
     const bool grid_lds = D <= 8 && !(G.flags & TPR_GRID_PER_TRAJ) && (160 * 1024) / (static_lds + grid_bytes) == (160 * 1024) / static_lds;
     return grid_lds ? grid_bytes : 0;
 }
