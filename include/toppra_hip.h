@@ -461,6 +461,37 @@ int tpr_chain_tool_acceleration_batch(const tpr_chain *chain, long long npoints,
 int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs,
                                             const double *qss, double *wa, double *wb, int flags, void *stream);
 
+/* A carried object: a rigid body fixed to the chain's last link, and the frame in which the wrench on it is reported.
+ *   mass >= 0; com [3] its centre of mass in the last link's frame; inertia [6] = xx, yy, zz, xy, xz, yz about com in
+ *   link-frame axes (the chain's convention); rot [3][3] row-major, columns = the contact frame's axes in last-link
+ *   coordinates; origin [3] the contact frame's origin in the last link's frame.
+ * ALWAYS A HOST STRUCT, with or without TPR_DEVICE_PTRS: it travels to the kernels by value.                           */
+typedef struct tpr_payload {
+    double mass, com[3], inertia[6], rot[9], origin[3];
+} tpr_payload;
+/* ABI guard, as tpr_chain_bytes: bytes of tpr_payload in the library.                                                  */
+int tpr_payload_bytes(void);
+/* The wrench the last link transmits to the payload, wrench(q, qd, qdd) = [f; n], [npoints][6].  With (w, wd, a) the last
+ * link's angular velocity, angular acceleration and origin acceleration in its own frame, from the forward recursion of
+ * tpr_chain_inverse_dynamics_batch started at a = -gravity (gravity IS applied):
+ *   Fl = m (a + wd x com + w x (w x com)),   Nl = I wd + w x (I w),
+ *   f = rot' Fl,   n = rot' (Nl + (com - origin) x Fl):
+ * the force the link exerts on the body and its moment about the contact frame's origin, both in contact-frame axes; at rest
+ * f is the support of the body's weight.  The chain's own masses are not read.  q, qd, qdd [npoints][d]; one thread per
+ * point, any dof, state in registers.  A zero result is +0 (so a massless, inertia-less payload gives +0 throughout).
+ * Refusals as tpr_chain_tool_acceleration_batch, and: a NULL payload, a negative or non-finite mass, any non-finite payload
+ * entry (TPR_E_BADARG).                                                                                                */
+int tpr_chain_tool_wrench_batch(const tpr_chain *chain, const tpr_payload *payload, long long npoints, const double *q,
+                                const double *qd, const double *qdd, double *wrench, int flags, void *stream);
+/* The three evaluations a second-order constraint on that wrench needs (tpr_second_order_block with p = 6), in one pass
+ * over the links: w0 = wrench(q, 0, 0) -- the static wrench, not zero under gravity --, wa = wrench(q, 0, qs),
+ * wb = wrench(q, qs, qss), [B][N+1][6].  Each output equals tpr_chain_tool_wrench_batch on the same arguments in every bit
+ * (products with an exact zero are dropped, no sum is reordered).  Refusals as tpr_chain_tool_acceleration_terms_batch plus
+ * the payload's above.                                                                                                 */
+int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload *payload, int B, int N, const double *q,
+                                      const double *qs, const double *qss, double *w0, double *wa, double *wb, int flags,
+                                      void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -18,11 +18,12 @@ import logging
 from . import algorithm, batch, chain, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
-from .chain import SerialChain
+from .chain import Payload, SerialChain
+from .constraint import BatchToolWrenchConstraint
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 
 __all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
-           "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain"]
+           "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint"]

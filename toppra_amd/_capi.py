@@ -78,6 +78,11 @@ class tpr_chain(C.Structure):
                 ("gravity", C.c_void_p), ("tool", C.c_void_p)]
 
 
+class tpr_payload(C.Structure):
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("inertia", C.c_double * 6), ("rot", C.c_double * 9),
+                ("origin", C.c_double * 3)]
+
+
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 # the numeric arrays of tpr_chain, in the order of one packed upload, with their doubles per link (0: per chain, three)
 CHAIN_ARRAYS = (("axis", 3), ("rot", 9), ("trans", 3), ("mass", 1), ("com", 3), ("inertia", 6), ("gravity", 0), ("tool", 0))
@@ -111,6 +116,7 @@ EXPORTS = (
     "tpr_feasible_sets_sampled_boxed_batch", "tpr_reachable_sets_sampled_boxed_batch",
     "tpr_chain_bytes", "tpr_chain_inverse_dynamics_batch", "tpr_chain_torque_terms_batch", "tpr_chain_tool_velocity_batch",
     "tpr_chain_tool_acceleration_batch", "tpr_chain_tool_acceleration_terms_batch",
+    "tpr_payload_bytes", "tpr_chain_tool_wrench_batch", "tpr_chain_tool_wrench_terms_batch",
 )
 
 _lib = None
@@ -262,6 +268,16 @@ def load():
         L.tpr_chain_tool_acceleration_batch.argtypes = [CP, C.c_longlong, V, V, V, V, C.c_int, V]
         L.tpr_chain_tool_acceleration_terms_batch.restype = C.c_int
         L.tpr_chain_tool_acceleration_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
+        L.tpr_payload_bytes.restype = C.c_int
+        L.tpr_payload_bytes.argtypes = []
+        if L.tpr_payload_bytes() != C.sizeof(tpr_payload):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_payload takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_payload_bytes(), C.sizeof(tpr_payload)))
+        PP = C.POINTER(tpr_payload)
+        L.tpr_chain_tool_wrench_batch.restype = C.c_int
+        L.tpr_chain_tool_wrench_batch.argtypes = [CP, PP, C.c_longlong, V, V, V, V, C.c_int, V]
+        L.tpr_chain_tool_wrench_terms_batch.restype = C.c_int
+        L.tpr_chain_tool_wrench_terms_batch.argtypes = [CP, PP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

@@ -246,7 +246,8 @@ class BatchTOPPRA(object):
     vlim, alim : [B, d, 2] joint velocity / acceleration limits (either may be None).
     constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
         ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback, or
-        ``BatchCartesianAccelerationConstraint`` (a limit on a chain's tool acceleration).  Their rows are built on the GPU
+        ``BatchCartesianAccelerationConstraint`` / ``BatchToolWrenchConstraint`` (limits on a chain's tool acceleration and
+        on the wrench it transmits to a carried object).  Their rows are built on the GPU
         once per object and every pass runs on the dense-row entries; without them nothing changes.
         ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` / ``BatchCartesianVelocityNormConstraint`` objects
         (first-order: they only tighten the box
@@ -324,8 +325,8 @@ class BatchTOPPRA(object):
         nC = 2 + ((4 if self.interpolation else 2) * d if self.alim is not None else 0)
         for con in self.constraints:
             if not (hasattr(con, "block") and hasattr(con, "rows_per_stage")):
-                raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint and BatchSecondOrderConstraint "
-                                          "are supported)" % type(con).__name__)
+                raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint, BatchSecondOrderConstraint, "
+                                          "BatchCartesianAccelerationConstraint and BatchToolWrenchConstraint are supported)" % type(con).__name__)
             con.check(B, N, d)
             nC += con.rows_per_stage(d) or 0
         if nC > _capi.MAX_DENSE_ROWS:

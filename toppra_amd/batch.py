@@ -23,7 +23,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "solve_sampled_boxed_batch", "solve_desired_duration_sampled_boxed_batch", "controllable_sets_sampled_boxed_batch",
            "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch",
            "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch",
-           "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch"]
+           "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch",
+           "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -771,6 +772,37 @@ def chain_tool_acceleration_terms_batch(chain, q, qs, qss):
                                                                      _capi.ptr(qss), _capi.ptr(wa), _capi.ptr(wb),
                                                                      _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
     return wa, wb
+
+
+def chain_tool_wrench_batch(chain, q, qd, qdd, payload):
+    """The wrench the last link transmits to ``payload`` (a :class:`toppra_amd.chain.Payload`) at every point: three arrays
+    [..., d] in, [..., 6] = [force; moment about the contact frame's origin] in contact-frame axes out.  Gravity is included:
+    at rest the force is the support of the body's weight (include/toppra_hip.h: tpr_chain_tool_wrench_batch)."""
+    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
+    body = payload.c_struct(chain)
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    wrench = _empty(q, shape[:-1] + (6,))
+    _capi.check(_capi.load().tpr_chain_tool_wrench_batch(C.byref(model), C.byref(body), npoints, _capi.ptr(q), _capi.ptr(qd),
+                                                         _capi.ptr(qdd), _capi.ptr(wrench),
+                                                         _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return wrench
+
+
+def chain_tool_wrench_terms_batch(chain, q, qs, qss, payload):
+    """(w0, wa, wb) = (wrench(q, 0, 0), wrench(q, 0, qs), wrench(q, qs, qss)) [..., 6] in one launch: what a constraint on the
+    wrench at the tool builds its rows from (w0 is the static wrench: not zero under gravity).  Each equals
+    :func:`chain_tool_wrench_batch` on the same arguments in every bit."""
+    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
+    body = payload.c_struct(chain)
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    w0, wa, wb = (_empty(q, shape[:-1] + (6,)) for _ in range(3))
+    _capi.check(_capi.load().tpr_chain_tool_wrench_terms_batch(C.byref(model), C.byref(body), npoints, 0, _capi.ptr(q),
+                                                               _capi.ptr(qs), _capi.ptr(qss), _capi.ptr(w0), _capi.ptr(wa),
+                                                               _capi.ptr(wb), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
+                                                               _stream_ptr(q)))
+    return w0, wa, wb
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

@@ -15,6 +15,81 @@ _JOINT_CODES = {REVOLUTE: _capi.JOINT_REVOLUTE, "r": _capi.JOINT_REVOLUTE, _capi
                 PRISMATIC: _capi.JOINT_PRISMATIC, "p": _capi.JOINT_PRISMATIC, _capi.JOINT_PRISMATIC: _capi.JOINT_PRISMATIC}
 
 
+def _inertia6(value, name):
+    """An inertia given as [6] = xx, yy, zz, xy, xz, yz or as a symmetric [3, 3], as [6]."""
+    value = np.array(value, dtype=np.float64)
+    if value.shape == (3, 3):
+        if not np.array_equal(value, value.T):
+            raise ValueError("%s must be symmetric" % name)
+        value = np.array([value[0, 0], value[1, 1], value[2, 2], value[0, 1], value[0, 2], value[1, 2]])
+    return value
+
+
+def _inertia33(I):
+    return np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
+
+
+class Payload(object):
+    """A carried object: a rigid body fixed to a chain's last link, and the contact frame its wrench is reported in.
+
+    Parameters
+    ----------
+    mass : >= 0.
+    com : [3] the centre of mass in the last link's frame.
+    inertia : [6] = xx, yy, zz, xy, xz, yz about ``com`` in link-frame axes (the chain's convention), or [3, 3] symmetric;
+        None = zeros (a point mass).
+    frame_rotation : [3, 3], columns = the contact frame's axes in last-link coordinates (orthonormal, determinant +1, to
+        1e-12); None = identity.
+    frame_origin : [3] the contact frame's origin in the last link's frame; None = the chain's ``tool`` at use.
+    """
+
+    def __init__(self, mass, com=(0.0, 0.0, 0.0), inertia=None, frame_rotation=None, frame_origin=None):
+        arr = {"mass": mass, "com": com, "inertia": np.zeros(6) if inertia is None else inertia,
+               "frame_rotation": np.eye(3) if frame_rotation is None else frame_rotation}
+        if frame_origin is not None:
+            arr["frame_origin"] = frame_origin
+        for name in arr:
+            try:
+                arr[name] = _inertia6(arr[name], name) if name == "inertia" else np.array(arr[name], dtype=np.float64)
+            except (TypeError, ValueError) as exc:
+                if "symmetric" in str(exc):
+                    raise
+                raise ValueError("%s is not an array of numbers" % name)
+        want = {"mass": (), "com": (3,), "inertia": (6,), "frame_rotation": (3, 3), "frame_origin": (3,)}
+        for name, value in arr.items():
+            if value.shape != want[name]:
+                raise ValueError("%s must have shape %s, got %s" % (name, list(want[name]), list(value.shape)))
+            if not np.all(np.isfinite(value)):
+                raise ValueError("%s holds a value that is not finite" % name)
+        if arr["mass"] < 0:
+            raise ValueError("mass must be >= 0")
+        rot = arr["frame_rotation"]
+        if np.any(np.abs(rot.T @ rot - np.eye(3)) > 1e-12) or abs(np.linalg.det(rot) - 1.0) > 1e-12:
+            raise ValueError("frame_rotation must be orthonormal with determinant +1 (to 1e-12)")
+        self.mass = float(arr["mass"])
+        self.com, self.inertia, self.frame_rotation = arr["com"], arr["inertia"], rot
+        self.frame_origin = arr.get("frame_origin")
+        for value in (self.com, self.inertia, self.frame_rotation, self.frame_origin):
+            if value is not None:
+                value.flags.writeable = False
+
+    def __repr__(self):
+        return "Payload(mass=%g)" % self.mass
+
+    def origin(self, chain):
+        """The contact frame's origin in the last link's frame: ``frame_origin``, or ``chain``'s tool point."""
+        return np.asarray(chain.tool if self.frame_origin is None else self.frame_origin, dtype=np.float64)
+
+    def c_struct(self, chain):
+        """The tpr_payload of a call on ``chain`` (a host struct, passed to the kernels by value)."""
+        body = _capi.tpr_payload(mass=self.mass)
+        body.com[:] = self.com.tolist()
+        body.inertia[:] = self.inertia.tolist()
+        body.rot[:] = self.frame_rotation.ravel().tolist()
+        body.origin[:] = self.origin(chain).tolist()
+        return body
+
+
 class SerialChain(object):
     """A fixed-base serial chain of 1 .. 32 revolute / prismatic joints.
 
@@ -132,3 +207,34 @@ class SerialChain(object):
         """(acc(q, 0, qs), acc(q, qs, qss)) in one launch: the evaluations a limit on the tool acceleration needs; acc(q, 0, 0)
         is an exact zero."""
         return _batch.chain_tool_acceleration_terms_batch(self, q, qs, qss)
+
+    def tool_wrench(self, q, qd, qdd, payload):
+        """The wrench [..., 6] = [force; moment] the last link transmits to ``payload`` (a :class:`Payload`): the force on the
+        body and its moment about the contact frame's origin, both in contact-frame axes.  Gravity is included: at rest the
+        force is the support of the body's weight.  With the payload bound (``lambda q, qd, qdd: chain.tool_wrench(q, qd, qdd,
+        payload)``) a valid batched ``inv_dyn`` of :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
+        return _batch.chain_tool_wrench_batch(self, q, qd, qdd, payload)
+
+    def tool_wrench_terms(self, q, qs, qss, payload):
+        """(wrench(q, 0, 0), wrench(q, 0, qs), wrench(q, qs, qss)) in one launch: the evaluations a limit on the wrench at the
+        tool needs; the first is the static wrench, which gravity keeps from being zero."""
+        return _batch.chain_tool_wrench_terms_batch(self, q, qs, qss, payload)
+
+    def with_payload(self, payload):
+        """A new chain whose last link carries ``payload``: its mass, centre of mass and inertia merged into the last link's
+        (parallel-axis theorem).  Host only; the contact frame plays no part.  Torque limits on the result load the joints
+        with the carried object: ``BatchJointTorqueConstraint(arm.with_payload(obj), ...)``."""
+        masses, coms, inertias = self.masses.copy(), self.coms.copy(), self.inertias.copy()
+        ml, cl, mp, cp = masses[-1], coms[-1].copy(), payload.mass, payload.com
+        total = ml + mp
+        if mp > 0:
+            cm = (ml * cl + mp * cp) / total
+            merged = np.zeros((3, 3))
+            for m, c, I in ((ml, cl, inertias[-1]), (mp, cp, payload.inertia)):
+                r = c - cm
+                merged += _inertia33(I) + m * (np.dot(r, r) * np.eye(3) - np.outer(r, r))
+            masses[-1], coms[-1], inertias[-1] = total, cm, _inertia6(merged, "inertia")
+        else:  # nothing moves the centre of mass
+            inertias[-1] = inertias[-1] + payload.inertia
+        return SerialChain(self.joint_types, self.axes, self.rotations, self.translations, masses, coms, inertias,
+                           gravity=self.gravity, tool=self.tool)

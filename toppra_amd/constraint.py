@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .chain import SerialChain
+from .chain import Payload, SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -519,6 +519,59 @@ def _host(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64)
 
 
+def _six_wide_limits(first, second, F, g):
+    """The limits of a constraint on a 6-wide quantity [first part; second part], given either as boxes on the parts --
+    (name, limit) each, a limit being None, a scalar, [3, 2] or [B, 3, 2] (lower, upper) -- or as rows F, g:
+    (F, g, the B of per-trajectory boxes or None).  Each box adds six rows, the signed identity on its part with
+    g = [upper; -lower], the first part's rows first."""
+    names = (first[0], second[0])
+    boxes, rows = first[1] is not None or second[1] is not None, F is not None or g is not None
+    if boxes and rows:
+        raise ValueError("give the limits either as %s / %s or as F and g, not both" % names)
+    if not boxes and not rows:
+        raise ValueError("no limit given: one of %s, %s, or F with g, is required" % names)
+    limit_batch = None
+    if boxes:
+        F_parts, g_parts = [], []
+        for (name, lim), at in ((first, 0), (second, 3)):
+            if lim is None:
+                continue
+            lim = _host(lim)
+            if lim.ndim == 0:
+                lim = np.stack([np.full(3, -float(lim)), np.full(3, float(lim))], -1)
+            if lim.ndim not in (2, 3) or lim.shape[-2:] != (3, 2):
+                raise ValueError("%s must be a scalar or have shape [3, 2] or [B, 3, 2], got %s" % (name, list(lim.shape)))
+            if not np.all(np.isfinite(lim)):
+                raise ValueError("%s holds a limit that is not finite" % name)
+            if np.any(lim[..., 0] > lim[..., 1]):
+                raise ValueError("%s holds a lower limit above its upper limit" % name)
+            if lim.ndim == 3:
+                if limit_batch not in (None, lim.shape[0]):
+                    raise ValueError("%s and %s are given per trajectory for %d and %d trajectories"
+                                     % (names + (limit_batch, lim.shape[0])))
+                limit_batch = int(lim.shape[0])
+            part = np.zeros((6, 6))
+            part[:3, at:at + 3], part[3:, at:at + 3] = np.eye(3), -np.eye(3)
+            F_parts.append(part)
+            g_parts.append(np.concatenate((lim[..., 1], -lim[..., 0]), -1))  # [upper; -lower]
+        if limit_batch is not None:
+            g_parts = [np.broadcast_to(p, (limit_batch, 6)) for p in g_parts]
+        return np.concatenate(F_parts, 0), np.ascontiguousarray(np.concatenate(g_parts, -1)), limit_batch
+    if F is None or g is None:
+        raise ValueError("F and g are given together")
+    fshape, gshape = _shape_of(F), _shape_of(g)
+    if len(fshape) not in (2, 3, 4) or fshape[-1] != 6:
+        raise ValueError("F must have shape [m, 6], [B, m, 6] or [B, N+1, m, 6], got %s" % (list(fshape),))
+    if len(gshape) not in (1, 2, 3):
+        raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
+    if gshape[-1] != fshape[-2]:
+        raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
+    for name, arr in (("F", F), ("g", g)):
+        if not np.all(np.isfinite(_host(arr))):
+            raise ValueError("%s holds a value that is not finite" % name)
+    return F, g, None
+
+
 class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
     """A limit on the tool point's acceleration for a batch (the reference's example examples-old/cartesian_accel.py: a
     ``SecondOrderConstraint`` whose ``inv_dyn`` returns the link's acceleration):  F acc <= g  on  acc(q, qd, qdd) =
@@ -545,52 +598,7 @@ class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
             raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
         self.chain = chain
         self.dof = chain.dof
-        boxes, rows = linear is not None or angular is not None, F is not None or g is not None
-        if boxes and rows:
-            raise ValueError("give the limits either as linear / angular or as F and g, not both")
-        if not boxes and not rows:
-            raise ValueError("no limit given: one of linear, angular, or F with g, is required")
-        self._limit_batch = None
-        if boxes:
-            F_parts, g_parts = [], []
-            for name, lim, first in (("linear", linear, 0), ("angular", angular, 3)):
-                if lim is None:
-                    continue
-                lim = _host(lim)
-                if lim.ndim == 0:
-                    lim = np.stack([np.full(3, -float(lim)), np.full(3, float(lim))], -1)
-                if lim.ndim not in (2, 3) or lim.shape[-2:] != (3, 2):
-                    raise ValueError("%s must be a scalar or have shape [3, 2] or [B, 3, 2], got %s" % (name, list(lim.shape)))
-                if not np.all(np.isfinite(lim)):
-                    raise ValueError("%s holds a limit that is not finite" % name)
-                if np.any(lim[..., 0] > lim[..., 1]):
-                    raise ValueError("%s holds a lower limit above its upper limit" % name)
-                if lim.ndim == 3:
-                    if self._limit_batch not in (None, lim.shape[0]):
-                        raise ValueError("linear and angular are given per trajectory for %d and %d trajectories"
-                                         % (self._limit_batch, lim.shape[0]))
-                    self._limit_batch = int(lim.shape[0])
-                part = np.zeros((6, 6))
-                part[:3, first:first + 3], part[3:, first:first + 3] = np.eye(3), -np.eye(3)
-                F_parts.append(part)
-                g_parts.append(np.concatenate((lim[..., 1], -lim[..., 0]), -1))  # [upper; -lower]
-            if self._limit_batch is not None:
-                g_parts = [np.broadcast_to(p, (self._limit_batch, 6)) for p in g_parts]
-            self.F, self.g = np.concatenate(F_parts, 0), np.ascontiguousarray(np.concatenate(g_parts, -1))
-        else:
-            if F is None or g is None:
-                raise ValueError("F and g are given together")
-            fshape, gshape = _shape_of(F), _shape_of(g)
-            if len(fshape) not in (2, 3, 4) or fshape[-1] != 6:
-                raise ValueError("F must have shape [m, 6], [B, m, 6] or [B, N+1, m, 6], got %s" % (list(fshape),))
-            if len(gshape) not in (1, 2, 3):
-                raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
-            if gshape[-1] != fshape[-2]:
-                raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
-            for name, arr in (("F", F), ("g", g)):
-                if not np.all(np.isfinite(_host(arr))):
-                    raise ValueError("%s holds a value that is not finite" % name)
-            self.F, self.g = F, g
+        self.F, self.g, self._limit_batch = _six_wide_limits(("linear", linear), ("angular", angular), F, g)
         self.linear, self.angular = linear, angular
         self.set_discretization_type(discretization_scheme)
         self.identical = True
@@ -614,6 +622,100 @@ class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
         self.check(B, n1 - 1, d)
         wa, wb = self.chain.tool_acceleration_terms(q, qs, qss)
         return {"w0": _zeros_like(wa), "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
+                "interpolation": self._interp()}
+
+
+class BatchToolWrenchConstraint(_BatchSecondOrder):
+    """A limit on the wrench a chain's last link transmits to a carried object, for a batch:  F w <= g  on
+    w(q, qd, qdd) = [force; moment] of ``chain`` on ``payload`` -- the force on the body and its moment about the contact
+    frame's origin, in contact-frame axes, gravity included (:meth:`toppra_amd.chain.SerialChain.tool_wrench`).  It is the
+    reference's ``SecondOrderConstraint`` with an ``inv_dyn`` that returns that wrench instead of joint torques; the three
+    evaluations the rows need come from one launch of the chain kernel.
+
+    ``chain``: a :class:`toppra_amd.chain.SerialChain`; ``payload``: a :class:`toppra_amd.chain.Payload`.  The limits are given
+    in one of three spellings (mixing them is a ValueError):
+
+    ``force`` / ``moment`` (either or both): a scalar ``wmax`` (-wmax <= component <= wmax on each contact-frame axis), [3, 2]
+    or [B, 3, 2] (lower, upper) -- the overload box of a force/torque sensor.  Each part given adds six rows, the signed
+    identity on that part with g = [upper; -lower]; with both, the force's rows come first.
+
+    ``F`` [m, 6], [B, m, 6] or [B, N+1, m, 6] with ``g`` [m], [B, m] or [B, N+1, m], as ``BatchSecondOrderConstraint`` takes
+    them.
+
+    :meth:`surface_contact`: the contact wrench cone of a flat rectangular patch with Coulomb friction.
+
+    The constraint is INFEASIBLE unless F w(q, 0, 0) <= g holds at every gridpoint: standing still must satisfy it (the
+    static wrench is the body's weight, and it enters every stage's rows).  Defaults are the reference's for
+    ``SecondOrderConstraint`` (Interpolation).  Needs the path positions: a ``from_path_samples`` batch must be given ``q``.
+    Per-trajectory payloads, a true (conic) friction cone and a body on another link than the last are out of scope."""
+
+    def __init__(self, chain, payload, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
+        super(BatchToolWrenchConstraint, self).__init__()
+        if not isinstance(chain, SerialChain):
+            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+        if not isinstance(payload, Payload):
+            raise ValueError("payload must be a toppra_amd.chain.Payload, got %s" % type(payload).__name__)
+        self.chain, self.payload = chain, payload
+        self.dof = chain.dof
+        self.F, self.g, self._limit_batch = _six_wide_limits(("force", force), ("moment", moment), F, g)
+        self.force, self.moment = force, moment
+        self.set_discretization_type(discretization_scheme)
+        self.identical = True
+        self._format_string = "    Batched tool wrench limit, %d dof, %d rows\n" % (self.dof, _shape_of(self.F)[-2])
+
+    @staticmethod
+    def surface_contact_rows(mu, half_extents, normal_force_min=0.0):
+        """(F [16 or 17, 6], g) of :meth:`surface_contact` on w = [fx, fy, fz, tx, ty, tz]."""
+        mu, fmin = float(mu), float(normal_force_min)
+        ext = np.array(half_extents, dtype=np.float64)
+        if ext.shape != (2,) or not np.all(np.isfinite(ext)) or np.any(ext <= 0):
+            raise ValueError("half_extents must be two finite lengths > 0, got %r" % (half_extents,))
+        if not np.isfinite(mu) or mu <= 0:
+            raise ValueError("mu must be finite and > 0, got %r" % (mu,))
+        if not np.isfinite(fmin) or fmin < 0:
+            raise ValueError("normal_force_min must be finite and >= 0, got %r" % (normal_force_min,))
+        X, Y = ext
+        rows = [[1, 0, -mu, 0, 0, 0], [-1, 0, -mu, 0, 0, 0], [0, 1, -mu, 0, 0, 0], [0, -1, -mu, 0, 0, 0],
+                [0, 0, -Y, 1, 0, 0], [0, 0, -Y, -1, 0, 0], [0, 0, -X, 0, 1, 0], [0, 0, -X, 0, -1, 0]]
+        for s1 in (1.0, -1.0):
+            for s2 in (1.0, -1.0):
+                rows.append([s1 * Y, s2 * X, -mu * (X + Y), s1 * mu, s2 * mu, 1.0])
+                rows.append([s1 * Y, s2 * X, -mu * (X + Y), -s1 * mu, -s2 * mu, -1.0])
+        g = [0.0] * 16
+        if fmin > 0:
+            rows.append([0, 0, -1, 0, 0, 0])
+            g.append(-fmin)
+        return np.array(rows, dtype=np.float64), np.array(g)
+
+    @classmethod
+    def surface_contact(cls, chain, payload, mu, half_extents, normal_force_min=0.0, **kwargs):
+        """The object rests on a flat rectangular patch [-X, X] x [-Y, Y] (``half_extents`` = (X, Y)) in the contact frame's
+        xy-plane, normal +z, centred at the frame's origin, with Coulomb friction ``mu`` linearised as a 4-sided pyramid at
+        the corners.  The contact wrench cone in closed form, 16 rows F w <= 0 on w = [fx, fy, fz, tx, ty, tz]:
+        +-fx - mu fz <= 0, +-fy - mu fz <= 0 (sliding); +-tx - Y fz <= 0, +-ty - X fz <= 0 (tipping); and for s1, s2 = +-1
+        s1 Y fx + s2 X fy - mu (X + Y) fz +- (s1 mu tx + s2 mu ty + tz) <= 0 (twisting).  ``normal_force_min`` > 0 adds the
+        row -fz <= -normal_force_min."""
+        F, g = cls.surface_contact_rows(mu, half_extents, normal_force_min)
+        return cls(chain, payload, F=F, g=g, **kwargs)
+
+    def rows_per_stage(self, d):
+        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
+        if self._limit_batch is not None and self._limit_batch != B:
+            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
+        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
+            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
+                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
+                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+
+    def block(self, q, qs, qss):
+        B, n1, d = (int(v) for v in q.shape)
+        self.check(B, n1 - 1, d)
+        w0, wa, wb = self.chain.tool_wrench_terms(q, qs, qss, self.payload)
+        return {"w0": w0, "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
                 "interpolation": self._interp()}
 
 

@@ -26,8 +26,8 @@
 // consecutive doubles, read back one row per lane at pitch d | 1 -- and so do the outputs.  9 .. 32 dof: runtime dof, the
 // state in LDS as [link][slot][lane] (conflict-free), d * slots * 512 bytes per block; the fused state fits 160 KB up to 18
 // dof, above that the three evaluations run one after another in one launch.  Chain parameters are addressed by the loop
-// index only: uniform loads.  The tool point's velocity and acceleration (at the end of this file) keep nothing per link:
-// runtime dof, registers only, at any dof.
+// index only: uniform loads.  The tool point's velocity and acceleration and the wrench on a carried body (at the end of this
+// file) keep nothing per link: runtime dof, registers only, at any dof.
 #pragma once
 #include "tpr_device.hpp"
 #include "tpr_chain_args.hpp"
@@ -447,6 +447,113 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_terms_ker
     chain_tool_accel_put<1>(W, K1, tool, oa + lane * 7);
     chain_tool_accel_put<2>(W, K2, tool, ob + lane * 7);
     __syncthreads();
+    chain_accel_rows_store(oa, A.wa, g0, npts);
+    chain_accel_rows_store(ob, A.wb, g0, npts);
+}
+
+// ---- the wrench at the tool: what the last link transmits to a body it carries, any dof, state in registers -------------------
+//   With (w, wd, a) of the last link in its own frame, from the recursion started at a = -gravity (as chain_rnea starts it), the
+//   payload's mass m, centre of mass c, inertia I about c (link axes), contact frame Rc (columns: its axes in link coordinates)
+//   and that frame's origin p:
+//     Fl = m (a + wd x c + w x (w x c)),  Nl = I wd + w x (I w),  wrench = [Rc' Fl; Rc' (Nl + (c - p) x Fl)]
+//   the force on the body and its moment about p, contact-frame axes; gravity included.  The result is in link axes, so the
+//   accumulated world rotation W is never formed.  The levels drop the products with an exact zero as chain_forward does and
+//   every output passes through "+ 0.0", so the fused outputs equal the single evaluation's in every bit, and a massless,
+//   inertia-less payload gives +0.  Staging and launch shape are the tool-acceleration kernels'; the payload comes by value.
+// The payload's 22 doubles are read from the kernel's argument block AFTER the loop over the links, behind an offset the
+// compiler cannot see through: fetched up front (where it moves loads of arguments to by itself) they sit in 44 scalar
+// registers across the loop, beside a link's parameters, and spill.  mass, com[3], inertia[6], rot[9], origin[3] in this order.
+typedef const __attribute__((address_space(4))) double *ChainPayloadWords;
+template <class Args>
+__device__ __forceinline__ ChainPayloadWords chain_payload_words() {
+    static_assert(sizeof(ChainPayload) == 22 * sizeof(double), "the payload is 22 packed doubles");
+    unsigned off = (unsigned)offsetof(Args, P);
+    asm volatile("" : "+s"(off));
+    return (ChainPayloadWords)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+__device__ __forceinline__ V3 payload_inertia_mul(ChainPayloadWords I, V3 w) {  // I = xx, yy, zz, xy, xz, yz
+    return {I[0] * w.x + I[3] * w.y + I[4] * w.z, I[3] * w.x + I[1] * w.y + I[5] * w.z, I[4] * w.x + I[5] * w.y + I[2] * w.z};
+}
+
+template <int Level>
+__device__ __forceinline__ void chain_tool_wrench_put(ChainPayloadWords P, const ChainKin &K, double *o) {
+    const double mass = P[0];
+    const V3 c{P[1], P[2], P[3]}, arm{P[1] - P[19], P[2] - P[20], P[3] - P[21]};
+    M3 Rc;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rc.m[k] = P[10 + k];
+    V3 ac = K.a;
+    if (Level >= 1) ac = ac + cross(K.wd, c);
+    if (Level >= 2) ac = ac + cross(K.w, cross(K.w, c));
+    const V3 Fl = ac * mass;
+    V3 n = cross(arm, Fl);
+    if (Level >= 1) {
+        V3 Nl = payload_inertia_mul(P + 4, K.wd);
+        if (Level >= 2) Nl = Nl + cross(K.w, payload_inertia_mul(P + 4, K.w));
+        n = Nl + n;
+    }
+    const V3 f = mul_t(Rc, Fl), t = mul_t(Rc, n);
+    o[0] = f.x + 0.0; o[1] = f.y + 0.0; o[2] = f.z + 0.0;
+    o[3] = t.x + 0.0; o[4] = t.y + 0.0; o[5] = t.z + 0.0;
+}
+
+// Lanes past the last point of the batch work on the last point's row again and rewrite its LDS row with its values (no lane is
+// masked out); only npts rows leave.
+static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_kernel(ChainWrenchArgs A) {
+    extern __shared__ double chain_lds[];
+    const ChainModel &M = A.M;
+    const int d = M.d, pitch = d | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    chain_rows_load(bq, b1, b2, A.q, A.qd, A.qdd, g0, npts, d, pitch);
+    __syncthreads();
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
+    ChainKin K{zero, zero, {-g.x, -g.y, -g.z}};
+#pragma nounroll
+    for (int i = 0; i < d; ++i) {
+        const ChainLink L = chain_link(M, i);
+        const double qi = bq[row + i];
+        const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+        chain_kinematics<2>(L, J, K, b1[row + i], b2[row + i]);
+    }
+    __syncthreads();
+    chain_tool_wrench_put<2>(chain_payload_words<ChainWrenchArgs>(), K, chain_lds + lane * 7);
+    __syncthreads();
+    chain_accel_rows_store(chain_lds, A.wrench, g0, npts);
+}
+
+// w0 = wrench(q, 0, 0), wa = wrench(q, 0, qs), wb = wrench(q, qs, qss) in one pass over the links.
+static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_terms_kernel(ChainWrenchTermsArgs A) {
+    extern __shared__ double chain_lds[];
+    const ChainModel &M = A.M;
+    const int d = M.d, pitch = d | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    chain_rows_load(bq, b1, b2, A.q, A.qs, A.qss, g0, npts, d, pitch);
+    __syncthreads();
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
+    ChainKin K0{zero, zero, {-g.x, -g.y, -g.z}}, K1 = K0, K2 = K0;
+#pragma nounroll
+    for (int i = 0; i < d; ++i) {
+        const ChainLink L = chain_link(M, i);
+        const double qi = bq[row + i], v1 = b1[row + i], v2 = b2[row + i];
+        const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+        chain_kinematics<0>(L, J, K0, 0.0, 0.0);
+        chain_kinematics<1>(L, J, K1, 0.0, v1);
+        chain_kinematics<2>(L, J, K2, v1, v2);
+    }
+    double *o0 = chain_lds, *oa = o0 + kChainBlock * 7, *ob = oa + kChainBlock * 7;
+    __syncthreads();
+    const ChainPayloadWords P = chain_payload_words<ChainWrenchTermsArgs>();
+    chain_tool_wrench_put<0>(P, K0, o0 + lane * 7);
+    chain_tool_wrench_put<1>(P, K1, oa + lane * 7);
+    chain_tool_wrench_put<2>(P, K2, ob + lane * 7);
+    __syncthreads();
+    chain_accel_rows_store(o0, A.w0, g0, npts);
     chain_accel_rows_store(oa, A.wa, g0, npts);
     chain_accel_rows_store(ob, A.wb, g0, npts);
 }

@@ -53,4 +53,25 @@ struct ChainAccelTermsArgs {
     const double *q, *qs, *qss;  // [npoints][d]
     double *wa, *wb;             // [npoints][6]
 };
+
+// A rigid body fixed to the last link (tpr_payload), by value: the same for every lane.
+struct ChainPayload {
+    double mass, com[3], inertia[6], rot[9], origin[3];
+};
+
+struct ChainWrenchArgs {
+    ChainModel M;
+    ChainPayload P;
+    int npoints;
+    const double *q, *qd, *qdd;  // [npoints][d]
+    double *wrench;              // [npoints][6]: force, moment about the contact frame's origin, contact-frame axes
+};
+
+struct ChainWrenchTermsArgs {
+    ChainModel M;
+    ChainPayload P;
+    int npoints;
+    const double *q, *qs, *qss;  // [npoints][d]
+    double *w0, *wa, *wb;        // [npoints][6]
+};
 }  // namespace tpr

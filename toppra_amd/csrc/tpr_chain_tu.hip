@@ -1,6 +1,7 @@
 // tpr_chain_tu.hip -- translation unit of the rigid-body chain kernels (tpr_chain.hip.inc): inverse dynamics, the three
-// evaluations of a torque constraint in one pass, the tool point's velocity and acceleration.  build.py compiles it in parallel
-// with the other units.  Five entry points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof.
+// evaluations of a torque constraint in one pass, the tool point's velocity and acceleration, the wrench on a carried body.
+// build.py compiles it in parallel with the other units.  Seven entry points, declared in tpr_kernels.hip; each returns
+// 0 = launched, -1 = no kernel for this dof.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -81,5 +82,20 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(c
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *A, hipStream_t stream) {
     if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
     hipLaunchKernelGGL(tpr::chain_tool_accel_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 2), stream, *A);
+    return 0;
+}
+
+// (the wrench kernels stage the same three inputs; their three 6-wide outputs take 10 752 bytes: the same 50 688 at 32 dof)
+static_assert(tpr::chain_accel_lds_bytes(TPR_MAX_DOF, 3) <= 64 * 1024, "the wrench kernels' staging area fits an unattributed launch");
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(const tpr::ChainWrenchArgs *A, hipStream_t stream) {
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    hipLaunchKernelGGL(tpr::chain_tool_wrench_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
+    return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *A, hipStream_t stream) {
+    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    hipLaunchKernelGGL(tpr::chain_tool_wrench_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 3), stream, *A);
     return 0;
 }

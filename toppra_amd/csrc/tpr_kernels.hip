@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -1651,6 +1652,8 @@ __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::C
 __attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(const tpr::ChainAccelArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(const tpr::ChainWrenchArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *, hipStream_t);
 }
 namespace {
 // What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
@@ -1684,6 +1687,21 @@ tpr::ChainModel stage_chain(const tpr_chain *c, Staging &S) {
     M.mass = S.in(c->mass, d); M.com = S.in(c->com, 3 * d); M.inertia = S.in(c->inertia, 6 * d);
     M.gravity = S.in(c->gravity, 3); M.tool = S.in(c->tool, 3);
     return M;
+}
+// A payload is a host struct of 22 doubles: read here, handed to the kernels by value.
+static_assert(sizeof(tpr_payload) == 22 * sizeof(double) && sizeof(tpr::ChainPayload) == sizeof(tpr_payload), "tpr_payload is 22 packed doubles");
+int check_payload(const tpr_payload *p, const char *who) {
+    if (!p) return fail(TPR_E_BADARG, std::string(who) + ": null payload");
+    const double *v = &p->mass;
+    for (int k = 0; k < 22; ++k)
+        if (!std::isfinite(v[k])) return fail(TPR_E_BADARG, std::string(who) + ": every entry of the payload must be finite");
+    if (!(p->mass >= 0.0)) return fail(TPR_E_BADARG, std::string(who) + ": the payload's mass must be >= 0");
+    return TPR_E_OK;
+}
+tpr::ChainPayload stage_payload(const tpr_payload *p) {
+    tpr::ChainPayload P;
+    std::memcpy(&P, p, sizeof(P));
+    return P;
 }
 }  // namespace
 
@@ -1787,6 +1805,50 @@ int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N
     if (int rc = S.failed()) return rc;
     if (npoints > 0 && tpr_tu_chain_accel_terms_launch(&A, S.stream) != 0)
         return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_acceleration_terms_batch: no kernel for this dof");
+    return S.finish();
+}
+
+int tpr_payload_bytes(void) { return (int)sizeof(tpr_payload); }
+
+int tpr_chain_tool_wrench_batch(const tpr_chain *chain, const tpr_payload *payload, long long npoints, const double *q, const double *qd,
+                                const double *qdd, double *wrench, int flags, void *stream_) {
+    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_wrench_batch")) return rc;
+    if (int rc = check_payload(payload, "tpr_chain_tool_wrench_batch")) return rc;
+    if (!q || !qd || !qdd || !wrench) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_batch: q, qd, qdd, wrench are required");
+    Staging S(flags & TPR_DEVICE_PTRS, wrench, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainWrenchArgs A{};
+    A.M = stage_chain(chain, S);
+    A.P = stage_payload(payload);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
+    A.wrench = S.out(wrench, 6 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_wrench_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_wrench_batch: no kernel for this dof");
+    return S.finish();
+}
+
+int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload *payload, int B, int N, const double *q, const double *qs,
+                                      const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_terms_batch: B >= 0, N >= 0");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_wrench_terms_batch")) return rc;
+    if (int rc = check_payload(payload, "tpr_chain_tool_wrench_terms_batch")) return rc;
+    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_terms_batch: q, qs, qss, w0, wa, wb are required");
+    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d;
+    tpr::ChainWrenchTermsArgs A{};
+    A.M = stage_chain(chain, S);
+    A.P = stage_payload(payload);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
+    A.w0 = S.out(w0, 6 * (size_t)npoints); A.wa = S.out(wa, 6 * (size_t)npoints); A.wb = S.out(wb, 6 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_wrench_terms_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_wrench_terms_batch: no kernel for this dof");
     return S.finish();
 }
 }  // extern "C"
