@@ -492,6 +492,43 @@ int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload 
                                       const double *qs, const double *qss, double *w0, double *wa, double *wb, int flags,
                                       void *stream);
 
+/* Control points: up to TPR_CHAIN_MAX_POINTS points fixed to ANY links of the chain -- an elbow, a camera bracket, a cable
+ * carrier -- evaluated in one pass over the links.  Point p sits in the frame of link[p] (0 .. d-1) at offset[p]; several points
+ * may share a link; every output lists the points in the struct's order.  ALWAYS A HOST STRUCT, with or without
+ * TPR_DEVICE_PTRS: it travels to the kernels by value, and the recursion ends after the deepest link that carries a point.  */
+#define TPR_CHAIN_MAX_POINTS 16
+typedef struct tpr_chain_points {
+    int32_t count;
+    int32_t link[TPR_CHAIN_MAX_POINTS];
+    double offset[TPR_CHAIN_MAX_POINTS][3];
+} tpr_chain_points;
+/* ABI guard, as tpr_chain_bytes: bytes of tpr_chain_points in the library.                                             */
+int tpr_chain_points_bytes(void);
+/* The squared speed of every point for qd = qs: speed2 [B][N+1][count] = |v_p|^2, v_p = W (v + w x offset_p) with (v, w, W)
+ * of link[p] from the recursion of tpr_chain_tool_velocity_batch -- a point (k, r) gives, in every bit, what that entry gives
+ * with S = NULL for the chain cut after link k with tool = r.  With limit [B][count] also the bound
+ * xbound [B][N+1][2] = (0, min_p limit[b][p] / speed2_p) on x = sd^2: ONE bound for the whole set (IEEE divisions: a point that
+ * stands still gives +inf and drops out of the minimum).  speed2 or xbound may be NULL, not both; xbound needs limit; limit > 0
+ * is the caller's responsibility, as for the tool entry.  Refusals as tpr_chain_tool_velocity_batch, and: a NULL points struct,
+ * count outside 1 .. TPR_CHAIN_MAX_POINTS, a link outside 0 .. d-1, a non-finite offset (TPR_E_BADARG).                  */
+int tpr_chain_points_speed_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q,
+                                 const double *qs, const double *limit, double *speed2, double *xbound, int flags, void *stream);
+/* The linear acceleration of every point, acc [npoints][3 count] (point-major, world axes), from the recursion of
+ * tpr_chain_tool_acceleration_batch (base at rest, no gravity):  lin_p = W (a + wd x offset_p + w x (w x offset_p)) with
+ * (w, wd, a, W) of link[p] -- the bits of that entry's lin for the chain cut after link k with tool = r.  A point's angular
+ * acceleration is its link's and is not part of the output.  A zero result is +0.  Refusals as
+ * tpr_chain_tool_acceleration_batch plus the point set's above.                                                        */
+int tpr_chain_points_acceleration_batch(const tpr_chain *chain, const tpr_chain_points *points, long long npoints,
+                                        const double *q, const double *qd, const double *qdd, double *acc, int flags,
+                                        void *stream);
+/* The evaluations a second-order constraint on those accelerations needs (tpr_second_order_block with p = 3 count), in one
+ * pass: wa = acc(q, 0, qs), wb = acc(q, qs, qss), [B][N+1][3 count]; w0 = acc(q, 0, 0) is an exact zero and is not computed.
+ * Each output equals tpr_chain_points_acceleration_batch on the same arguments in every bit.  Refusals as
+ * tpr_chain_tool_acceleration_terms_batch plus the point set's above.                                                   */
+int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N,
+                                              const double *q, const double *qs, const double *qss, double *wa, double *wb,
+                                              int flags, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

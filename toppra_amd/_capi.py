@@ -83,6 +83,13 @@ class tpr_payload(C.Structure):
                 ("origin", C.c_double * 3)]
 
 
+CHAIN_MAX_POINTS = 16  # TPR_CHAIN_MAX_POINTS: control points in one set
+
+
+class tpr_chain_points(C.Structure):
+    _fields_ = [("count", C.c_int32), ("link", C.c_int32 * CHAIN_MAX_POINTS), ("offset", C.c_double * 3 * CHAIN_MAX_POINTS)]
+
+
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 # the numeric arrays of tpr_chain, in the order of one packed upload, with their doubles per link (0: per chain, three)
 CHAIN_ARRAYS = (("axis", 3), ("rot", 9), ("trans", 3), ("mass", 1), ("com", 3), ("inertia", 6), ("gravity", 0), ("tool", 0))
@@ -117,6 +124,8 @@ EXPORTS = (
     "tpr_chain_bytes", "tpr_chain_inverse_dynamics_batch", "tpr_chain_torque_terms_batch", "tpr_chain_tool_velocity_batch",
     "tpr_chain_tool_acceleration_batch", "tpr_chain_tool_acceleration_terms_batch",
     "tpr_payload_bytes", "tpr_chain_tool_wrench_batch", "tpr_chain_tool_wrench_terms_batch",
+    "tpr_chain_points_bytes", "tpr_chain_points_speed_batch", "tpr_chain_points_acceleration_batch",
+    "tpr_chain_points_acceleration_terms_batch",
 )
 
 _lib = None
@@ -278,6 +287,18 @@ def load():
         L.tpr_chain_tool_wrench_batch.argtypes = [CP, PP, C.c_longlong, V, V, V, V, C.c_int, V]
         L.tpr_chain_tool_wrench_terms_batch.restype = C.c_int
         L.tpr_chain_tool_wrench_terms_batch.argtypes = [CP, PP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
+        L.tpr_chain_points_bytes.restype = C.c_int
+        L.tpr_chain_points_bytes.argtypes = []
+        if L.tpr_chain_points_bytes() != C.sizeof(tpr_chain_points):
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_chain_points takes %d bytes, this "
+                                 "binding declares %d" % (L.tpr_chain_points_bytes(), C.sizeof(tpr_chain_points)))
+        XP = C.POINTER(tpr_chain_points)
+        L.tpr_chain_points_speed_batch.restype = C.c_int
+        L.tpr_chain_points_speed_batch.argtypes = [CP, XP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
+        L.tpr_chain_points_acceleration_batch.restype = C.c_int
+        L.tpr_chain_points_acceleration_batch.argtypes = [CP, XP, C.c_longlong, V, V, V, V, C.c_int, V]
+        L.tpr_chain_points_acceleration_terms_batch.restype = C.c_int
+        L.tpr_chain_points_acceleration_terms_batch.argtypes = [CP, XP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

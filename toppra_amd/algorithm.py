@@ -246,10 +246,12 @@ class BatchTOPPRA(object):
     vlim, alim : [B, d, 2] joint velocity / acceleration limits (either may be None).
     constraints : further constraints, in list order after vlim and alim: ``BatchJointTorqueConstraint`` /
         ``BatchSecondOrderConstraint`` objects with a batched inverse-dynamics callback, or
-        ``BatchCartesianAccelerationConstraint`` / ``BatchToolWrenchConstraint`` (limits on a chain's tool acceleration and
-        on the wrench it transmits to a carried object).  Their rows are built on the GPU
+        ``BatchCartesianAccelerationConstraint`` / ``BatchToolWrenchConstraint`` / ``BatchPointAccelerationConstraint`` (limits on
+        a chain's tool acceleration, on the wrench it transmits to a carried object, on the accelerations of control points on
+        any links).  Their rows are built on the GPU
         once per object and every pass runs on the dense-row entries; without them nothing changes.
-        ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` / ``BatchCartesianVelocityNormConstraint`` objects
+        ``BatchJointVelocityConstraintVarying`` / ``BatchBoundConstraint`` / ``BatchCartesianVelocityNormConstraint`` /
+        ``BatchPointSpeedConstraint`` objects
         (first-order: they only tighten the box
         of a stage's variables) may stand anywhere among them: their bounds and vlim are folded into stage boxes on the GPU
         once per object, in list order, and the passes run on the boxed sampled entries (or, with second-order constraints
@@ -289,7 +291,7 @@ class BatchTOPPRA(object):
             self._check_constraints()
         if self.first_order:
             if q is None and any(getattr(c, "needs_q", False) for c in self.first_order):
-                raise ValueError("a tool velocity limit evaluates the chain at q: give the path positions")
+                raise ValueError("a tool or control-point velocity limit evaluates the chain at q: give the path positions")
             self._check_first_order()
         return self
 
@@ -326,7 +328,8 @@ class BatchTOPPRA(object):
         for con in self.constraints:
             if not (hasattr(con, "block") and hasattr(con, "rows_per_stage")):
                 raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint, BatchSecondOrderConstraint, "
-                                          "BatchCartesianAccelerationConstraint and BatchToolWrenchConstraint are supported)" % type(con).__name__)
+                                          "BatchCartesianAccelerationConstraint, BatchPointAccelerationConstraint and BatchToolWrenchConstraint "
+                                          "are supported)" % type(con).__name__)
             con.check(B, N, d)
             nC += con.rows_per_stage(d) or 0
         if nC > _capi.MAX_DENSE_ROWS:

@@ -24,7 +24,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "feasible_sets_sampled_boxed_batch", "reachable_sets_sampled_boxed_batch",
            "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch",
            "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch",
-           "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch"]
+           "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch",
+           "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -803,6 +804,83 @@ def chain_tool_wrench_terms_batch(chain, q, qs, qss, payload):
                                                                _capi.ptr(wb), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
                                                                _stream_ptr(q)))
     return w0, wa, wb
+
+
+def _control_points(chain, points):
+    """The tpr_chain_points of ``points`` (a :class:`toppra_amd.chain.ControlPoints`) on ``chain``: ValueError for anything else,
+    and for a link outside the chain -- before any launch."""
+    if not (hasattr(points, "c_struct") and hasattr(points, "count")):
+        raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
+    return points.c_struct(chain)
+
+
+def chain_points_speed_batch(chain, q, qs, points, limit=None):
+    """The squared speed of every control point for qd = qs: ``speed2`` of the shape of q with P in place of d, the points in
+    their order (include/toppra_hip.h: tpr_chain_points_speed_batch).  With ``limit`` (> 0: a scalar, [P] or [B, P], the SQUARE
+    of a speed; q must be [B, N+1, d] then) also the one bound on x = sd^2 the set implies: (speed2, xbound) with xbound
+    [B, N+1, 2] = (0, min_p limit_p / speed2_p) -- +inf where every point stands still -- the array a ``("xbound", ...)`` source
+    of :func:`stage_boxes_batch` takes."""
+    pts = _control_points(chain, points)
+    (q, qs), shape, npoints = _chain_points(chain, (q, qs), ("q", "qs"))
+    dev = _capi.is_torch_cuda(q)
+    P = int(pts.count)
+    B, N, xbound = npoints, 0, None
+    if limit is not None:
+        if len(shape) != 3:
+            raise ValueError("with a limit, q must have shape [B, N+1, d], got %s" % (list(shape),))
+        B, N = shape[0], shape[1] - 1
+        if dev:
+            import torch
+            if not (hasattr(limit, "is_cuda") and limit.is_cuda):
+                limit = torch.as_tensor(np.asarray(limit, dtype=np.float64), device=q.device)
+            _capi.check_tensor("limit", limit, q)
+        else:
+            limit = np.asarray(limit, dtype=np.float64)
+        if tuple(limit.shape) not in ((), (P,), (B, P)):
+            raise ValueError("limit must be a scalar or have shape [P] = [%d] or [B, P] = [%d, %d], got %s" % (P, B, P, tuple(limit.shape)))
+        if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
+            raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
+        limit = limit.expand(B, P).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(limit, (B, P)))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    speed2 = _empty(q, shape[:-1] + (P,))
+    if limit is not None:
+        xbound = _empty(q, shape[:-1] + (2,))
+    _capi.check(_capi.load().tpr_chain_points_speed_batch(C.byref(model), C.byref(pts), B, N, _capi.ptr(q), _capi.ptr(qs),
+                                                          _capi.ptr(limit), _capi.ptr(speed2), _capi.ptr(xbound),
+                                                          _capi.DEVICE_PTRS if dev else 0, _stream_ptr(q)))
+    return speed2 if limit is None else (speed2, xbound)
+
+
+def chain_points_acceleration_batch(chain, q, qd, qdd, points):
+    """The linear acceleration of every control point in world axes at every point of the path: three arrays [..., d] in,
+    [..., P, 3] out.  Kinematics only (no gravity); each is the classical acceleration of the point, as the linear part of
+    :func:`chain_tool_acceleration_batch` is for the tool (include/toppra_hip.h: tpr_chain_points_acceleration_batch)."""
+    pts = _control_points(chain, points)
+    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    acc = _empty(q, shape[:-1] + (int(pts.count), 3))
+    _capi.check(_capi.load().tpr_chain_points_acceleration_batch(C.byref(model), C.byref(pts), npoints, _capi.ptr(q), _capi.ptr(qd),
+                                                                 _capi.ptr(qdd), _capi.ptr(acc),
+                                                                 _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return acc
+
+
+def chain_points_acceleration_terms_batch(chain, q, qs, qss, points):
+    """(wa, wb) = (acc(q, 0, qs), acc(q, qs, qss)) [..., P, 3] of :func:`chain_points_acceleration_batch` in one launch: what a
+    constraint on the control points' accelerations builds its rows from (w0 = acc(q, 0, 0) is an exact zero).  Each equals the
+    single evaluation on the same arguments in every bit."""
+    pts = _control_points(chain, points)
+    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
+    _prepare(q)
+    model, keep = chain.c_struct(q)
+    wa, wb = (_empty(q, shape[:-1] + (int(pts.count), 3)) for _ in range(2))
+    _capi.check(_capi.load().tpr_chain_points_acceleration_terms_batch(C.byref(model), C.byref(pts), npoints, 0, _capi.ptr(q),
+                                                                       _capi.ptr(qs), _capi.ptr(qss), _capi.ptr(wa), _capi.ptr(wb),
+                                                                       _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
+                                                                       _stream_ptr(q)))
+    return wa, wb
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

@@ -90,6 +90,66 @@ class Payload(object):
         return body
 
 
+class ControlPoints(object):
+    """Points fixed to ANY links of a chain -- an elbow, a camera bracket, a cable carrier: what the whole-arm speed and
+    acceleration limits are set on.
+
+    Parameters
+    ----------
+    links : [P] integers, the link (0 .. d-1) in whose frame each point is fixed; -1 = the chain's last link.  Several points
+        may sit on one link.
+    offsets : [P, 3] the points in their links' frames.
+
+    P is 1 .. 16 (several sets may be used side by side).  The given order is the order of every output.  The links are checked
+    against a chain where the set is used with one (:meth:`c_struct`).
+    """
+
+    def __init__(self, links, offsets):
+        try:
+            raw = np.array(links)
+        except (TypeError, ValueError):
+            raise ValueError("links is not an array of integers")
+        if raw.ndim != 1 or not 1 <= raw.shape[0] <= _capi.CHAIN_MAX_POINTS:
+            raise ValueError("a control-point set holds 1..%d points: links must have shape [P], got %s"
+                             % (_capi.CHAIN_MAX_POINTS, list(raw.shape)))
+        if raw.dtype.kind not in "iu":
+            raise ValueError("links must hold integers (link indices 0 .. d-1, or -1 for the last link), got %r" % (links,))
+        try:
+            off = np.array(offsets, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("offsets is not an array of numbers")
+        if off.shape != (raw.shape[0], 3):
+            raise ValueError("offsets must have shape [P, 3] = [%d, 3], got %s" % (raw.shape[0], list(off.shape)))
+        if not np.all(np.isfinite(off)):
+            raise ValueError("offsets holds a value that is not finite")
+        if np.any(raw.astype(np.int64) < -1) or np.any(raw.astype(np.int64) >= _capi.MAX_DOF):
+            raise ValueError("links must lie in -1 .. %d, got %r" % (_capi.MAX_DOF - 1, raw.tolist()))
+        self.links, self.offsets = raw.astype(np.int32), off
+        self.count = int(raw.shape[0])
+        self.links.flags.writeable = self.offsets.flags.writeable = False
+
+    def __len__(self):
+        return self.count
+
+    def __repr__(self):
+        return "ControlPoints(%d points on links %s)" % (self.count, self.links.tolist())
+
+    def on(self, chain):
+        """The link of every point on ``chain`` ([P], -1 resolved to its last link); ValueError for a link outside it."""
+        links = np.where(self.links < 0, chain.dof - 1, self.links).astype(np.int32)
+        if np.any(links >= chain.dof):
+            raise ValueError("a control point sits on link %d, the chain has links 0..%d" % (int(links.max()), chain.dof - 1))
+        return links
+
+    def c_struct(self, chain):
+        """The tpr_chain_points of a call on ``chain`` (a host struct, passed to the kernels by value)."""
+        pts = _capi.tpr_chain_points(count=self.count)
+        pts.link[:self.count] = self.on(chain).tolist()
+        for p in range(self.count):
+            pts.offset[p][:] = self.offsets[p].tolist()
+        return pts
+
+
 class SerialChain(object):
     """A fixed-base serial chain of 1 .. 32 revolute / prismatic joints.
 
@@ -219,6 +279,22 @@ class SerialChain(object):
         """(wrench(q, 0, 0), wrench(q, 0, qs), wrench(q, qs, qss)) in one launch: the evaluations a limit on the wrench at the
         tool needs; the first is the static wrench, which gravity keeps from being zero."""
         return _batch.chain_tool_wrench_terms_batch(self, q, qs, qss, payload)
+
+    def point_speeds(self, q, qs, points):
+        """The squared speed of every point of ``points`` (a :class:`ControlPoints`) for qd = qs, shape [..., P]: per unit of path
+        velocity, in the points' order.  A point (k, r) gives the bits of :meth:`tool_velocity_norm` on the chain cut after link k
+        with tool = r."""
+        return _batch.chain_points_speed_batch(self, q, qs, points)
+
+    def point_accelerations(self, q, qd, qdd, points):
+        """The linear acceleration of every point of ``points`` in world axes, [..., P, 3]: the classical acceleration of each
+        point, as the first three of :meth:`tool_acceleration` are for the tool.  Kinematics only: gravity does not enter."""
+        return _batch.chain_points_acceleration_batch(self, q, qd, qdd, points)
+
+    def point_acceleration_terms(self, q, qs, qss, points):
+        """(acc(q, 0, qs), acc(q, qs, qss)) of :meth:`point_accelerations` in one launch, [..., P, 3] each: the evaluations a
+        limit on the points' accelerations needs; acc(q, 0, 0) is an exact zero."""
+        return _batch.chain_points_acceleration_terms_batch(self, q, qs, qss, points)
 
     def with_payload(self, payload):
         """A new chain whose last link carries ``payload``: its mass, centre of mass and inertia merged into the last link's

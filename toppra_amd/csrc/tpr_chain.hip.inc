@@ -558,4 +558,168 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_terms_ke
     chain_accel_rows_store(ob, A.wb, g0, npts);
 }
 
+// ---- control points on any link: speed and linear acceleration of up to 16 points in one pass over the links -------------------
+//   A point p is fixed in the frame of link[p] at offset[p].  The recursions are the tool kernels' (velocity: v, w, W; acceleration:
+//   chain_kinematics<Level>, base at rest, no gravity); after link i is updated every point that sits on it reads the link's state
+//   with the tool kernels' own expressions in their order, so a point (k, r) gives the bits of the tool kernel on the chain cut
+//   after link k with tool = r.  The loop over the links ends after the deepest link that carries a point (nlinks, found by the
+//   host).  The set comes by value and is the same for every lane: "does point p sit on link i" is a scalar compare.  Its words are
+//   read from the kernel's argument block behind an offset the compiler cannot see through (as the payload's are), by the running
+//   index p: nothing of the set is held in registers across the links.
+typedef const __attribute__((address_space(4))) int32_t *ChainPointLinks;
+template <class Args>
+__device__ __forceinline__ ChainPointLinks chain_point_links() {
+    unsigned off = (unsigned)(offsetof(Args, P) + offsetof(ChainPoints, link));
+    asm volatile("" : "+s"(off));
+    return (ChainPointLinks)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+template <class Args>
+__device__ __forceinline__ ChainPayloadWords chain_point_offsets() {
+    unsigned off = (unsigned)(offsetof(Args, P) + offsetof(ChainPoints, offset));
+    asm volatile("" : "+s"(off));
+    return (ChainPayloadWords)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+
+// speed2 [npoints][count] = |velocity of point p|^2 for qd = qs; xbound [npoints][2] = (0, min_p limit[b][p] / speed2_p): an IEEE
+// division, so a point that stands still gives +inf and drops out of the minimum.  q, qs are read in place, as the tool kernel reads.
+static __global__ void __launch_bounds__(kChainBlock) chain_points_speed_kernel(ChainPointsSpeedArgs A) {
+    const ChainModel &M = A.M;
+    const ChainPointLinks links = chain_point_links<ChainPointsSpeedArgs>();
+    const ChainPayloadWords offsets = chain_point_offsets<ChainPointsSpeedArgs>();
+    const int count = A.P.count;
+    const size_t g = (size_t)blockIdx.x * kChainBlock + threadIdx.x;
+    const size_t pt = g < (size_t)A.npoints ? g : (size_t)A.npoints - 1, at = pt * (size_t)M.d;
+    const size_t out = pt * (size_t)count, lim = (pt / (size_t)A.n1) * (size_t)count;
+    const V3 zero{0.0, 0.0, 0.0};
+    V3 v = zero, w = zero;
+    M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+    double best = __builtin_huge_val();
+#pragma nounroll
+    for (int i = 0; i < A.nlinks; ++i) {
+        const ChainLink L = chain_link(M, i);
+        const double qi = A.q[at + i], qd = A.qs[at + i];
+        const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+        const V3 zr = L.prismatic ? zero : L.axis, zp = L.prismatic ? L.axis : zero;
+        v = mul_t(J.E, v + cross(w, J.r)) + zp * qd;
+        w = mul_t(J.E, w) + zr * qd;
+        W = mul(W, J.E);
+#pragma nounroll
+        for (int p = 0; p < count; ++p) {
+            if (links[p] != i) continue;  // (the same for every lane)
+            const V3 vw = mul(W, v + cross(w, V3{offsets[3 * p], offsets[3 * p + 1], offsets[3 * p + 2]}));
+            const double s = dot(vw, vw);
+            // (a lane past the end repeats the last point's stores with the last point's values)
+            if (A.speed2) A.speed2[out + p] = s;
+            if (A.xbound) {
+                const double x = A.limit[lim + p] / s;
+                best = x < best ? x : best;
+            }
+        }
+    }
+    if (A.xbound) {
+        A.xbound[2 * pt] = 0.0;
+        A.xbound[2 * pt + 1] = best;
+    }
+}
+
+// The acceleration kernels stage a block's q, q', q'' through LDS as the tool kernels do -- loaded with consecutive lanes on
+// consecutive doubles of a row's part, read back one row per lane -- but kChainPointsChunk = 3 links at a time, at pitch 3 (odd:
+// conflict-free), and keep the block's outputs [64][3 count] in LDS at the odd pitch 3 count | 1 BESIDE them until the links are
+// done, so that the global stores are contiguous.  The two areas cannot share their space as the tool kernels' do: a point's
+// output exists from its link on, while the inputs of the deeper links are still to be read -- with 16 points on link 0 of a
+// 32-dof chain that is 96 + 93 columns of 64 doubles at once, more than either area.  Staging few links at a time keeps the sum
+// small, and that is what the kernels' speed hangs on: a block's LDS bounds the waves a CU holds, and the recursion's latencies
+// want many.  Measured (65 536 x 201 points, 4 points, 7 / 12 / 20 dof, fused kernel): every link staged at once 2.70 / 5.55 /
+// 10.9 ms, 7 links 2.73 / 4.24 / 6.43, 5 links 2.46 / 3.79 / 6.10, 3 links 2.16 / 3.46 / 6.02, 1 link 2.17 / 5.23 / 13.6 (8-byte
+// pieces of a row per load).  At most 4 608 + 2 * 64 * 49 * 8 = 54 784 bytes: under the 64 KB any launch may take.
+__host__ __device__ constexpr size_t chain_points_lds_bytes(int count, int outputs) {
+    return (3 * (size_t)kChainBlock * (size_t)kChainPointsChunk + (size_t)outputs * kChainBlock * (size_t)(3 * count | 1)) * sizeof(double);
+}
+static_assert(kChainPointsChunk % 2 == 1, "the staging pitch is the chunk itself: odd, or the rows' reads conflict");
+
+// Columns [c0, c0 + nc) of the block's rows [npts][d] of three arrays into LDS at `pitch`: chain_rows_load for a part of the row.
+__device__ __forceinline__ void chain_cols_load(double *b0, double *b1, double *b2, const double *s0, const double *s1, const double *s2,
+                                                size_t g0, int npts, int d, int c0, int nc, int pitch) {
+    const size_t base = g0 * (size_t)d + (size_t)c0;
+    const int step_r = kChainBlock / nc, step_c = kChainBlock % nc;
+    int r = (int)threadIdx.x / nc, c = (int)threadIdx.x % nc;
+    for (int k = threadIdx.x; k < npts * nc; k += kChainBlock) {
+        const int at = r * pitch + c;
+        const size_t from = base + (size_t)r * (size_t)d + (size_t)c;
+        b0[at] = s0[from]; b1[at] = s1[from]; b2[at] = s2[from];
+        r += step_r; c += step_c;
+        if (c >= nc) { c -= nc; ++r; }
+    }
+}
+// ... and a block's outputs [npts][n] from LDS at `pitch`.
+__device__ __forceinline__ void chain_points_rows_store(const double *buf, double *dst, size_t g0, int npts, int n, int pitch) {
+    const size_t base = g0 * (size_t)n;
+    const int step_r = kChainBlock / n, step_c = kChainBlock % n;
+    int r = (int)threadIdx.x / n, c = (int)threadIdx.x % n;
+    for (int k = threadIdx.x; k < npts * n; k += kChainBlock) {
+        dst[base + k] = buf[r * pitch + c];
+        r += step_r; c += step_c;
+        if (c >= n) { c -= n; ++r; }
+    }
+}
+
+// The linear three of chain_tool_accel_put, in its order.
+template <int Level>
+__device__ __forceinline__ void chain_point_accel_put(const M3 &W, const ChainKin &K, V3 at, double *o) {
+    V3 al = K.a + cross(K.wd, at);
+    if (Level >= 2) al = al + cross(K.w, cross(K.w, at));
+    const V3 lin = mul(W, al);
+    o[0] = lin.x + 0.0; o[1] = lin.y + 0.0; o[2] = lin.z + 0.0;
+}
+
+// Terms: wa = acc(q, 0, v1) and acc = acc(q, v1, v2) in one pass; otherwise acc alone.  Lanes past the last point of the batch work
+// on the last point's row again and rewrite its LDS row with its values (no lane is masked out); only npts rows leave.
+template <bool Terms>
+__device__ __forceinline__ void chain_points_accel(const ChainPointsAccelArgs &A) {
+    extern __shared__ double chain_lds[];
+    const ChainModel &M = A.M;
+    const ChainPointLinks links = chain_point_links<ChainPointsAccelArgs>();
+    const ChainPayloadWords offsets = chain_point_offsets<ChainPointsAccelArgs>();
+    constexpr int chunk = kChainPointsChunk, pitch = kChainPointsChunk;
+    const int d = M.d, count = A.P.count, width = 3 * count, opitch = width | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    double *ob = b2 + kChainBlock * pitch, *oa = ob + kChainBlock * opitch;  // (oa: Terms only)
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch, orow = lane * opitch;
+    const V3 zero{0.0, 0.0, 0.0};
+    ChainKin K1{zero, zero, zero}, K2 = K1;
+    M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+#pragma nounroll
+    for (int c0 = 0; c0 < A.nlinks; c0 += chunk) {
+        const int nc = A.nlinks - c0 < chunk ? A.nlinks - c0 : chunk;
+        if (c0 > 0) __syncthreads();  // every lane has read its row of the links before
+        chain_cols_load(bq, b1, b2, A.q, A.v1, A.v2, g0, npts, d, c0, nc, pitch);
+        __syncthreads();
+#pragma nounroll
+        for (int j = 0; j < nc; ++j) {
+            const int i = c0 + j;
+            const ChainLink L = chain_link(M, i);
+            const double qi = bq[row + j], v1 = b1[row + j], v2 = b2[row + j];
+            const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
+            if (Terms) chain_kinematics<1>(L, J, K1, 0.0, v1);
+            chain_kinematics<2>(L, J, K2, v1, v2);
+            W = mul(W, J.E);
+#pragma nounroll
+            for (int p = 0; p < count; ++p) {
+                if (links[p] != i) continue;  // (the same for every lane)
+                const V3 at{offsets[3 * p], offsets[3 * p + 1], offsets[3 * p + 2]};
+                if (Terms) chain_point_accel_put<1>(W, K1, at, oa + orow + 3 * p);
+                chain_point_accel_put<2>(W, K2, at, ob + orow + 3 * p);
+            }
+        }
+    }
+    __syncthreads();
+    if (Terms) chain_points_rows_store(oa, A.wa, g0, npts, width, opitch);
+    chain_points_rows_store(ob, A.acc, g0, npts, width, opitch);
+}
+
+static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_kernel(ChainPointsAccelArgs A) { chain_points_accel<false>(A); }
+static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_terms_kernel(ChainPointsAccelArgs A) { chain_points_accel<true>(A); }
+
 }  // namespace tpr

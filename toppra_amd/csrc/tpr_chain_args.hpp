@@ -74,4 +74,30 @@ struct ChainWrenchTermsArgs {
     const double *q, *qs, *qss;  // [npoints][d]
     double *w0, *wa, *wb;        // [npoints][6]
 };
+// Control points (tpr_chain_points), by value: points fixed in the frames of any links, the same set for every lane.
+constexpr int kChainMaxPoints = 16;
+constexpr int kChainPointsChunk = 3;  // links whose q, q', q'' the acceleration kernels stage in LDS at a time
+struct ChainPoints {
+    int32_t count, link[kChainMaxPoints];
+    double offset[kChainMaxPoints][3];
+};
+
+struct ChainPointsSpeedArgs {
+    ChainModel M;
+    ChainPoints P;
+    int npoints, n1, nlinks;  // B (N + 1); N + 1; the deepest link that carries a point, plus one
+    const double *q, *qs;     // [npoints][d]
+    const double *limit;      // [B][count] or null
+    double *speed2;           // [npoints][count] or null
+    double *xbound;           // [npoints][2] or null
+};
+
+// One block for both acceleration kernels: the single evaluation writes acc alone (wa is null).
+struct ChainPointsAccelArgs {
+    ChainModel M;
+    ChainPoints P;
+    int npoints, nlinks;         // nlinks as above
+    const double *q, *v1, *v2;   // [npoints][d]: (q, qd, qdd), or (q, qs, qss)
+    double *wa, *acc;            // [npoints][3 count]: acc(q, 0, v1) [terms only], acc(q, v1, v2)
+};
 }  // namespace tpr

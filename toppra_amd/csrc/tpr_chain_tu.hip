@@ -1,7 +1,7 @@
 // tpr_chain_tu.hip -- translation unit of the rigid-body chain kernels (tpr_chain.hip.inc): inverse dynamics, the three
-// evaluations of a torque constraint in one pass, the tool point's velocity and acceleration, the wrench on a carried body.
-// build.py compiles it in parallel with the other units.  Seven entry points, declared in tpr_kernels.hip; each returns
-// 0 = launched, -1 = no kernel for this dof.
+// evaluations of a torque constraint in one pass, the tool point's velocity and acceleration, the wrench on a carried body,
+// speed and acceleration of control points on any link.  build.py compiles it in parallel with the other units.  Nine entry
+// points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof (or this point set).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -97,5 +97,39 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *A, hipStream_t stream) {
     if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
     hipLaunchKernelGGL(tpr::chain_tool_wrench_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 3), stream, *A);
+    return 0;
+}
+
+// ---- control points: the launchers find the deepest link that carries a point (the kernels' loops end there); the set is
+// validated by the C-ABI entries, and once more here because the kernels index LDS and the outputs by it.
+static_assert(TPR_CHAIN_MAX_POINTS == tpr::kChainMaxPoints && sizeof(tpr_chain_points) == sizeof(tpr::ChainPoints), "tpr_chain_points is ChainPoints");
+static_assert(tpr::chain_points_lds_bytes(TPR_CHAIN_MAX_POINTS, 2) <= 64 * 1024, "the control-point kernels' LDS fits an unattributed launch");
+namespace {
+int chain_points_links(const tpr::ChainPoints &P, int d) {
+    if (d < 1 || d > TPR_MAX_DOF || P.count < 1 || P.count > tpr::kChainMaxPoints) return -1;
+    int deepest = 0;
+    for (int p = 0; p < P.count; ++p) {
+        if (P.link[p] < 0 || P.link[p] >= d) return -1;
+        if (P.link[p] > deepest) deepest = P.link[p];
+    }
+    return deepest + 1;
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_points_speed_launch(const tpr::ChainPointsSpeedArgs *A, hipStream_t stream) {
+    tpr::ChainPointsSpeedArgs K = *A;
+    if ((K.nlinks = chain_points_links(K.P, K.M.d)) < 0) return -1;
+    hipLaunchKernelGGL(tpr::chain_points_speed_kernel, dim3(chain_blocks(K.npoints)), dim3(tpr::kChainBlock), 0, stream, K);
+    return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const tpr::ChainPointsAccelArgs *A, int terms, hipStream_t stream) {
+    tpr::ChainPointsAccelArgs K = *A;
+    if ((K.nlinks = chain_points_links(K.P, K.M.d)) < 0) return -1;
+    const int outputs = terms ? 2 : 1;
+    const size_t lds = tpr::chain_points_lds_bytes(K.P.count, outputs);
+    const dim3 grid(chain_blocks(K.npoints)), block(tpr::kChainBlock);
+    if (terms) hipLaunchKernelGGL(tpr::chain_points_accel_terms_kernel, grid, block, lds, stream, K);
+    else hipLaunchKernelGGL(tpr::chain_points_accel_kernel, grid, block, lds, stream, K);
     return 0;
 }

@@ -1654,6 +1654,8 @@ __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(const tpr::C
 __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(const tpr::ChainWrenchArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_points_speed_launch(const tpr::ChainPointsSpeedArgs *, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const tpr::ChainPointsAccelArgs *, int terms, hipStream_t);
 }
 namespace {
 // What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
@@ -1701,6 +1703,29 @@ int check_payload(const tpr_payload *p, const char *who) {
 tpr::ChainPayload stage_payload(const tpr_payload *p) {
     tpr::ChainPayload P;
     std::memcpy(&P, p, sizeof(P));
+    return P;
+}
+// A control-point set is a host struct: read here, handed to the kernels by value.  Checked before anything else of a call (it
+// needs no device), against the chain's dof: the kernels index their outputs by it.
+static_assert(sizeof(tpr::ChainPoints) == sizeof(tpr_chain_points) && TPR_CHAIN_MAX_POINTS == tpr::kChainMaxPoints, "tpr_chain_points is ChainPoints");
+int check_points(const tpr_chain *c, const tpr_chain_points *p, const char *who) {
+    if (!c) return fail(TPR_E_BADARG, std::string(who) + ": null chain");
+    if (!p) return fail(TPR_E_BADARG, std::string(who) + ": null control points");
+    if (p->count < 1 || p->count > TPR_CHAIN_MAX_POINTS) return fail(TPR_E_BADARG, std::string(who) + ": the point count must be in [1, TPR_CHAIN_MAX_POINTS]");
+    for (int k = 0; k < p->count; ++k) {
+        if (p->link[k] < 0 || p->link[k] >= c->d) return fail(TPR_E_BADARG, std::string(who) + ": a control point's link is outside the chain");
+        for (int j = 0; j < 3; ++j)
+            if (!std::isfinite(p->offset[k][j])) return fail(TPR_E_BADARG, std::string(who) + ": every control point's offset must be finite");
+    }
+    return TPR_E_OK;
+}
+tpr::ChainPoints stage_points(const tpr_chain_points *p) {
+    tpr::ChainPoints P{};
+    P.count = p->count;
+    for (int k = 0; k < p->count; ++k) {  // (entries past count stay zero)
+        P.link[k] = p->link[k];
+        for (int j = 0; j < 3; ++j) P.offset[k][j] = p->offset[k][j];
+    }
     return P;
 }
 }  // namespace
@@ -1849,6 +1874,75 @@ int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload 
     if (int rc = S.failed()) return rc;
     if (npoints > 0 && tpr_tu_chain_wrench_terms_launch(&A, S.stream) != 0)
         return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_wrench_terms_batch: no kernel for this dof");
+    return S.finish();
+}
+
+int tpr_chain_points_bytes(void) { return (int)sizeof(tpr_chain_points); }
+
+int tpr_chain_points_speed_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q, const double *qs,
+                                 const double *limit, double *speed2, double *xbound, int flags, void *stream_) {
+    if (int rc = check_points(chain, points, "tpr_chain_points_speed_batch")) return rc;
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: B >= 0, N >= 0");
+    if (!q || !qs) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: q, qs are required");
+    if (!speed2 && !xbound) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: one of speed2, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: xbound needs limit");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_points_speed_batch")) return rc;
+    Staging S(flags & TPR_DEVICE_PTRS, speed2 ? speed2 : xbound, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d, count = (size_t)points->count;
+    tpr::ChainPointsSpeedArgs A{};
+    A.M = stage_chain(chain, S);
+    A.P = stage_points(points);
+    A.npoints = (int)npoints; A.n1 = N + 1;
+    A.q = S.in(q, n); A.qs = S.in(qs, n);
+    A.limit = xbound ? S.in(limit, (size_t)B * count) : nullptr;
+    A.speed2 = S.out(speed2, (size_t)npoints * count); A.xbound = S.out(xbound, 2 * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_points_speed_launch(&A, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_speed_batch: no kernel for this dof and point set");
+    return S.finish();
+}
+
+int tpr_chain_points_acceleration_batch(const tpr_chain *chain, const tpr_chain_points *points, long long npoints, const double *q,
+                                        const double *qd, const double *qdd, double *acc, int flags, void *stream_) {
+    if (int rc = check_points(chain, points, "tpr_chain_points_acceleration_batch")) return rc;
+    if (!q || !qd || !qdd || !acc) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_batch: q, qd, qdd, acc are required");
+    if (int rc = check_chain(chain, npoints, "tpr_chain_points_acceleration_batch")) return rc;
+    Staging S(flags & TPR_DEVICE_PTRS, acc, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d, width = 3 * (size_t)points->count;
+    tpr::ChainPointsAccelArgs A{};
+    A.M = stage_chain(chain, S);
+    A.P = stage_points(points);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.v1 = S.in(qd, n); A.v2 = S.in(qdd, n);
+    A.acc = S.out(acc, width * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_points_accel_launch(&A, 0, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_acceleration_batch: no kernel for this dof and point set");
+    return S.finish();
+}
+
+int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q,
+                                              const double *qs, const double *qss, double *wa, double *wb, int flags, void *stream_) {
+    if (int rc = check_points(chain, points, "tpr_chain_points_acceleration_terms_batch")) return rc;
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_terms_batch: B >= 0, N >= 0");
+    if (!q || !qs || !qss || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_terms_batch: q, qs, qss, wa, wb are required");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_chain(chain, npoints, "tpr_chain_points_acceleration_terms_batch")) return rc;
+    Staging S(flags & TPR_DEVICE_PTRS, wa, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)chain->d, width = 3 * (size_t)points->count;
+    tpr::ChainPointsAccelArgs A{};
+    A.M = stage_chain(chain, S);
+    A.P = stage_points(points);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.v1 = S.in(qs, n); A.v2 = S.in(qss, n);
+    A.wa = S.out(wa, width * (size_t)npoints); A.acc = S.out(wb, width * (size_t)npoints);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_chain_points_accel_launch(&A, 1, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_acceleration_terms_batch: no kernel for this dof and point set");
     return S.finish();
 }
 }  // extern "C"
