@@ -409,7 +409,7 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
  *   gravity [3]            gravitational acceleration in the world frame, applied as a base acceleration of -gravity
  *   tool [3]               a point in the last link's frame
  * The numeric arrays follow TPR_DEVICE_PTRS of the call's flags; every lane reads them through uniform loads.  Not modelled:
- * rotor inertia, viscous damping, branched trees, floating bases.  fp64, every operation rounded on its own; sine and cosine
+ * rotor inertia, viscous damping, floating bases (branched trees: the tpr_tree_* entries below).  fp64, every operation rounded on its own; sine and cosine
  * are the device library's (1 - 2 ulp), so results agree with a host evaluation to rounding, not in bits.                */
 #define TPR_JOINT_REVOLUTE 0
 #define TPR_JOINT_PRISMATIC 1
@@ -528,6 +528,36 @@ int tpr_chain_points_acceleration_batch(const tpr_chain *chain, const tpr_chain_
 int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N,
                                               const double *q, const double *qs, const double *qss, double *wa, double *wb,
                                               int flags, void *stream);
+
+/* ---- a kinematic TREE evaluated on the GPU: inverse dynamics of a branched robot for a batch -------------------------------
+ * Two arms on a torso, an arm beside a pan-tilt head, an arm with an articulated gripper, several robots on one base: the
+ * torque at a joint below a branching link depends on every joint beyond it in every branch.  The model is tpr_chain's -- `links`
+ * gives d = 1 .. TPR_MAX_DOF links with the chain's arrays and conventions; links->tool is NOT read (a tree has no single tip)
+ * and may be NULL -- with a parent table beside it:
+ *   parent [d] int32   parent[i] is the link that joint i attaches link i to, -1 = the fixed base; the numbering is topological,
+ *                      -1 <= parent[i] < i.  Several links may have parent -1 (a forest).  rot[i], trans[i] place joint i in the
+ *                      frame of parent[i].  ALWAYS A HOST ARRAY of links->d entries, with or without TPR_DEVICE_PTRS, as
+ *                      joint_type is: the structure is read by the host and travels to the kernels by value.
+ * A FORK is a link j that is the parent of some link i != j + 1 (the base is never one); it keeps one bank of LDS for what its
+ * later children need, and a tree may have at most TPR_TREE_MAX_FORKS of them.  parent = -1, 0, 1, ... is the serial chain.
+ * Runtime dof at every dof: one wave of 64 points per block, a point's state in LDS, d * 8 * 512 + forks * 9 * 512 bytes (fused
+ * d * 17 * 512 + forks * 18 * 512 while that fits 160 KB, i.e. up to 17 dof with one fork; otherwise the three evaluations run
+ * one after another in the same launch).  The children's wrenches are summed at a fork in a fixed order: the children
+ * i != j + 1 in descending link number, then child j + 1 plus that sum.  Two bit properties follow from it:
+ *   - a chain-shaped tree gives the bits of tpr_chain_inverse_dynamics_batch / tpr_chain_torque_terms_batch at every dof;
+ *   - each output of tpr_tree_torque_terms_batch equals tpr_tree_inverse_dynamics_batch on the same arguments in every bit
+ *     (products with an exact zero are dropped, no sum is reordered).                                                      */
+#define TPR_TREE_MAX_FORKS 4
+/* tau = RNEA(q, qd, qdd) of the tree at npoints points: q, qd, qdd, tau [npoints][d].  flags: TPR_DEVICE_PTRS.  Refused before
+ * any launch: everything tpr_chain_inverse_dynamics_batch refuses (links->tool apart), a NULL parent, a device pointer as
+ * parent, an entry outside -1 .. i-1 (TPR_E_BADARG); more than TPR_TREE_MAX_FORKS forks (TPR_E_UNSUPPORTED).             */
+int tpr_tree_inverse_dynamics_batch(const tpr_chain *links, const int32_t *parent, long long npoints, const double *q,
+                                    const double *qd, const double *qdd, double *tau, int flags, void *stream);
+/* The three evaluations of tpr_second_order_block in one launch, as tpr_chain_torque_terms_batch: w0 = tau(q, 0, 0),
+ * wa = tau(q, 0, qs), wb = tau(q, qs, qss); q, qs, qss, w0, wa, wb [B][N+1][d].  Refusals as above, with B (N + 1) as the point
+ * count.                                                                                                                  */
+int tpr_tree_torque_terms_batch(const tpr_chain *links, const int32_t *parent, int B, int N, const double *q, const double *qs,
+                                const double *qss, double *w0, double *wa, double *wb, int flags, void *stream);
 
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).

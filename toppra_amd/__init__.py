@@ -18,7 +18,7 @@ import logging
 from . import algorithm, batch, chain, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
-from .chain import ControlPoints, Payload, SerialChain
+from .chain import ControlPoints, KinematicTree, Payload, SerialChain
 from .constraint import BatchToolWrenchConstraint
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
@@ -26,4 +26,4 @@ logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 
 __all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
-           "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint", "ControlPoints"]
+           "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint", "ControlPoints", "KinematicTree"]

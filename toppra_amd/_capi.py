@@ -90,6 +90,7 @@ class tpr_chain_points(C.Structure):
     _fields_ = [("count", C.c_int32), ("link", C.c_int32 * CHAIN_MAX_POINTS), ("offset", C.c_double * 3 * CHAIN_MAX_POINTS)]
 
 
+TREE_MAX_FORKS = 4  # TPR_TREE_MAX_FORKS: forks (links with a child that is not the next link) of a kinematic tree
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 # the numeric arrays of tpr_chain, in the order of one packed upload, with their doubles per link (0: per chain, three)
 CHAIN_ARRAYS = (("axis", 3), ("rot", 9), ("trans", 3), ("mass", 1), ("com", 3), ("inertia", 6), ("gravity", 0), ("tool", 0))
@@ -126,6 +127,7 @@ EXPORTS = (
     "tpr_payload_bytes", "tpr_chain_tool_wrench_batch", "tpr_chain_tool_wrench_terms_batch",
     "tpr_chain_points_bytes", "tpr_chain_points_speed_batch", "tpr_chain_points_acceleration_batch",
     "tpr_chain_points_acceleration_terms_batch",
+    "tpr_tree_inverse_dynamics_batch", "tpr_tree_torque_terms_batch",
 )
 
 _lib = None
@@ -299,6 +301,10 @@ def load():
         L.tpr_chain_points_acceleration_batch.argtypes = [CP, XP, C.c_longlong, V, V, V, V, C.c_int, V]
         L.tpr_chain_points_acceleration_terms_batch.restype = C.c_int
         L.tpr_chain_points_acceleration_terms_batch.argtypes = [CP, XP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
+        L.tpr_tree_inverse_dynamics_batch.restype = C.c_int
+        L.tpr_tree_inverse_dynamics_batch.argtypes = [CP, V, C.c_longlong, V, V, V, V, C.c_int, V]
+        L.tpr_tree_torque_terms_batch.restype = C.c_int
+        L.tpr_tree_torque_terms_batch.argtypes = [CP, V, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

@@ -25,7 +25,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "chain_inverse_dynamics_batch", "chain_torque_terms_batch", "chain_tool_bound_batch",
            "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch",
            "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch",
-           "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch"]
+           "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch",
+           "tree_inverse_dynamics_batch", "tree_torque_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -881,6 +882,35 @@ def chain_points_acceleration_terms_batch(chain, q, qs, qss, points):
                                                                        _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
                                                                        _stream_ptr(q)))
     return wa, wb
+
+
+# a kinematic tree evaluated on the GPU (include/toppra_hip.h: tpr_tree_*; the model object is toppra_amd.chain.KinematicTree)
+
+def tree_inverse_dynamics_batch(tree, q, qd, qdd):
+    """tau = RNEA(q, qd, qdd) of ``tree`` (a :class:`toppra_amd.chain.KinematicTree`) at every point: three arrays [..., d] in,
+    [..., d] out; numpy in -> numpy out, tensors in -> a tensor out on the current stream.  A chain-shaped tree gives the bits of
+    :func:`chain_inverse_dynamics_batch`."""
+    (q, qd, qdd), shape, npoints = _chain_points(tree, (q, qd, qdd), ("q", "qd", "qdd"))
+    _prepare(q)
+    model, parent, keep = tree.c_struct(q)
+    tau = _empty(q, shape)
+    _capi.check(_capi.load().tpr_tree_inverse_dynamics_batch(C.byref(model), parent.ctypes.data, npoints, _capi.ptr(q), _capi.ptr(qd),
+                                                             _capi.ptr(qdd), _capi.ptr(tau),
+                                                             _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return tau
+
+
+def tree_torque_terms_batch(tree, q, qs, qss):
+    """(w0, wa, wb) = (tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) of ``tree`` in one launch: what a torque constraint's rows
+    are built from.  Each equals :func:`tree_inverse_dynamics_batch` on the same arguments in every bit."""
+    (q, qs, qss), shape, npoints = _chain_points(tree, (q, qs, qss), ("q", "qs", "qss"))
+    _prepare(q)
+    model, parent, keep = tree.c_struct(q)
+    w0, wa, wb = _empty(q, shape), _empty(q, shape), _empty(q, shape)
+    _capi.check(_capi.load().tpr_tree_torque_terms_batch(C.byref(model), parent.ctypes.data, npoints, 0, _capi.ptr(q), _capi.ptr(qs),
+                                                         _capi.ptr(qss), _capi.ptr(w0), _capi.ptr(wa), _capi.ptr(wb),
+                                                         _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return w0, wa, wb
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

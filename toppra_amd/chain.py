@@ -1,9 +1,11 @@
-"""A serial rigid-body chain evaluated on the GPU: the robot model behind a batch's torque and tool-speed limits.
+"""A serial rigid-body chain, or a branched tree of links, evaluated on the GPU: the robot model behind a batch's torque and
+tool-speed limits.
 
 The reference's Python side leaves the robot to the caller (``JointTorqueConstraint`` takes an ``inv_dyn`` callback); its C++
 twin evaluates a pinocchio model (constraint/joint_torque/pinocchio.hpp, constraint/cartesian_velocity_norm/pinocchio.hpp).
 :class:`SerialChain` is that piece here: one model for the whole batch, evaluated by the chain kernels at every gridpoint
-of every trajectory (include/toppra_hip.h: ``tpr_chain``).
+of every trajectory (include/toppra_hip.h: ``tpr_chain``).  :class:`KinematicTree` is the same model with a parent table: two
+arms on a torso, an arm beside a pan-tilt head, several robots on one base (``tpr_tree_*``).
 """
 import numpy as np
 
@@ -27,6 +29,24 @@ def _inertia6(value, name):
 
 def _inertia33(I):
     return np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
+
+
+def _with_payload_on(masses, coms, inertias, link, payload):
+    """Copies of (masses, coms, inertias) with ``payload`` (a :class:`Payload` fixed in the frame of ``link``) merged into that
+    link's mass, centre of mass and inertia (parallel-axis theorem)."""
+    masses, coms, inertias = masses.copy(), coms.copy(), inertias.copy()
+    ml, cl, mp, cp = masses[link], coms[link].copy(), payload.mass, payload.com
+    total = ml + mp
+    if mp > 0:
+        cm = (ml * cl + mp * cp) / total
+        merged = np.zeros((3, 3))
+        for m, c, I in ((ml, cl, inertias[link]), (mp, cp, payload.inertia)):
+            r = c - cm
+            merged += _inertia33(I) + m * (np.dot(r, r) * np.eye(3) - np.outer(r, r))
+        masses[link], coms[link], inertias[link] = total, cm, _inertia6(merged, "inertia")
+    else:  # nothing moves the centre of mass
+        inertias[link] = inertias[link] + payload.inertia
+    return masses, coms, inertias
 
 
 class Payload(object):
@@ -167,8 +187,8 @@ class SerialChain(object):
     gravity : gravitational acceleration in the world frame (applied as a base acceleration of -gravity).
     tool : a point in the last link's frame (:meth:`tool_velocity_norm`, :meth:`tool_acceleration`).
 
-    Not modelled: rotor inertia, viscous damping, branched trees, floating bases; dry friction stays with the constraints
-    (``fs_coef`` / ``friction``).  The model is uploaded to a device once per object, on first use there.
+    Not modelled: rotor inertia, viscous damping, floating bases (branched robots: :class:`KinematicTree`); dry friction stays
+    with the constraints (``fs_coef`` / ``friction``).  The model is uploaded to a device once per object, on first use there.
     """
 
     def __init__(self, joint_types, axes, rotations, translations, masses, coms, inertias, gravity=(0.0, 0.0, -9.81),
@@ -300,17 +320,115 @@ class SerialChain(object):
         """A new chain whose last link carries ``payload``: its mass, centre of mass and inertia merged into the last link's
         (parallel-axis theorem).  Host only; the contact frame plays no part.  Torque limits on the result load the joints
         with the carried object: ``BatchJointTorqueConstraint(arm.with_payload(obj), ...)``."""
-        masses, coms, inertias = self.masses.copy(), self.coms.copy(), self.inertias.copy()
-        ml, cl, mp, cp = masses[-1], coms[-1].copy(), payload.mass, payload.com
-        total = ml + mp
-        if mp > 0:
-            cm = (ml * cl + mp * cp) / total
-            merged = np.zeros((3, 3))
-            for m, c, I in ((ml, cl, inertias[-1]), (mp, cp, payload.inertia)):
-                r = c - cm
-                merged += _inertia33(I) + m * (np.dot(r, r) * np.eye(3) - np.outer(r, r))
-            masses[-1], coms[-1], inertias[-1] = total, cm, _inertia6(merged, "inertia")
-        else:  # nothing moves the centre of mass
-            inertias[-1] = inertias[-1] + payload.inertia
+        masses, coms, inertias = _with_payload_on(self.masses, self.coms, self.inertias, self.dof - 1, payload)
         return SerialChain(self.joint_types, self.axes, self.rotations, self.translations, masses, coms, inertias,
                            gravity=self.gravity, tool=self.tool)
+
+
+class KinematicTree(object):
+    """A fixed-base tree of 1 .. 32 revolute / prismatic joints: a branched robot -- two arms on a torso or a lifting column, an
+    arm beside a pan-tilt head, an arm with an articulated gripper -- or several robots on one base planned as one path.
+
+    Parameters
+    ----------
+    parents : [d] integers.  ``parents[i]`` is the link that joint i attaches link i to, -1 = the fixed base (the world frame).
+        The numbering is topological: ``-1 <= parents[i] < i``.  Several links may have parent -1 (a forest).
+    joint_types, axes, rotations, translations, masses, coms, inertias, gravity : as for :class:`SerialChain`, per link;
+        ``rotations[i]``, ``translations[i]`` place joint i in the frame of ``parents[i]``.
+
+    There is no ``tool``: a tree has no single tip (:meth:`chain_to` gives the serial chain to any link, for the tool and
+    control-point limits).  A FORK is a link j that is the parent of some link i != j + 1; a tree may have at most 4
+    (``TPR_TREE_MAX_FORKS``).  ``parents = [-1, 0, 1, ...]`` is the serial chain and gives :class:`SerialChain`'s torques bit for
+    bit.  Not modelled: floating bases, closed loops, rotor inertia, viscous damping.
+    """
+
+    def __init__(self, parents, joint_types, axes, rotations, translations, masses, coms, inertias, gravity=(0.0, 0.0, -9.81)):
+        try:
+            raw = np.array(parents)
+        except (TypeError, ValueError):
+            raise ValueError("parents is not an array of integers")
+        if raw.ndim != 1 or raw.dtype.kind not in "iu":
+            raise ValueError("parents must be an integer array [d] (the parent link of every link, -1 = the base), got %r" % (parents,))
+        d = int(raw.shape[0])
+        if not 1 <= d <= _capi.MAX_DOF:
+            raise ValueError("a tree has 1..%d joints, got %d" % (_capi.MAX_DOF, d))
+        try:
+            count = len(joint_types)
+        except TypeError:
+            raise ValueError("joint_types must hold one entry per link")
+        if count != d:
+            raise ValueError("parents has %d entries, joint_types %d: one per link each" % (d, count))
+        raw = raw.astype(np.int64)
+        for i in range(d):
+            if not -1 <= raw[i] < i:
+                raise ValueError("the parent of link %d is %d, outside -1 .. %d: links are numbered after their parents"
+                                 % (i, int(raw[i]), i - 1))
+        forks = sorted(set(int(raw[i]) for i in range(d) if raw[i] >= 0 and raw[i] != i - 1))
+        if len(forks) > _capi.TREE_MAX_FORKS:
+            raise NotImplementedError("the tree has %d forks (links %s), the kernels keep banks for %d"
+                                      % (len(forks), forks, _capi.TREE_MAX_FORKS))
+        # the links are a chain's: validated, packed and uploaded as one (its tool is not read)
+        self._links = SerialChain(joint_types, axes, rotations, translations, masses, coms, inertias, gravity=gravity)
+        self.dof = d
+        self.parents = raw.astype(np.int32)
+        self.parents.flags.writeable = False
+        self.forks = forks
+        for name in ("joint_types", "axes", "rotations", "translations", "masses", "coms", "inertias", "gravity"):
+            setattr(self, name, getattr(self._links, name))
+
+    def __repr__(self):
+        leaves = self.dof - len(set(int(p) for p in self.parents if p >= 0))
+        return "KinematicTree(%d dof, %d forks, %d leaves: %s)" % (
+            self.dof, len(self.forks), leaves, "".join("P" if t == PRISMATIC else "R" for t in self.joint_types))
+
+    @classmethod
+    def from_chain(cls, chain):
+        """The tree that is ``chain`` (its tool is dropped): parents -1, 0, 1, ..."""
+        return cls(np.arange(chain.dof) - 1, chain.joint_types, chain.axes, chain.rotations, chain.translations, chain.masses,
+                   chain.coms, chain.inertias, gravity=chain.gravity)
+
+    def c_struct(self, like):
+        """(tpr_chain of the links, the host parent array, what they point to) for a call whose arrays are of the kind of
+        ``like`` (see :meth:`SerialChain.c_struct`).  The parent table is a host array in both cases."""
+        model, keep = self._links.c_struct(like)
+        return model, self.parents, (keep, self.parents)
+
+    def inverse_dynamics(self, q, qd, qdd):
+        """Joint torques / forces tau(q, qd, qdd) by recursive Newton-Euler over the tree: arrays [..., d] in, [..., d] out
+        (numpy in -> numpy out, torch-ROCm tensors in -> a tensor out on the current stream).  A valid ``inv_dyn`` callback of
+        the torque constraints."""
+        return _batch.tree_inverse_dynamics_batch(self, q, qd, qdd)
+
+    def torque_terms(self, q, qs, qss):
+        """(tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: the three evaluations a torque constraint needs."""
+        return _batch.tree_torque_terms_batch(self, q, qs, qss)
+
+    def path_to(self, link):
+        """The links from the base to ``link``, in order: the joints that move it."""
+        link = int(link)
+        if not 0 <= link < self.dof:
+            raise ValueError("link %d is outside the tree's links 0..%d" % (link, self.dof - 1))
+        path = []
+        while link >= 0:
+            path.append(link)
+            link = int(self.parents[link])
+        return np.array(path[::-1], dtype=np.int64)
+
+    def chain_to(self, link, tool=(0.0, 0.0, 0.0)):
+        """(SerialChain, joints): the serial chain from the base to ``link`` with ``tool`` in that link's frame, and the indices
+        of its joints in the tree.  The tool and control-point entries of :class:`SerialChain` then evaluate on
+        ``q[..., joints]``; their bounds enter a batch through ``BatchBoundConstraint``."""
+        joints = self.path_to(link)
+        chain = SerialChain([self.joint_types[i] for i in joints], self.axes[joints], self.rotations[joints], self.translations[joints],
+                            self.masses[joints], self.coms[joints], self.inertias[joints], gravity=self.gravity, tool=tool)
+        return chain, joints
+
+    def with_payload(self, payload, link):
+        """A new tree whose link ``link`` carries ``payload`` (a :class:`Payload` fixed in that link's frame): its mass, centre
+        of mass and inertia merged into the link's, as :meth:`SerialChain.with_payload` does for a chain's last link."""
+        link = int(link)
+        if not 0 <= link < self.dof:
+            raise ValueError("link %d is outside the tree's links 0..%d" % (link, self.dof - 1))
+        masses, coms, inertias = _with_payload_on(self.masses, self.coms, self.inertias, link, payload)
+        return KinematicTree(self.parents, self.joint_types, self.axes, self.rotations, self.translations, masses, coms, inertias,
+                             gravity=self.gravity)

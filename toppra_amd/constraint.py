@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .chain import ControlPoints, Payload, SerialChain
+from .chain import ControlPoints, KinematicTree, Payload, SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -323,8 +323,9 @@ def _zeros_like(x):
 
 
 def _check_chain_dof(inv_dyn, d):
-    if isinstance(inv_dyn, SerialChain) and inv_dyn.dof != d:
-        raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(inv_dyn.dof, d))
+    if isinstance(inv_dyn, (SerialChain, KinematicTree)) and inv_dyn.dof != d:
+        raise ValueError("Wrong dimension: the {:s} has {:d} joints, the path {:d} dof".format(
+            "tree" if isinstance(inv_dyn, KinematicTree) else "chain", inv_dyn.dof, d))
 
 
 class _BatchSecondOrder(LinearConstraint):
@@ -334,8 +335,9 @@ class _BatchSecondOrder(LinearConstraint):
 
     def _evaluate(self, q, qs, qss):
         """w0 = tau(q, 0, 0), wa = tau(q, 0, q'), wb = tau(q, q', q''): exactly three calls, each checked -- or, for a
-        :class:`toppra_amd.chain.SerialChain`, one launch that evaluates the three (the values of the three calls)."""
-        if isinstance(self.inv_dyn, SerialChain):
+        :class:`toppra_amd.chain.SerialChain` or :class:`toppra_amd.chain.KinematicTree`, one launch that evaluates the three
+        (the values of the three calls)."""
+        if isinstance(self.inv_dyn, (SerialChain, KinematicTree)):
             return list(self.inv_dyn.torque_terms(q, qs, qss))
         zero = _zeros_like(q)
         out = []
@@ -374,8 +376,9 @@ class BatchJointTorqueConstraint(_BatchSecondOrder):
 
     ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, d] out -- numpy arrays when the problem was
     given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times.  A
-    :class:`toppra_amd.chain.SerialChain` may stand in its place: the robot's inverse dynamics then run on the GPU, the
-    three evaluations in one launch (the values of ``inv_dyn=chain.inverse_dynamics``).  ``tau_lim``:
+    :class:`toppra_amd.chain.SerialChain` -- or, for a branched robot, a :class:`toppra_amd.chain.KinematicTree` -- may stand in
+    its place: the robot's inverse dynamics then run on the GPU, the three evaluations in one launch (the values of
+    ``inv_dyn=chain.inverse_dynamics``).  ``tau_lim``:
     [d, 2] or [B, d, 2]; ``fs_coef``: [d] or [B, d].  Defaults are the reference's (Collocation)."""
 
     def __init__(self, inv_dyn, tau_lim, fs_coef, discretization_scheme=DiscretizationType.Collocation):
@@ -425,7 +428,8 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
 
     ``inv_dyn(q, qd, qdd)`` is BATCHED: three arrays [B, N+1, d] in, [B, N+1, p] out -- numpy arrays when the problem was
     given as numpy, torch tensors on the problem's device otherwise -- and is called exactly three times; or a
-    :class:`toppra_amd.chain.SerialChain` (p = d: its joint torques, the three evaluations in one launch).  ``F``: [m, p],
+    :class:`toppra_amd.chain.SerialChain` or :class:`toppra_amd.chain.KinematicTree` (p = d: its joint torques, the three
+    evaluations in one launch).  ``F``: [m, p],
     [B, m, p], [B, N+1, m, p], a batched callable of q returning [B, N+1, m, p], or None for the signed identity [I; -I]
     (what :meth:`joint_torque_constraint` builds: m = 2 p); ``g``: [m], [B, m], [B, N+1, m] or a batched callable of q.
     ``friction``: dry friction [d] or [B, d], friction * sign(q') is added to c (the ``custom_term`` of the reference's

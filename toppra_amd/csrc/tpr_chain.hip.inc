@@ -281,6 +281,9 @@ __device__ __forceinline__ size_t chain_row(int npoints, int d) {
     return (g < (size_t)npoints ? g : (size_t)npoints - 1) * (size_t)d;
 }
 
+// (TPR_CHAIN_NO_KERNELS: a unit that takes the recursion from this file and brings kernels of its own -- tpr_tree.hip.inc; a
+// kernel is emitted wherever it is defined, used or not)
+#ifndef TPR_CHAIN_NO_KERNELS
 static __global__ void __launch_bounds__(kChainBlock) chain_inverse_dynamics_lds_kernel(ChainDynArgs A) {
     extern __shared__ double chain_lds[];
     const size_t at = chain_row(A.npoints, A.M.d);
@@ -721,5 +724,6 @@ __device__ __forceinline__ void chain_points_accel(const ChainPointsAccelArgs &A
 
 static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_kernel(ChainPointsAccelArgs A) { chain_points_accel<false>(A); }
 static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_terms_kernel(ChainPointsAccelArgs A) { chain_points_accel<true>(A); }
+#endif  // TPR_CHAIN_NO_KERNELS
 
 }  // namespace tpr

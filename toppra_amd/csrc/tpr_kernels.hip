@@ -1659,11 +1659,12 @@ __attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const
 }
 namespace {
 // What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
-int check_chain(const tpr_chain *c, long long npoints, const char *who) {
+// (a tree's links are a tpr_chain whose tool is not read: need_tool = false)
+int check_chain(const tpr_chain *c, long long npoints, const char *who, bool need_tool = true) {
     if (default_device() < 0) return fail(TPR_E_HIP, "tpr_init() has not succeeded");
     if (!c) return fail(TPR_E_BADARG, std::string(who) + ": null chain");
     if (c->d < 1 || c->d > TPR_MAX_DOF) return fail(TPR_E_BADARG, std::string(who) + ": the chain's dof must be in [1, TPR_MAX_DOF]");
-    if (!c->joint_type || !c->axis || !c->rot || !c->trans || !c->mass || !c->com || !c->inertia || !c->gravity || !c->tool)
+    if (!c->joint_type || !c->axis || !c->rot || !c->trans || !c->mass || !c->com || !c->inertia || !c->gravity || (need_tool && !c->tool))
         return fail(TPR_E_BADARG, std::string(who) + ": every array of the chain is required");
     {  // joint_type is read here, on the host: a device pointer in its place is refused, not dereferenced
         hipPointerAttribute_t attr;
@@ -1943,6 +1944,90 @@ int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_
     if (int rc = S.failed()) return rc;
     if (npoints > 0 && tpr_tu_chain_points_accel_launch(&A, 1, S.stream) != 0)
         return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_acceleration_terms_batch: no kernel for this dof and point set");
+    return S.finish();
+}
+}  // extern "C"
+
+// ---- a kinematic tree evaluated on the GPU (tpr_tree.hip.inc, tpr_tree_tu.hip) ---------------------------------------------------
+#include "tpr_tree_args.hpp"
+extern "C" {
+__attribute__((visibility("hidden"))) int tpr_tu_tree_dynamics_launch(const tpr::TreeDynArgs *, const int32_t *parent, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_tree_terms_launch(const tpr::TreeTermsArgs *, const int32_t *parent, hipStream_t);
+}
+namespace {
+// What the tree entries refuse before any launch: what the chain entries refuse (the tool apart), and the parent table -- a host
+// array like joint_type, read here.
+int check_tree(const tpr_chain *links, const int32_t *parent, long long npoints, const char *who) {
+    if (int rc = check_chain(links, npoints, who, false)) return rc;
+    if (!parent) return fail(TPR_E_BADARG, std::string(who) + ": null parent array");
+    {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, parent) == hipSuccess) {
+            if (attr.type == hipMemoryTypeDevice) return fail(TPR_E_BADARG, std::string(who) + ": parent must be a host array, also with TPR_DEVICE_PTRS");
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    tpr::TreeTables T;
+    const int forks = tpr::tree_tables(parent, links->d, T);
+    if (forks < 0) {
+        const int i = -1 - forks;
+        return fail(TPR_E_BADARG, std::string(who) + ": the parent of link " + std::to_string(i) + " is " + std::to_string(parent[i]) +
+                                      ", outside -1 .. " + std::to_string(i - 1) + " (links are numbered after their parents)");
+    }
+    if (forks > TPR_TREE_MAX_FORKS)
+        return fail(TPR_E_UNSUPPORTED, std::string(who) + ": the tree has " + std::to_string(forks) + " forks, more than TPR_TREE_MAX_FORKS = " +
+                                           std::to_string(TPR_TREE_MAX_FORKS));
+    return TPR_E_OK;
+}
+tpr::ChainModel stage_tree_links(const tpr_chain *c, Staging &S) {
+    tpr::ChainModel M{};
+    const size_t d = (size_t)c->d;
+    M.d = c->d;
+    for (int i = 0; i < c->d; ++i) M.prismatic |= (uint32_t)(c->joint_type[i] == TPR_JOINT_PRISMATIC) << i;
+    M.axis = S.in(c->axis, 3 * d); M.rot = S.in(c->rot, 9 * d); M.trans = S.in(c->trans, 3 * d);
+    M.mass = S.in(c->mass, d); M.com = S.in(c->com, 3 * d); M.inertia = S.in(c->inertia, 6 * d);
+    M.gravity = S.in(c->gravity, 3);
+    return M;  // (tool stays null: the tree kernels do not read it)
+}
+}  // namespace
+
+extern "C" {
+int tpr_tree_inverse_dynamics_batch(const tpr_chain *links, const int32_t *parent, long long npoints, const double *q, const double *qd,
+                                    const double *qdd, double *tau, int flags, void *stream_) {
+    if (int rc = check_tree(links, parent, npoints, "tpr_tree_inverse_dynamics_batch")) return rc;
+    if (!q || !qd || !qdd || !tau) return fail(TPR_E_BADARG, "tpr_tree_inverse_dynamics_batch: q, qd, qdd, tau are required");
+    Staging S(flags & TPR_DEVICE_PTRS, tau, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)links->d;
+    tpr::TreeDynArgs A{};
+    A.M = stage_tree_links(links, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
+    A.tau = S.out(tau, n);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_tree_dynamics_launch(&A, parent, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_tree_inverse_dynamics_batch: the kernel's LDS could not be reserved");
+    return S.finish();
+}
+
+int tpr_tree_torque_terms_batch(const tpr_chain *links, const int32_t *parent, int B, int N, const double *q, const double *qs,
+                                const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_tree_torque_terms_batch: B >= 0, N >= 0");
+    const long long npoints = (long long)B * ((long long)N + 1);
+    if (int rc = check_tree(links, parent, npoints, "tpr_tree_torque_terms_batch")) return rc;
+    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_tree_torque_terms_batch: q, qs, qss, w0, wa, wb are required");
+    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
+    if (int rc = S.failed()) return rc;
+    const size_t n = (size_t)npoints * (size_t)links->d;
+    tpr::TreeTermsArgs A{};
+    A.M = stage_tree_links(links, S);
+    A.npoints = (int)npoints;
+    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
+    A.w0 = S.out(w0, n); A.wa = S.out(wa, n); A.wb = S.out(wb, n);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && tpr_tu_tree_terms_launch(&A, parent, S.stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, "tpr_tree_torque_terms_batch: the kernel's LDS could not be reserved");
     return S.finish();
 }
 }  // extern "C"
