@@ -34,7 +34,7 @@ def random_chain(d, seed):
 
 
 def torch_inverse_dynamics(chain, device):
-    """The recursion of csrc/tpr_chain.hip.inc as batched torch ops: inv_dyn(q, qd, qdd) on [B, N+1, d] device tensors."""
+    """The recursion of csrc/tpr_chain_rnea.hip.inc as batched torch ops: inv_dyn(q, qd, qdd) on [B, N+1, d] device tensors."""
     import torch
     t = lambda x: torch.as_tensor(np.array(x), dtype=torch.float64, device=device)  # noqa: E731
     rot, trans, axis, com, mass = t(chain.rotations), t(chain.translations), t(chain.axes), t(chain.coms), chain.masses

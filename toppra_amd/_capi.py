@@ -263,48 +263,30 @@ def load():
         L.tpr_feasible_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V]
         L.tpr_reachable_sets_sampled_boxed_batch.restype = C.c_int
         L.tpr_reachable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V, V]
-        L.tpr_chain_bytes.restype = C.c_int
-        L.tpr_chain_bytes.argtypes = []
-        if L.tpr_chain_bytes() != C.sizeof(tpr_chain):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_chain takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_chain_bytes(), C.sizeof(tpr_chain)))
-        CP = C.POINTER(tpr_chain)
-        L.tpr_chain_inverse_dynamics_batch.restype = C.c_int
-        L.tpr_chain_inverse_dynamics_batch.argtypes = [CP, C.c_longlong, V, V, V, V, C.c_int, V]
-        L.tpr_chain_torque_terms_batch.restype = C.c_int
-        L.tpr_chain_torque_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
-        L.tpr_chain_tool_velocity_batch.restype = C.c_int
-        L.tpr_chain_tool_velocity_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
-        L.tpr_chain_tool_acceleration_batch.restype = C.c_int
-        L.tpr_chain_tool_acceleration_batch.argtypes = [CP, C.c_longlong, V, V, V, V, C.c_int, V]
-        L.tpr_chain_tool_acceleration_terms_batch.restype = C.c_int
-        L.tpr_chain_tool_acceleration_terms_batch.argtypes = [CP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
-        L.tpr_payload_bytes.restype = C.c_int
-        L.tpr_payload_bytes.argtypes = []
-        if L.tpr_payload_bytes() != C.sizeof(tpr_payload):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_payload takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_payload_bytes(), C.sizeof(tpr_payload)))
-        PP = C.POINTER(tpr_payload)
-        L.tpr_chain_tool_wrench_batch.restype = C.c_int
-        L.tpr_chain_tool_wrench_batch.argtypes = [CP, PP, C.c_longlong, V, V, V, V, C.c_int, V]
-        L.tpr_chain_tool_wrench_terms_batch.restype = C.c_int
-        L.tpr_chain_tool_wrench_terms_batch.argtypes = [CP, PP, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
-        L.tpr_chain_points_bytes.restype = C.c_int
-        L.tpr_chain_points_bytes.argtypes = []
-        if L.tpr_chain_points_bytes() != C.sizeof(tpr_chain_points):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_chain_points takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_chain_points_bytes(), C.sizeof(tpr_chain_points)))
-        XP = C.POINTER(tpr_chain_points)
-        L.tpr_chain_points_speed_batch.restype = C.c_int
-        L.tpr_chain_points_speed_batch.argtypes = [CP, XP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
-        L.tpr_chain_points_acceleration_batch.restype = C.c_int
-        L.tpr_chain_points_acceleration_batch.argtypes = [CP, XP, C.c_longlong, V, V, V, V, C.c_int, V]
-        L.tpr_chain_points_acceleration_terms_batch.restype = C.c_int
-        L.tpr_chain_points_acceleration_terms_batch.argtypes = [CP, XP, C.c_int, C.c_int, V, V, V, V, V, C.c_int, V]
-        L.tpr_tree_inverse_dynamics_batch.restype = C.c_int
-        L.tpr_tree_inverse_dynamics_batch.argtypes = [CP, V, C.c_longlong, V, V, V, V, C.c_int, V]
-        L.tpr_tree_torque_terms_batch.restype = C.c_int
-        L.tpr_tree_torque_terms_batch.argtypes = [CP, V, C.c_int, C.c_int, V, V, V, V, V, V, C.c_int, V]
+        # the rigid-body family: three by-value structs with their size checks, and one table of signatures
+        for struct in (tpr_chain, tpr_payload, tpr_chain_points):
+            size = getattr(L, struct.__name__ + "_bytes")
+            size.restype, size.argtypes = C.c_int, []
+            if size() != C.sizeof(struct):
+                raise ToppraHipError("libtoppra_hip.so was built from another header: its %s takes %d bytes, this "
+                                     "binding declares %d" % (struct.__name__, size(), C.sizeof(struct)))
+        CP, PP, XP = C.POINTER(tpr_chain), C.POINTER(tpr_payload), C.POINTER(tpr_chain_points)
+        I, LL = C.c_int, C.c_longlong
+        for name, argtypes in {
+                "tpr_chain_inverse_dynamics_batch": [CP, LL, V, V, V, V],
+                "tpr_chain_torque_terms_batch": [CP, I, I, V, V, V, V, V, V],
+                "tpr_chain_tool_velocity_batch": [CP, I, I, V, V, V, V, V, V],
+                "tpr_chain_tool_acceleration_batch": [CP, LL, V, V, V, V],
+                "tpr_chain_tool_acceleration_terms_batch": [CP, I, I, V, V, V, V, V],
+                "tpr_chain_tool_wrench_batch": [CP, PP, LL, V, V, V, V],
+                "tpr_chain_tool_wrench_terms_batch": [CP, PP, I, I, V, V, V, V, V, V],
+                "tpr_chain_points_speed_batch": [CP, XP, I, I, V, V, V, V, V],
+                "tpr_chain_points_acceleration_batch": [CP, XP, LL, V, V, V, V],
+                "tpr_chain_points_acceleration_terms_batch": [CP, XP, I, I, V, V, V, V, V],
+                "tpr_tree_inverse_dynamics_batch": [CP, V, LL, V, V, V, V],
+                "tpr_tree_torque_terms_batch": [CP, V, I, I, V, V, V, V, V, V]}.items():
+            entry = getattr(L, name)
+            entry.restype, entry.argtypes = C.c_int, argtypes + [I, V]  # (..., int flags, void *stream)
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

@@ -684,30 +684,51 @@ def _chain_points(chain, arrays, names):
     return out, shape, npoints
 
 
+def _rigid_call(model, entry, arrays, names, tails, structs=(), by_grid=False, limits=None):
+    """One call of the rigid-body entry ``entry`` on ``model`` (a :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``).
+    ``arrays``, named ``names``, are its inputs [..., d].  ``structs`` is what it takes by value after the model: a ready ctypes
+    struct, or an object whose ``c_struct(model)`` makes one.  ``tails`` are the last axes of its outputs, each of the inputs'
+    shape otherwise; None in place of a tail leaves that output out (a null pointer).  ``by_grid``: the entry takes (B, N) in
+    place of npoints -- (npoints, 0), unless ``limits(q, shape, npoints)`` -> ((B, N), further inputs, tails) says otherwise; it
+    runs after the inputs are converted and before anything touches the device.  Returns the list of outputs."""
+    arrays, shape, npoints = _chain_points(model, arrays, names)
+    q = arrays[0]
+    structs = [s if isinstance(s, C.Structure) else s.c_struct(model) for s in structs]
+    size = (npoints, 0) if by_grid else (npoints,)
+    if limits is not None:
+        size, more, tails = limits(q, shape, npoints)
+        arrays = arrays + list(more)
+    _prepare(q)
+    links = model.c_struct(q)  # (tpr_chain, what it points to) of a chain; a tree's host parent array between the two
+    head = [C.byref(links[0])] + [parent.ctypes.data for parent in links[1:-1]] + [C.byref(s) for s in structs]
+    outs = [None if tail is None else _empty(q, shape[:-1] + tuple(tail)) for tail in tails]
+    _capi.check(getattr(_capi.load(), entry)(*head, *size, *[_capi.ptr(a) for a in arrays + outs],
+                                             _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
+    return outs
+
+
+def _bound_limits(limit, shape, convert):
+    """What the two bound functions share once a ``limit`` is given: q must be [B, N+1, d]; ``convert(limit, B)`` makes the
+    limit the array the entry reads (its shape is the caller's); a host limit must be > 0.  Returns (B, N, limit)."""
+    if len(shape) != 3:
+        raise ValueError("with a limit, q must have shape [B, N+1, d], got %s" % (list(shape),))
+    B, N = shape[0], shape[1] - 1
+    limit = convert(limit, B)
+    if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
+        raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
+    return B, N, limit
+
+
 def chain_inverse_dynamics_batch(chain, q, qd, qdd):
     """tau = RNEA(q, qd, qdd) of ``chain`` (a :class:`toppra_amd.chain.SerialChain`) at every point: three arrays [..., d] in,
     [..., d] out; numpy in -> numpy out, tensors in -> a tensor out on the current stream."""
-    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    tau = _empty(q, shape)
-    _capi.check(_capi.load().tpr_chain_inverse_dynamics_batch(C.byref(model), npoints, _capi.ptr(q), _capi.ptr(qd), _capi.ptr(qdd),
-                                                              _capi.ptr(tau), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
-                                                              _stream_ptr(q)))
-    return tau
+    return _rigid_call(chain, "tpr_chain_inverse_dynamics_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(chain.dof,)])[0]
 
 
 def chain_torque_terms_batch(chain, q, qs, qss):
     """(w0, wa, wb) = (tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: what a torque constraint's rows are built
     from (``second_order_rows_batch``).  Each equals :func:`chain_inverse_dynamics_batch` on the same arguments."""
-    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    w0, wa, wb = _empty(q, shape), _empty(q, shape), _empty(q, shape)
-    _capi.check(_capi.load().tpr_chain_torque_terms_batch(C.byref(model), npoints, 0, _capi.ptr(q), _capi.ptr(qs), _capi.ptr(qss),
-                                                          _capi.ptr(w0), _capi.ptr(wa), _capi.ptr(wb),
-                                                          _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return w0, wa, wb
+    return tuple(_rigid_call(chain, "tpr_chain_torque_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(chain.dof,)] * 3, by_grid=True))
 
 
 def chain_tool_bound_batch(chain, q, qs, limit=None, S=None):
@@ -716,35 +737,24 @@ def chain_tool_bound_batch(chain, q, qs, limit=None, S=None):
     doubles), None = the linear speed only (|v|^2).  With ``limit`` (> 0, a scalar or [B]; q must be
     [B, N+1, d] then) also the bound on x = sd^2 it implies: (vSv, xbound) with xbound [B, N+1, 2] = (0, limit / vSv) --
     +inf where the tool stands still -- the array a ``("xbound", ...)`` source of :func:`stage_boxes_batch` takes."""
-    (q, qs), shape, npoints = _chain_points(chain, (q, qs), ("q", "qs"))
-    dev = _capi.is_torch_cuda(q)
-    conv = _capi.converter(q, "q")
-    if S is not None:
-        if not dev:
-            S = np.asarray(S, dtype=np.float64)
-        elif not hasattr(S, "is_cuda"):
-            import torch
-            S = torch.as_tensor(np.asarray(S, dtype=np.float64), device=q.device)
-        S = conv("S", S)
-        if tuple(S.shape) != (6, 6):
-            raise ValueError("S must have shape [6, 6], got %s" % (tuple(S.shape),))
-        _capi.check_weight(S)
-    B, N, xbound = npoints, 0, None
-    if limit is not None:
-        if len(shape) != 3:
-            raise ValueError("with a limit, q must have shape [B, N+1, d], got %s" % (list(shape),))
-        B, N = shape[0], shape[1] - 1
-        limit = _capi.per_traj_vector("limit", limit, B, q)
-        if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
-            raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    vSv = _empty(q, shape[:-1])
-    if limit is not None:
-        xbound = _empty(q, shape[:-1] + (2,))
-    _capi.check(_capi.load().tpr_chain_tool_velocity_batch(C.byref(model), B, N, _capi.ptr(q), _capi.ptr(qs), _capi.ptr(S),
-                                                           _capi.ptr(limit), _capi.ptr(vSv), _capi.ptr(xbound),
-                                                           _capi.DEVICE_PTRS if dev else 0, _stream_ptr(q)))
+    def limits(q, shape, npoints):
+        weight, lim, size = S, limit, (npoints, 0)
+        if weight is not None:
+            if not _capi.is_torch_cuda(q):
+                weight = np.asarray(weight, dtype=np.float64)
+            elif not hasattr(weight, "is_cuda"):
+                import torch
+                weight = torch.as_tensor(np.asarray(weight, dtype=np.float64), device=q.device)
+            weight = _capi.converter(q, "q")("S", weight)
+            if tuple(weight.shape) != (6, 6):
+                raise ValueError("S must have shape [6, 6], got %s" % (tuple(weight.shape),))
+            _capi.check_weight(weight)
+        if lim is not None:
+            B, N, lim = _bound_limits(lim, shape, lambda x, B: _capi.per_traj_vector("limit", x, B, q))
+            size = (B, N)
+        return size, (weight, lim), [(), None if lim is None else (2,)]
+
+    vSv, xbound = _rigid_call(chain, "tpr_chain_tool_velocity_batch", (q, qs), ("q", "qs"), None, by_grid=True, limits=limits)
     return vSv if limit is None else (vSv, xbound)
 
 
@@ -752,59 +762,29 @@ def chain_tool_acceleration_batch(chain, q, qd, qdd):
     """The tool point's acceleration acc(q, qd, qdd) = [linear; angular] in world axes at every point: three arrays [..., d]
     in, [..., 6] out.  Kinematics only (no gravity); the linear part is the classical acceleration of the point, the second
     time derivative of its world position (include/toppra_hip.h: tpr_chain_tool_acceleration_batch)."""
-    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    acc = _empty(q, shape[:-1] + (6,))
-    _capi.check(_capi.load().tpr_chain_tool_acceleration_batch(C.byref(model), npoints, _capi.ptr(q), _capi.ptr(qd), _capi.ptr(qdd),
-                                                               _capi.ptr(acc), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
-                                                               _stream_ptr(q)))
-    return acc
+    return _rigid_call(chain, "tpr_chain_tool_acceleration_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(6,)])[0]
 
 
 def chain_tool_acceleration_terms_batch(chain, q, qs, qss):
     """(wa, wb) = (acc(q, 0, qs), acc(q, qs, qss)) [..., 6] in one launch: what a constraint on the tool point's acceleration
     builds its rows from (w0 = acc(q, 0, 0) is an exact zero).  Each equals :func:`chain_tool_acceleration_batch` on the same
     arguments in every bit."""
-    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    wa, wb = _empty(q, shape[:-1] + (6,)), _empty(q, shape[:-1] + (6,))
-    _capi.check(_capi.load().tpr_chain_tool_acceleration_terms_batch(C.byref(model), npoints, 0, _capi.ptr(q), _capi.ptr(qs),
-                                                                     _capi.ptr(qss), _capi.ptr(wa), _capi.ptr(wb),
-                                                                     _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return wa, wb
+    return tuple(_rigid_call(chain, "tpr_chain_tool_acceleration_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(6,)] * 2, by_grid=True))
 
 
 def chain_tool_wrench_batch(chain, q, qd, qdd, payload):
     """The wrench the last link transmits to ``payload`` (a :class:`toppra_amd.chain.Payload`) at every point: three arrays
     [..., d] in, [..., 6] = [force; moment about the contact frame's origin] in contact-frame axes out.  Gravity is included:
     at rest the force is the support of the body's weight (include/toppra_hip.h: tpr_chain_tool_wrench_batch)."""
-    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
-    body = payload.c_struct(chain)
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    wrench = _empty(q, shape[:-1] + (6,))
-    _capi.check(_capi.load().tpr_chain_tool_wrench_batch(C.byref(model), C.byref(body), npoints, _capi.ptr(q), _capi.ptr(qd),
-                                                         _capi.ptr(qdd), _capi.ptr(wrench),
-                                                         _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return wrench
+    return _rigid_call(chain, "tpr_chain_tool_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(6,)], structs=[payload])[0]
 
 
 def chain_tool_wrench_terms_batch(chain, q, qs, qss, payload):
     """(w0, wa, wb) = (wrench(q, 0, 0), wrench(q, 0, qs), wrench(q, qs, qss)) [..., 6] in one launch: what a constraint on the
     wrench at the tool builds its rows from (w0 is the static wrench: not zero under gravity).  Each equals
     :func:`chain_tool_wrench_batch` on the same arguments in every bit."""
-    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
-    body = payload.c_struct(chain)
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    w0, wa, wb = (_empty(q, shape[:-1] + (6,)) for _ in range(3))
-    _capi.check(_capi.load().tpr_chain_tool_wrench_terms_batch(C.byref(model), C.byref(body), npoints, 0, _capi.ptr(q),
-                                                               _capi.ptr(qs), _capi.ptr(qss), _capi.ptr(w0), _capi.ptr(wa),
-                                                               _capi.ptr(wb), _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
-                                                               _stream_ptr(q)))
-    return w0, wa, wb
+    return tuple(_rigid_call(chain, "tpr_chain_tool_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(6,)] * 3, structs=[payload],
+                             by_grid=True))
 
 
 def _control_points(chain, points):
@@ -822,34 +802,30 @@ def chain_points_speed_batch(chain, q, qs, points, limit=None):
     [B, N+1, 2] = (0, min_p limit_p / speed2_p) -- +inf where every point stands still -- the array a ``("xbound", ...)`` source
     of :func:`stage_boxes_batch` takes."""
     pts = _control_points(chain, points)
-    (q, qs), shape, npoints = _chain_points(chain, (q, qs), ("q", "qs"))
-    dev = _capi.is_torch_cuda(q)
     P = int(pts.count)
-    B, N, xbound = npoints, 0, None
-    if limit is not None:
-        if len(shape) != 3:
-            raise ValueError("with a limit, q must have shape [B, N+1, d], got %s" % (list(shape),))
-        B, N = shape[0], shape[1] - 1
-        if dev:
-            import torch
-            if not (hasattr(limit, "is_cuda") and limit.is_cuda):
-                limit = torch.as_tensor(np.asarray(limit, dtype=np.float64), device=q.device)
-            _capi.check_tensor("limit", limit, q)
-        else:
-            limit = np.asarray(limit, dtype=np.float64)
-        if tuple(limit.shape) not in ((), (P,), (B, P)):
-            raise ValueError("limit must be a scalar or have shape [P] = [%d] or [B, P] = [%d, %d], got %s" % (P, B, P, tuple(limit.shape)))
-        if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
-            raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
-        limit = limit.expand(B, P).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(limit, (B, P)))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    speed2 = _empty(q, shape[:-1] + (P,))
-    if limit is not None:
-        xbound = _empty(q, shape[:-1] + (2,))
-    _capi.check(_capi.load().tpr_chain_points_speed_batch(C.byref(model), C.byref(pts), B, N, _capi.ptr(q), _capi.ptr(qs),
-                                                          _capi.ptr(limit), _capi.ptr(speed2), _capi.ptr(xbound),
-                                                          _capi.DEVICE_PTRS if dev else 0, _stream_ptr(q)))
+
+    def limits(q, shape, npoints):
+        if limit is None:
+            return (npoints, 0), (None,), [(P,), None]
+        dev = _capi.is_torch_cuda(q)
+
+        def convert(lim, B):
+            if dev:
+                import torch
+                if not (hasattr(lim, "is_cuda") and lim.is_cuda):
+                    lim = torch.as_tensor(np.asarray(lim, dtype=np.float64), device=q.device)
+                _capi.check_tensor("limit", lim, q)
+            else:
+                lim = np.asarray(lim, dtype=np.float64)
+            if tuple(lim.shape) not in ((), (P,), (B, P)):
+                raise ValueError("limit must be a scalar or have shape [P] = [%d] or [B, P] = [%d, %d], got %s" % (P, B, P, tuple(lim.shape)))
+            return lim.expand(B, P).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(lim, (B, P)))
+
+        B, N, lim = _bound_limits(limit, shape, convert)
+        return (B, N), (lim,), [(P,), (2,)]
+
+    speed2, xbound = _rigid_call(chain, "tpr_chain_points_speed_batch", (q, qs), ("q", "qs"), None, structs=[pts], by_grid=True,
+                                 limits=limits)
     return speed2 if limit is None else (speed2, xbound)
 
 
@@ -858,14 +834,8 @@ def chain_points_acceleration_batch(chain, q, qd, qdd, points):
     [..., P, 3] out.  Kinematics only (no gravity); each is the classical acceleration of the point, as the linear part of
     :func:`chain_tool_acceleration_batch` is for the tool (include/toppra_hip.h: tpr_chain_points_acceleration_batch)."""
     pts = _control_points(chain, points)
-    (q, qd, qdd), shape, npoints = _chain_points(chain, (q, qd, qdd), ("q", "qd", "qdd"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    acc = _empty(q, shape[:-1] + (int(pts.count), 3))
-    _capi.check(_capi.load().tpr_chain_points_acceleration_batch(C.byref(model), C.byref(pts), npoints, _capi.ptr(q), _capi.ptr(qd),
-                                                                 _capi.ptr(qdd), _capi.ptr(acc),
-                                                                 _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return acc
+    return _rigid_call(chain, "tpr_chain_points_acceleration_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(int(pts.count), 3)],
+                       structs=[pts])[0]
 
 
 def chain_points_acceleration_terms_batch(chain, q, qs, qss, points):
@@ -873,15 +843,8 @@ def chain_points_acceleration_terms_batch(chain, q, qs, qss, points):
     constraint on the control points' accelerations builds its rows from (w0 = acc(q, 0, 0) is an exact zero).  Each equals the
     single evaluation on the same arguments in every bit."""
     pts = _control_points(chain, points)
-    (q, qs, qss), shape, npoints = _chain_points(chain, (q, qs, qss), ("q", "qs", "qss"))
-    _prepare(q)
-    model, keep = chain.c_struct(q)
-    wa, wb = (_empty(q, shape[:-1] + (int(pts.count), 3)) for _ in range(2))
-    _capi.check(_capi.load().tpr_chain_points_acceleration_terms_batch(C.byref(model), C.byref(pts), npoints, 0, _capi.ptr(q),
-                                                                       _capi.ptr(qs), _capi.ptr(qss), _capi.ptr(wa), _capi.ptr(wb),
-                                                                       _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0,
-                                                                       _stream_ptr(q)))
-    return wa, wb
+    return tuple(_rigid_call(chain, "tpr_chain_points_acceleration_terms_batch", (q, qs, qss), ("q", "qs", "qss"),
+                             [(int(pts.count), 3)] * 2, structs=[pts], by_grid=True))
 
 
 # a kinematic tree evaluated on the GPU (include/toppra_hip.h: tpr_tree_*; the model object is toppra_amd.chain.KinematicTree)
@@ -890,27 +853,13 @@ def tree_inverse_dynamics_batch(tree, q, qd, qdd):
     """tau = RNEA(q, qd, qdd) of ``tree`` (a :class:`toppra_amd.chain.KinematicTree`) at every point: three arrays [..., d] in,
     [..., d] out; numpy in -> numpy out, tensors in -> a tensor out on the current stream.  A chain-shaped tree gives the bits of
     :func:`chain_inverse_dynamics_batch`."""
-    (q, qd, qdd), shape, npoints = _chain_points(tree, (q, qd, qdd), ("q", "qd", "qdd"))
-    _prepare(q)
-    model, parent, keep = tree.c_struct(q)
-    tau = _empty(q, shape)
-    _capi.check(_capi.load().tpr_tree_inverse_dynamics_batch(C.byref(model), parent.ctypes.data, npoints, _capi.ptr(q), _capi.ptr(qd),
-                                                             _capi.ptr(qdd), _capi.ptr(tau),
-                                                             _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return tau
+    return _rigid_call(tree, "tpr_tree_inverse_dynamics_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(tree.dof,)])[0]
 
 
 def tree_torque_terms_batch(tree, q, qs, qss):
     """(w0, wa, wb) = (tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) of ``tree`` in one launch: what a torque constraint's rows
     are built from.  Each equals :func:`tree_inverse_dynamics_batch` on the same arguments in every bit."""
-    (q, qs, qss), shape, npoints = _chain_points(tree, (q, qs, qss), ("q", "qs", "qss"))
-    _prepare(q)
-    model, parent, keep = tree.c_struct(q)
-    w0, wa, wb = _empty(q, shape), _empty(q, shape), _empty(q, shape)
-    _capi.check(_capi.load().tpr_tree_torque_terms_batch(C.byref(model), parent.ctypes.data, npoints, 0, _capi.ptr(q), _capi.ptr(qs),
-                                                         _capi.ptr(qss), _capi.ptr(w0), _capi.ptr(wa), _capi.ptr(wb),
-                                                         _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))
-    return w0, wa, wb
+    return tuple(_rigid_call(tree, "tpr_tree_torque_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(tree.dof,)] * 3, by_grid=True))
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

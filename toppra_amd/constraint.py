@@ -523,6 +523,34 @@ def _host(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64)
 
 
+def _need_chain(chain):
+    if not isinstance(chain, SerialChain):
+        raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+
+
+def _need_points(points, chain):
+    if not isinstance(points, ControlPoints):
+        raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
+    points.on(chain)  # (a link outside the chain: ValueError)
+
+
+def _row_limits(F, g, width, shapes):
+    """Limits given as rows F, g on a quantity ``width`` wide (``shapes``: the shapes of F in words): (F, g, None)."""
+    if F is None or g is None:
+        raise ValueError("F and g are given together")
+    fshape, gshape = _shape_of(F), _shape_of(g)
+    if len(fshape) not in (2, 3, 4) or fshape[-1] != width:
+        raise ValueError("F must have shape %s, got %s" % (shapes, list(fshape)))
+    if len(gshape) not in (1, 2, 3):
+        raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
+    if gshape[-1] != fshape[-2]:
+        raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
+    for name, arr in (("F", F), ("g", g)):
+        if not np.all(np.isfinite(_host(arr))):
+            raise ValueError("%s holds a value that is not finite" % name)
+    return F, g, None
+
+
 def _six_wide_limits(first, second, F, g):
     """The limits of a constraint on a 6-wide quantity [first part; second part], given either as boxes on the parts --
     (name, limit) each, a limit being None, a scalar, [3, 2] or [B, 3, 2] (lower, upper) -- or as rows F, g:
@@ -561,22 +589,49 @@ def _six_wide_limits(first, second, F, g):
         if limit_batch is not None:
             g_parts = [np.broadcast_to(p, (limit_batch, 6)) for p in g_parts]
         return np.concatenate(F_parts, 0), np.ascontiguousarray(np.concatenate(g_parts, -1)), limit_batch
-    if F is None or g is None:
-        raise ValueError("F and g are given together")
-    fshape, gshape = _shape_of(F), _shape_of(g)
-    if len(fshape) not in (2, 3, 4) or fshape[-1] != 6:
-        raise ValueError("F must have shape [m, 6], [B, m, 6] or [B, N+1, m, 6], got %s" % (list(fshape),))
-    if len(gshape) not in (1, 2, 3):
-        raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
-    if gshape[-1] != fshape[-2]:
-        raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
-    for name, arr in (("F", F), ("g", g)):
-        if not np.all(np.isfinite(_host(arr))):
-            raise ValueError("%s holds a value that is not finite" % name)
-    return F, g, None
+    return _row_limits(F, g, 6, "[m, 6], [B, m, 6] or [B, N+1, m, 6]")
 
 
-class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
+class _BatchChainRows(_BatchSecondOrder):
+    """Shared part of the constraints  F w <= g  on a quantity w(q, qd, qdd) that a chain kernel evaluates: the limits
+    (``F``, ``g``, and the B of limits given per trajectory), the checks against a problem's sizes and the block.  A subclass
+    is its constructor and :meth:`_terms`."""
+
+    def __init__(self, chain, limits, discretization_scheme, what):
+        super(_BatchChainRows, self).__init__()
+        self.chain = chain
+        self.dof = chain.dof
+        self.F, self.g, self._limit_batch = limits
+        self.set_discretization_type(discretization_scheme)
+        self.identical = True
+        self._format_string = "    Batched %s, %d rows\n" % (what, _shape_of(self.F)[-2])
+
+    def _terms(self, q, qs, qss):
+        """(w(q, 0, 0) -- None for an exact zero --, w(q, 0, q'), w(q, q', q'')), each [B, N+1, width]: one launch."""
+        raise NotImplementedError
+
+    def rows_per_stage(self, d):
+        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
+        if self._limit_batch is not None and self._limit_batch != B:
+            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
+        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
+            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
+                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
+                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+
+    def block(self, q, qs, qss):
+        B, n1, d = (int(v) for v in q.shape)
+        self.check(B, n1 - 1, d)
+        w0, wa, wb = self._terms(q, qs, qss)
+        return {"w0": _zeros_like(wa) if w0 is None else w0, "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q),
+                "friction": None, "interpolation": self._interp()}
+
+
+class BatchCartesianAccelerationConstraint(_BatchChainRows):
     """A limit on the tool point's acceleration for a batch (the reference's example examples-old/cartesian_accel.py: a
     ``SecondOrderConstraint`` whose ``inv_dyn`` returns the link's acceleration):  F acc <= g  on  acc(q, qd, qdd) =
     [linear; angular] of ``chain``'s tool point in world axes -- the classical acceleration of the point and the last link's
@@ -597,39 +652,17 @@ class BatchCartesianAccelerationConstraint(_BatchSecondOrder):
     the last are :class:`BatchPointAccelerationConstraint`'s."""
 
     def __init__(self, chain, linear=None, angular=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
-        super(BatchCartesianAccelerationConstraint, self).__init__()
-        if not isinstance(chain, SerialChain):
-            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
-        self.chain = chain
-        self.dof = chain.dof
-        self.F, self.g, self._limit_batch = _six_wide_limits(("linear", linear), ("angular", angular), F, g)
+        _need_chain(chain)
+        super(BatchCartesianAccelerationConstraint, self).__init__(
+            chain, _six_wide_limits(("linear", linear), ("angular", angular), F, g), discretization_scheme,
+            "tool acceleration limit, %d dof" % chain.dof)
         self.linear, self.angular = linear, angular
-        self.set_discretization_type(discretization_scheme)
-        self.identical = True
-        self._format_string = "    Batched tool acceleration limit, %d dof, %d rows\n" % (self.dof, _shape_of(self.F)[-2])
 
-    def rows_per_stage(self, d):
-        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
-
-    def check(self, B, N, d):
-        if self.dof != d:
-            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
-        if self._limit_batch is not None and self._limit_batch != B:
-            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
-            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
-                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
-                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
-
-    def block(self, q, qs, qss):
-        B, n1, d = (int(v) for v in q.shape)
-        self.check(B, n1 - 1, d)
-        wa, wb = self.chain.tool_acceleration_terms(q, qs, qss)
-        return {"w0": _zeros_like(wa), "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
-                "interpolation": self._interp()}
+    def _terms(self, q, qs, qss):
+        return (None,) + tuple(self.chain.tool_acceleration_terms(q, qs, qss))
 
 
-class BatchToolWrenchConstraint(_BatchSecondOrder):
+class BatchToolWrenchConstraint(_BatchChainRows):
     """A limit on the wrench a chain's last link transmits to a carried object, for a batch:  F w <= g  on
     w(q, qd, qdd) = [force; moment] of ``chain`` on ``payload`` -- the force on the body and its moment about the contact
     frame's origin, in contact-frame axes, gravity included (:meth:`toppra_amd.chain.SerialChain.tool_wrench`).  It is the
@@ -654,18 +687,14 @@ class BatchToolWrenchConstraint(_BatchSecondOrder):
     Per-trajectory payloads, a true (conic) friction cone and a body on another link than the last are out of scope."""
 
     def __init__(self, chain, payload, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
-        super(BatchToolWrenchConstraint, self).__init__()
-        if not isinstance(chain, SerialChain):
-            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+        _need_chain(chain)
         if not isinstance(payload, Payload):
             raise ValueError("payload must be a toppra_amd.chain.Payload, got %s" % type(payload).__name__)
-        self.chain, self.payload = chain, payload
-        self.dof = chain.dof
-        self.F, self.g, self._limit_batch = _six_wide_limits(("force", force), ("moment", moment), F, g)
+        super(BatchToolWrenchConstraint, self).__init__(
+            chain, _six_wide_limits(("force", force), ("moment", moment), F, g), discretization_scheme,
+            "tool wrench limit, %d dof" % chain.dof)
+        self.payload = payload
         self.force, self.moment = force, moment
-        self.set_discretization_type(discretization_scheme)
-        self.identical = True
-        self._format_string = "    Batched tool wrench limit, %d dof, %d rows\n" % (self.dof, _shape_of(self.F)[-2])
 
     @staticmethod
     def surface_contact_rows(mu, half_extents, normal_force_min=0.0):
@@ -702,25 +731,8 @@ class BatchToolWrenchConstraint(_BatchSecondOrder):
         F, g = cls.surface_contact_rows(mu, half_extents, normal_force_min)
         return cls(chain, payload, F=F, g=g, **kwargs)
 
-    def rows_per_stage(self, d):
-        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
-
-    def check(self, B, N, d):
-        if self.dof != d:
-            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
-        if self._limit_batch is not None and self._limit_batch != B:
-            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
-            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
-                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
-                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
-
-    def block(self, q, qs, qss):
-        B, n1, d = (int(v) for v in q.shape)
-        self.check(B, n1 - 1, d)
-        w0, wa, wb = self.chain.tool_wrench_terms(q, qs, qss, self.payload)
-        return {"w0": w0, "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
-                "interpolation": self._interp()}
+    def _terms(self, q, qs, qss):
+        return self.chain.tool_wrench_terms(q, qs, qss, self.payload)
 
 
 def _point_limits(count, linear, F, g):
@@ -752,22 +764,10 @@ def _point_limits(count, linear, F, g):
             Fm[6 * p:6 * p + 3, 3 * p:3 * p + 3], Fm[6 * p + 3:6 * p + 6, 3 * p:3 * p + 3] = np.eye(3), -np.eye(3)
         gm = np.concatenate((lim[..., 1], -lim[..., 0]), -1)  # [..., P, 6] = [upper; -lower] per point
         return Fm, np.ascontiguousarray(gm.reshape(gm.shape[:-2] + (2 * width,))), (int(lim.shape[0]) if lim.ndim == 4 else None)
-    if F is None or g is None:
-        raise ValueError("F and g are given together")
-    fshape, gshape = _shape_of(F), _shape_of(g)
-    if len(fshape) not in (2, 3, 4) or fshape[-1] != width:
-        raise ValueError("F must have shape [m, 3 P], [B, m, 3 P] or [B, N+1, m, 3 P] with 3 P = %d, got %s" % (width, list(fshape)))
-    if len(gshape) not in (1, 2, 3):
-        raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (list(gshape),))
-    if gshape[-1] != fshape[-2]:
-        raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], fshape[-2]))
-    for name, arr in (("F", F), ("g", g)):
-        if not np.all(np.isfinite(_host(arr))):
-            raise ValueError("%s holds a value that is not finite" % name)
-    return F, g, None
+    return _row_limits(F, g, width, "[m, 3 P], [B, m, 3 P] or [B, N+1, m, 3 P] with 3 P = %d" % width)
 
 
-class BatchPointAccelerationConstraint(_BatchSecondOrder):
+class BatchPointAccelerationConstraint(_BatchChainRows):
     """A limit on the accelerations of control points on ANY links of a chain, for a batch -- an elbow, a camera bracket, a
     cable carrier:  F acc <= g  on  acc(q, qd, qdd) = the linear accelerations of ``points`` in world axes, [3 P], point-major
     (:meth:`toppra_amd.chain.SerialChain.point_accelerations`; kinematics, no gravity).  It is
@@ -789,41 +789,18 @@ class BatchPointAccelerationConstraint(_BatchSecondOrder):
     branched chains are out of scope."""
 
     def __init__(self, chain, points, linear=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
-        super(BatchPointAccelerationConstraint, self).__init__()
-        if not isinstance(chain, SerialChain):
-            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
-        if not isinstance(points, ControlPoints):
-            raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
-        points.on(chain)  # (a link outside the chain: ValueError)
-        self.chain, self.points = chain, points
-        self.dof = chain.dof
-        self.F, self.g, self._limit_batch = _point_limits(points.count, linear, F, g)
+        _need_chain(chain)
+        _need_points(points, chain)
+        super(BatchPointAccelerationConstraint, self).__init__(
+            chain, _point_limits(points.count, linear, F, g), discretization_scheme,
+            "control-point acceleration limit, %d dof, %d points" % (chain.dof, points.count))
+        self.points = points
         self.linear = linear
-        self.set_discretization_type(discretization_scheme)
-        self.identical = True
-        self._format_string = "    Batched control-point acceleration limit, %d dof, %d points, %d rows\n" % (
-            self.dof, points.count, _shape_of(self.F)[-2])
 
-    def rows_per_stage(self, d):
-        return (2 if self._interp() else 1) * int(_shape_of(self.F)[-2])
-
-    def check(self, B, N, d):
-        if self.dof != d:
-            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
-        if self._limit_batch is not None and self._limit_batch != B:
-            raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
-            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
-                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
-                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
-
-    def block(self, q, qs, qss):
-        B, n1, d = (int(v) for v in q.shape)
-        self.check(B, n1 - 1, d)
+    def _terms(self, q, qs, qss):
         wa, wb = self.chain.point_acceleration_terms(q, qs, qss, self.points)
-        wa, wb = wa.reshape(B, n1, 3 * self.points.count), wb.reshape(B, n1, 3 * self.points.count)
-        return {"w0": _zeros_like(wa), "wa": wa, "wb": wb, "F": _like(self.F, q), "g": _like(self.g, q), "friction": None,
-                "interpolation": self._interp()}
+        flat = tuple(q.shape[:2]) + (3 * self.points.count,)
+        return None, wa.reshape(flat), wb.reshape(flat)
 
 
 # ---- batched first-order constraints: they only tighten a stage's variable box (BatchTOPPRA(..., constraints=[...])) -------
@@ -929,7 +906,30 @@ class BatchBoundConstraint(_BatchFirstOrder):
         return [(kind, _like(arr, like)) for kind, arr in (("ubound", self.ubound), ("xbound", self.xbound)) if arr is not None]
 
 
-class BatchCartesianVelocityNormConstraint(_BatchFirstOrder):
+class _BatchChainBound(_BatchFirstOrder):
+    """Shared part of the first-order constraints that a chain kernel evaluates at the path positions: one ``xbound`` source
+    from ``chain``, ``limit`` and the ``_limit_batch`` of a limit given per trajectory."""
+    needs_q = True
+    no_q = None  # the refusal of a batch without path positions
+
+    def source_count(self):
+        return 1
+
+    def check(self, B, N, d):
+        if self.dof != d:
+            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
+        if self._limit_batch is not None and self._limit_batch != B:
+            raise ValueError("limit is given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
+
+    def _limit_like(self, B, N, d, like, q):
+        """The checks of a ``bound_sources`` call; the limit as an array of the kind of ``like``."""
+        self.check(B, N, d)
+        if q is None:
+            raise ValueError(self.no_q)
+        return self.limit if hasattr(self.limit, "is_cuda") and self.limit.is_cuda else _like(self.limit, like)
+
+
+class BatchCartesianVelocityNormConstraint(_BatchChainBound):
     """A limit on the tool point's velocity for a batch (the C++ twin's ``CartesianVelocityNorm``,
     constraint/cartesian_velocity_norm.hpp):  v' S v * x <= limit  at every gridpoint, x = sd^2, where [v; w] are the linear
     and angular velocity of ``chain``'s tool point per unit of path velocity (qd = q'), in world axes.
@@ -939,12 +939,11 @@ class BatchCartesianVelocityNormConstraint(_BatchFirstOrder):
     of 0.25 holds the tool to 0.5 length units per second.  The bound (0, limit / v' S v) comes from the chain kernel and is one
     ``xbound`` source of the stage boxes; where the tool stands still it is +inf and the box keeps its 1e8.  Needs the path
     positions: a ``from_path_samples`` batch must be given ``q``."""
-    needs_q = True
+    no_q = "a tool velocity limit evaluates the chain at q: give the path positions"
 
     def __init__(self, chain, limit, S=None):
         super(BatchCartesianVelocityNormConstraint, self).__init__()
-        if not isinstance(chain, SerialChain):
-            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+        _need_chain(chain)
         self.chain, self.limit, self.S = chain, limit, S
         self.dof = chain.dof
         lshape = _shape_of(limit)
@@ -960,25 +959,13 @@ class BatchCartesianVelocityNormConstraint(_BatchFirstOrder):
             _capi.check_weight(S)
         self._format_string = "    Batched tool velocity limit, %d dof\n" % self.dof
 
-    def source_count(self):
-        return 1
-
-    def check(self, B, N, d):
-        if self.dof != d:
-            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
-        if self._limit_batch is not None and self._limit_batch != B:
-            raise ValueError("limit is given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-
     def bound_sources(self, gridpoints, B, N, d, like, q=None):
-        self.check(B, N, d)
-        if q is None:
-            raise ValueError("a tool velocity limit evaluates the chain at q: give the path positions")
-        limit = self.limit if hasattr(self.limit, "is_cuda") and self.limit.is_cuda else _like(self.limit, like)
+        limit = self._limit_like(B, N, d, like, q)
         S = None if self.S is None else _like(self.S, like)
         return [("xbound", _batch.chain_tool_bound_batch(self.chain, q, like, limit, S)[1])]
 
 
-class BatchPointSpeedConstraint(_BatchFirstOrder):
+class BatchPointSpeedConstraint(_BatchChainBound):
     """A limit on the speeds of control points on ANY links of a chain, for a batch:  |v_p|^2 * x <= limit_p  at every
     gridpoint and for every point p of ``points``, x = sd^2, where v_p is the point's velocity per unit of path velocity
     (qd = q').  It is :class:`BatchCartesianVelocityNormConstraint` (with its default ``S``) for points that need not sit on
@@ -990,15 +977,12 @@ class BatchPointSpeedConstraint(_BatchFirstOrder):
     of the chain kernel and is ONE ``xbound`` source of the stage boxes however many points the set has; a point that stands
     still drops out of the minimum, and where all of them do the box keeps its 1e8.  Needs the path positions: a
     ``from_path_samples`` batch must be given ``q``.  Angular and S-weighted limits stay with the tool constraint."""
-    needs_q = True
+    no_q = "a control-point speed limit evaluates the chain at q: give the path positions"
 
     def __init__(self, chain, points, limit):
         super(BatchPointSpeedConstraint, self).__init__()
-        if not isinstance(chain, SerialChain):
-            raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
-        if not isinstance(points, ControlPoints):
-            raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
-        points.on(chain)  # (a link outside the chain: ValueError)
+        _need_chain(chain)
+        _need_points(points, chain)
         self.chain, self.points, self.limit = chain, points, limit
         self.dof = chain.dof
         lshape = _shape_of(limit)
@@ -1009,20 +993,8 @@ class BatchPointSpeedConstraint(_BatchFirstOrder):
             raise ValueError("limit must be > 0 (NaN is refused; 0 / 0 at a standstill would be a NaN bound)")
         self._format_string = "    Batched control-point speed limit, %d dof, %d points\n" % (self.dof, points.count)
 
-    def source_count(self):
-        return 1
-
-    def check(self, B, N, d):
-        if self.dof != d:
-            raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
-        if self._limit_batch is not None and self._limit_batch != B:
-            raise ValueError("limit is given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-
     def bound_sources(self, gridpoints, B, N, d, like, q=None):
-        self.check(B, N, d)
-        if q is None:
-            raise ValueError("a control-point speed limit evaluates the chain at q: give the path positions")
-        limit = self.limit if hasattr(self.limit, "is_cuda") and self.limit.is_cuda else _like(self.limit, like)
+        limit = self._limit_like(B, N, d, like, q)
         return [("xbound", _batch.chain_points_speed_batch(self.chain, q, like, self.points, limit)[1])]
 
 

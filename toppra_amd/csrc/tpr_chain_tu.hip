@@ -2,30 +2,14 @@
 // evaluations of a torque constraint in one pass, the tool point's velocity and acceleration, the wrench on a carried body,
 // speed and acceleration of control points on any link.  build.py compiles it in parallel with the other units.  Nine entry
 // points, declared in tpr_kernels.hip; each returns 0 = launched, -1 = no kernel for this dof (or this point set).
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-
-#include "../../include/toppra_hip.h"
+#include "tpr_chain_launch.hpp"
 #include "tpr_chain.hip.inc"
 
-namespace {
-inline unsigned chain_blocks(int npoints) { return (unsigned)(((long long)npoints + tpr::kChainBlock - 1) / tpr::kChainBlock); }
+using tpr::chain_allow_lds;
+using tpr::chain_blocks;
+using tpr::chain_launch;
 
-// The runtime-dof kernels take up to the whole LDS of a CU; above 64 KB a kernel has to be told so, once per device: `done`
-// is the kernel's bit mask of the devices that have been told (the attribute is raised to the full 160 KB, so one call serves
-// every dof).
-template <class Kernel>
-int chain_allow_lds(Kernel kernel, size_t lds, std::atomic<unsigned long long> &done) {
-    if (lds > (size_t)tpr::kChainLdsBytes) return -1;
-    if (lds <= 64 * 1024) return 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (done.load(std::memory_order_relaxed) >> dev & 1ull) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tpr::kChainLdsBytes) != hipSuccess) return -1;
-    done.fetch_or(1ull << dev, std::memory_order_relaxed);
-    return 0;
-}
+namespace {
 std::atomic<unsigned long long> g_dyn_lds{0}, g_terms_fused_lds{0}, g_terms_serial_lds{0};
 }  // namespace
 
@@ -37,7 +21,7 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launc
         TPR_CHAIN_CASE(5); TPR_CHAIN_CASE(6); TPR_CHAIN_CASE(7); TPR_CHAIN_CASE(8);
 #undef TPR_CHAIN_CASE
     }
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    if (!tpr::chain_dof_ok(A->M.d)) return -1;
     const size_t lds = (size_t)A->M.d * tpr::kChainSlotsSingle * tpr::kChainBlock * sizeof(double);
     if (chain_allow_lds(tpr::chain_inverse_dynamics_lds_kernel, lds, g_dyn_lds) != 0) return -1;
     hipLaunchKernelGGL(tpr::chain_inverse_dynamics_lds_kernel, grid, block, lds, stream, *A);
@@ -52,7 +36,7 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(c
         TPR_CHAIN_CASE(5); TPR_CHAIN_CASE(6); TPR_CHAIN_CASE(7); TPR_CHAIN_CASE(8);
 #undef TPR_CHAIN_CASE
     }
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
+    if (!tpr::chain_dof_ok(A->M.d)) return -1;
     const size_t per_slot = (size_t)A->M.d * tpr::kChainBlock * sizeof(double);
     if (per_slot * tpr::kChainSlotsFused <= (size_t)tpr::kChainLdsBytes) {
         const size_t lds = per_slot * tpr::kChainSlotsFused;
@@ -67,37 +51,27 @@ extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(c
 }
 
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_tool_launch(const tpr::ChainToolArgs *A, hipStream_t stream) {
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
-    hipLaunchKernelGGL(tpr::chain_tool_velocity_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), 0, stream, *A);
-    return 0;
+    return chain_launch(tpr::chain_tool_velocity_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), 0, stream, *A);
 }
 
 // (the tool-acceleration kernels' staging area is at most 3 * 64 * 33 doubles = 50 688 bytes at 32 dof: under the 64 KB any kernel may take)
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_launch(const tpr::ChainAccelArgs *A, hipStream_t stream) {
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
-    hipLaunchKernelGGL(tpr::chain_tool_accel_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
-    return 0;
+    return chain_launch(tpr::chain_tool_accel_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_accel_terms_launch(const tpr::ChainAccelTermsArgs *A, hipStream_t stream) {
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
-    hipLaunchKernelGGL(tpr::chain_tool_accel_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 2), stream, *A);
-    return 0;
+    return chain_launch(tpr::chain_tool_accel_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 2), stream, *A);
 }
 
 // (the wrench kernels stage the same three inputs; their three 6-wide outputs take 10 752 bytes: the same 50 688 at 32 dof)
 static_assert(tpr::chain_accel_lds_bytes(TPR_MAX_DOF, 3) <= 64 * 1024, "the wrench kernels' staging area fits an unattributed launch");
 
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(const tpr::ChainWrenchArgs *A, hipStream_t stream) {
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
-    hipLaunchKernelGGL(tpr::chain_tool_wrench_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
-    return 0;
+    return chain_launch(tpr::chain_tool_wrench_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 1), stream, *A);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *A, hipStream_t stream) {
-    if (A->M.d < 1 || A->M.d > TPR_MAX_DOF) return -1;
-    hipLaunchKernelGGL(tpr::chain_tool_wrench_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 3), stream, *A);
-    return 0;
+    return chain_launch(tpr::chain_tool_wrench_terms_kernel, dim3(chain_blocks(A->npoints)), dim3(tpr::kChainBlock), tpr::chain_accel_lds_bytes(A->M.d, 3), stream, *A);
 }
 
 // ---- control points: the launchers find the deepest link that carries a point (the kernels' loops end there); the set is
@@ -106,7 +80,7 @@ static_assert(TPR_CHAIN_MAX_POINTS == tpr::kChainMaxPoints && sizeof(tpr_chain_p
 static_assert(tpr::chain_points_lds_bytes(TPR_CHAIN_MAX_POINTS, 2) <= 64 * 1024, "the control-point kernels' LDS fits an unattributed launch");
 namespace {
 int chain_points_links(const tpr::ChainPoints &P, int d) {
-    if (d < 1 || d > TPR_MAX_DOF || P.count < 1 || P.count > tpr::kChainMaxPoints) return -1;
+    if (!tpr::chain_dof_ok(d) || P.count < 1 || P.count > tpr::kChainMaxPoints) return -1;
     int deepest = 0;
     for (int p = 0; p < P.count; ++p) {
         if (P.link[p] < 0 || P.link[p] >= d) return -1;
@@ -119,17 +93,12 @@ int chain_points_links(const tpr::ChainPoints &P, int d) {
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_points_speed_launch(const tpr::ChainPointsSpeedArgs *A, hipStream_t stream) {
     tpr::ChainPointsSpeedArgs K = *A;
     if ((K.nlinks = chain_points_links(K.P, K.M.d)) < 0) return -1;
-    hipLaunchKernelGGL(tpr::chain_points_speed_kernel, dim3(chain_blocks(K.npoints)), dim3(tpr::kChainBlock), 0, stream, K);
-    return 0;
+    return chain_launch(tpr::chain_points_speed_kernel, dim3(chain_blocks(K.npoints)), dim3(tpr::kChainBlock), 0, stream, K);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const tpr::ChainPointsAccelArgs *A, int terms, hipStream_t stream) {
     tpr::ChainPointsAccelArgs K = *A;
     if ((K.nlinks = chain_points_links(K.P, K.M.d)) < 0) return -1;
-    const int outputs = terms ? 2 : 1;
-    const size_t lds = tpr::chain_points_lds_bytes(K.P.count, outputs);
-    const dim3 grid(chain_blocks(K.npoints)), block(tpr::kChainBlock);
-    if (terms) hipLaunchKernelGGL(tpr::chain_points_accel_terms_kernel, grid, block, lds, stream, K);
-    else hipLaunchKernelGGL(tpr::chain_points_accel_kernel, grid, block, lds, stream, K);
-    return 0;
+    return chain_launch(terms ? tpr::chain_points_accel_terms_kernel : tpr::chain_points_accel_kernel, dim3(chain_blocks(K.npoints)),
+                        dim3(tpr::kChainBlock), tpr::chain_points_lds_bytes(K.P.count, terms ? 2 : 1), stream, K);
 }

@@ -1644,8 +1644,10 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
 }
 }  // extern "C"
 
-// ---- a rigid-body chain evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip) ------------------------------------------
-#include "tpr_chain_args.hpp"
+// ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip) --
+// One host path for the family: an entry is its argument checks, in an order that is its own and is behaviour (which refusal
+// wins when two arguments are bad: tests/test_rigid_refusal_order.py), then run_rigid() with what it stages and what it launches.
+#include "tpr_tree_args.hpp"
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
@@ -1656,8 +1658,29 @@ __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_launch(const tpr::
 __attribute__((visibility("hidden"))) int tpr_tu_chain_wrench_terms_launch(const tpr::ChainWrenchTermsArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_points_speed_launch(const tpr::ChainPointsSpeedArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const tpr::ChainPointsAccelArgs *, int terms, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_tree_dynamics_launch(const tpr::TreeDynArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_tree_terms_launch(const tpr::TreeTermsArgs *, int forks, hipStream_t);
 }
 namespace {
+// The gridpoints of a batch given as (B, N).
+int batch_points(int B, int N, const char *who, long long &npoints) {
+    if (B < 0 || N < 0) return fail(TPR_E_BADARG, std::string(who) + ": B >= 0, N >= 0");
+    npoints = (long long)B * ((long long)N + 1);
+    return TPR_E_OK;
+}
+int required(bool all_given, const char *who, const char *names) {
+    return all_given ? TPR_E_OK : fail(TPR_E_BADARG, std::string(who) + ": " + names + " are required");
+}
+// joint_type and parent are read here, on the host: a device pointer in their place is refused, not dereferenced
+int refuse_device_pointer(const void *ptr, const char *who, const char *what) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return TPR_E_OK;
+    }
+    if (attr.type != hipMemoryTypeDevice) return TPR_E_OK;
+    return fail(TPR_E_BADARG, std::string(who) + ": " + what + " must be a host array, also with TPR_DEVICE_PTRS");
+}
 // What every chain entry refuses before any launch: the model's shape, its joint types (a host array), the point count.
 // (a tree's links are a tpr_chain whose tool is not read: need_tool = false)
 int check_chain(const tpr_chain *c, long long npoints, const char *who, bool need_tool = true) {
@@ -1666,14 +1689,7 @@ int check_chain(const tpr_chain *c, long long npoints, const char *who, bool nee
     if (c->d < 1 || c->d > TPR_MAX_DOF) return fail(TPR_E_BADARG, std::string(who) + ": the chain's dof must be in [1, TPR_MAX_DOF]");
     if (!c->joint_type || !c->axis || !c->rot || !c->trans || !c->mass || !c->com || !c->inertia || !c->gravity || (need_tool && !c->tool))
         return fail(TPR_E_BADARG, std::string(who) + ": every array of the chain is required");
-    {  // joint_type is read here, on the host: a device pointer in its place is refused, not dereferenced
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, c->joint_type) == hipSuccess) {
-            if (attr.type == hipMemoryTypeDevice) return fail(TPR_E_BADARG, std::string(who) + ": joint_type must be a host array, also with TPR_DEVICE_PTRS");
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    if (int rc = refuse_device_pointer(c->joint_type, who, "joint_type")) return rc;
     for (int i = 0; i < c->d; ++i)
         if (c->joint_type[i] != TPR_JOINT_REVOLUTE && c->joint_type[i] != TPR_JOINT_PRISMATIC)
             return fail(TPR_E_BADARG, std::string(who) + ": unknown joint type");
@@ -1681,14 +1697,16 @@ int check_chain(const tpr_chain *c, long long npoints, const char *who, bool nee
     if (npoints > 0x7fffffffLL) return fail(TPR_E_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 points");
     return TPR_E_OK;
 }
-tpr::ChainModel stage_chain(const tpr_chain *c, Staging &S) {
+// (a tree's kernels do not read the tool: it stays null)
+tpr::ChainModel stage_links(const tpr_chain *c, Staging &S, bool with_tool) {
     tpr::ChainModel M{};
     const size_t d = (size_t)c->d;
     M.d = c->d;
     for (int i = 0; i < c->d; ++i) M.prismatic |= (uint32_t)(c->joint_type[i] == TPR_JOINT_PRISMATIC) << i;
     M.axis = S.in(c->axis, 3 * d); M.rot = S.in(c->rot, 9 * d); M.trans = S.in(c->trans, 3 * d);
     M.mass = S.in(c->mass, d); M.com = S.in(c->com, 3 * d); M.inertia = S.in(c->inertia, 6 * d);
-    M.gravity = S.in(c->gravity, 3); M.tool = S.in(c->tool, 3);
+    M.gravity = S.in(c->gravity, 3);
+    if (with_tool) M.tool = S.in(c->tool, 3);
     return M;
 }
 // A payload is a host struct of 22 doubles: read here, handed to the kernels by value.
@@ -1729,247 +1747,13 @@ tpr::ChainPoints stage_points(const tpr_chain_points *p) {
     }
     return P;
 }
-}  // namespace
-
-extern "C" {
-int tpr_chain_bytes(void) { return (int)sizeof(tpr_chain); }
-
-int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
-                                     double *tau, int flags, void *stream_) {
-    if (int rc = check_chain(chain, npoints, "tpr_chain_inverse_dynamics_batch")) return rc;
-    if (!q || !qd || !qdd || !tau) return fail(TPR_E_BADARG, "tpr_chain_inverse_dynamics_batch: q, qd, qdd, tau are required");
-    Staging S(flags & TPR_DEVICE_PTRS, tau, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainDynArgs A{};
-    A.M = stage_chain(chain, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
-    A.tau = S.out(tau, n);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_dynamics_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_inverse_dynamics_batch: the kernel's LDS could not be reserved");
-    return S.finish();
-}
-
-int tpr_chain_torque_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
-                                 double *w0, double *wa, double *wb, int flags, void *stream_) {
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_torque_terms_batch: B >= 0, N >= 0");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_torque_terms_batch")) return rc;
-    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_torque_terms_batch: q, qs, qss, w0, wa, wb are required");
-    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainTermsArgs A{};
-    A.M = stage_chain(chain, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
-    A.w0 = S.out(w0, n); A.wa = S.out(wa, n); A.wb = S.out(wb, n);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_terms_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_torque_terms_batch: the kernel's LDS could not be reserved");
-    return S.finish();
-}
-
-int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *Sm,
-                                  const double *limit, double *vSv, double *xbound, int flags, void *stream_) {
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: B >= 0, N >= 0");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_velocity_batch")) return rc;
-    if (!q || !qs) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: q, qs are required");
-    if (!vSv && !xbound) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: one of vSv, xbound is required");
-    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: xbound needs limit");
-    Staging S(flags & TPR_DEVICE_PTRS, vSv ? vSv : xbound, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainToolArgs A{};
-    A.M = stage_chain(chain, S);
-    A.npoints = (int)npoints; A.n1 = N + 1;
-    A.q = S.in(q, n); A.qs = S.in(qs, n);
-    A.S = S.in(Sm, 36);
-    A.limit = xbound ? S.in(limit, (size_t)B) : nullptr;
-    A.vSv = S.out(vSv, (size_t)npoints); A.xbound = S.out(xbound, 2 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_tool_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_velocity_batch: no kernel for this dof");
-    return S.finish();
-}
-
-int tpr_chain_tool_acceleration_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
-                                      double *acc, int flags, void *stream_) {
-    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_acceleration_batch")) return rc;
-    if (!q || !qd || !qdd || !acc) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_batch: q, qd, qdd, acc are required");
-    Staging S(flags & TPR_DEVICE_PTRS, acc, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainAccelArgs A{};
-    A.M = stage_chain(chain, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
-    A.acc = S.out(acc, 6 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_accel_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_acceleration_batch: no kernel for this dof");
-    return S.finish();
-}
-
-int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
-                                            double *wa, double *wb, int flags, void *stream_) {
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_terms_batch: B >= 0, N >= 0");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_acceleration_terms_batch")) return rc;
-    if (!q || !qs || !qss || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_tool_acceleration_terms_batch: q, qs, qss, wa, wb are required");
-    Staging S(flags & TPR_DEVICE_PTRS, wa, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainAccelTermsArgs A{};
-    A.M = stage_chain(chain, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
-    A.wa = S.out(wa, 6 * (size_t)npoints); A.wb = S.out(wb, 6 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_accel_terms_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_acceleration_terms_batch: no kernel for this dof");
-    return S.finish();
-}
-
-int tpr_payload_bytes(void) { return (int)sizeof(tpr_payload); }
-
-int tpr_chain_tool_wrench_batch(const tpr_chain *chain, const tpr_payload *payload, long long npoints, const double *q, const double *qd,
-                                const double *qdd, double *wrench, int flags, void *stream_) {
-    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_wrench_batch")) return rc;
-    if (int rc = check_payload(payload, "tpr_chain_tool_wrench_batch")) return rc;
-    if (!q || !qd || !qdd || !wrench) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_batch: q, qd, qdd, wrench are required");
-    Staging S(flags & TPR_DEVICE_PTRS, wrench, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainWrenchArgs A{};
-    A.M = stage_chain(chain, S);
-    A.P = stage_payload(payload);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
-    A.wrench = S.out(wrench, 6 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_wrench_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_wrench_batch: no kernel for this dof");
-    return S.finish();
-}
-
-int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload *payload, int B, int N, const double *q, const double *qs,
-                                      const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_terms_batch: B >= 0, N >= 0");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_tool_wrench_terms_batch")) return rc;
-    if (int rc = check_payload(payload, "tpr_chain_tool_wrench_terms_batch")) return rc;
-    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_tool_wrench_terms_batch: q, qs, qss, w0, wa, wb are required");
-    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d;
-    tpr::ChainWrenchTermsArgs A{};
-    A.M = stage_chain(chain, S);
-    A.P = stage_payload(payload);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
-    A.w0 = S.out(w0, 6 * (size_t)npoints); A.wa = S.out(wa, 6 * (size_t)npoints); A.wb = S.out(wb, 6 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_wrench_terms_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_tool_wrench_terms_batch: no kernel for this dof");
-    return S.finish();
-}
-
-int tpr_chain_points_bytes(void) { return (int)sizeof(tpr_chain_points); }
-
-int tpr_chain_points_speed_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q, const double *qs,
-                                 const double *limit, double *speed2, double *xbound, int flags, void *stream_) {
-    if (int rc = check_points(chain, points, "tpr_chain_points_speed_batch")) return rc;
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: B >= 0, N >= 0");
-    if (!q || !qs) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: q, qs are required");
-    if (!speed2 && !xbound) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: one of speed2, xbound is required");
-    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: xbound needs limit");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_points_speed_batch")) return rc;
-    Staging S(flags & TPR_DEVICE_PTRS, speed2 ? speed2 : xbound, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d, count = (size_t)points->count;
-    tpr::ChainPointsSpeedArgs A{};
-    A.M = stage_chain(chain, S);
-    A.P = stage_points(points);
-    A.npoints = (int)npoints; A.n1 = N + 1;
-    A.q = S.in(q, n); A.qs = S.in(qs, n);
-    A.limit = xbound ? S.in(limit, (size_t)B * count) : nullptr;
-    A.speed2 = S.out(speed2, (size_t)npoints * count); A.xbound = S.out(xbound, 2 * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_points_speed_launch(&A, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_speed_batch: no kernel for this dof and point set");
-    return S.finish();
-}
-
-int tpr_chain_points_acceleration_batch(const tpr_chain *chain, const tpr_chain_points *points, long long npoints, const double *q,
-                                        const double *qd, const double *qdd, double *acc, int flags, void *stream_) {
-    if (int rc = check_points(chain, points, "tpr_chain_points_acceleration_batch")) return rc;
-    if (!q || !qd || !qdd || !acc) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_batch: q, qd, qdd, acc are required");
-    if (int rc = check_chain(chain, npoints, "tpr_chain_points_acceleration_batch")) return rc;
-    Staging S(flags & TPR_DEVICE_PTRS, acc, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d, width = 3 * (size_t)points->count;
-    tpr::ChainPointsAccelArgs A{};
-    A.M = stage_chain(chain, S);
-    A.P = stage_points(points);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.v1 = S.in(qd, n); A.v2 = S.in(qdd, n);
-    A.acc = S.out(acc, width * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_points_accel_launch(&A, 0, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_acceleration_batch: no kernel for this dof and point set");
-    return S.finish();
-}
-
-int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q,
-                                              const double *qs, const double *qss, double *wa, double *wb, int flags, void *stream_) {
-    if (int rc = check_points(chain, points, "tpr_chain_points_acceleration_terms_batch")) return rc;
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_terms_batch: B >= 0, N >= 0");
-    if (!q || !qs || !qss || !wa || !wb) return fail(TPR_E_BADARG, "tpr_chain_points_acceleration_terms_batch: q, qs, qss, wa, wb are required");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_chain(chain, npoints, "tpr_chain_points_acceleration_terms_batch")) return rc;
-    Staging S(flags & TPR_DEVICE_PTRS, wa, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)chain->d, width = 3 * (size_t)points->count;
-    tpr::ChainPointsAccelArgs A{};
-    A.M = stage_chain(chain, S);
-    A.P = stage_points(points);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.v1 = S.in(qs, n); A.v2 = S.in(qss, n);
-    A.wa = S.out(wa, width * (size_t)npoints); A.acc = S.out(wb, width * (size_t)npoints);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_chain_points_accel_launch(&A, 1, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_chain_points_acceleration_terms_batch: no kernel for this dof and point set");
-    return S.finish();
-}
-}  // extern "C"
-
-// ---- a kinematic tree evaluated on the GPU (tpr_tree.hip.inc, tpr_tree_tu.hip) ---------------------------------------------------
-#include "tpr_tree_args.hpp"
-extern "C" {
-__attribute__((visibility("hidden"))) int tpr_tu_tree_dynamics_launch(const tpr::TreeDynArgs *, const int32_t *parent, hipStream_t);
-__attribute__((visibility("hidden"))) int tpr_tu_tree_terms_launch(const tpr::TreeTermsArgs *, const int32_t *parent, hipStream_t);
-}
-namespace {
 // What the tree entries refuse before any launch: what the chain entries refuse (the tool apart), and the parent table -- a host
-// array like joint_type, read here.
-int check_tree(const tpr_chain *links, const int32_t *parent, long long npoints, const char *who) {
+// array like joint_type, read here, once per call: T takes the kernels' tables, forks their fork count.
+int check_tree(const tpr_chain *links, const int32_t *parent, long long npoints, const char *who, tpr::TreeTables &T, int &forks) {
     if (int rc = check_chain(links, npoints, who, false)) return rc;
     if (!parent) return fail(TPR_E_BADARG, std::string(who) + ": null parent array");
-    {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, parent) == hipSuccess) {
-            if (attr.type == hipMemoryTypeDevice) return fail(TPR_E_BADARG, std::string(who) + ": parent must be a host array, also with TPR_DEVICE_PTRS");
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    tpr::TreeTables T;
-    const int forks = tpr::tree_tables(parent, links->d, T);
+    if (int rc = refuse_device_pointer(parent, who, "parent")) return rc;
+    forks = tpr::tree_tables(parent, links->d, T);
     if (forks < 0) {
         const int i = -1 - forks;
         return fail(TPR_E_BADARG, std::string(who) + ": the parent of link " + std::to_string(i) + " is " + std::to_string(parent[i]) +
@@ -1980,54 +1764,239 @@ int check_tree(const tpr_chain *links, const int32_t *parent, long long npoints,
                                            std::to_string(TPR_TREE_MAX_FORKS));
     return TPR_E_OK;
 }
-tpr::ChainModel stage_tree_links(const tpr_chain *c, Staging &S) {
-    tpr::ChainModel M{};
-    const size_t d = (size_t)c->d;
-    M.d = c->d;
-    for (int i = 0; i < c->d; ++i) M.prismatic |= (uint32_t)(c->joint_type[i] == TPR_JOINT_PRISMATIC) << i;
-    M.axis = S.in(c->axis, 3 * d); M.rot = S.in(c->rot, 9 * d); M.trans = S.in(c->trans, 3 * d);
-    M.mass = S.in(c->mass, d); M.com = S.in(c->com, 3 * d); M.inertia = S.in(c->inertia, 6 * d);
-    M.gravity = S.in(c->gravity, 3);
-    return M;  // (tool stays null: the tree kernels do not read it)
+
+// The argument block of a launch on the links `c`: the model staged, the point count set, the rest zero.
+template <class Args>
+Args rigid_args(const tpr_chain *c, long long npoints, Staging &S, bool with_tool = true) {
+    Args A{};
+    A.M = stage_links(c, S, with_tool);
+    A.npoints = (int)npoints;
+    return A;
+}
+// Arrays of `count` doubles each into fields of any argument block.
+struct StagedIn { const double **field; const double *from; };
+struct StagedOut { double **field; double *to; };
+void stage_inputs(Staging &S, size_t count, std::initializer_list<StagedIn> arrays) {
+    for (const StagedIn &a : arrays) *a.field = S.in(a.from, count);
+}
+void stage_outputs(Staging &S, size_t count, std::initializer_list<StagedOut> arrays) {
+    for (const StagedOut &a : arrays) *a.field = S.out(a.to, count);
+}
+// A checked call from here to its return: `fill(S)` stages the arrays and returns the argument block, `launch(&block, stream)`
+// is the unit's launcher (not called for an empty batch); `device_ptr` tells the device under TPR_DEVICE_PTRS.
+template <class Fill, class Launch>
+int run_rigid(int flags, const void *device_ptr, void *stream_, long long npoints, const char *no_kernel, Fill fill, Launch launch) {
+    Staging S(flags & TPR_DEVICE_PTRS, device_ptr, stream_);
+    if (int rc = S.failed()) return rc;
+    const auto A = fill(S);
+    if (int rc = S.failed()) return rc;
+    if (npoints > 0 && launch(&A, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, no_kernel);
+    return S.finish();
 }
 }  // namespace
 
 extern "C" {
+int tpr_chain_bytes(void) { return (int)sizeof(tpr_chain); }
+int tpr_payload_bytes(void) { return (int)sizeof(tpr_payload); }
+int tpr_chain_points_bytes(void) { return (int)sizeof(tpr_chain_points); }
+
+int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
+                                     double *tau, int flags, void *stream_) {
+    const char *who = "tpr_chain_inverse_dynamics_batch";
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = required(q && qd && qdd && tau, who, "q, qd, qdd, tau")) return rc;
+    return run_rigid(flags, tau, stream_, npoints, "tpr_chain_inverse_dynamics_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainDynArgs>(chain, npoints, S);
+        const size_t n = (size_t)npoints * (size_t)chain->d;
+        stage_inputs(S, n, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, n, {{&A.tau, tau}});
+        return A;
+    }, tpr_tu_chain_dynamics_launch);
+}
+
+int tpr_chain_torque_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
+                                 double *w0, double *wa, double *wb, int flags, void *stream_) {
+    const char *who = "tpr_chain_torque_terms_batch";
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = required(q && qs && qss && w0 && wa && wb, who, "q, qs, qss, w0, wa, wb")) return rc;
+    return run_rigid(flags, w0, stream_, npoints, "tpr_chain_torque_terms_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainTermsArgs>(chain, npoints, S);
+        const size_t n = (size_t)npoints * (size_t)chain->d;
+        stage_inputs(S, n, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, n, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, tpr_tu_chain_terms_launch);
+}
+
+int tpr_chain_tool_velocity_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *Sm,
+                                  const double *limit, double *vSv, double *xbound, int flags, void *stream_) {
+    const char *who = "tpr_chain_tool_velocity_batch";
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = required(q && qs, who, "q, qs")) return rc;
+    if (!vSv && !xbound) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: one of vSv, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_tool_velocity_batch: xbound needs limit");
+    return run_rigid(flags, vSv ? vSv : xbound, stream_, npoints, "tpr_chain_tool_velocity_batch: no kernel for this dof", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainToolArgs>(chain, npoints, S);
+        A.n1 = N + 1;
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qs, qs}});
+        A.S = S.in(Sm, 36);
+        A.limit = xbound ? S.in(limit, (size_t)B) : nullptr;
+        A.vSv = S.out(vSv, (size_t)npoints); A.xbound = S.out(xbound, 2 * (size_t)npoints);
+        return A;
+    }, tpr_tu_chain_tool_launch);
+}
+
+int tpr_chain_tool_acceleration_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
+                                      double *acc, int flags, void *stream_) {
+    const char *who = "tpr_chain_tool_acceleration_batch";
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = required(q && qd && qdd && acc, who, "q, qd, qdd, acc")) return rc;
+    return run_rigid(flags, acc, stream_, npoints, "tpr_chain_tool_acceleration_batch: no kernel for this dof", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainAccelArgs>(chain, npoints, S);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.acc, acc}});
+        return A;
+    }, tpr_tu_chain_accel_launch);
+}
+
+int tpr_chain_tool_acceleration_terms_batch(const tpr_chain *chain, int B, int N, const double *q, const double *qs, const double *qss,
+                                            double *wa, double *wb, int flags, void *stream_) {
+    const char *who = "tpr_chain_tool_acceleration_terms_batch";
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = required(q && qs && qss && wa && wb, who, "q, qs, qss, wa, wb")) return rc;
+    return run_rigid(flags, wa, stream_, npoints, "tpr_chain_tool_acceleration_terms_batch: no kernel for this dof", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainAccelTermsArgs>(chain, npoints, S);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, tpr_tu_chain_accel_terms_launch);
+}
+
+int tpr_chain_tool_wrench_batch(const tpr_chain *chain, const tpr_payload *payload, long long npoints, const double *q, const double *qd,
+                                const double *qdd, double *wrench, int flags, void *stream_) {
+    const char *who = "tpr_chain_tool_wrench_batch";
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = check_payload(payload, who)) return rc;
+    if (int rc = required(q && qd && qdd && wrench, who, "q, qd, qdd, wrench")) return rc;
+    return run_rigid(flags, wrench, stream_, npoints, "tpr_chain_tool_wrench_batch: no kernel for this dof", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainWrenchArgs>(chain, npoints, S);
+        A.P = stage_payload(payload);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.wrench, wrench}});
+        return A;
+    }, tpr_tu_chain_wrench_launch);
+}
+
+int tpr_chain_tool_wrench_terms_batch(const tpr_chain *chain, const tpr_payload *payload, int B, int N, const double *q, const double *qs,
+                                      const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
+    const char *who = "tpr_chain_tool_wrench_terms_batch";
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    if (int rc = check_payload(payload, who)) return rc;
+    if (int rc = required(q && qs && qss && w0 && wa && wb, who, "q, qs, qss, w0, wa, wb")) return rc;
+    return run_rigid(flags, w0, stream_, npoints, "tpr_chain_tool_wrench_terms_batch: no kernel for this dof", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainWrenchTermsArgs>(chain, npoints, S);
+        A.P = stage_payload(payload);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, tpr_tu_chain_wrench_terms_launch);
+}
+
+int tpr_chain_points_speed_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q, const double *qs,
+                                 const double *limit, double *speed2, double *xbound, int flags, void *stream_) {
+    const char *who = "tpr_chain_points_speed_batch";
+    long long npoints = 0;
+    if (int rc = check_points(chain, points, who)) return rc;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = required(q && qs, who, "q, qs")) return rc;
+    if (!speed2 && !xbound) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: one of speed2, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_chain_points_speed_batch: xbound needs limit");
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    return run_rigid(flags, speed2 ? speed2 : xbound, stream_, npoints, "tpr_chain_points_speed_batch: no kernel for this dof and point set", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainPointsSpeedArgs>(chain, npoints, S);
+        const size_t count = (size_t)points->count;
+        A.P = stage_points(points);
+        A.n1 = N + 1;
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.qs, qs}});
+        A.limit = xbound ? S.in(limit, (size_t)B * count) : nullptr;
+        A.speed2 = S.out(speed2, (size_t)npoints * count); A.xbound = S.out(xbound, 2 * (size_t)npoints);
+        return A;
+    }, tpr_tu_chain_points_speed_launch);
+}
+
+int tpr_chain_points_acceleration_batch(const tpr_chain *chain, const tpr_chain_points *points, long long npoints, const double *q,
+                                        const double *qd, const double *qdd, double *acc, int flags, void *stream_) {
+    const char *who = "tpr_chain_points_acceleration_batch";
+    if (int rc = check_points(chain, points, who)) return rc;
+    if (int rc = required(q && qd && qdd && acc, who, "q, qd, qdd, acc")) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    return run_rigid(flags, acc, stream_, npoints, "tpr_chain_points_acceleration_batch: no kernel for this dof and point set", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainPointsAccelArgs>(chain, npoints, S);
+        A.P = stage_points(points);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.v1, qd}, {&A.v2, qdd}});
+        stage_outputs(S, 3 * (size_t)points->count * (size_t)npoints, {{&A.acc, acc}});
+        return A;
+    }, [](const tpr::ChainPointsAccelArgs *A, hipStream_t stream) { return tpr_tu_chain_points_accel_launch(A, 0, stream); });
+}
+
+int tpr_chain_points_acceleration_terms_batch(const tpr_chain *chain, const tpr_chain_points *points, int B, int N, const double *q,
+                                              const double *qs, const double *qss, double *wa, double *wb, int flags, void *stream_) {
+    const char *who = "tpr_chain_points_acceleration_terms_batch";
+    long long npoints = 0;
+    if (int rc = check_points(chain, points, who)) return rc;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = required(q && qs && qss && wa && wb, who, "q, qs, qss, wa, wb")) return rc;
+    if (int rc = check_chain(chain, npoints, who)) return rc;
+    return run_rigid(flags, wa, stream_, npoints, "tpr_chain_points_acceleration_terms_batch: no kernel for this dof and point set", [&](Staging &S) {
+        auto A = rigid_args<tpr::ChainPointsAccelArgs>(chain, npoints, S);
+        A.P = stage_points(points);
+        stage_inputs(S, (size_t)npoints * (size_t)chain->d, {{&A.q, q}, {&A.v1, qs}, {&A.v2, qss}});
+        stage_outputs(S, 3 * (size_t)points->count * (size_t)npoints, {{&A.wa, wa}, {&A.acc, wb}});
+        return A;
+    }, [](const tpr::ChainPointsAccelArgs *A, hipStream_t stream) { return tpr_tu_chain_points_accel_launch(A, 1, stream); });
+}
+
 int tpr_tree_inverse_dynamics_batch(const tpr_chain *links, const int32_t *parent, long long npoints, const double *q, const double *qd,
                                     const double *qdd, double *tau, int flags, void *stream_) {
-    if (int rc = check_tree(links, parent, npoints, "tpr_tree_inverse_dynamics_batch")) return rc;
-    if (!q || !qd || !qdd || !tau) return fail(TPR_E_BADARG, "tpr_tree_inverse_dynamics_batch: q, qd, qdd, tau are required");
-    Staging S(flags & TPR_DEVICE_PTRS, tau, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)links->d;
-    tpr::TreeDynArgs A{};
-    A.M = stage_tree_links(links, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qd = S.in(qd, n); A.qdd = S.in(qdd, n);
-    A.tau = S.out(tau, n);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_tree_dynamics_launch(&A, parent, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_tree_inverse_dynamics_batch: the kernel's LDS could not be reserved");
-    return S.finish();
+    const char *who = "tpr_tree_inverse_dynamics_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = required(q && qd && qdd && tau, who, "q, qd, qdd, tau")) return rc;
+    return run_rigid(flags, tau, stream_, npoints, "tpr_tree_inverse_dynamics_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::TreeDynArgs>(links, npoints, S, false);
+        const size_t n = (size_t)npoints * (size_t)links->d;
+        A.T = T;
+        stage_inputs(S, n, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, n, {{&A.tau, tau}});
+        return A;
+    }, [forks](const tpr::TreeDynArgs *A, hipStream_t stream) { return tpr_tu_tree_dynamics_launch(A, forks, stream); });
 }
 
 int tpr_tree_torque_terms_batch(const tpr_chain *links, const int32_t *parent, int B, int N, const double *q, const double *qs,
                                 const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
-    if (B < 0 || N < 0) return fail(TPR_E_BADARG, "tpr_tree_torque_terms_batch: B >= 0, N >= 0");
-    const long long npoints = (long long)B * ((long long)N + 1);
-    if (int rc = check_tree(links, parent, npoints, "tpr_tree_torque_terms_batch")) return rc;
-    if (!q || !qs || !qss || !w0 || !wa || !wb) return fail(TPR_E_BADARG, "tpr_tree_torque_terms_batch: q, qs, qss, w0, wa, wb are required");
-    Staging S(flags & TPR_DEVICE_PTRS, w0, stream_);
-    if (int rc = S.failed()) return rc;
-    const size_t n = (size_t)npoints * (size_t)links->d;
-    tpr::TreeTermsArgs A{};
-    A.M = stage_tree_links(links, S);
-    A.npoints = (int)npoints;
-    A.q = S.in(q, n); A.qs = S.in(qs, n); A.qss = S.in(qss, n);
-    A.w0 = S.out(w0, n); A.wa = S.out(wa, n); A.wb = S.out(wb, n);
-    if (int rc = S.failed()) return rc;
-    if (npoints > 0 && tpr_tu_tree_terms_launch(&A, parent, S.stream) != 0)
-        return fail(TPR_E_UNSUPPORTED, "tpr_tree_torque_terms_batch: the kernel's LDS could not be reserved");
-    return S.finish();
+    const char *who = "tpr_tree_torque_terms_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = required(q && qs && qss && w0 && wa && wb, who, "q, qs, qss, w0, wa, wb")) return rc;
+    return run_rigid(flags, w0, stream_, npoints, "tpr_tree_torque_terms_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::TreeTermsArgs>(links, npoints, S, false);
+        const size_t n = (size_t)npoints * (size_t)links->d;
+        A.T = T;
+        stage_inputs(S, n, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, n, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, [forks](const tpr::TreeTermsArgs *A, hipStream_t stream) { return tpr_tu_tree_terms_launch(A, forks, stream); });
 }
 }  // extern "C"

@@ -1,6 +1,6 @@
 // tpr_tree.hip.inc -- recursive Newton-Euler inverse dynamics of a kinematic TREE (a branched robot: two arms on a torso, an arm
 // beside a pan-tilt head, a forest of robots on one base) at every gridpoint of every trajectory.  The model is tpr_chain's with
-// a parent table beside it; the recursion is tpr_chain.hip.inc's -- chain_link, chain_joint, chain_forward<Level> and
+// a parent table beside it; the recursion is tpr_chain_rnea.hip.inc's -- chain_link, chain_joint, chain_forward<Level> and
 // chain_backward<Level> are used as they are -- and what is new is the walk around them.
 //
 // The walk.  Links are numbered topologically (parent[i] < i), so one loop up and one loop down visit every link after (before)
@@ -33,8 +33,7 @@
 // d * 17 * 512 + forks * 18 * 512.  Lanes past the last point of the batch evaluate the last point again and store the very same
 // values where its own lane does.
 #pragma once
-#define TPR_CHAIN_NO_KERNELS
-#include "tpr_chain.hip.inc"
+#include "tpr_chain_rnea.hip.inc"
 #include "tpr_tree_args.hpp"
 
 namespace tpr {
