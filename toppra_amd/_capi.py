@@ -206,17 +206,6 @@ def load():
         L.tpr_param_spline_batch.argtypes = [P, V, V, V, V, V]
         L.tpr_ppoly_eval_batch.restype = C.c_int
         L.tpr_ppoly_eval_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, V, V, C.c_int, V, C.c_int, V, C.c_int, V]
-        DP = C.POINTER(tpr_dense_problem)
-        L.tpr_solve_dense_batch.restype = C.c_int
-        L.tpr_solve_dense_batch.argtypes = [DP, R, V]
-        L.tpr_solve_desired_duration_dense_batch.restype = C.c_int
-        L.tpr_solve_desired_duration_dense_batch.argtypes = [DP, V, C.c_double, R, V, V]
-        L.tpr_reachable_sets_dense_batch.restype = C.c_int
-        L.tpr_reachable_sets_dense_batch.argtypes = [DP, V, V, V, V, V]
-        L.tpr_controllable_sets_dense_batch.restype = C.c_int
-        L.tpr_controllable_sets_dense_batch.argtypes = [DP, V, V, V, V]
-        L.tpr_feasible_sets_dense_batch.restype = C.c_int
-        L.tpr_feasible_sets_dense_batch.argtypes = [DP, V, V]
         L.tpr_second_order_block_bytes.restype = C.c_int
         L.tpr_second_order_block_bytes.argtypes = []
         if L.tpr_second_order_block_bytes() != C.sizeof(tpr_second_order_block):
@@ -234,16 +223,6 @@ def load():
         SP = C.POINTER(tpr_sampled_problem)
         L.tpr_sampled_rows_batch.restype = C.c_int
         L.tpr_sampled_rows_batch.argtypes = [SP, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V, V]
-        L.tpr_solve_sampled_batch.restype = C.c_int
-        L.tpr_solve_sampled_batch.argtypes = [SP, R, V]
-        L.tpr_solve_desired_duration_sampled_batch.restype = C.c_int
-        L.tpr_solve_desired_duration_sampled_batch.argtypes = [SP, V, C.c_double, R, V, V]
-        L.tpr_reachable_sets_sampled_batch.restype = C.c_int
-        L.tpr_reachable_sets_sampled_batch.argtypes = [SP, V, V, V, V, V]
-        L.tpr_controllable_sets_sampled_batch.restype = C.c_int
-        L.tpr_controllable_sets_sampled_batch.argtypes = [SP, V, V, V, V]
-        L.tpr_feasible_sets_sampled_batch.restype = C.c_int
-        L.tpr_feasible_sets_sampled_batch.argtypes = [SP, V, V]
         L.tpr_param_spline_samples_batch.restype = C.c_int
         L.tpr_param_spline_samples_batch.argtypes = [SP, V, V, V, V, V]
         L.tpr_bound_source_bytes.restype = C.c_int
@@ -253,17 +232,7 @@ def load():
                                  "binding declares %d" % (L.tpr_bound_source_bytes(), C.sizeof(tpr_bound_source)))
         L.tpr_stage_boxes_batch.restype = C.c_int
         L.tpr_stage_boxes_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, C.c_int, C.POINTER(tpr_bound_source), C.c_int, V, V, V]
-        L.tpr_solve_sampled_boxed_batch.restype = C.c_int
-        L.tpr_solve_sampled_boxed_batch.argtypes = [SP, V, V, R, V]
-        L.tpr_solve_desired_duration_sampled_boxed_batch.restype = C.c_int
-        L.tpr_solve_desired_duration_sampled_boxed_batch.argtypes = [SP, V, V, V, C.c_double, R, V, V]
-        L.tpr_controllable_sets_sampled_boxed_batch.restype = C.c_int
-        L.tpr_controllable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V]
-        L.tpr_feasible_sets_sampled_boxed_batch.restype = C.c_int
-        L.tpr_feasible_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V]
-        L.tpr_reachable_sets_sampled_boxed_batch.restype = C.c_int
-        L.tpr_reachable_sets_sampled_boxed_batch.argtypes = [SP, V, V, V, V, V, V, V]
-        # the rigid-body family: three by-value structs with their size checks, and one table of signatures
+        # the rigid-body family: three by-value structs with their size checks
         for struct in (tpr_chain, tpr_payload, tpr_chain_points):
             size = getattr(L, struct.__name__ + "_bytes")
             size.restype, size.argtypes = C.c_int, []
@@ -272,7 +241,15 @@ def load():
                                      "binding declares %d" % (struct.__name__, size(), C.sizeof(struct)))
         CP, PP, XP = C.POINTER(tpr_chain), C.POINTER(tpr_payload), C.POINTER(tpr_chain_points)
         I, LL = C.c_int, C.c_longlong
-        for name, argtypes in {
+        # One table of signatures, all returning int.  The dense-row passes: a source's leading arguments (the problem; the boxed
+        # entries' low, high), the pass's own, the stream ...
+        DP = C.POINTER(tpr_dense_problem)
+        passes = {"solve": [R], "solve_desired_duration": [V, C.c_double, R, V], "controllable_sets": [V, V, V],
+                  "feasible_sets": [V], "reachable_sets": [V, V, V, V]}
+        signatures = {"tpr_%s_%s_batch" % (name, source): lead + own + [V]
+                      for source, lead in (("dense", [DP]), ("sampled", [SP]), ("sampled_boxed", [SP, V, V])) for name, own in passes.items()}
+        # ... and the rigid-body family: (..., int flags, void *stream)
+        signatures.update({name: argtypes + [I, V] for name, argtypes in {
                 "tpr_chain_inverse_dynamics_batch": [CP, LL, V, V, V, V],
                 "tpr_chain_torque_terms_batch": [CP, I, I, V, V, V, V, V, V],
                 "tpr_chain_tool_velocity_batch": [CP, I, I, V, V, V, V, V, V],
@@ -284,9 +261,10 @@ def load():
                 "tpr_chain_points_acceleration_batch": [CP, XP, LL, V, V, V, V],
                 "tpr_chain_points_acceleration_terms_batch": [CP, XP, I, I, V, V, V, V, V],
                 "tpr_tree_inverse_dynamics_batch": [CP, V, LL, V, V, V, V],
-                "tpr_tree_torque_terms_batch": [CP, V, I, I, V, V, V, V, V, V]}.items():
+                "tpr_tree_torque_terms_batch": [CP, V, I, I, V, V, V, V, V, V]}.items()})
+        for name, argtypes in signatures.items():
             entry = getattr(L, name)
-            entry.restype, entry.argtypes = C.c_int, argtypes + [I, V]  # (..., int flags, void *stream)
+            entry.restype, entry.argtypes = C.c_int, argtypes
         L.tpr_lp1d_batch.restype = C.c_int
         L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
         L.tpr_lp2d_batch.restype = C.c_int

@@ -393,7 +393,21 @@ class BatchTOPPRA(object):
         return self._boxed
 
     @staticmethod
-    def _to_host(out):
+    def _device_copy(arrays, like):
+        """``arrays`` themselves when ``like`` is a tensor.  A numpy problem: a device copy, made once per object (the passes
+        would otherwise upload the samples and boxes, or 3 B (N+1) nC doubles of rows, every time)."""
+        if _capi.is_torch_cuda(like):
+            return arrays
+        import torch
+        dev = torch.device("cuda", _capi.init())
+        return tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev) for v in arrays)
+
+    @staticmethod
+    def _device_pass(fn, given, device, *args, **kw):
+        """``fn`` on ``device``, the device copy of the arrays ``given``; outputs in the kind of ``given``."""
+        out = fn(*device, *args, **kw)
+        if device is given:
+            return out
         host = lambda v: v.cpu().numpy()  # noqa: E731
         if isinstance(out, dict):
             return {k: host(v) for k, v in out.items()}
@@ -402,16 +416,8 @@ class BatchTOPPRA(object):
     def _boxed_pass(self, fn, *args, **kw):
         """One pass on the device-resident samples and boxes; outputs in the kind of the inputs."""
         if self._boxed_dev is None:
-            self._boxed_dev = self._boxed_state()
-            if not _capi.is_torch_cuda(self._boxed[1]):
-                # numpy problem: the passes read a device copy of the samples and the boxes made once; results come back as
-                # numpy arrays
-                import torch
-                dev = torch.device("cuda", _capi.init())
-                self._boxed_dev = tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
-                                        for v in self._boxed)
-        out = fn(*self._boxed_dev, *args, **kw)
-        return out if self._boxed_dev is self._boxed else self._to_host(out)
+            self._boxed_dev = self._device_copy(self._boxed_state(), self._boxed_state()[1])
+        return self._device_pass(fn, self._boxed, self._boxed_dev, *args, **kw)
 
     def dense_rows(self):
         """(a, b, c, low, high, deltas) of the constraint list, as arrays of the kind the problem was given in: the arguments
@@ -432,25 +438,28 @@ class BatchTOPPRA(object):
             if self.first_order:
                 rows["low"], rows["high"] = self.stage_boxes()
             self._rows = tuple(rows[k] for k in ("a", "b", "c", "low", "high", "deltas"))
-            self._rows_dev = self._rows
-            if not _capi.is_torch_cuda(rows["a"]):
-                # numpy problem: the passes read a device copy made once (3 B (N+1) nC doubles would otherwise be uploaded by
-                # every pass); results come back as numpy arrays
-                import torch
-                dev = torch.device("cuda", _capi.init())
-                self._rows_dev = tuple(torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in self._rows)
+            self._rows_dev = self._device_copy(self._rows, rows["a"])
         return self._rows
 
     def _dense_pass(self, fn, *args, **kw):
         """One pass on the device-resident rows; outputs in the kind of the inputs."""
         self.dense_rows()
-        out = fn(*self._rows_dev, *args, **kw)
-        if self._rows_dev is self._rows:
-            return out
-        host = lambda v: v.cpu().numpy()  # noqa: E731
-        if isinstance(out, dict):
-            return {k: host(v) for k, v in out.items()}
-        return tuple(host(v) for v in out) if isinstance(out, tuple) else host(out)
+        return self._device_pass(fn, self._rows, self._rows_dev, *args, **kw)
+
+    def _pass(self, name, *args, table=(), **kw):
+        """The pass ``name`` -- the stem of its ``batch.*`` functions -- on the route this object takes: dense rows (with
+        ``constraints``), boxed samples (with first-order constraints), samples, else the spline table.  ``table``: keywords of
+        the spline-table function alone."""
+        if self.constraints:
+            return self._dense_pass(getattr(_batch, name + "_dense_batch"), *args, **kw)
+        kw["interpolation"] = self.interpolation
+        if self.first_order:
+            return self._boxed_pass(getattr(_batch, name + "_sampled_boxed_batch"), *args, **kw)
+        if self._samples is not None:
+            return getattr(_batch, name + "_sampled_batch")(*self._sampled_args(), *args, **kw)
+        if name == "solve_desired_duration":  # (the spline-table TOPPRAsd is not told the discretisation)
+            del kw["interpolation"]
+        return getattr(_batch, name + "_batch")(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, *args, **kw, **dict(table))
 
     @classmethod
     def from_waypoints(cls, knots, waypoints, gridpoints, vlim, alim, bc_type="not-a-knot", gpu_fit=True, **kw):
@@ -470,28 +479,12 @@ class BatchTOPPRA(object):
         FailUncontrollable / ErrUnknown, failed rows NaN-filled.  ``want_K`` / ``want_u`` = False leave the
         controllable sets / path accelerations in a device workspace (fewer bytes back to a host caller).
         With ``constraints`` the dense-row entry serves the call (``variant`` does not apply; K and u are always returned)."""
-        if self.constraints:
-            return self._dense_pass(_batch.solve_dense_batch, sd_start, sd_end, want_sd=want_sd)
-        if self.first_order:  # (the boxed entry always returns K and u; ``variant`` does not apply)
-            return self._boxed_pass(_batch.solve_sampled_boxed_batch, sd_start, sd_end, self.interpolation, want_sd=want_sd)
-        if self._samples is not None:  # (the sampled entry always returns K and u; ``variant`` does not apply)
-            return _batch.solve_sampled_batch(*self._sampled_args(), sd_start, sd_end, self.interpolation, want_sd=want_sd)
-        return _batch.solve_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
-                                  sd_start, sd_end, self.interpolation, want_sd=want_sd, variant=variant,
-                                  want_K=want_K, want_u=want_u)
+        # (the dense, boxed and sampled entries always return K and u; ``variant`` does not apply to them)
+        return self._pass("solve", sd_start, sd_end, want_sd=want_sd, table=dict(variant=variant, want_K=want_K, want_u=want_u))
 
     def compute_parameterization_sd(self, desired_duration, sd_start=None, sd_end=None, atol=1e-5):
         """TOPPRAsd for the batch: dict(sd2, sd, u, K, status, alpha)."""
-        if self.constraints:
-            return self._dense_pass(_batch.solve_desired_duration_dense_batch, desired_duration, sd_start, sd_end, atol)
-        if self.first_order:
-            return self._boxed_pass(_batch.solve_desired_duration_sampled_boxed_batch, desired_duration, sd_start, sd_end, atol,
-                                    self.interpolation)
-        if self._samples is not None:
-            return _batch.solve_desired_duration_sampled_batch(*self._sampled_args(), desired_duration, sd_start, sd_end, atol,
-                                                               self.interpolation)
-        return _batch.solve_desired_duration_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim,
-                                                   desired_duration, sd_start, sd_end, atol)
+        return self._pass("solve_desired_duration", desired_duration, sd_start, sd_end, atol)
 
     def compute_trajectory(self, sd_start=None, sd_end=None, parametrizer="ParametrizeSpline"):
         """``ParameterizationAlgorithm.compute_trajectory`` (algorithm/algorithm.py:174-215) for the batch:
@@ -535,35 +528,14 @@ class BatchTOPPRA(object):
         return out
 
     def compute_controllable_sets(self, sdmin, sdmax):
-        if self.constraints:
-            return self._dense_pass(_batch.controllable_sets_dense_batch, sdmin, sdmax)
-        if self.first_order:
-            return self._boxed_pass(_batch.controllable_sets_sampled_boxed_batch, sdmin, sdmax, self.interpolation)
-        if self._samples is not None:
-            return _batch.controllable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
-        return _batch.controllable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
-                                              self.alim, sdmin, sdmax, self.interpolation)
+        return self._pass("controllable_sets", sdmin, sdmax)
 
     def compute_feasible_sets(self):
-        if self.constraints:
-            return self._dense_pass(_batch.feasible_sets_dense_batch)
-        if self.first_order:
-            return self._boxed_pass(_batch.feasible_sets_sampled_boxed_batch, self.interpolation)
-        if self._samples is not None:
-            return _batch.feasible_sets_sampled_batch(*self._sampled_args(), self.interpolation)
-        return _batch.feasible_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim,
-                                          self.alim, self.interpolation)
+        return self._pass("feasible_sets")
 
     def compute_reachable_sets(self, sdmin, sdmax):
         """L[B, N+1, 2] (reachability_algorithm.py:409-431 per trajectory)."""
-        if self.constraints:
-            return self._dense_pass(_batch.reachable_sets_dense_batch, sdmin, sdmax)
-        if self.first_order:
-            return self._boxed_pass(_batch.reachable_sets_sampled_boxed_batch, sdmin, sdmax, self.interpolation)
-        if self._samples is not None:
-            return _batch.reachable_sets_sampled_batch(*self._sampled_args(), sdmin, sdmax, self.interpolation)
-        return _batch.reachable_sets_batch(self.coef, self.breaks, self.gridpoints, self.vlim, self.alim, sdmin, sdmax,
-                                           self.interpolation)
+        return self._pass("reachable_sets", sdmin, sdmax)
 
     @staticmethod
     def return_codes(status):

@@ -7,6 +7,7 @@ one call = B independent trajectories, each solved exactly as the reference's
 With numpy inputs the library stages host<->device copies itself; with torch CUDA tensors the
 device pointers are passed through and the kernels run on torch's current stream.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -178,74 +179,116 @@ def controllable_sets_batch(coef, breaks, grid, vlim, alim, sdmin, sdmax, interp
     return K
 
 
+# --------------------------------------------------------------------------------------------
+# the dense-row passes (solve, TOPPRAsd, controllable / feasible / reachable sets) on each of their three sources: the public
+# functions below are their signatures and docstrings; a source adaptor builds the problem, a pass helper does the rest
+
+# the entries' suffix, the problem, the array that outputs are made like, the C arguments between the problem and the pass's
+# own, the converted arrays the problem points to (alive as long as the source is)
+_Source = collections.namedtuple("_Source", "family p like lead keep")
+
+
+def _dense_source(a, b, c, low, high, deltas, **problem):
+    _prepare(a)
+    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, **problem)
+    return _Source("dense", p, a, (), keep)
+
+
+def _sampled_source(grid, qs, qss, vlim, alim, **problem):
+    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, **problem)
+    _prepare(keep[2])
+    return _Source("sampled", p, keep[2], (), keep)
+
+
+def _boxed_source(grid, qs, qss, alim, low, high, **problem):
+    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, **problem)
+    _prepare(keep[2])
+    return _Source("sampled_boxed", p, keep[2], (_capi.ptr(low), _capi.ptr(high)), keep)
+
+
+def _rows_call(source, name, *args):
+    """tpr_<name>_<family>_batch on ``source``: the problem, the source's leading arguments, ``args``, the stream."""
+    entry = getattr(_capi.load(), "tpr_%s_%s_batch" % (name, source.family))
+    _capi.check(entry(C.byref(source.p), *source.lead, *args, _stream_ptr(source.like)))
+
+
+def _rows_solve(source, want_sd):
+    p, like = source.p, source.like
+    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
+           "status": _empty(like, (p.B,), "i32")}
+    if want_sd:
+        out["sd"] = _empty(like, (p.B, p.N + 1))
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
+                         status=_capi.ptr(out["status"]))
+    _rows_call(source, "solve", C.byref(r))
+    return out
+
+
+def _rows_solve_desired_duration(source, desired_duration, atol):
+    p, like = source.p, source.like
+    B, N = p.B, p.N
+    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
+    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
+           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
+    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
+                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
+    _rows_call(source, "solve_desired_duration", _capi.ptr(desired), float(atol), C.byref(r), _capi.ptr(out["alpha"]))
+    return out
+
+
+def _rows_sets(source, name, sdmin, sdmax, want_X=None):
+    """controllable_sets -> K; reachable_sets (``want_X`` given) -> L, or (L, X)."""
+    p, like = source.p, source.like
+    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
+    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
+    sets = _empty(like, (p.B, p.N + 1, 2))
+    if want_X is None:
+        _rows_call(source, name, _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(sets))
+        return sets
+    X = _empty(like, (p.B, p.N + 1, 2)) if want_X else None
+    _rows_call(source, name, _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(sets), _capi.ptr(X))
+    return (sets, X) if want_X else sets
+
+
+def _rows_feasible_sets(source):
+    p, like = source.p, source.like
+    X = _empty(like, (p.B, p.N + 1, 2))
+    _rows_call(source, "feasible_sets", _capi.ptr(X))
+    return X
+
+
 def solve_dense_batch(a, b, c, low, high, deltas, sd_start=None, sd_end=None, want_sd=False, squared=False, active=None):
     """compute_parameterization on DENSE rows -- any canonical-linear constraint list, flattened as the reference's
     seidelWrapper flattens it (cy_seidel_solverwrapper.pyx:425-531; :func:`toppra_amd.solverwrapper.dense_rows` does it for
     constraint objects): a, b, c [B, N+1, nC], low, high [B, N+1, 2], deltas [N] or [B, N].  Returns the dict of
     :func:`solve_batch`.  Every stage LP runs the reference's full Seidel iteration: the reference's bits.  ``active``
     (int32 [B, 4], in / out; all dense entries): the wrapper object's warm-start state, for passes chained on one object."""
-    _prepare(a)
-    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, sd_start, sd_end, squared=squared, active=active)
-    out = {"sd2": _empty(a, (p.B, p.N + 1)), "u": _empty(a, (p.B, p.N)), "K": _empty(a, (p.B, p.N + 1, 2)),
-           "status": _empty(a, (p.B,), "i32")}
-    if want_sd:
-        out["sd"] = _empty(a, (p.B, p.N + 1))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
-                         status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_dense_batch(C.byref(p), C.byref(r), _stream_ptr(a)))
-    return out
+    source = _dense_source(a, b, c, low, high, deltas, sd_start=sd_start, sd_end=sd_end, squared=squared, active=active)
+    return _rows_solve(source, want_sd)
 
 
 def solve_desired_duration_dense_batch(a, b, c, low, high, deltas, desired_duration, sd_start=None, sd_end=None, atol=1e-5,
                                        active=None, squared=False):
     """TOPPRAsd.compute_parameterization on dense rows (see :func:`solve_dense_batch`, :func:`solve_desired_duration_batch`):
     dict(sd2, sd, u, K, status, alpha)."""
-    _prepare(a)
-    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, sd_start, sd_end, active=active, squared=squared)
-    B, N = p.B, p.N
-    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, a)
-    out = {"sd2": _empty(a, (B, N + 1)), "sd": _empty(a, (B, N + 1)), "u": _empty(a, (B, N)),
-           "K": _empty(a, (B, N + 1, 2)), "status": _empty(a, (B,), "i32"), "alpha": _empty(a, (B,))}
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_desired_duration_dense_batch(C.byref(p), _capi.ptr(desired), float(atol), C.byref(r),
-                                                                    _capi.ptr(out["alpha"]), _stream_ptr(a)))
-    return out
+    source = _dense_source(a, b, c, low, high, deltas, sd_start=sd_start, sd_end=sd_end, active=active, squared=squared)
+    return _rows_solve_desired_duration(source, desired_duration, atol)
 
 
 def controllable_sets_dense_batch(a, b, c, low, high, deltas, sdmin, sdmax, squared=False, active=None):
     """compute_controllable_sets(sdmin, sdmax) on dense rows (see :func:`solve_dense_batch`) -> K [B, N+1, 2]."""
-    _prepare(a)
-    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, squared=squared, active=active)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, a)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, a)
-    K = _empty(a, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_controllable_sets_dense_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(K),
-                                                               _stream_ptr(a)))
-    return K
+    return _rows_sets(_dense_source(a, b, c, low, high, deltas, squared=squared, active=active), "controllable_sets", sdmin, sdmax)
 
 
 def reachable_sets_dense_batch(a, b, c, low, high, deltas, sdmin, sdmax, want_X=False, active=None, squared=False):
     """compute_reachable_sets(sdmin, sdmax) on dense rows (see :func:`solve_dense_batch`) -> L [B, N+1, 2] (and the feasible
     sets X it computes on the way with ``want_X``)."""
-    _prepare(a)
-    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, active=active, squared=squared)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, a)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, a)
-    L = _empty(a, (p.B, p.N + 1, 2))
-    X = _empty(a, (p.B, p.N + 1, 2)) if want_X else None
-    _capi.check(_capi.load().tpr_reachable_sets_dense_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L),
-                                                            _capi.ptr(X), _stream_ptr(a)))
-    return (L, X) if want_X else L
+    return _rows_sets(_dense_source(a, b, c, low, high, deltas, active=active, squared=squared), "reachable_sets", sdmin, sdmax, bool(want_X))
 
 
 def feasible_sets_dense_batch(a, b, c, low, high, deltas, active=None):
     """compute_feasible_sets on dense rows (see :func:`solve_dense_batch`) -> X [B, N+1, 2]."""
-    _prepare(a)
-    p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, active=active)
-    X = _empty(a, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_feasible_sets_dense_batch(C.byref(p), _capi.ptr(X), _stream_ptr(a)))
-    return X
+    return _rows_feasible_sets(_dense_source(a, b, c, low, high, deltas, active=active))
 
 
 def reachable_sets_batch(coef, breaks, grid, vlim, alim, sdmin, sdmax, interpolation=True, want_X=False, squared=False):
@@ -425,78 +468,37 @@ def solve_sampled_batch(grid, qs, qss, vlim, alim, sd_start=None, sd_end=None, i
     :func:`solve_dense_batch`, and its bits on the rows :func:`sampled_rows_batch` writes -- without materialising them (a
     stage's rows are produced in registers from qs / qss at gridpoints i and i+1).  d <= 30 under Interpolation, <= 32 under
     Collocation (NotImplementedError beyond, before any launch).  ``active`` / ``squared``: as the dense entries."""
-    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, sd_start, sd_end, interpolation, active=active,
-                                         squared=squared)
-    like = keep[2]
-    _prepare(like)
-    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
-           "status": _empty(like, (p.B,), "i32")}
-    if want_sd:
-        out["sd"] = _empty(like, (p.B, p.N + 1))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
-                         status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_sampled_batch(C.byref(p), C.byref(r), _stream_ptr(like)))
-    return out
+    source = _sampled_source(grid, qs, qss, vlim, alim, sd_start=sd_start, sd_end=sd_end, interpolation=interpolation, active=active,
+                             squared=squared)
+    return _rows_solve(source, want_sd)
 
 
 def solve_desired_duration_sampled_batch(grid, qs, qss, vlim, alim, desired_duration, sd_start=None, sd_end=None, atol=1e-5,
                                          interpolation=True, active=None, squared=False):
     """TOPPRAsd.compute_parameterization for B sampled paths (see :func:`solve_sampled_batch`,
     :func:`solve_desired_duration_dense_batch`): dict(sd2, sd, u, K, status, alpha)."""
-    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, sd_start, sd_end, interpolation, active=active,
-                                         squared=squared)
-    like = keep[2]
-    _prepare(like)
-    B, N = p.B, p.N
-    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
-    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
-           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_desired_duration_sampled_batch(C.byref(p), _capi.ptr(desired), float(atol), C.byref(r),
-                                                                      _capi.ptr(out["alpha"]), _stream_ptr(like)))
-    return out
+    source = _sampled_source(grid, qs, qss, vlim, alim, sd_start=sd_start, sd_end=sd_end, interpolation=interpolation, active=active,
+                             squared=squared)
+    return _rows_solve_desired_duration(source, desired_duration, atol)
 
 
 def controllable_sets_sampled_batch(grid, qs, qss, vlim, alim, sdmin, sdmax, interpolation=True, squared=False, active=None):
     """compute_controllable_sets(sdmin, sdmax) for B sampled paths (see :func:`solve_sampled_batch`) -> K [B, N+1, 2]."""
-    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active,
-                                         squared=squared)
-    like = keep[2]
-    _prepare(like)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
-    K = _empty(like, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_controllable_sets_sampled_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(K),
-                                                                 _stream_ptr(like)))
-    return K
+    source = _sampled_source(grid, qs, qss, vlim, alim, interpolation=interpolation, active=active, squared=squared)
+    return _rows_sets(source, "controllable_sets", sdmin, sdmax)
 
 
 def feasible_sets_sampled_batch(grid, qs, qss, vlim, alim, interpolation=True, active=None):
     """compute_feasible_sets for B sampled paths (see :func:`solve_sampled_batch`) -> X [B, N+1, 2]."""
-    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active)
-    like = keep[2]
-    _prepare(like)
-    X = _empty(like, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_feasible_sets_sampled_batch(C.byref(p), _capi.ptr(X), _stream_ptr(like)))
-    return X
+    return _rows_feasible_sets(_sampled_source(grid, qs, qss, vlim, alim, interpolation=interpolation, active=active))
 
 
 def reachable_sets_sampled_batch(grid, qs, qss, vlim, alim, sdmin, sdmax, interpolation=True, want_X=False, active=None,
                                  squared=False):
     """compute_reachable_sets(sdmin, sdmax) for B sampled paths (see :func:`solve_sampled_batch`) -> L [B, N+1, 2] (and the
     feasible sets X with ``want_X``)."""
-    p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, active=active,
-                                         squared=squared)
-    like = keep[2]
-    _prepare(like)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
-    L = _empty(like, (p.B, p.N + 1, 2))
-    X = _empty(like, (p.B, p.N + 1, 2)) if want_X else None
-    _capi.check(_capi.load().tpr_reachable_sets_sampled_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L),
-                                                              _capi.ptr(X), _stream_ptr(like)))
-    return (L, X) if want_X else L
+    source = _sampled_source(grid, qs, qss, vlim, alim, interpolation=interpolation, active=active, squared=squared)
+    return _rows_sets(source, "reachable_sets", sdmin, sdmax, bool(want_X))
 
 
 def param_spline_samples_batch(grid, q, qs, sd):
@@ -579,82 +581,37 @@ def solve_sampled_boxed_batch(grid, qs, qss, alim, low, high, sd_start=None, sd_
     velocity limits: compute_parameterization for B sampled paths under an acceleration constraint and any list of
     first-order constraints.  Same keywords and dict; the bits of :func:`solve_dense_batch` on the rows
     :func:`sampled_rows_batch` writes without vlim, with these boxes.  ``vlim`` must stay None."""
-    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, sd_start, sd_end, interpolation, active=active,
-                                                  squared=squared, vlim=vlim)
-    like = keep[2]
-    _prepare(like)
-    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
-           "status": _empty(like, (p.B,), "i32")}
-    if want_sd:
-        out["sd"] = _empty(like, (p.B, p.N + 1))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
-                         status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_sampled_boxed_batch(C.byref(p), _capi.ptr(low), _capi.ptr(high), C.byref(r), _stream_ptr(like)))
-    return out
+    source = _boxed_source(grid, qs, qss, alim, low, high, sd_start=sd_start, sd_end=sd_end, interpolation=interpolation, active=active,
+                           squared=squared, vlim=vlim)
+    return _rows_solve(source, want_sd)
 
 
 def solve_desired_duration_sampled_boxed_batch(grid, qs, qss, alim, low, high, desired_duration, sd_start=None, sd_end=None,
                                                atol=1e-5, interpolation=True, active=None, squared=False, vlim=None):
     """:func:`solve_desired_duration_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`)."""
-    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, sd_start, sd_end, interpolation, active=active,
-                                                  squared=squared, vlim=vlim)
-    like = keep[2]
-    _prepare(like)
-    B, N = p.B, p.N
-    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
-    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
-           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_desired_duration_sampled_boxed_batch(
-        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(desired), float(atol), C.byref(r), _capi.ptr(out["alpha"]),
-        _stream_ptr(like)))
-    return out
+    source = _boxed_source(grid, qs, qss, alim, low, high, sd_start=sd_start, sd_end=sd_end, interpolation=interpolation, active=active,
+                           squared=squared, vlim=vlim)
+    return _rows_solve_desired_duration(source, desired_duration, atol)
 
 
 def controllable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sdmax, interpolation=True, squared=False,
                                           active=None, vlim=None):
     """:func:`controllable_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> K [B, N+1, 2]."""
-    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
-                                                  squared=squared, vlim=vlim)
-    like = keep[2]
-    _prepare(like)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
-    K = _empty(like, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_controllable_sets_sampled_boxed_batch(
-        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(K), _stream_ptr(like)))
-    return K
+    source = _boxed_source(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active, squared=squared, vlim=vlim)
+    return _rows_sets(source, "controllable_sets", sdmin, sdmax)
 
 
 def feasible_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, interpolation=True, active=None, vlim=None):
     """:func:`feasible_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> X [B, N+1, 2]."""
-    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
-                                                  vlim=vlim)
-    like = keep[2]
-    _prepare(like)
-    X = _empty(like, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_feasible_sets_sampled_boxed_batch(C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(X),
-                                                                   _stream_ptr(like)))
-    return X
+    return _rows_feasible_sets(_boxed_source(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active, vlim=vlim))
 
 
 def reachable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sdmax, interpolation=True, want_X=False,
                                        active=None, squared=False, vlim=None):
     """:func:`reachable_sets_sampled_batch` on stage boxes (see :func:`solve_sampled_boxed_batch`) -> L [B, N+1, 2] (and the
     feasible sets X with ``want_X``)."""
-    p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active,
-                                                  squared=squared, vlim=vlim)
-    like = keep[2]
-    _prepare(like)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, like)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, like)
-    L = _empty(like, (p.B, p.N + 1, 2))
-    X = _empty(like, (p.B, p.N + 1, 2)) if want_X else None
-    _capi.check(_capi.load().tpr_reachable_sets_sampled_boxed_batch(
-        C.byref(p), _capi.ptr(low), _capi.ptr(high), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L), _capi.ptr(X),
-        _stream_ptr(like)))
-    return (L, X) if want_X else L
+    source = _boxed_source(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active, squared=squared, vlim=vlim)
+    return _rows_sets(source, "reachable_sets", sdmin, sdmax, bool(want_X))
 
 
 # --------------------------------------------------------------------------------------------

@@ -12,22 +12,9 @@
 #include "tpr_boxed_stage.hip.inc"
 #include "tpr_boxes.hip.inc"
 
-// The (D, L) table of tpr_sampled_tu.hip: nC = 2 + (4 | 2 | 0) d by the flags, same layouts.
+// The same passes with the rows generated from path samples and the stage boxes read (BoxedSampledStage).
 extern "C" __attribute__((visibility("hidden"))) int tpr_tu_boxed_launch(const tpr::BoxedArgs *A, int feasible, hipStream_t stream) {
-    const int D = A->nC <= 6 ? 1 : (A->nC - 2 + 3) / 4;
-    switch (D) {
-#define TPR_BOXED_CASE(DD, LL) case DD: return tpr::dense_launch<DD, LL, tpr::BoxedSampledStage<DD, LL>>(*A, feasible, stream)
-        TPR_BOXED_CASE(1, 8); TPR_BOXED_CASE(2, 8); TPR_BOXED_CASE(3, 8); TPR_BOXED_CASE(4, 8);
-        TPR_BOXED_CASE(5, 8); TPR_BOXED_CASE(6, 8); TPR_BOXED_CASE(7, 8); TPR_BOXED_CASE(8, 8);
-        TPR_BOXED_CASE(9, 16); TPR_BOXED_CASE(10, 16); TPR_BOXED_CASE(11, 16); TPR_BOXED_CASE(12, 16);
-        TPR_BOXED_CASE(13, 16); TPR_BOXED_CASE(14, 16); TPR_BOXED_CASE(15, 16); TPR_BOXED_CASE(16, 16);
-        TPR_BOXED_CASE(17, 32); TPR_BOXED_CASE(18, 32); TPR_BOXED_CASE(19, 32); TPR_BOXED_CASE(20, 32);
-        TPR_BOXED_CASE(21, 32); TPR_BOXED_CASE(22, 32); TPR_BOXED_CASE(23, 32); TPR_BOXED_CASE(24, 32);
-        TPR_BOXED_CASE(25, 32); TPR_BOXED_CASE(26, 32); TPR_BOXED_CASE(27, 32); TPR_BOXED_CASE(28, 32);
-        TPR_BOXED_CASE(29, 32); TPR_BOXED_CASE(30, 32);
-#undef TPR_BOXED_CASE
-    }
-    return -1;
+    return tpr::dense_dispatch<tpr::BoxedSampledStage>(*A, feasible, stream);
 }
 
 // Tile and LDS of the box kernel: up to kBoxesTile gridpoints per block, halved until the two fp32 candidate arrays

@@ -13,7 +13,7 @@
 // Missing rows of the last slots hold the disabled row (0, 0, -1), which Seidel never pivots on and never projects.
 // Row traffic: 24 (nC + 2) bytes per stage and pass, 8 consecutive rows per group load; it hides behind the iteration's
 // instruction count, which is what bounds these kernels (DESIGN.md section 3.5).
-// Included by tpr_dense_tu.hip and tpr_sampled_tu.hip (after tpr_dense_args.hpp).
+// Included by tpr_dense_tu.hip, tpr_sampled_tu.hip and tpr_boxed_tu.hip (after tpr_dense_args.hpp).
 
 namespace tpr {
 
@@ -417,6 +417,27 @@ static int dense_launch(const typename Stage::Args &A, int feasible /* 0 solve, 
     else if (feasible == 2) hipLaunchKernelGGL((dense_sd_forward_kernel<D, L, Stage>), grid, block, lds, stream, A);
     else hipLaunchKernelGGL((dense_solve_kernel<D, L, Stage>), grid, block, lds, stream, A);
     return 0;
+}
+
+// ... and the layout of a call, the one table of the three units: nC rows per stage (incl. the two x_next rows; 2 + (4 | 2 | 0) d
+// by the flags when they are generated) -> the smallest row-slot layout that holds them, 2 + 4 D >= nC, on 8 / 16 / 32 lanes.
+// 0 = launched, -1 = more rows than the layouts hold (122: the row keys carry the virtual row index in 7 bits).
+template <template <int, int> class Stage>
+static int dense_dispatch(const typename Stage<1, 8>::Args &A, int feasible, hipStream_t stream) {
+    const int D = A.nC <= 6 ? 1 : (A.nC - 2 + 3) / 4;
+    switch (D) {
+#define TPR_DENSE_CASE(DD, LL) case DD: return dense_launch<DD, LL, Stage<DD, LL>>(A, feasible, stream)
+        TPR_DENSE_CASE(1, 8); TPR_DENSE_CASE(2, 8); TPR_DENSE_CASE(3, 8); TPR_DENSE_CASE(4, 8);
+        TPR_DENSE_CASE(5, 8); TPR_DENSE_CASE(6, 8); TPR_DENSE_CASE(7, 8); TPR_DENSE_CASE(8, 8);
+        TPR_DENSE_CASE(9, 16); TPR_DENSE_CASE(10, 16); TPR_DENSE_CASE(11, 16); TPR_DENSE_CASE(12, 16);
+        TPR_DENSE_CASE(13, 16); TPR_DENSE_CASE(14, 16); TPR_DENSE_CASE(15, 16); TPR_DENSE_CASE(16, 16);
+        TPR_DENSE_CASE(17, 32); TPR_DENSE_CASE(18, 32); TPR_DENSE_CASE(19, 32); TPR_DENSE_CASE(20, 32);
+        TPR_DENSE_CASE(21, 32); TPR_DENSE_CASE(22, 32); TPR_DENSE_CASE(23, 32); TPR_DENSE_CASE(24, 32);
+        TPR_DENSE_CASE(25, 32); TPR_DENSE_CASE(26, 32); TPR_DENSE_CASE(27, 32); TPR_DENSE_CASE(28, 32);
+        TPR_DENSE_CASE(29, 32); TPR_DENSE_CASE(30, 32);
+#undef TPR_DENSE_CASE
+    }
+    return -1;
 }
 
 }  // namespace tpr

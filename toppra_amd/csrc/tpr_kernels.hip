@@ -564,6 +564,109 @@ int reachable_sets(Staging &S, const Args &A, void (*kernel)(Args, const double 
     return S.finish();
 }
 
+// ---- the dense-row passes (tpr_dense.hip.inc), whatever feeds a stage's rows ------------------------------------------------
+// One host path for the three families: rows read from arrays (tpr_*_dense_batch), generated from path samples
+// (tpr_*_sampled_batch), generated from samples with the stage boxes read (tpr_*_sampled_boxed_batch).  A source -- DenseSource,
+// SampledSource, BoxedSource below, each next to its check and its stager -- holds the call's problem and says what differs:
+//   check()     what is refused before anything is staged;
+//   anchor()    the pointer whose device the call runs on;
+//   stage(S)    -> Args: DenseArgs / SampledArgs / BoxedArgs;
+//   launch      its unit's tpr_tu_*_launch (0 = solve, 1 = feasible sets, 2 = TOPPRAsd's forward scans; != 0: no layout);
+//   reachable   its instantiation of lane_dense_reachable_kernel;
+//   grid(A)     what TOPPRAsd's steps are differences of (null: they are A.deltas);
+//   name        the prefix of its messages.
+// A pass is the source's check, the check of its own pointers, the staging and the launch, in this order (which refusal wins
+// when two arguments are bad: tests/test_dense_refusal_order.py); an entry is one call of its pass on its source.
+template <class Src>
+int launch_rows(const typename Src::Args &A, int pass, const char *what, hipStream_t stream) {
+    if (A.B > 0 && Src::launch(&A, pass, stream) != 0)
+        return fail(TPR_E_UNSUPPORTED, std::string(Src::name) + " " + what + ": no kernel for this row count");
+    return TPR_E_OK;
+}
+
+template <class Src>
+int rows_solve(const Src &src, const tpr_result *r, void *stream_) {
+    if (int rc = src.check()) return rc;
+    if (!r || !r->K) return fail(TPR_E_BADARG, std::string(Src::name) + " solve: r->K is required");
+    Staging S(src.p->flags & TPR_DEVICE_PTRS, src.anchor(), stream_);
+    if (int rc = S.failed()) return rc;
+    typename Src::Args A = src.stage(S);
+    const size_t B = (size_t)A.B, N = (size_t)A.N;
+    A.sd_start = S.in(src.p->sd_start, B); A.sd_end = S.in(src.p->sd_end, B);
+    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    if (int rc = S.failed()) return rc;
+    if (int rc = launch_rows<Src>(A, 0, "solve", S.stream)) return rc;
+    return S.finish();
+}
+
+template <class Src>
+int rows_solve_desired_duration(const Src &src, const double *desired, double atol, const tpr_result *r, double *alpha, void *stream_) {
+    if (int rc = src.check()) return rc;
+    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
+    Staging S(src.p->flags & TPR_DEVICE_PTRS, src.anchor(), stream_);
+    if (int rc = S.failed()) return rc;
+    typename Src::Args A = src.stage(S);
+    const size_t B = (size_t)A.B, N = (size_t)A.N;
+    const double *ddes = S.in(desired, B);
+    A.sd_start = S.in(src.p->sd_start, B); A.sd_end = S.in(src.p->sd_end, B);
+    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
+    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
+    double *dalpha = S.out(alpha, B);
+    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
+    if (int rc = S.failed()) return rc;
+    if (!dalpha) dalpha = W.extra;
+    if (A.B > 0) {
+        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
+        // backward scan -> K and the controllability verdict, the two forward scans, then durations / bisection / blend
+        A.backward_only = 1;
+        if (Src::launch(&A, 0, S.stream) != 0 || Src::launch(&A, 2, S.stream) != 0)
+            return fail(TPR_E_UNSUPPORTED, std::string(Src::name) + " TOPPRAsd: no kernel for this row count");
+        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, Src::grid(A), ddes, nullptr, nullptr, nullptr, nullptr, A.status,
+                           dsd2, dsd, du, dalpha, A.status, A.deltas};
+        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
+    }
+    return S.finish();
+}
+
+template <class Src>
+int rows_controllable_sets(const Src &src, const double *sdmin, const double *sdmax, double *K, void *stream_) {
+    if (int rc = src.check()) return rc;
+    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
+    Staging S(src.p->flags & TPR_DEVICE_PTRS, src.anchor(), stream_);
+    if (int rc = S.failed()) return rc;
+    typename Src::Args A = src.stage(S);
+    const size_t B = (size_t)A.B, N = (size_t)A.N;
+    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
+    A.K = S.out(K, B * (N + 1) * 2);
+    A.backward_only = 1;
+    if (int rc = S.failed()) return rc;
+    if (int rc = launch_rows<Src>(A, 0, "controllable sets", S.stream)) return rc;
+    return S.finish();
+}
+
+template <class Src>
+int rows_feasible_sets(const Src &src, double *X, void *stream_) {
+    if (int rc = src.check()) return rc;
+    if (!X) return fail(TPR_E_BADARG, "X is required");
+    Staging S(src.p->flags & TPR_DEVICE_PTRS, src.anchor(), stream_);
+    if (int rc = S.failed()) return rc;
+    typename Src::Args A = src.stage(S);
+    A.X = S.out(X, (size_t)A.B * ((size_t)A.N + 1) * 2);
+    if (int rc = S.failed()) return rc;
+    if (int rc = launch_rows<Src>(A, 1, "feasible sets", S.stream)) return rc;
+    return S.finish();
+}
+
+template <class Src>
+int rows_reachable_sets(const Src &src, const double *sdmin, const double *sdmax, double *L, double *X, void *stream_) {
+    if (int rc = src.check()) return rc;
+    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
+    Staging S(src.p->flags & TPR_DEVICE_PTRS, src.anchor(), stream_);
+    if (int rc = S.failed()) return rc;
+    return reachable_sets(S, src.stage(S), Src::reachable, sdmin, sdmax, L, X);
+}
+
 // Knot-parallel spline parametrizer (tpr_spline.hip.inc): a block per trajectory, all N + 1 knots in LDS -- their times,
 // their d right-hand sides and `xcols` working columns (the kernel's XC: max(d - 1, 2) for the coefficient table,
 // max(d, 2) when it samples).  Up to 16 dof and 1024 knots, 256 bytes of static LDS beside the columns.
@@ -815,88 +918,40 @@ tpr::DenseArgs stage_dense(const tpr_dense_problem *p, Staging &S) {
     A.active = S.out(p->active, B * 4, true);
     return A;
 }
+struct DenseSource {
+    using Args = tpr::DenseArgs;
+    static constexpr const char *name = "dense";
+    static constexpr auto launch = tpr_tu_dense_launch;
+    static constexpr auto reachable = tpr::lane_dense_reachable_kernel<Args>;
+    const tpr_dense_problem *p;
+    int check() const { return check_dense(p); }
+    const void *anchor() const { return p->a; }
+    Args stage(Staging &S) const { return stage_dense(p, S); }
+    static const double *grid(const Args &) { return nullptr; }
+};
 }  // namespace
 
 int tpr_solve_dense_batch(const tpr_dense_problem *p, const tpr_result *r, void *stream_) {
-    if (int rc = check_dense(p)) return rc;
-    if (!r || !r->K) return fail(TPR_E_BADARG, "dense solve: r->K is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::DenseArgs A = stage_dense(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_dense_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "dense solve: no kernel for this row count");
-    return S.finish();
+    return rows_solve(DenseSource{p}, r, stream_);
 }
 
 int tpr_solve_desired_duration_dense_batch(const tpr_dense_problem *p, const double *desired, double atol, const tpr_result *r,
                                            double *alpha, void *stream_) {
-    if (int rc = check_dense(p)) return rc;
-    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::DenseArgs A = stage_dense(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    const double *ddes = S.in(desired, B);
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    double *dalpha = S.out(alpha, B);
-    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
-    if (int rc = S.failed()) return rc;
-    if (!dalpha) dalpha = W.extra;
-    if (A.B > 0) {
-        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
-        // backward scan -> K and the controllability verdict, the two forward scans, then durations / bisection / blend
-        A.backward_only = 1;
-        if (tpr_tu_dense_launch(&A, 0, S.stream) != 0 || tpr_tu_dense_launch(&A, 2, S.stream) != 0)
-            return fail(TPR_E_UNSUPPORTED, "dense TOPPRAsd: no kernel for this row count");
-        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, nullptr, ddes, nullptr, nullptr, nullptr, nullptr, A.status,
-                           dsd2, dsd, du, dalpha, A.status, A.deltas};
-        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
-    }
-    return S.finish();
+    return rows_solve_desired_duration(DenseSource{p}, desired, atol, r, alpha, stream_);
 }
 
 int tpr_reachable_sets_dense_batch(const tpr_dense_problem *p, const double *sdmin, const double *sdmax, double *L, double *X,
                                    void *stream_) {
-    if (int rc = check_dense(p)) return rc;
-    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::DenseArgs A = stage_dense(p, S);
-    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::DenseArgs>, sdmin, sdmax, L, X);
+    return rows_reachable_sets(DenseSource{p}, sdmin, sdmax, L, X, stream_);
 }
 
 int tpr_controllable_sets_dense_batch(const tpr_dense_problem *p, const double *sdmin, const double *sdmax, double *K,
                                       void *stream_) {
-    if (int rc = check_dense(p)) return rc;
-    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::DenseArgs A = stage_dense(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
-    A.K = S.out(K, B * (N + 1) * 2);
-    A.backward_only = 1;
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_dense_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "dense controllable sets: no kernel for this row count");
-    return S.finish();
+    return rows_controllable_sets(DenseSource{p}, sdmin, sdmax, K, stream_);
 }
 
 int tpr_feasible_sets_dense_batch(const tpr_dense_problem *p, double *X, void *stream_) {
-    if (int rc = check_dense(p)) return rc;
-    if (!X) return fail(TPR_E_BADARG, "X is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->a, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::DenseArgs A = stage_dense(p, S);
-    A.X = S.out(X, (size_t)p->B * ((size_t)p->N + 1) * 2);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_dense_launch(&A, 1, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "dense feasible sets: no kernel for this row count");
-    return S.finish();
+    return rows_feasible_sets(DenseSource{p}, X, stream_);
 }
 
 int tpr_reachable_sets_batch(const tpr_problem *p, const double *sdmin, const double *sdmax, double *L, double *X,
@@ -1345,90 +1400,43 @@ tpr::SampledArgs stage_sampled(const tpr_sampled_problem *p, Staging &S) {
     A.active = S.out(p->active, B * 4, true);
     return A;
 }
+struct SampledSource {
+    using Args = tpr::SampledArgs;
+    static constexpr const char *name = "sampled";
+    static constexpr auto launch = tpr_tu_sampled_launch;
+    static constexpr auto reachable = tpr::lane_dense_reachable_kernel<Args>;
+    const tpr_sampled_problem *p;
+    int check() const { return check_sampled(p, true); }
+    const void *anchor() const { return p->qs; }
+    Args stage(Staging &S) const { return stage_sampled(p, S); }
+    static const double *grid(const Args &A) { return A.grid; }
+};
 }  // namespace
 
 extern "C" {
 int tpr_sampled_problem_bytes(void) { return (int)sizeof(tpr_sampled_problem); }
 
 int tpr_solve_sampled_batch(const tpr_sampled_problem *p, const tpr_result *r, void *stream_) {
-    if (int rc = check_sampled(p, true)) return rc;
-    if (!r || !r->K) return fail(TPR_E_BADARG, "sampled solve: r->K is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::SampledArgs A = stage_sampled(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_sampled_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled solve: no kernel for this row count");
-    return S.finish();
+    return rows_solve(SampledSource{p}, r, stream_);
 }
 
 int tpr_solve_desired_duration_sampled_batch(const tpr_sampled_problem *p, const double *desired, double atol, const tpr_result *r,
                                              double *alpha, void *stream_) {
-    if (int rc = check_sampled(p, true)) return rc;
-    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::SampledArgs A = stage_sampled(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    const double *ddes = S.in(desired, B);
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    double *dalpha = S.out(alpha, B);
-    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
-    if (int rc = S.failed()) return rc;
-    if (!dalpha) dalpha = W.extra;
-    if (A.B > 0) {
-        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
-        A.backward_only = 1;
-        if (tpr_tu_sampled_launch(&A, 0, S.stream) != 0 || tpr_tu_sampled_launch(&A, 2, S.stream) != 0)
-            return fail(TPR_E_UNSUPPORTED, "sampled TOPPRAsd: no kernel for this row count");
-        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, A.grid, ddes, nullptr, nullptr, nullptr, nullptr, A.status,
-                           dsd2, dsd, du, dalpha, A.status};
-        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
-    }
-    return S.finish();
+    return rows_solve_desired_duration(SampledSource{p}, desired, atol, r, alpha, stream_);
 }
 
 int tpr_controllable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *K,
                                         void *stream_) {
-    if (int rc = check_sampled(p, true)) return rc;
-    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::SampledArgs A = stage_sampled(p, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
-    A.K = S.out(K, B * (N + 1) * 2);
-    A.backward_only = 1;
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_sampled_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled controllable sets: no kernel for this row count");
-    return S.finish();
+    return rows_controllable_sets(SampledSource{p}, sdmin, sdmax, K, stream_);
 }
 
 int tpr_feasible_sets_sampled_batch(const tpr_sampled_problem *p, double *X, void *stream_) {
-    if (int rc = check_sampled(p, true)) return rc;
-    if (!X) return fail(TPR_E_BADARG, "X is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::SampledArgs A = stage_sampled(p, S);
-    A.X = S.out(X, (size_t)p->B * ((size_t)p->N + 1) * 2);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_sampled_launch(&A, 1, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "sampled feasible sets: no kernel for this row count");
-    return S.finish();
+    return rows_feasible_sets(SampledSource{p}, X, stream_);
 }
 
 int tpr_reachable_sets_sampled_batch(const tpr_sampled_problem *p, const double *sdmin, const double *sdmax, double *L, double *X,
                                      void *stream_) {
-    if (int rc = check_sampled(p, true)) return rc;
-    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::SampledArgs A = stage_sampled(p, S);
-    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::SampledArgs>, sdmin, sdmax, L, X);
+    return rows_reachable_sets(SampledSource{p}, sdmin, sdmax, L, X, stream_);
 }
 
 int tpr_sampled_rows_batch(const tpr_sampled_problem *p, int nblocks, const tpr_second_order_block *blocks, double *a, double *b,
@@ -1512,6 +1520,18 @@ tpr::BoxedArgs stage_boxed(const tpr_sampled_problem *p, const double *low, cons
     A.low = S.in(low, pts * 2); A.high = S.in(high, pts * 2);
     return A;
 }
+struct BoxedSource {
+    using Args = tpr::BoxedArgs;
+    static constexpr const char *name = "boxed sampled";
+    static constexpr auto launch = tpr_tu_boxed_launch;
+    static constexpr auto reachable = tpr::lane_dense_reachable_kernel<Args>;
+    const tpr_sampled_problem *p;
+    const double *low, *high;
+    int check() const { return check_boxed(p, low, high); }
+    const void *anchor() const { return p->qs; }
+    Args stage(Staging &S) const { return stage_boxed(p, low, high, S); }
+    static const double *grid(const Args &A) { return A.grid; }
+};
 }  // namespace
 
 extern "C" {
@@ -1561,86 +1581,28 @@ int tpr_stage_boxes_batch(int B, int N, int d, const double *qs, int nsrc, const
 
 int tpr_solve_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, const tpr_result *r,
                                   void *stream_) {
-    if (int rc = check_boxed(p, low, high)) return rc;
-    if (!r || !r->K) return fail(TPR_E_BADARG, "boxed sampled solve: r->K is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    A.sd2 = S.out(r->sd2, B * (N + 1)); A.sd = S.out(r->sd, B * (N + 1)); A.u = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_boxed_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled solve: no kernel for this row count");
-    return S.finish();
+    return rows_solve(BoxedSource{p, low, high}, r, stream_);
 }
 
 int tpr_solve_desired_duration_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
                                                    const double *desired, double atol, const tpr_result *r, double *alpha,
                                                    void *stream_) {
-    if (int rc = check_boxed(p, low, high)) return rc;
-    if (!r || !r->K || !desired) return fail(TPR_E_BADARG, "result.K and desired are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    const double *ddes = S.in(desired, B);
-    A.sd_start = S.in(p->sd_start, B); A.sd_end = S.in(p->sd_end, B);
-    double *dsd2 = S.out(r->sd2, B * (N + 1)), *dsd = S.out(r->sd, B * (N + 1)), *du = S.out(r->u, B * N);
-    A.K = S.out(r->K, B * (N + 1) * 2); A.status = S.out(r->status, B);
-    double *dalpha = S.out(alpha, B);
-    const SdWork W = sd_workspace(S, B, N, dalpha ? 0 : 1, A.status);
-    if (int rc = S.failed()) return rc;
-    if (!dalpha) dalpha = W.extra;
-    if (A.B > 0) {
-        A.sd_xf = W.xf; A.sd_uf = W.uf; A.sd_xl = W.xl; A.sd_ul = W.ul;
-        A.backward_only = 1;
-        if (tpr_tu_boxed_launch(&A, 0, S.stream) != 0 || tpr_tu_boxed_launch(&A, 2, S.stream) != 0)
-            return fail(TPR_E_UNSUPPORTED, "boxed sampled TOPPRAsd: no kernel for this row count");
-        tpr::SdBlendArgs G{A.B, A.N, A.flags, atol, A.grid, ddes, nullptr, nullptr, nullptr, nullptr, A.status,
-                           dsd2, dsd, du, dalpha, A.status};
-        if (int rc = launch_sd_finish(G, W, nullptr, S.stream)) return rc;
-    }
-    return S.finish();
+    return rows_solve_desired_duration(BoxedSource{p, low, high}, desired, atol, r, alpha, stream_);
 }
 
 int tpr_controllable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
                                               const double *sdmin, const double *sdmax, double *K, void *stream_) {
-    if (int rc = check_boxed(p, low, high)) return rc;
-    if (!sdmin || !sdmax || !K) return fail(TPR_E_BADARG, "sdmin/sdmax/K are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
-    const size_t B = (size_t)p->B, N = (size_t)p->N;
-    A.sd_end = S.in(sdmin, B); A.sd_end_hi = S.in(sdmax, B);
-    A.K = S.out(K, B * (N + 1) * 2);
-    A.backward_only = 1;
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_boxed_launch(&A, 0, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled controllable sets: no kernel for this row count");
-    return S.finish();
+    return rows_controllable_sets(BoxedSource{p, low, high}, sdmin, sdmax, K, stream_);
 }
 
 int tpr_feasible_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high, double *X,
                                           void *stream_) {
-    if (int rc = check_boxed(p, low, high)) return rc;
-    if (!X) return fail(TPR_E_BADARG, "X is required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
-    A.X = S.out(X, (size_t)p->B * ((size_t)p->N + 1) * 2);
-    if (int rc = S.failed()) return rc;
-    if (A.B > 0 && tpr_tu_boxed_launch(&A, 1, S.stream) != 0) return fail(TPR_E_UNSUPPORTED, "boxed sampled feasible sets: no kernel for this row count");
-    return S.finish();
+    return rows_feasible_sets(BoxedSource{p, low, high}, X, stream_);
 }
 
 int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const double *low, const double *high,
                                            const double *sdmin, const double *sdmax, double *L, double *X, void *stream_) {
-    if (int rc = check_boxed(p, low, high)) return rc;
-    if (!sdmin || !sdmax || !L) return fail(TPR_E_BADARG, "sdmin/sdmax/L are required");
-    Staging S(p->flags & TPR_DEVICE_PTRS, p->qs, stream_);
-    if (int rc = S.failed()) return rc;
-    tpr::BoxedArgs A = stage_boxed(p, low, high, S);
-    return reachable_sets(S, A, tpr::lane_dense_reachable_kernel<tpr::BoxedArgs>, sdmin, sdmax, L, X);
+    return rows_reachable_sets(BoxedSource{p, low, high}, sdmin, sdmax, L, X, stream_);
 }
 }  // extern "C"
 

@@ -221,7 +221,42 @@ def dense_rows(constraint_list, path, path_discretization):
     return out
 
 
-class hipDenseSeidelWrapper(SolverWrapper):
+class _RowPassesWrapper(SolverWrapper):
+    """The five passes of a wrapper object on the dense-row entries, each a batch of one: the class names the ``_family`` of its
+    ``batch.*_<family>_batch`` functions, :meth:`_source` gives their leading arguments and the keywords every call takes.
+    Boundary velocities are handed over squared (``squared=True``: no sqrt / square round trip); ``_active`` is the object's
+    warm-start state, carried from pass to pass as the reference object carries it."""
+
+    def _pass(self, name, *args, **kw):
+        lead, common = self._source()
+        return getattr(batch, "%s_%s_batch" % (name, self._family))(*lead, *args, active=self._active, **common, **kw)
+
+    @staticmethod
+    def _squared(sd):
+        return np.array([sd ** 2], dtype=np.float64)
+
+    def controllable_sets(self, sdmin, sdmax):
+        return self._pass("controllable_sets", self._squared(sdmin), self._squared(sdmax), squared=True)[0]
+
+    def feasible_sets(self):
+        return self._pass("feasible_sets")[0]
+
+    def reachable_sets(self, sdmin, sdmax):
+        L, X = self._pass("reachable_sets", self._squared(sdmin), self._squared(sdmax), want_X=True, squared=True)
+        return L[0], X[0]
+
+    def parameterization(self, sd_start, sd_end):
+        out = self._pass("solve", self._squared(sd_start), self._squared(sd_end), want_sd=True, squared=True)
+        res = {k: v[0] for k, v in out.items() if k != "status"}
+        res["status"] = int(out["status"][0])
+        return res
+
+    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
+        out = self._pass("solve_desired_duration", desired_duration, self._squared(sd_start), self._squared(sd_end), atol, squared=True)
+        return {k: v[0] for k, v in out.items()}
+
+
+class hipDenseSeidelWrapper(_RowPassesWrapper):
     """seidelWrapper for ANY list of canonical-linear constraints (SecondOrderConstraint, JointTorqueConstraint, the
     reference's own constraint objects, hand-written ones): the constraints' parameters are evaluated on the host, as in
     the reference, flattened by :func:`dense_rows`, and the passes run on the dense-row entries of the library
@@ -254,19 +289,10 @@ class hipDenseSeidelWrapper(SolverWrapper):
         self._active = np.zeros((1, 4), dtype=np.int32) if active is None else active
         self._active_up, self._active_down = self._active[0, 0:2], self._active[0, 2:4]
 
-    def controllable_sets(self, sdmin, sdmax):
-        return batch.controllable_sets_dense_batch(*self._rows, np.array([sdmin ** 2], dtype=np.float64),
-                                                   np.array([sdmax ** 2], dtype=np.float64), squared=True, active=self._active)[0]
+    _family = "dense"
 
-    def feasible_sets(self):
-        return batch.feasible_sets_dense_batch(*self._rows, active=self._active)[0]
-
-    def parameterization(self, sd_start, sd_end):
-        out = batch.solve_dense_batch(*self._rows, np.array([sd_start ** 2], dtype=np.float64),
-                                      np.array([sd_end ** 2], dtype=np.float64), want_sd=True, squared=True, active=self._active)
-        res = {k: v[0] for k, v in out.items() if k != "status"}
-        res["status"] = int(out["status"][0])
-        return res
+    def _source(self):
+        return self._rows, {}
 
     # -- single-LP compatibility entry (cy_seidel_solverwrapper.pyx:549-697) on the stage's dense rows: the bounds and the
     # x_next pair are set up as the reference sets them up, the LP itself runs on the library's LP entries
@@ -311,20 +337,8 @@ class hipDenseSeidelWrapper(SolverWrapper):
         warm[:] = active
         return var
 
-    def reachable_sets(self, sdmin, sdmax):
-        L, X = batch.reachable_sets_dense_batch(*self._rows, np.array([sdmin ** 2], dtype=np.float64),
-                                                np.array([sdmax ** 2], dtype=np.float64), want_X=True, active=self._active,
-                                                squared=True)
-        return L[0], X[0]
 
-    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
-        out = batch.solve_desired_duration_dense_batch(*self._rows, desired_duration, np.array([sd_start ** 2], dtype=np.float64),
-                                                       np.array([sd_end ** 2], dtype=np.float64), atol, active=self._active,
-                                                       squared=True)
-        return {k: v[0] for k, v in out.items()}
-
-
-class hipSampledSeidelWrapper(SolverWrapper):
+class hipSampledSeidelWrapper(_RowPassesWrapper):
     """seidelWrapper for velocity + acceleration limits on ANY geometric path (SimplePath, PolynomialPath,
     UnivariateSplineInterpolator, a user's own ``AbstractGeometricPath``): the path is evaluated on the host at the gridpoints,
     as the reference's constraints evaluate it -- ``path(gridpoints, 1)`` and ``path(gridpoints, 2)`` are all they read --
@@ -360,33 +374,10 @@ class hipSampledSeidelWrapper(SolverWrapper):
             self._params = [c.compute_constraint_params(self.path, self.path_discretization) for c in self.constraints]
         return self._params
 
-    def controllable_sets(self, sdmin, sdmax):
-        return batch.controllable_sets_sampled_batch(*self._args, np.array([sdmin ** 2], dtype=np.float64),
-                                                     np.array([sdmax ** 2], dtype=np.float64), self._interp, squared=True,
-                                                     active=self._active)[0]
+    _family = "sampled"
 
-    def feasible_sets(self):
-        return batch.feasible_sets_sampled_batch(*self._args, self._interp, active=self._active)[0]
-
-    def reachable_sets(self, sdmin, sdmax):
-        L, X = batch.reachable_sets_sampled_batch(*self._args, np.array([sdmin ** 2], dtype=np.float64),
-                                                  np.array([sdmax ** 2], dtype=np.float64), self._interp, want_X=True,
-                                                  active=self._active, squared=True)
-        return L[0], X[0]
-
-    def parameterization(self, sd_start, sd_end):
-        out = batch.solve_sampled_batch(*self._args, np.array([sd_start ** 2], dtype=np.float64),
-                                        np.array([sd_end ** 2], dtype=np.float64), self._interp, want_sd=True, squared=True,
-                                        active=self._active)
-        res = {k: v[0] for k, v in out.items() if k != "status"}
-        res["status"] = int(out["status"][0])
-        return res
-
-    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
-        out = batch.solve_desired_duration_sampled_batch(*self._args, desired_duration, np.array([sd_start ** 2], dtype=np.float64),
-                                                         np.array([sd_end ** 2], dtype=np.float64), atol, self._interp,
-                                                         active=self._active, squared=True)
-        return {k: v[0] for k, v in out.items()}
+    def _source(self):
+        return self._args, {"interpolation": self._interp}
 
     def solve_stagewise_optim(self, i, H, g, x_min, x_max, x_next_min, x_next_max):
         """The single-LP compatibility entry: served by a :class:`hipDenseSeidelWrapper` on the same constraints (its rows are
