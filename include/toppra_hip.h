@@ -559,6 +559,43 @@ int tpr_tree_inverse_dynamics_batch(const tpr_chain *links, const int32_t *paren
 int tpr_tree_torque_terms_batch(const tpr_chain *links, const int32_t *parent, int B, int N, const double *q, const double *qs,
                                 const double *qss, double *w0, double *wa, double *wb, int flags, void *stream);
 
+/* ---- the base reaction: the wrench a robot's mount exerts ON the robot, for a batch -----------------------------------------
+ * What a pedestal's flange, a linear axis, a ceiling plate or the footprint of a cart has to supply: the sum over EVERY link of
+ * every root of a tree (a serial chain is the tree parent = -1, 0, 1, ...), gravity included -- at rest the force holds up the
+ * weight.  The moment is taken about the origin of a mount frame and both parts are expressed in that frame's axes:
+ *   rot [3][3] row-major, columns = the mount frame's axes in base coordinates (orthonormal, determinant +1, to 1e-12);
+ *   origin [3] its origin in base coordinates; mass >= 0, com [3]: a rigid platform fixed to the base (the cart or column whose
+ *   weight keeps a mobile manipulator upright), its centre of mass in base coordinates; it adds -mass gravity at com.
+ * ALWAYS A HOST STRUCT, with or without TPR_DEVICE_PTRS: it travels to the kernels by value.  A NULL mount is the base frame
+ * itself without a platform.                                                                                              */
+typedef struct tpr_mount {
+    double rot[9], origin[3], mass, com[3];
+} tpr_mount;
+/* ABI guard, as tpr_chain_bytes: bytes of tpr_mount in the library.                                                     */
+int tpr_mount_bytes(void);
+/* wrench(q, qd, qdd) = [f'; n'], [npoints][6].  With W_i the link frame's rotation and p_i its origin in base coordinates, m_i and
+ * c_i the link's mass and centre of mass, and F_i, N_i the net force on link i and its net moment about c_i from the forward
+ * recursion of tpr_tree_inverse_dynamics_batch started from a base AT REST (gravity is not in it):
+ *   f = sum_i -m_i gravity - mass gravity + sum_i W_i F_i,
+ *   n = sum_i (p_i + W_i c_i) x (-m_i gravity) + com x (-mass gravity) + sum_i [W_i (N_i + c_i x F_i) + p_i x (W_i F_i)],
+ *   f' = rot' f,   n' = rot' (n - origin x f):
+ * the weight is summed in base coordinates, where no rotation touches it, and only the rest goes through the recursion.
+ * Forward only, a point's state in registers at any dof; the links are summed in ascending number.  One wave of 64 points per
+ * block; dynamic LDS stages a block's inputs and outputs and keeps one bank of 21 doubles per lane and fork (27 in the terms
+ * entry): at most 50 688 + 4 * 27 * 512 = 105 984 bytes.  A zero result is +0.  links, parent and their refusals are those of
+ * tpr_tree_inverse_dynamics_batch; then: a non-finite entry of the mount, a rot that is not orthonormal with determinant +1 to
+ * 1e-12, a negative mass (TPR_E_BADARG); then NULL arrays.                                                                */
+int tpr_tree_base_wrench_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, long long npoints,
+                               const double *q, const double *qd, const double *qdd, double *wrench, int flags, void *stream);
+/* The three evaluations a second-order constraint on that wrench needs (tpr_second_order_block with p = 6), in one pass over
+ * the links: w0 = wrench(q, 0, 0) -- the static reaction, not zero under gravity --, wa = wrench(q, 0, qs),
+ * wb = wrench(q, qs, qss), [B][N+1][6].  Each output equals tpr_tree_base_wrench_batch on the same arguments in every bit
+ * (products with an exact zero are dropped, no sum is reordered).  Refusals as tpr_tree_torque_terms_batch plus the mount's
+ * above.                                                                                                                  */
+int tpr_tree_base_wrench_terms_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, int B, int N,
+                                     const double *q, const double *qs, const double *qss, double *w0, double *wa, double *wb,
+                                     int flags, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

@@ -27,7 +27,7 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch",
            "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch",
            "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch",
-           "tree_inverse_dynamics_batch", "tree_torque_terms_batch"]
+           "tree_inverse_dynamics_batch", "tree_torque_terms_batch", "base_wrench_batch", "base_wrench_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -817,6 +817,45 @@ def tree_torque_terms_batch(tree, q, qs, qss):
     """(w0, wa, wb) = (tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) of ``tree`` in one launch: what a torque constraint's rows
     are built from.  Each equals :func:`tree_inverse_dynamics_batch` on the same arguments in every bit."""
     return tuple(_rigid_call(tree, "tpr_tree_torque_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(tree.dof,)] * 3, by_grid=True))
+
+
+# the base reaction of a chain or tree (include/toppra_hip.h: tpr_tree_base_wrench_*; the frame is toppra_amd.chain.Mount)
+
+class _AsTree(object):
+    """A :class:`toppra_amd.chain.SerialChain` as the tree-walking entries take it: its links with the parent table -1, 0, 1, ..."""
+
+    def __init__(self, chain):
+        self.dof, self._chain = chain.dof, chain
+        self.parents = (np.arange(chain.dof) - 1).astype(np.int32)
+
+    def c_struct(self, like):
+        model, keep = self._chain.c_struct(like)
+        return model, self.parents, (keep, self.parents)
+
+
+def _base_wrench_call(robot, entry, arrays, names, count, mount, **kwargs):
+    if mount is None:
+        from .chain import Mount
+        mount = Mount()
+    if not (hasattr(mount, "c_struct") and hasattr(mount, "rotation")):
+        raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
+    return _rigid_call(tree, entry, arrays, names, [(6,)] * count, structs=[mount], **kwargs)
+
+
+def base_wrench_batch(robot, q, qd, qdd, mount=None):
+    """The base reaction of ``robot`` (a :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``) at every point: three arrays
+    [..., d] in, [..., 6] = [force; moment about the mount frame's origin] in mount-frame axes out -- the wrench the mount exerts
+    on the robot, every link of every root summed, gravity included.  ``mount``: a :class:`toppra_amd.chain.Mount`, None = the
+    base frame without a platform (include/toppra_hip.h: tpr_tree_base_wrench_batch)."""
+    return _base_wrench_call(robot, "tpr_tree_base_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), 1, mount)[0]
+
+
+def base_wrench_terms_batch(robot, q, qs, qss, mount=None):
+    """(w0, wa, wb) = (w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) [..., 6] of :func:`base_wrench_batch` in one launch: what a
+    constraint on the base reaction builds its rows from (w0 is the static reaction: not zero under gravity).  Each equals
+    :func:`base_wrench_batch` on the same arguments in every bit."""
+    return tuple(_base_wrench_call(robot, "tpr_tree_base_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, mount, by_grid=True))
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

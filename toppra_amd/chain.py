@@ -110,6 +110,56 @@ class Payload(object):
         return body
 
 
+class Mount(object):
+    """What a robot is bolted to or stands on: the frame its base reaction is reported in, and an optional rigid platform.
+
+    Parameters
+    ----------
+    rotation : [3, 3], columns = the mount frame's axes in base coordinates (orthonormal, determinant +1, to 1e-12); None =
+        identity.
+    origin : [3] the mount frame's origin in base coordinates: the point the moment is taken about.
+    mass : >= 0, com : [3] -- a rigid platform fixed to the base (the cart or column whose weight keeps a mobile manipulator
+        upright): its mass and its centre of mass in base coordinates.  It adds ``-mass * gravity`` at ``com`` to every
+        evaluation.
+
+    The default is the base frame itself without a platform.
+    """
+
+    def __init__(self, rotation=None, origin=(0.0, 0.0, 0.0), mass=0.0, com=(0.0, 0.0, 0.0)):
+        arr = {"rotation": np.eye(3) if rotation is None else rotation, "origin": origin, "mass": mass, "com": com}
+        for name in arr:
+            try:
+                arr[name] = np.array(arr[name], dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("%s is not an array of numbers" % name)
+        want = {"rotation": (3, 3), "origin": (3,), "mass": (), "com": (3,)}
+        for name, value in arr.items():
+            if value.shape != want[name]:
+                raise ValueError("%s must have shape %s, got %s" % (name, list(want[name]), list(value.shape)))
+            if not np.all(np.isfinite(value)):
+                raise ValueError("%s holds a value that is not finite" % name)
+        if arr["mass"] < 0:
+            raise ValueError("mass must be >= 0")
+        rot = arr["rotation"]
+        if np.any(np.abs(rot.T @ rot - np.eye(3)) > 1e-12) or abs(np.linalg.det(rot) - 1.0) > 1e-12:
+            raise ValueError("rotation must be orthonormal with determinant +1 (to 1e-12)")
+        self.mass = float(arr["mass"])
+        self.rotation, self.origin, self.com = rot, arr["origin"], arr["com"]
+        for value in (self.rotation, self.origin, self.com):
+            value.flags.writeable = False
+
+    def __repr__(self):
+        return "Mount(origin=%s, mass=%g)" % (self.origin.tolist(), self.mass)
+
+    def c_struct(self, robot=None):
+        """The tpr_mount of a call (a host struct, passed to the kernels by value); the same for every robot."""
+        frame = _capi.tpr_mount(mass=self.mass)
+        frame.rot[:] = self.rotation.ravel().tolist()
+        frame.origin[:] = self.origin.tolist()
+        frame.com[:] = self.com.tolist()
+        return frame
+
+
 class ControlPoints(object):
     """Points fixed to ANY links of a chain -- an elbow, a camera bracket, a cable carrier: what the whole-arm speed and
     acceleration limits are set on.
@@ -316,6 +366,19 @@ class SerialChain(object):
         limit on the points' accelerations needs; acc(q, 0, 0) is an exact zero."""
         return _batch.chain_points_acceleration_terms_batch(self, q, qs, qss, points)
 
+    def base_wrench(self, q, qd, qdd, mount=None):
+        """The base reaction [..., 6] = [force; moment]: the wrench the mount exerts ON the robot, summed over every link,
+        gravity included -- at rest the force holds up the weight.  ``mount`` (a :class:`Mount`, None = the base frame, no
+        platform) gives the frame: the moment is about its origin, both parts are in its axes.  With the mount bound
+        (``lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount)``) a valid batched ``inv_dyn`` of
+        :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
+        return _batch.base_wrench_batch(self, q, qd, qdd, mount)
+
+    def base_wrench_terms(self, q, qs, qss, mount=None):
+        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
+        reaction needs; the first is the static reaction, which gravity keeps from being zero."""
+        return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
+
     def with_payload(self, payload):
         """A new chain whose last link carries ``payload``: its mass, centre of mass and inertia merged into the last link's
         (parallel-axis theorem).  Host only; the contact frame plays no part.  Torque limits on the result load the joints
@@ -402,6 +465,19 @@ class KinematicTree(object):
     def torque_terms(self, q, qs, qss):
         """(tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: the three evaluations a torque constraint needs."""
         return _batch.tree_torque_terms_batch(self, q, qs, qss)
+
+    def base_wrench(self, q, qd, qdd, mount=None):
+        """The base reaction [..., 6] = [force; moment]: the wrench the mount exerts ON the robot, summed over every link,
+        gravity included -- at rest the force holds up the weight.  ``mount`` (a :class:`Mount`, None = the base frame, no
+        platform) gives the frame: the moment is about its origin, both parts are in its axes.  With the mount bound
+        (``lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount)``) a valid batched ``inv_dyn`` of
+        :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
+        return _batch.base_wrench_batch(self, q, qd, qdd, mount)
+
+    def base_wrench_terms(self, q, qs, qss, mount=None):
+        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
+        reaction needs; the first is the static reaction, which gravity keeps from being zero."""
+        return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
 
     def path_to(self, link):
         """The links from the base to ``link``, in order: the joints that move it."""

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .chain import ControlPoints, KinematicTree, Payload, SerialChain
+from .chain import ControlPoints, KinematicTree, Mount, Payload, SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -733,6 +733,58 @@ class BatchToolWrenchConstraint(_BatchChainRows):
 
     def _terms(self, q, qs, qss):
         return self.chain.tool_wrench_terms(q, qs, qss, self.payload)
+
+
+class BatchBaseWrenchConstraint(_BatchChainRows):
+    """A limit on the base reaction of a robot, for a batch:  F w <= g  on  w(q, qd, qdd) = [force; moment], the wrench the
+    mount exerts ON the robot -- every link of every root summed, gravity included; the moment about the origin of ``mount``'s
+    frame, both parts in its axes (:meth:`toppra_amd.chain.SerialChain.base_wrench`).  It is what a pedestal, a linear axis, a
+    ceiling plate or a machine frame limits at its flange, and what keeps a mobile manipulator from tipping, sliding or spinning
+    on its footprint.  It is the reference's ``SecondOrderConstraint`` with an ``inv_dyn`` that returns that wrench instead of
+    joint torques; the three evaluations the rows need come from one launch.
+
+    ``robot``: a :class:`toppra_amd.chain.SerialChain` or a :class:`toppra_amd.chain.KinematicTree` (two arms on a torso: the
+    reaction is the sum over both); ``mount``: a :class:`toppra_amd.chain.Mount`, None = the base frame without a platform.  The
+    limits are given in one of three spellings (mixing them is a ValueError):
+
+    ``force`` / ``moment`` (either or both): a scalar ``wmax`` (-wmax <= component <= wmax on each mount-frame axis), [3, 2] or
+    [B, 3, 2] (lower, upper) -- the data-sheet box of a flange.  Each part given adds six rows, the signed identity on that part
+    with g = [upper; -lower]; with both, the force's rows come first.
+
+    ``F`` [m, 6], [B, m, 6] or [B, N+1, m, 6] with ``g`` [m], [B, m] or [B, N+1, m], as ``BatchSecondOrderConstraint`` takes
+    them.
+
+    :meth:`surface_contact`: the contact wrench cone of a flat rectangular footprint with Coulomb friction.
+
+    The constraint is INFEASIBLE unless F w(q, 0, 0) <= g holds at every gridpoint: standing still must satisfy it (the static
+    reaction carries the robot's and the platform's weight, and it enters every stage's rows).  Defaults are the reference's for
+    ``SecondOrderConstraint`` (Interpolation).  Needs the path positions: a ``from_path_samples`` batch must be given ``q``.
+    Per-trajectory mounts, a floating base, a true (conic) friction cone and non-rectangular footprints are out of scope."""
+
+    def __init__(self, robot, mount=None, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
+        if not isinstance(robot, (SerialChain, KinematicTree)):
+            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
+        if mount is None:
+            mount = Mount()
+        if not isinstance(mount, Mount):
+            raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+        super(BatchBaseWrenchConstraint, self).__init__(
+            robot, _six_wide_limits(("force", force), ("moment", moment), F, g), discretization_scheme,
+            "base wrench limit, %d dof" % robot.dof)
+        self.robot, self.mount = robot, mount
+        self.force, self.moment = force, moment
+
+    @classmethod
+    def surface_contact(cls, robot, mu, half_extents, mount=None, normal_force_min=0.0, **kwargs):
+        """The robot (and its platform) stands on a flat rectangular footprint [-X, X] x [-Y, Y] (``half_extents`` = (X, Y)) in
+        the mount frame's xy-plane, normal +z, centred at the frame's origin, with Coulomb friction ``mu``: the contact wrench
+        cone of :meth:`BatchToolWrenchConstraint.surface_contact`, its rows unchanged, on the floor -> robot wrench -- no tipping
+        over an edge, no sliding, no spinning."""
+        F, g = BatchToolWrenchConstraint.surface_contact_rows(mu, half_extents, normal_force_min)
+        return cls(robot, mount, F=F, g=g, **kwargs)
+
+    def _terms(self, q, qs, qss):
+        return self.robot.base_wrench_terms(q, qs, qss, self.mount)
 
 
 def _point_limits(count, linear, F, g):

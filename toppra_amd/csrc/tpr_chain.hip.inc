@@ -16,6 +16,37 @@
 
 namespace tpr {
 
+// ---- staging a block's rows through LDS: the tool kernels below, and the base-reaction kernels (tpr_mount.hip.inc), which take
+// this part of the file alone (TPR_CHAIN_STAGING_ONLY: a unit that saw the kernels below would carry a second copy of each) -----
+// A block is one wave of 64 consecutive points.  Their q, q', q'' [64][d] are contiguous in memory and pass through LDS, as
+// in the 1 .. 8-dof torque kernels but with a runtime d: loaded with consecutive lanes on consecutive doubles, read back one
+// row per lane at the odd pitch d | 1 (conflict-free).  Read in place instead, a wave's rows -- 64 lanes x 3 arrays x d doubles,
+// re-read link after link -- outgrow the caches from about 12 dof on and the lines come from memory again and again.  The
+// 6-wide outputs leave through the same LDS at pitch 7.  Dynamic LDS: chain_accel_lds_bytes.
+__host__ __device__ constexpr size_t chain_accel_lds_bytes(int d, int outputs) {
+    const size_t in = 3 * (size_t)kChainBlock * (size_t)(d | 1), out = (size_t)outputs * kChainBlock * 7;
+    return (in > out ? in : out) * sizeof(double);
+}
+
+// The block's rows [npts][d] of three arrays into LDS at `pitch`: (row, column) of element k advance without a division.
+__device__ __forceinline__ void chain_rows_load(double *b0, double *b1, double *b2, const double *s0, const double *s1, const double *s2,
+                                                size_t g0, int npts, int d, int pitch) {
+    const size_t base = g0 * (size_t)d;
+    const int step_r = kChainBlock / d, step_c = kChainBlock % d;
+    int r = (int)threadIdx.x / d, c = (int)threadIdx.x % d;
+    for (int k = threadIdx.x; k < npts * d; k += kChainBlock) {
+        const int at = r * pitch + c;
+        b0[at] = s0[base + k]; b1[at] = s1[base + k]; b2[at] = s2[base + k];
+        r += step_r; c += step_c;
+        if (c >= d) { c -= d; ++r; }
+    }
+}
+// ... and a block's outputs [npts][6] from LDS at pitch 7.
+__device__ __forceinline__ void chain_accel_rows_store(const double *buf, double *dst, size_t g0, int npts) {
+    for (int k = threadIdx.x; k < npts * 6; k += kChainBlock) dst[g0 * 6 + k] = buf[(k / 6) * 7 + (k % 6)];
+}
+
+#ifndef TPR_CHAIN_STAGING_ONLY
 // ---- 1 .. 8 dof: a block's 64 points through LDS, a point's state in registers ------------------------------------------
 template <int D>
 struct ChainTile {
@@ -142,34 +173,7 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_velocity_kernel
 //   angular acceleration, world axes; no gravity.  Per evaluation the state is (w, wd, a) of the current link, W is shared.
 // Every output passes through "+ 0.0": a zero leaves as +0 whatever the signs of the vanishing products were, so the fused
 // outputs equal the single evaluation's in every bit and acc(q, 0, 0) is the +0 a constraint's w0 is given as.
-// A block is one wave of 64 consecutive points.  Their q, q', q'' [64][d] are contiguous in memory and pass through LDS, as
-// in the 1 .. 8-dof torque kernels but with a runtime d: loaded with consecutive lanes on consecutive doubles, read back one
-// row per lane at the odd pitch d | 1 (conflict-free).  Read in place instead, a wave's rows -- 64 lanes x 3 arrays x d doubles,
-// re-read link after link -- outgrow the caches from about 12 dof on and the lines come from memory again and again.  The
-// 6-wide outputs leave through the same LDS at pitch 7.  Dynamic LDS: chain_accel_lds_bytes.
-__host__ __device__ constexpr size_t chain_accel_lds_bytes(int d, int outputs) {
-    const size_t in = 3 * (size_t)kChainBlock * (size_t)(d | 1), out = (size_t)outputs * kChainBlock * 7;
-    return (in > out ? in : out) * sizeof(double);
-}
-
-// The block's rows [npts][d] of three arrays into LDS at `pitch`: (row, column) of element k advance without a division.
-__device__ __forceinline__ void chain_rows_load(double *b0, double *b1, double *b2, const double *s0, const double *s1, const double *s2,
-                                                size_t g0, int npts, int d, int pitch) {
-    const size_t base = g0 * (size_t)d;
-    const int step_r = kChainBlock / d, step_c = kChainBlock % d;
-    int r = (int)threadIdx.x / d, c = (int)threadIdx.x % d;
-    for (int k = threadIdx.x; k < npts * d; k += kChainBlock) {
-        const int at = r * pitch + c;
-        b0[at] = s0[base + k]; b1[at] = s1[base + k]; b2[at] = s2[base + k];
-        r += step_r; c += step_c;
-        if (c >= d) { c -= d; ++r; }
-    }
-}
-// ... and a block's outputs [npts][6] from LDS at pitch 7.
-__device__ __forceinline__ void chain_accel_rows_store(const double *buf, double *dst, size_t g0, int npts) {
-    for (int k = threadIdx.x; k < npts * 6; k += kChainBlock) dst[g0 * 6 + k] = buf[(k / 6) * 7 + (k % 6)];
-}
-
+// How a block's rows pass through LDS (chain_accel_lds_bytes, chain_rows_load, chain_accel_rows_store) is at the head of this file.
 template <int Level>
 __device__ __forceinline__ void chain_tool_accel_put(const M3 &W, const ChainKin &K, V3 tool, double *o) {
     V3 al = K.a + cross(K.wd, tool);
@@ -511,5 +515,7 @@ __device__ __forceinline__ void chain_points_accel(const ChainPointsAccelArgs &A
 
 static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_kernel(ChainPointsAccelArgs A) { chain_points_accel<false>(A); }
 static __global__ void __launch_bounds__(kChainBlock) chain_points_accel_terms_kernel(ChainPointsAccelArgs A) { chain_points_accel<true>(A); }
+
+#endif  // TPR_CHAIN_STAGING_ONLY
 
 }  // namespace tpr

@@ -1606,10 +1606,11 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
 }
 }  // extern "C"
 
-// ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip) --
+// ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip;
+// tpr_mount.hip.inc, tpr_mount_tu.hip) -----------------------------------------------------------------------------------------
 // One host path for the family: an entry is its argument checks, in an order that is its own and is behaviour (which refusal
 // wins when two arguments are bad: tests/test_rigid_refusal_order.py), then run_rigid() with what it stages and what it launches.
-#include "tpr_tree_args.hpp"
+#include "tpr_mount_args.hpp"
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
@@ -1622,6 +1623,8 @@ __attribute__((visibility("hidden"))) int tpr_tu_chain_points_speed_launch(const
 __attribute__((visibility("hidden"))) int tpr_tu_chain_points_accel_launch(const tpr::ChainPointsAccelArgs *, int terms, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_tree_dynamics_launch(const tpr::TreeDynArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_tree_terms_launch(const tpr::TreeTermsArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_launch(const tpr::MountWrenchArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_terms_launch(const tpr::MountWrenchTermsArgs *, int forks, hipStream_t);
 }
 namespace {
 // The gridpoints of a batch given as (B, N).
@@ -1726,6 +1729,29 @@ int check_tree(const tpr_chain *links, const int32_t *parent, long long npoints,
                                            std::to_string(TPR_TREE_MAX_FORKS));
     return TPR_E_OK;
 }
+// A mount is a host struct of 16 doubles: read here, handed to the kernels by value; null = the base frame, no platform.  Its
+// frame is held to what a chain's rotations and a payload's frame are: orthonormal with determinant +1, to 1e-12.
+static_assert(sizeof(tpr_mount) == 16 * sizeof(double) && sizeof(tpr::MountFrame) == sizeof(tpr_mount), "tpr_mount is 16 packed doubles");
+int check_mount(const tpr_mount *m, const char *who) {
+    if (!m) return TPR_E_OK;
+    const double *v = m->rot, *R = m->rot;
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(v[k])) return fail(TPR_E_BADARG, std::string(who) + ": every entry of the mount must be finite");
+    bool frame = true;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            frame = frame && std::fabs(R[r] * R[c] + R[3 + r] * R[3 + c] + R[6 + r] * R[6 + c] - (r == c ? 1.0 : 0.0)) <= 1e-12;
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    if (!frame || !(std::fabs(det - 1.0) <= 1e-12))
+        return fail(TPR_E_BADARG, std::string(who) + ": the mount's rot must be orthonormal with determinant +1 (to 1e-12)");
+    if (!(m->mass >= 0.0)) return fail(TPR_E_BADARG, std::string(who) + ": the mount's mass must be >= 0");
+    return TPR_E_OK;
+}
+tpr::MountFrame stage_mount(const tpr_mount *m) {
+    tpr::MountFrame P{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}, 0.0, {0.0, 0.0, 0.0}};
+    if (m) std::memcpy(&P, m, sizeof(P));
+    return P;
+}
 
 // The argument block of a launch on the links `c`: the model staged, the point count set, the rest zero.
 template <class Args>
@@ -1761,6 +1787,7 @@ extern "C" {
 int tpr_chain_bytes(void) { return (int)sizeof(tpr_chain); }
 int tpr_payload_bytes(void) { return (int)sizeof(tpr_payload); }
 int tpr_chain_points_bytes(void) { return (int)sizeof(tpr_chain_points); }
+int tpr_mount_bytes(void) { return (int)sizeof(tpr_mount); }
 
 int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
                                      double *tau, int flags, void *stream_) {
@@ -1960,5 +1987,43 @@ int tpr_tree_torque_terms_batch(const tpr_chain *links, const int32_t *parent, i
         stage_outputs(S, n, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
         return A;
     }, [forks](const tpr::TreeTermsArgs *A, hipStream_t stream) { return tpr_tu_tree_terms_launch(A, forks, stream); });
+}
+
+int tpr_tree_base_wrench_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, long long npoints, const double *q,
+                               const double *qd, const double *qdd, double *wrench, int flags, void *stream_) {
+    const char *who = "tpr_tree_base_wrench_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_mount(mount, who)) return rc;
+    if (int rc = required(q && qd && qdd && wrench, who, "q, qd, qdd, wrench")) return rc;
+    return run_rigid(flags, wrench, stream_, npoints, "tpr_tree_base_wrench_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::MountWrenchArgs>(links, npoints, S, false);
+        A.T = T;
+        A.P = stage_mount(mount);
+        stage_inputs(S, (size_t)npoints * (size_t)links->d, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.wrench, wrench}});
+        return A;
+    }, [forks](const tpr::MountWrenchArgs *A, hipStream_t stream) { return tpr_tu_mount_wrench_launch(A, forks, stream); });
+}
+
+int tpr_tree_base_wrench_terms_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, int B, int N, const double *q,
+                                     const double *qs, const double *qss, double *w0, double *wa, double *wb, int flags, void *stream_) {
+    const char *who = "tpr_tree_base_wrench_terms_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_mount(mount, who)) return rc;
+    if (int rc = required(q && qs && qss && w0 && wa && wb, who, "q, qs, qss, w0, wa, wb")) return rc;
+    return run_rigid(flags, w0, stream_, npoints, "tpr_tree_base_wrench_terms_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::MountWrenchTermsArgs>(links, npoints, S, false);
+        A.T = T;
+        A.P = stage_mount(mount);
+        stage_inputs(S, (size_t)npoints * (size_t)links->d, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, 6 * (size_t)npoints, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, [forks](const tpr::MountWrenchTermsArgs *A, hipStream_t stream) { return tpr_tu_mount_wrench_terms_launch(A, forks, stream); });
 }
 }  // extern "C"
