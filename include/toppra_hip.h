@@ -596,6 +596,44 @@ int tpr_tree_base_wrench_terms_batch(const tpr_chain *links, const int32_t *pare
                                      const double *q, const double *qs, const double *qss, double *w0, double *wa, double *wb,
                                      int flags, void *stream);
 
+/* ---- joint loads: the wrench ACROSS any joint of a chain or tree, for a batch -------------------------------------------------
+ * What a gearbox's output bearing, a linear guide's carriage or a link's flange carries beside the joint's own torque: the tilting
+ * moment and the axial and radial force.  (f_i, n_i) of the recursion of tpr_tree_inverse_dynamics_batch is the force the parent
+ * side exerts ON link i through joint i and its moment about link i's origin, in link i's axes, gravity included (at rest f is the
+ * support of the weight of everything that hangs on the joint; for a fork, every child branch).  A SECTION k reports it in a frame
+ * fixed to link link[k]:
+ *   rot[k] [3][3] row-major, columns = the section frame's axes in link coordinates (orthonormal, determinant +1, to 1e-12);
+ *   origin[k] [3] its origin in link coordinates;
+ *   w_k = [ rot' f ; rot' (n - origin x f) ]   -- with rot = 1, origin = 0: axis . n (revolute) or axis . f (prismatic) is the
+ *   joint's torque or force.
+ * A set holds 1 .. TPR_JOINT_MAX_SECTIONS sections, several may share a joint, and each section's output is independent of what
+ * else is in the set.  ALWAYS A HOST STRUCT, with or without TPR_DEVICE_PTRS: it travels to the kernels by value.            */
+#define TPR_JOINT_MAX_SECTIONS 8
+typedef struct tpr_joint_sections {
+    int32_t count;
+    int32_t link[TPR_JOINT_MAX_SECTIONS];
+    double rot[TPR_JOINT_MAX_SECTIONS][9];
+    double origin[TPR_JOINT_MAX_SECTIONS][3];
+} tpr_joint_sections;
+/* ABI guard, as tpr_mount_bytes: bytes of tpr_joint_sections in the library.                                             */
+int tpr_joint_sections_bytes(void);
+/* wrench(q, qd, qdd), [npoints][count][6] in the set's order.  The plain link-local recursion on the tree kernels' walk (their
+ * summation order at a fork), with (f, n) kept; the way down stops at the lowest-numbered section link.  One wave of 64 points per
+ * block, the tree kernels' dynamic LDS (per-link state plus one bank per fork: at most 149 504 bytes), outputs by direct stores.
+ * A zero result is +0.  links, parent and their refusals are those of tpr_tree_inverse_dynamics_batch; then the sections: NULL,
+ * a count outside 1 .. 8, a link outside 0 .. d-1, a non-finite entry, a rot that is not orthonormal with determinant +1 to 1e-12
+ * (TPR_E_BADARG); then NULL arrays.                                                                                       */
+int tpr_tree_joint_wrench_batch(const tpr_chain *links, const int32_t *parent, const tpr_joint_sections *sections, long long npoints,
+                                const double *q, const double *qd, const double *qdd, double *wrench, int flags, void *stream);
+/* The three evaluations a second-order constraint on those wrenches needs (tpr_second_order_block with p = 6 count), in one
+ * launch: w0 = wrench(q, 0, 0) -- the static load, not zero under gravity --, wa = wrench(q, 0, qs), wb = wrench(q, qs, qss),
+ * [B][N+1][count][6].  One pass over the links where the fused per-link state fits the LDS (a chain to 18 dof, one fork to 17),
+ * otherwise the three evaluations one after another in the same launch.  Each output equals tpr_tree_joint_wrench_batch on the
+ * same arguments in every bit.  Refusals: B, N first, then as above.                                                       */
+int tpr_tree_joint_wrench_terms_batch(const tpr_chain *links, const int32_t *parent, const tpr_joint_sections *sections, int B, int N,
+                                      const double *q, const double *qs, const double *qss, double *w0, double *wa, double *wb,
+                                      int flags, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

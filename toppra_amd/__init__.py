@@ -18,8 +18,8 @@ import logging
 from . import algorithm, batch, chain, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
-from .chain import ControlPoints, KinematicTree, Mount, Payload, SerialChain
-from .constraint import BatchBaseWrenchConstraint, BatchToolWrenchConstraint
+from .chain import ControlPoints, JointSections, KinematicTree, Mount, Payload, SerialChain
+from .constraint import BatchBaseWrenchConstraint, BatchJointLoadConstraint, BatchToolWrenchConstraint
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
@@ -27,4 +27,4 @@ logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 __all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
            "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint", "ControlPoints", "KinematicTree",
-           "Mount", "BatchBaseWrenchConstraint"]
+           "Mount", "BatchBaseWrenchConstraint", "JointSections", "BatchJointLoadConstraint"]

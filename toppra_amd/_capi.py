@@ -87,6 +87,14 @@ class tpr_mount(C.Structure):
     _fields_ = [("rot", C.c_double * 9), ("origin", C.c_double * 3), ("mass", C.c_double), ("com", C.c_double * 3)]
 
 
+JOINT_MAX_SECTIONS = 8  # TPR_JOINT_MAX_SECTIONS: sections in one set
+
+
+class tpr_joint_sections(C.Structure):
+    _fields_ = [("count", C.c_int32), ("link", C.c_int32 * JOINT_MAX_SECTIONS), ("rot", (C.c_double * 9) * JOINT_MAX_SECTIONS),
+                ("origin", (C.c_double * 3) * JOINT_MAX_SECTIONS)]
+
+
 CHAIN_MAX_POINTS = 16  # TPR_CHAIN_MAX_POINTS: control points in one set
 
 
@@ -133,6 +141,7 @@ EXPORTS = (
     "tpr_chain_points_acceleration_terms_batch",
     "tpr_tree_inverse_dynamics_batch", "tpr_tree_torque_terms_batch",
     "tpr_mount_bytes", "tpr_tree_base_wrench_batch", "tpr_tree_base_wrench_terms_batch",
+    "tpr_joint_sections_bytes", "tpr_tree_joint_wrench_batch", "tpr_tree_joint_wrench_terms_batch",
 )
 
 _lib = None
@@ -237,14 +246,15 @@ def load():
                                  "binding declares %d" % (L.tpr_bound_source_bytes(), C.sizeof(tpr_bound_source)))
         L.tpr_stage_boxes_batch.restype = C.c_int
         L.tpr_stage_boxes_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, C.c_int, C.POINTER(tpr_bound_source), C.c_int, V, V, V]
-        # the rigid-body family: four by-value structs with their size checks
-        for struct in (tpr_chain, tpr_payload, tpr_chain_points, tpr_mount):
+        # the rigid-body family: five by-value structs with their size checks
+        for struct in (tpr_chain, tpr_payload, tpr_chain_points, tpr_mount, tpr_joint_sections):
             size = getattr(L, struct.__name__ + "_bytes")
             size.restype, size.argtypes = C.c_int, []
             if size() != C.sizeof(struct):
                 raise ToppraHipError("libtoppra_hip.so was built from another header: its %s takes %d bytes, this "
                                      "binding declares %d" % (struct.__name__, size(), C.sizeof(struct)))
         CP, PP, XP, MP = C.POINTER(tpr_chain), C.POINTER(tpr_payload), C.POINTER(tpr_chain_points), C.POINTER(tpr_mount)
+        JP = C.POINTER(tpr_joint_sections)
         I, LL = C.c_int, C.c_longlong
         # One table of signatures, all returning int.  The dense-row passes: a source's leading arguments (the problem; the boxed
         # entries' low, high), the pass's own, the stream ...
@@ -268,7 +278,9 @@ def load():
                 "tpr_tree_inverse_dynamics_batch": [CP, V, LL, V, V, V, V],
                 "tpr_tree_torque_terms_batch": [CP, V, I, I, V, V, V, V, V, V],
                 "tpr_tree_base_wrench_batch": [CP, V, MP, LL, V, V, V, V],
-                "tpr_tree_base_wrench_terms_batch": [CP, V, MP, I, I, V, V, V, V, V, V]}.items()})
+                "tpr_tree_base_wrench_terms_batch": [CP, V, MP, I, I, V, V, V, V, V, V],
+                "tpr_tree_joint_wrench_batch": [CP, V, JP, LL, V, V, V, V],
+                "tpr_tree_joint_wrench_terms_batch": [CP, V, JP, I, I, V, V, V, V, V, V]}.items()})
         for name, argtypes in signatures.items():
             entry = getattr(L, name)
             entry.restype, entry.argtypes = C.c_int, argtypes

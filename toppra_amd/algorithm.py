@@ -328,8 +328,8 @@ class BatchTOPPRA(object):
         for con in self.constraints:
             if not (hasattr(con, "block") and hasattr(con, "rows_per_stage")):
                 raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint, BatchSecondOrderConstraint, "
-                                          "BatchCartesianAccelerationConstraint, BatchPointAccelerationConstraint, BatchBaseWrenchConstraint and "
-                                          "BatchToolWrenchConstraint are supported)" % type(con).__name__)
+                                          "BatchCartesianAccelerationConstraint, BatchPointAccelerationConstraint, BatchJointLoadConstraint, "
+                                          "BatchBaseWrenchConstraint and BatchToolWrenchConstraint are supported)" % type(con).__name__)
             con.check(B, N, d)
             nC += con.rows_per_stage(d) or 0
         if nC > _capi.MAX_DENSE_ROWS:

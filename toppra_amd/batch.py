@@ -27,7 +27,8 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "chain_tool_acceleration_batch", "chain_tool_acceleration_terms_batch",
            "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch",
            "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch",
-           "tree_inverse_dynamics_batch", "tree_torque_terms_batch", "base_wrench_batch", "base_wrench_terms_batch"]
+           "tree_inverse_dynamics_batch", "tree_torque_terms_batch", "base_wrench_batch", "base_wrench_terms_batch",
+           "joint_wrench_batch", "joint_wrench_terms_batch"]
 
 
 def _stream_ptr(like):
@@ -856,6 +857,31 @@ def base_wrench_terms_batch(robot, q, qs, qss, mount=None):
     constraint on the base reaction builds its rows from (w0 is the static reaction: not zero under gravity).  Each equals
     :func:`base_wrench_batch` on the same arguments in every bit."""
     return tuple(_base_wrench_call(robot, "tpr_tree_base_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, mount, by_grid=True))
+
+
+# the wrench across any joint of a chain or tree (include/toppra_hip.h: tpr_tree_joint_wrench_*; the set is toppra_amd.chain.JointSections)
+
+def _joint_wrench_call(robot, entry, arrays, names, count, sections, **kwargs):
+    if not (hasattr(sections, "c_struct") and hasattr(sections, "joints")):
+        raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
+    set_ = sections.c_struct(robot)  # (a link outside the robot: ValueError, before anything else)
+    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
+    return _rigid_call(tree, entry, arrays, names, [(int(set_.count), 6)] * count, structs=[set_], **kwargs)
+
+
+def joint_wrench_batch(robot, q, qd, qdd, sections):
+    """The wrench across the joints of ``sections`` (a :class:`toppra_amd.chain.JointSections`) of ``robot`` (a
+    :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``) at every point: three arrays [..., d] in, [..., S, 6] out in the
+    set's order -- per section [force; moment about its origin] in its axes: the wrench the parent side exerts ON the section's
+    link through its joint, gravity included (include/toppra_hip.h: tpr_tree_joint_wrench_batch)."""
+    return _joint_wrench_call(robot, "tpr_tree_joint_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), 1, sections)[0]
+
+
+def joint_wrench_terms_batch(robot, q, qs, qss, sections):
+    """(w0, wa, wb) = (w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) [..., S, 6] of :func:`joint_wrench_batch` in one launch: what a
+    constraint on joint loads builds its rows from (w0 is the static load: not zero under gravity).  Each equals
+    :func:`joint_wrench_batch` on the same arguments in every bit."""
+    return tuple(_joint_wrench_call(robot, "tpr_tree_joint_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, sections, by_grid=True))
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtoppra_hip.so")
-SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_sampled_tu.hip", "tpr_rows_tu.hip", "tpr_boxed_tu.hip", "tpr_chain_tu.hip", "tpr_tree_tu.hip", "tpr_mount_tu.hip"]
+SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_sampled_tu.hip", "tpr_rows_tu.hip", "tpr_boxed_tu.hip", "tpr_chain_tu.hip", "tpr_tree_tu.hip", "tpr_mount_tu.hip", "tpr_joint_tu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-Wno-unused-variable"]
 
@@ -103,6 +103,7 @@ def compile_jobs(measurement=False):
     jobs.append(("chain", "tpr_chain_tu.hip", []))  # a rigid-body chain: inverse dynamics and tool velocity at every gridpoint
     jobs.append(("tree", "tpr_tree_tu.hip", []))  # a kinematic tree (branched robots): inverse dynamics at every gridpoint
     jobs.append(("mount", "tpr_mount_tu.hip", []))  # the base reaction of a chain or tree: the wrench on its mount at every gridpoint
+    jobs.append(("joint", "tpr_joint_tu.hip", []))  # joint loads of a chain or tree: the wrench across any joint at every gridpoint
     for d in range(1, max_dof + 1):
         for part, flags in sorted(({0: []} if measurement else CERT_UNITS[d]).items()):
             if part == 0:
@@ -151,7 +152,7 @@ def _compile_and_link(target, flags, defines, verbose):
             name, src, extra = job
             src = os.path.join(CSRC, src)
             obj = os.path.join(tmp, name + ".o")
-            verify = check and name.startswith(("cert", "rows", "boxed", "chain", "tree", "mount"))  # family 3, the row-assembly, stage-box, chain, tree and mount units
+            verify = check and name.startswith(("cert", "rows", "boxed", "chain", "tree", "mount", "joint"))  # family 3, the row-assembly, stage-box, chain, tree, mount and joint units
             fkey = hashlib.sha256((cc_id + " ".join(cflags + extra) + (" [checked]" if verify else "")).encode()).hexdigest()[:12]
             skey = hashlib.sha256((dep_hash.hexdigest() + os.path.basename(src)).encode()).hexdigest()[:12]
             cached = os.path.join(cache, "%s_%s_%s.o" % (name, fkey, skey))

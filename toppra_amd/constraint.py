@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .chain import ControlPoints, KinematicTree, Mount, Payload, SerialChain
+from .chain import ControlPoints, JointSections, KinematicTree, Mount, Payload, SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -785,6 +785,152 @@ class BatchBaseWrenchConstraint(_BatchChainRows):
 
     def _terms(self, q, qs, qss):
         return self.robot.base_wrench_terms(q, qs, qss, self.mount)
+
+
+def _section_limits(count, force, moment, F, g):
+    """The limits of a constraint on the 6 S-wide wrenches of S sections, section-major, given either as boxes -- ``force`` /
+    ``moment``: None, a scalar, [S] (a magnitude per section), [S, 3, 2] or [B, S, 3, 2] (lower, upper) -- or as rows F, g:
+    (F, g, the B of per-trajectory boxes or None).  Each part given adds six rows per section, the signed identity on that
+    part with g = [upper; -lower]; the force's rows come first within a section, the sections follow in order."""
+    boxes, rows = force is not None or moment is not None, F is not None or g is not None
+    if boxes and rows:
+        raise ValueError("give the limits either as force / moment or as F and g, not both")
+    if not boxes and not rows:
+        raise ValueError("no limit given: one of force, moment, or F with g, is required")
+    width = 6 * count
+    if not boxes:
+        return _row_limits(F, g, width, "[m, 6 S], [B, m, 6 S] or [B, N+1, m, 6 S] with 6 S = %d" % width)
+    limit_batch, parts = None, []
+    for name, lim, at in (("force", force, 0), ("moment", moment, 3)):
+        if lim is None:
+            continue
+        lim = _host(lim)
+        if lim.ndim == 0:
+            lim = np.full(count, float(lim))
+        if lim.shape == (count,):
+            lim = np.stack([np.repeat(-lim[:, None], 3, 1), np.repeat(lim[:, None], 3, 1)], -1)
+        if lim.ndim not in (3, 4) or lim.shape[-3:] != (count, 3, 2):
+            raise ValueError("%s must be a scalar or have shape [S], [S, 3, 2] or [B, S, 3, 2] with S = %d, got %s"
+                             % (name, count, list(lim.shape)))
+        if not np.all(np.isfinite(lim)):
+            raise ValueError("%s holds a limit that is not finite" % name)
+        if np.any(lim[..., 0] > lim[..., 1]):
+            raise ValueError("%s holds a lower limit above its upper limit" % name)
+        if lim.ndim == 4:
+            if limit_batch not in (None, lim.shape[0]):
+                raise ValueError("force and moment are given per trajectory for %d and %d trajectories" % (limit_batch, lim.shape[0]))
+            limit_batch = int(lim.shape[0])
+        parts.append((at, np.concatenate((lim[..., 1], -lim[..., 0]), -1)))  # [..., S, 6] = [upper; -lower] per section
+    per = 6 * len(parts)  # rows per section
+    Fm = np.zeros((per * count, width))
+    for k in range(count):
+        for j, (at, _) in enumerate(parts):
+            r, c = per * k + 6 * j, 6 * k + at
+            Fm[r:r + 3, c:c + 3], Fm[r + 3:r + 6, c:c + 3] = np.eye(3), -np.eye(3)
+    lead = () if limit_batch is None else (limit_batch,)
+    gm = np.concatenate([np.broadcast_to(gp, lead + (count, 6)) for _, gp in parts], -1)  # [..., S, per]
+    return Fm, np.ascontiguousarray(gm.reshape(lead + (per * count,))), limit_batch
+
+
+class BatchJointLoadConstraint(_BatchChainRows):
+    """A limit on the loads ACROSS joints of a robot, for a batch:  F w <= g  on  w(q, qd, qdd) = the wrenches of ``sections``,
+    [6 S] section-major, per section [force; moment] -- what the parent side exerts ON the section's link through its joint, the
+    moment about the section's origin, both parts in the section's axes, gravity included
+    (:meth:`toppra_amd.chain.SerialChain.joint_wrenches`).  It is what a gearbox's output bearing (tilting moment, axial and
+    radial force), a linear guide's carriage or a slender link's flange limits beside the joint's rated torque, and what a light
+    arm with a heavy tool oversteps first.  It is the reference's ``SecondOrderConstraint`` with an ``inv_dyn`` that returns those
+    wrenches instead of joint torques; the three evaluations the rows need come from one launch for the whole set.
+
+    ``robot``: a :class:`toppra_amd.chain.SerialChain` or a :class:`toppra_amd.chain.KinematicTree`; ``sections``: a
+    :class:`toppra_amd.chain.JointSections` (1 .. 8; several constraints may be listed).  The limits are given in one of three
+    spellings (mixing them is a ValueError):
+
+    ``force`` / ``moment`` (either or both): a scalar (-max <= component <= max on each section axis, every section), [S] (a
+    magnitude per section), [S, 3, 2] or [B, S, 3, 2] (lower, upper per component).  Each part given adds six rows per section,
+    the signed identity on that part with g = [upper; -lower]; the force's rows come first within a section, the sections follow
+    in order.
+
+    ``F`` [m, 6 S], [B, m, 6 S] or [B, N+1, m, 6 S] with ``g`` [m], [B, m] or [B, N+1, m], as ``BatchSecondOrderConstraint``
+    takes them.
+
+    :meth:`bearing`: a bearing's data-sheet limits -- tilting moment, axial and radial force -- as inscribed polygons.
+
+    The constraint is INFEASIBLE unless F w(q, 0, 0) <= g holds at every gridpoint: standing still must satisfy it (the static
+    load carries the weight of everything beyond the joint, and it enters every stage's rows).  Defaults are the reference's for
+    ``SecondOrderConstraint`` (Interpolation).  Needs the path positions: a ``from_path_samples`` batch must be given ``q``.  The
+    cap on the rows of one stage over all listed constraints applies as for every dense-row constraint (``BatchTOPPRA`` refuses a
+    list above it).  True (conic) norm limits, frames fixed to the parent side of a joint and per-trajectory sections are out of
+    scope."""
+
+    def __init__(self, robot, sections, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
+        if not isinstance(robot, (SerialChain, KinematicTree)):
+            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
+        if not isinstance(sections, JointSections):
+            raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
+        sections.on(robot)  # (a joint outside the robot: ValueError)
+        super(BatchJointLoadConstraint, self).__init__(
+            robot, _section_limits(sections.count, force, moment, F, g), discretization_scheme,
+            "joint load limit, %d dof, %d sections" % (robot.dof, sections.count))
+        self.robot, self.sections = robot, sections
+        self.force, self.moment = force, moment
+
+    @staticmethod
+    def bearing_rows(count, tilting=None, axial=None, radial=None, sides=8):
+        """(F [m, 6 count], g [m]) of :meth:`bearing`: per section, in this order, ``sides`` rows
+        cos(t_j) n_x + sin(t_j) n_y <= tilting cos(pi / sides), t_j = 2 pi j / sides (when ``tilting`` is given); the same
+        polygon on (f_x, f_y) for ``radial``; +f_z <= axial, -f_z <= axial.  Each limit: None, a scalar or [count], > 0."""
+        count, sides = int(count), int(sides)
+        if count < 1:
+            raise ValueError("count must be >= 1")
+        if sides < 3:
+            raise ValueError("sides must be >= 3: a polygon")
+        lims = {}
+        for name, lim in (("tilting", tilting), ("axial", axial), ("radial", radial)):
+            if lim is None:
+                continue
+            lim = _host(lim)
+            if lim.ndim == 0:
+                lim = np.full(count, float(lim))
+            if lim.shape != (count,):
+                raise ValueError("%s must be a scalar or have shape [S] = [%d], got %s" % (name, count, list(lim.shape)))
+            if not np.all(np.isfinite(lim)) or np.any(lim <= 0):
+                raise ValueError("%s must be finite and > 0" % name)
+            lims[name] = lim
+        if not lims:
+            raise ValueError("no limit given: one of tilting, axial, radial is required")
+        t = 2.0 * np.pi * np.arange(sides) / sides
+        shrink = np.cos(np.pi / sides)
+        F_rows, g_rows = [], []
+        for k in range(count):
+            for name, at in (("tilting", 3), ("radial", 0)):
+                if name in lims:
+                    part = np.zeros((sides, 6 * count))
+                    part[:, 6 * k + at], part[:, 6 * k + at + 1] = np.cos(t), np.sin(t)
+                    F_rows.append(part)
+                    g_rows.append(np.full(sides, lims[name][k] * shrink))
+            if "axial" in lims:
+                part = np.zeros((2, 6 * count))
+                part[0, 6 * k + 2], part[1, 6 * k + 2] = 1.0, -1.0
+                F_rows.append(part)
+                g_rows.append(np.full(2, lims["axial"][k]))
+        return np.concatenate(F_rows, 0), np.concatenate(g_rows)
+
+    @classmethod
+    def bearing(cls, robot, sections, tilting=None, axial=None, radial=None, sides=8, **kwargs):
+        """A bearing's data-sheet limits on every section, whose z-axis is taken as the bearing axis
+        (:meth:`toppra_amd.chain.JointSections.on_axes`): the tilting moment |(n_x, n_y)| <= ``tilting`` and the radial force
+        |(f_x, f_y)| <= ``radial`` as the polygon with ``sides`` sides INSCRIBED in the circle -- the rows never allow more than
+        the data sheet does --, and the axial force -``axial`` <= f_z <= ``axial``.  Each limit: None, a scalar or [S].  The moment
+        about the axis is the joint's torque and is left to the torque limit."""
+        if not isinstance(sections, JointSections):
+            raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
+        F, g = cls.bearing_rows(sections.count, tilting, axial, radial, sides)
+        return cls(robot, sections, F=F, g=g, **kwargs)
+
+    def _terms(self, q, qs, qss):
+        w0, wa, wb = self.robot.joint_wrench_terms(q, qs, qss, self.sections)
+        flat = tuple(q.shape[:2]) + (6 * self.sections.count,)
+        return w0.reshape(flat), wa.reshape(flat), wb.reshape(flat)
 
 
 def _point_limits(count, linear, F, g):

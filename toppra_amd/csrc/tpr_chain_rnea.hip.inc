@@ -143,6 +143,19 @@ __device__ __forceinline__ double chain_backward(const ChainLink &L, const Chain
     return L.prismatic ? tp : tr;
 }
 
+// chain_backward's sibling for what wants the whole wrench and not its projection on the joint axis (tpr_joint.hip.inc): f, n =
+// the force ON link i through joint i and its moment about link i's origin, link axes -- the very sums chain_backward forms, in
+// its order; C becomes what link i hands to its parent, as there.
+template <int Level>
+__device__ __forceinline__ void chain_backward_wrench(const ChainLink &L, const ChainJoint &J, V3 F, V3 Nm, ChainWrench &C, V3 &f, V3 &n) {
+    f = F + C.f;
+    n = cross(L.com, F);
+    if (Level >= 1) n = Nm + n;
+    n = n + C.n;
+    C.f = mul(J.E, f);
+    C.n = mul(J.E, n) + cross(J.r, C.f);
+}
+
 // A point's per-link state: registers (compile-time dof, constant indices after unrolling) or LDS [link][slot][lane].
 template <int D, int Slots>
 struct ChainRegState {

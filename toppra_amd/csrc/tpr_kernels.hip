@@ -1607,10 +1607,11 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
 }  // extern "C"
 
 // ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip;
-// tpr_mount.hip.inc, tpr_mount_tu.hip) -----------------------------------------------------------------------------------------
+// tpr_mount.hip.inc, tpr_mount_tu.hip; tpr_joint.hip.inc, tpr_joint_tu.hip) ------------------------------------------------------
 // One host path for the family: an entry is its argument checks, in an order that is its own and is behaviour (which refusal
 // wins when two arguments are bad: tests/test_rigid_refusal_order.py), then run_rigid() with what it stages and what it launches.
 #include "tpr_mount_args.hpp"
+#include "tpr_joint_args.hpp"
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
@@ -1625,6 +1626,8 @@ __attribute__((visibility("hidden"))) int tpr_tu_tree_dynamics_launch(const tpr:
 __attribute__((visibility("hidden"))) int tpr_tu_tree_terms_launch(const tpr::TreeTermsArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_launch(const tpr::MountWrenchArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_terms_launch(const tpr::MountWrenchTermsArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_launch(const tpr::JointWrenchArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_terms_launch(const tpr::JointWrenchTermsArgs *, int forks, hipStream_t);
 }
 namespace {
 // The gridpoints of a batch given as (B, N).
@@ -1752,6 +1755,48 @@ tpr::MountFrame stage_mount(const tpr_mount *m) {
     if (m) std::memcpy(&P, m, sizeof(P));
     return P;
 }
+// A section set is a host struct: read here, handed to the kernels by value with the mask of its links and the lowest of them.
+// Its frames are held to what a mount's is: orthonormal with determinant +1, to 1e-12.
+static_assert(sizeof(tpr_joint_sections) == 40 + 8 * 12 * sizeof(double) && TPR_JOINT_MAX_SECTIONS == tpr::kJointMaxSections,
+              "tpr_joint_sections is a count, 8 links, a word of padding and 96 doubles");
+int check_sections(const tpr_chain *links, const tpr_joint_sections *s, const char *who) {
+    if (!s) return fail(TPR_E_BADARG, std::string(who) + ": null sections");
+    if (s->count < 1 || s->count > TPR_JOINT_MAX_SECTIONS)
+        return fail(TPR_E_BADARG, std::string(who) + ": the section count must be in [1, TPR_JOINT_MAX_SECTIONS]");
+    for (int k = 0; k < s->count; ++k)
+        if (s->link[k] < 0 || s->link[k] >= links->d) return fail(TPR_E_BADARG, std::string(who) + ": a section's link is outside the robot");
+    for (int k = 0; k < s->count; ++k) {
+        const double *R = s->rot[k];
+        for (int j = 0; j < 9; ++j)
+            if (!std::isfinite(R[j])) return fail(TPR_E_BADARG, std::string(who) + ": every entry of the sections must be finite");
+        for (int j = 0; j < 3; ++j)
+            if (!std::isfinite(s->origin[k][j])) return fail(TPR_E_BADARG, std::string(who) + ": every entry of the sections must be finite");
+    }
+    for (int k = 0; k < s->count; ++k) {
+        const double *R = s->rot[k];
+        bool frame = true;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                frame = frame && std::fabs(R[r] * R[c] + R[3 + r] * R[3 + c] + R[6 + r] * R[6 + c] - (r == c ? 1.0 : 0.0)) <= 1e-12;
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!frame || !(std::fabs(det - 1.0) <= 1e-12))
+            return fail(TPR_E_BADARG, std::string(who) + ": a section's rot must be orthonormal with determinant +1 (to 1e-12)");
+    }
+    return TPR_E_OK;
+}
+tpr::JointSections stage_sections(const tpr_joint_sections *s) {
+    tpr::JointSections P{};
+    P.count = s->count;
+    P.lowest = s->link[0];
+    for (int k = 0; k < s->count; ++k) {  // (entries past count stay zero)
+        P.link[k] = s->link[k];
+        P.mask |= 1u << s->link[k];
+        if (s->link[k] < P.lowest) P.lowest = s->link[k];
+        for (int j = 0; j < 9; ++j) P.rot[k][j] = s->rot[k][j];
+        for (int j = 0; j < 3; ++j) P.origin[k][j] = s->origin[k][j];
+    }
+    return P;
+}
 
 // The argument block of a launch on the links `c`: the model staged, the point count set, the rest zero.
 template <class Args>
@@ -1788,6 +1833,7 @@ int tpr_chain_bytes(void) { return (int)sizeof(tpr_chain); }
 int tpr_payload_bytes(void) { return (int)sizeof(tpr_payload); }
 int tpr_chain_points_bytes(void) { return (int)sizeof(tpr_chain_points); }
 int tpr_mount_bytes(void) { return (int)sizeof(tpr_mount); }
+int tpr_joint_sections_bytes(void) { return (int)sizeof(tpr_joint_sections); }
 
 int tpr_chain_inverse_dynamics_batch(const tpr_chain *chain, long long npoints, const double *q, const double *qd, const double *qdd,
                                      double *tau, int flags, void *stream_) {
@@ -2025,5 +2071,44 @@ int tpr_tree_base_wrench_terms_batch(const tpr_chain *links, const int32_t *pare
         stage_outputs(S, 6 * (size_t)npoints, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
         return A;
     }, [forks](const tpr::MountWrenchTermsArgs *A, hipStream_t stream) { return tpr_tu_mount_wrench_terms_launch(A, forks, stream); });
+}
+
+int tpr_tree_joint_wrench_batch(const tpr_chain *links, const int32_t *parent, const tpr_joint_sections *sections, long long npoints,
+                                const double *q, const double *qd, const double *qdd, double *wrench, int flags, void *stream_) {
+    const char *who = "tpr_tree_joint_wrench_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_sections(links, sections, who)) return rc;
+    if (int rc = required(q && qd && qdd && wrench, who, "q, qd, qdd, wrench")) return rc;
+    return run_rigid(flags, wrench, stream_, npoints, "tpr_tree_joint_wrench_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::JointWrenchArgs>(links, npoints, S, false);
+        A.T = T;
+        A.S = stage_sections(sections);
+        stage_inputs(S, (size_t)npoints * (size_t)links->d, {{&A.q, q}, {&A.qd, qd}, {&A.qdd, qdd}});
+        stage_outputs(S, 6 * (size_t)sections->count * (size_t)npoints, {{&A.wrench, wrench}});
+        return A;
+    }, [forks](const tpr::JointWrenchArgs *A, hipStream_t stream) { return tpr_tu_joint_wrench_launch(A, forks, stream); });
+}
+
+int tpr_tree_joint_wrench_terms_batch(const tpr_chain *links, const int32_t *parent, const tpr_joint_sections *sections, int B, int N,
+                                      const double *q, const double *qs, const double *qss, double *w0, double *wa, double *wb, int flags,
+                                      void *stream_) {
+    const char *who = "tpr_tree_joint_wrench_terms_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_sections(links, sections, who)) return rc;
+    if (int rc = required(q && qs && qss && w0 && wa && wb, who, "q, qs, qss, w0, wa, wb")) return rc;
+    return run_rigid(flags, w0, stream_, npoints, "tpr_tree_joint_wrench_terms_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::JointWrenchTermsArgs>(links, npoints, S, false);
+        A.T = T;
+        A.S = stage_sections(sections);
+        stage_inputs(S, (size_t)npoints * (size_t)links->d, {{&A.q, q}, {&A.qs, qs}, {&A.qss, qss}});
+        stage_outputs(S, 6 * (size_t)sections->count * (size_t)npoints, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
+        return A;
+    }, [forks](const tpr::JointWrenchTermsArgs *A, hipStream_t stream) { return tpr_tu_joint_wrench_terms_launch(A, forks, stream); });
 }
 }  // extern "C"

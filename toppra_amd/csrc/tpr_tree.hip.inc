@@ -147,6 +147,7 @@ __device__ __forceinline__ void tree_rnea(const ChainModel &M, const TreeTables 
     }
 }
 
+#ifndef TPR_TREE_WALK_ONLY  // (tpr_joint.hip.inc takes TreeBanks and the walk's conventions from here, and no copy of the kernels)
 static __global__ void __launch_bounds__(kChainBlock) tree_inverse_dynamics_kernel(TreeDynArgs A) {
     extern __shared__ double chain_lds[];
     const size_t at = chain_row(A.npoints, A.M.d);
@@ -172,5 +173,6 @@ static __global__ void __launch_bounds__(kChainBlock) tree_torque_terms_kernel(T
         tree_rnea<false>(A.M, A.T, St, banks, A.q + at, A.qs + at, A.qss + at, nullptr, nullptr, A.wb + at);
     }
 }
+#endif  // TPR_TREE_WALK_ONLY
 
 }  // namespace tpr
