@@ -58,19 +58,8 @@ def evaluations(q, qs, qss):
 def reference_of(robot, mount, q, qs, qss):
     """float64 references of w0, wa, wb, wrench with their magnitudes (name + "_mag") and, under "yardstick", the error each
     shows against np.longdouble in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        if name == "wrench":
-            ref["wrench"], ref["wrench_mag"], ref["yardstick"]["wrench"] = ref["wb"], ref["wb_mag"], ref["yardstick"]["wb"]
-            continue
-        ref[name] = base_wrench_ref.base_wrench(robot, *args, mount=mount)
-        ref[name + "_mag"] = base_wrench_ref.base_wrench(robot, *args, mount=mount, absolute=True)
-        ref["yardstick"][name] = cc._own_error(ref[name], base_wrench_ref.base_wrench(robot, *args, mount=mount, dtype=np.longdouble),
-                                               ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    fn, ev = functools.partial(base_wrench_ref.base_wrench, mount=mount), evaluations(q, qs, qss)
+    return cc.alias(cc.references({name: (fn, (robot,) + ev[name]) for name in ("w0", "wa", "wb")}), "wrench", "wb")
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,4 +73,4 @@ def bound(key, name):
 
 def accuracy_table():
     """{case: {quantity: {"yardstick", "bound"}}}: what profiles/base_wrench_accuracy.json records."""
-    return {str(k): {n: {"yardstick": v, "bound": BOUND_FACTOR * v} for n, v in reference(k)["yardstick"].items()} for k in CASES}
+    return cc.table({str(k): reference(k)["yardstick"] for k in CASES})

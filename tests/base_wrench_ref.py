@@ -1,9 +1,8 @@
 """Plain numpy reference for the base reaction of include/toppra_hip.h (tpr_tree_base_wrench_*): the wrench a robot's mount
 exerts ON the robot.  Written the textbook way, the opposite way round from the kernels (which sum every link's share on the way
-up and never come back down): tests/tree_ref.py's recursion in WORLD coordinates -- the same operations in the same order on
-the way up -- and then the backward pass of recursive Newton-Euler with the children's wrenches handed down link by link to the
-base, where the roots' wrenches are summed in ascending root number; then the platform and the mount frame.  ``dtype`` and
-``absolute`` as in tests/tree_ref.py.
+up and never come back down): tests/chain_ref.py's way up in WORLD coordinates and its way down, the children's wrenches handed
+down link by link to the base, where the roots' wrenches are summed in ascending root number; then the platform and the mount
+frame.  ``dtype`` and ``absolute`` as in tests/chain_ref.py.
 
 A robot is a tree dict (tests/tree_ref.py), or a chain dict (tests/chain_ref.py; no "parent": the tree -1, 0, 1, ...).  A mount is
 a dict: rot [3, 3] (columns = the mount frame's axes in base coordinates), origin [3], mass, com [3]; None = the base frame
@@ -11,90 +10,27 @@ without a platform.
 """
 import numpy as np
 
-from tests.chain_ref import _Mag, _add, _cross, _mm, _mtv, _mv, _rodrigues, _scale
+from tests.chain_ref import _add, _cross, _mtv, _scale, backward, forward, parents_of  # noqa: F401  (parents_of: read from here)
 
 NO_MOUNT = {"rot": np.eye(3), "origin": np.zeros(3), "mass": 0.0, "com": np.zeros(3)}
 
 
-def parents_of(robot):
-    return [int(p) for p in robot["parent"]] if "parent" in robot else list(range(-1, len(robot["joint_type"]) - 1))
-
-
 def base_wrench(robot, q, qd, qdd, mount=None, dtype=np.float64, absolute=False):
     """w(q, qd, qdd) [..., 6] = [force; moment about the mount's origin] in mount-frame axes; arrays [..., d]."""
-    wrap = (lambda x: _Mag(x)) if absolute else (lambda x: x)
     mount = NO_MOUNT if mount is None else mount
-    qa, qda, qdda = (np.asarray(a, dtype=dtype) for a in (q, qd, qdd))
-    lead = qa.shape[:-1]
-    par = {k: np.asarray(robot[k], dtype=dtype) for k in ("axis", "rot", "trans", "mass", "com", "inertia", "gravity")}
-    parent = parents_of(robot)
-    d = len(parent)
-    one, zero = wrap(np.ones(lead, dtype=dtype)), wrap(np.zeros(lead, dtype=dtype))
-    vec = lambda x: [wrap(x[j]) * one for j in range(3)]  # noqa: E731
-    base = {"R": [[one if r == c else zero for c in range(3)] for r in range(3)], "p": [zero] * 3, "w": [zero] * 3,
-            "wd": [zero] * 3, "a": [zero - wrap(par["gravity"][k]) * one for k in range(3)]}
-    links = []
-    for i in range(d):  # (tree_ref.rnea's way up)
-        assert -1 <= parent[i] < i, (i, parent[i])
-        up = base if parent[i] < 0 else links[parent[i]]
-        R, w, wd, a = up["R"], up["w"], up["wd"], up["a"]
-        qi, qdi, qddi = wrap(qa[..., i]), wrap(qda[..., i]), wrap(qdda[..., i])
-        rot = [[wrap(par["rot"][i, r, c]) * one for c in range(3)] for r in range(3)]
-        k = vec(par["axis"][i])
-        Rj = _mm(R, rot)
-        z = _mv(Rj, k)
-        r = _mv(R, vec(par["trans"][i]))
-        prismatic = int(robot["joint_type"][i]) == 1
-        if prismatic:
-            Rl = Rj
-            r = _add(r, _scale(z, qi))
-        else:
-            Rl = _mm(Rj, _rodrigues(k, wrap(np.sin(qa[..., i])), wrap(np.cos(qa[..., i]))))
-        a_new = _add(_add(a, _cross(wd, r)), _cross(w, _cross(w, r)))
-        if prismatic:
-            w_new, wd_new = w, wd
-            a_new = _add(_add(a_new, _scale(z, qddi)), _scale(_cross(w, z), 2 * qdi))
-        else:
-            w_new = _add(w, _scale(z, qdi))
-            wd_new = _add(_add(wd, _scale(z, qddi)), _scale(_cross(w, z), qdi))
-        L = {"R": Rl, "p": _add(up["p"], r), "w": w_new, "wd": wd_new, "a": a_new}
-        com = _mv(Rl, vec(par["com"][i]))
-        ac = _add(_add(L["a"], _cross(L["wd"], com)), _cross(L["w"], _cross(L["w"], com)))
-        I = par["inertia"][i]
-        Il = [[wrap(I[0]), wrap(I[3]), wrap(I[4])], [wrap(I[3]), wrap(I[1]), wrap(I[5])], [wrap(I[4]), wrap(I[5]), wrap(I[2])]]
-        inertia = lambda x, Rl=Rl, Il=Il: _mv(Rl, _mv(Il, _mtv(Rl, x)))  # noqa: E731
-        L["F"] = _scale(ac, wrap(par["mass"][i]))
-        L["N"] = _add(inertia(L["wd"]), _cross(L["w"], inertia(L["w"])))
-        L["c"] = com
-        links.append(L)
-    # the way down: (force, moment about the receiving link's origin); the base receives about its own origin
-    handed = [None] * d
-    f0, n0 = [zero] * 3, [zero] * 3
-    for i in range(d - 1, -1, -1):
-        L = links[i]
-        f, n = handed[i] if handed[i] is not None else ([zero] * 3, [zero] * 3)
-        f = _add(L["F"], f)
-        n = _add(_add(L["N"], _cross(L["c"], L["F"])), n)
-        p = parent[i]
-        if p >= 0:
-            lever = [L["p"][k] - links[p]["p"][k] for k in range(3)]
-            give = (f, _add(n, _cross(lever, f)))
-            handed[p] = give if handed[p] is None else (_add(handed[p][0], give[0]), _add(handed[p][1], give[1]))
-        else:
-            handed[i] = (f, _add(n, _cross(L["p"], f)))  # (kept for the sum over the roots below)
-    for i in range(d):
-        if parent[i] < 0:
-            f0, n0 = _add(f0, handed[i][0]), _add(n0, handed[i][1])
-    # the platform: its weight's support at its centre of mass
-    mb, cb = wrap(np.asarray(mount["mass"], dtype=dtype)) * one, vec(np.asarray(mount["com"], dtype=dtype))
-    fp = _scale(base["a"], mb)
-    f0, n0 = _add(f0, fp), _add(n0, _cross(cb, fp))
+    links, ar = forward(robot, q, qd, qdd, dtype, absolute, dynamics=True)
+    # the roots' wrenches, each moved to the base's origin, in ascending root number
+    f0, n0 = [ar.zero] * 3, [ar.zero] * 3
+    for L, (f, n) in zip(links, backward(links, ar)):
+        if L["parent"] < 0:
+            f0, n0 = _add(f0, f), _add(n0, _add(n, _cross(L["p"], f)))
+    # the platform: its weight's support at its centre of mass (the base accelerates by -gravity)
+    fp = _scale([ar.zero - g for g in ar.vec(robot["gravity"])], ar.scalar(mount["mass"]))
+    f0, n0 = _add(f0, fp), _add(n0, _cross(ar.vec(mount["com"]), fp))
     # the mount frame
-    Rm = [[wrap(np.asarray(mount["rot"], dtype=dtype)[r, c]) * one for c in range(3)] for r in range(3)]
-    pm = vec(np.asarray(mount["origin"], dtype=dtype))
-    shift = _cross(pm, f0)
-    out = _mtv(Rm, f0) + _mtv(Rm, [n0[k] - shift[k] for k in range(3)])
-    return np.stack([t.v if absolute else t for t in out], -1)
+    Rm = ar.mat(mount["rot"])
+    shift = _cross(ar.vec(mount["origin"]), f0)
+    return ar.stack(_mtv(Rm, f0) + _mtv(Rm, [n0[k] - shift[k] for k in range(3)]))
 
 
 def mount_of(m):

@@ -61,20 +61,35 @@ def _own_error(val, ld, mag):
     return float(np.max(np.abs(val - ld)[live] / mag[live])) if live.any() else 0.0
 
 
+def references(quantities):
+    """The scaffold every cases module of the family builds its references with.  ``quantities`` is {name: (fn, args)}, fn taking
+    ``dtype=`` and ``absolute=``; returns {name: fn(*args) in float64, name + "_mag": its all-absolute magnitude, "yardstick":
+    {name: the error the float64 value shows against np.longdouble, in the metric}}, the arrays read-only."""
+    ref = {"yardstick": {}}
+    for name, (fn, args) in quantities.items():
+        ref[name], ref[name + "_mag"] = fn(*args), fn(*args, absolute=True)
+        ref["yardstick"][name] = _own_error(ref[name], fn(*args, dtype=np.longdouble), ref[name + "_mag"])
+        ref[name].flags.writeable = ref[name + "_mag"].flags.writeable = False
+    return ref
+
+
+def alias(ref, name, of):
+    """Quantity ``name`` is quantity ``of`` under another entry's name: the same arrays, the same yardstick."""
+    ref[name], ref[name + "_mag"], ref["yardstick"][name] = ref[of], ref[of + "_mag"], ref["yardstick"][of]
+    return ref
+
+
+def table(yardsticks):
+    """{case: {quantity: {"yardstick", "bound"}}} of {case: a reference's "yardstick"}: what an accuracy profile records."""
+    return {case: {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in ys.items()} for case, ys in yardsticks.items()}
+
+
 def reference_of(chain, q, qs, qss):
     """float64 references of w0, wa, wb, vsv (S = None) and vsv_S (S_FULL) with their magnitudes (name + "_mag"), and under
     "yardstick" the error each of them shows against the same recursion in np.longdouble, in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        ref[name], ref[name + "_mag"] = chain_ref.rnea(chain, *args), chain_ref.rnea(chain, *args, absolute=True)
-        ref["yardstick"][name] = _own_error(ref[name], chain_ref.rnea(chain, *args, dtype=np.longdouble), ref[name + "_mag"])
-    for name, S in (("vsv", None), ("vsv_S", S_FULL)):
-        ref[name], ref[name + "_mag"] = chain_ref.tool_vsv(chain, q, qs, S), chain_ref.tool_vsv(chain, q, qs, S, absolute=True)
-        ref["yardstick"][name] = _own_error(ref[name], chain_ref.tool_vsv(chain, q, qs, S, dtype=np.longdouble), ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    quantities = {name: (chain_ref.rnea, (chain,) + args) for name, args in evaluations(q, qs, qss).items()}
+    quantities.update({name: (chain_ref.tool_vsv, (chain, q, qs, S)) for name, S in (("vsv", None), ("vsv_S", S_FULL))})
+    return references(quantities)
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,7 +104,7 @@ def bound(d, name):
 
 def accuracy_table():
     """{dof: {quantity: {"yardstick", "bound"}}}: what profiles/chain_dynamics_accuracy.json records."""
-    return {str(d): {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in reference(d)["yardstick"].items()} for d in DOFS}
+    return table({str(d): reference(d)["yardstick"] for d in DOFS})
 
 
 def metric(got, ref, mag):

@@ -4,6 +4,10 @@ nothing but the model is shared).  Every function takes ``dtype`` and runs in np
 evaluates the same expression with every product and sum taken in absolute value -- the magnitude against which the GPU
 tests measure an error.
 
+The recursion exists once, here: ``forward`` (the way up, over a parent table: the chain is the tree -1, 0, 1, ...) and
+``backward`` (the way down).  tests/tree_ref.py, tool_accel_ref.py, tool_wrench_ref.py, base_wrench_ref.py and joint_load_ref.py
+add only what is their own to it, so one correction reaches every accuracy bound of the family.
+
 A chain is a dict: joint_type [d] (0 revolute, 1 prismatic), axis [d, 3], rot [d, 3, 3], trans [d, 3], mass [d], com [d, 3],
 inertia [d, 6] = xx, yy, zz, xy, xz, yz, gravity [3], tool [3].
 """
@@ -68,91 +72,120 @@ def _rodrigues(k, s, c):
             [t * k[0] * k[2] - s * k[1], t * k[1] * k[2] + s * k[0], c + t * k[2] * k[2]]]
 
 
-def _prepare(chain, arrays, dtype, absolute):
-    wrap = (lambda x: _Mag(x)) if absolute else (lambda x: x)
-    arrays = [np.asarray(a, dtype=dtype) for a in arrays]
-    lead = arrays[0].shape[:-1]
-    cols = [[wrap(a[..., i]) for i in range(a.shape[-1])] for a in arrays]
-    par = {k: np.asarray(chain[k], dtype=dtype) for k in ("axis", "rot", "trans", "mass", "com", "inertia", "gravity", "tool")}
-    one, zero = wrap(np.ones(lead, dtype=dtype)), wrap(np.zeros(lead, dtype=dtype))
-    return wrap, arrays, cols, par, one, zero, lead
+class _Arith(object):
+    """The arithmetic of one evaluation over the leading shape ``lead``: ``dtype``, and plain or (``absolute``) nothing-cancels."""
+
+    def __init__(self, lead, dtype, absolute):
+        self.dtype, self.absolute = dtype, absolute
+        self.wrap = (lambda x: _Mag(x)) if absolute else (lambda x: x)
+        self.one, self.zero = self.wrap(np.ones(lead, dtype=dtype)), self.wrap(np.zeros(lead, dtype=dtype))
+
+    def scalar(self, x):
+        return self.wrap(np.asarray(x, dtype=self.dtype)) * self.one
+
+    def vec(self, x):
+        x = np.asarray(x, dtype=self.dtype)
+        return [self.wrap(x[j]) * self.one for j in range(3)]
+
+    def mat(self, M):
+        M = np.asarray(M, dtype=self.dtype)
+        return [[self.wrap(M[r, c]) * self.one for c in range(3)] for r in range(3)]
+
+    def inertia(self, R, I):
+        """x -> R I R' x for I = xx, yy, zz, xy, xz, yz in the frame R."""
+        I = [self.wrap(x) for x in np.asarray(I, dtype=self.dtype)]
+        Il = [[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]]
+        return lambda x: _mv(R, _mv(Il, _mtv(R, x)))
+
+    def stack(self, parts):
+        return np.stack([t.v if self.absolute else t for t in parts], -1)
 
 
-def _walk(chain, qarr, qcols, qd, qdd, par, wrap, one, zero, dynamics):
-    """The forward recursion in world coordinates.  Per link: rotation Rl, origin p, axis z, angular velocity w, origin
-    velocity v and (``dynamics``) angular acceleration wd, origin acceleration a."""
-    d = len(chain["joint_type"])
-    R = [[one if r == c else zero for c in range(3)] for r in range(3)]
-    p, w, v = [zero] * 3, [zero] * 3, [zero] * 3
-    wd, a = [zero] * 3, [zero - wrap(par["gravity"][k]) * one for k in range(3)]
+def parents_of(robot):
+    """The parent table of a robot dict: a tree's own, the chain's -1, 0, 1, ..."""
+    return [int(p) for p in robot["parent"]] if "parent" in robot else list(range(-1, len(robot["joint_type"]) - 1))
+
+
+def forward(robot, q, qd, qdd=None, dtype=np.float64, absolute=False, dynamics=False):
+    """The way up in world coordinates, over the robot's parent table; arrays [..., d], qdd None = zero.  Returns (links, ar):
+    per link its parent, rotation R, origin p, axis z, angular velocity w, origin velocity v, angular acceleration wd, origin
+    acceleration a (the base accelerates by -gravity) and prismatic; with ``dynamics`` also the inertial force F on the link, the
+    inertial moment N about its centre of mass and that centre c from the link's origin.  ``ar`` is the evaluation's _Arith."""
+    qa, qda = np.asarray(q, dtype=dtype), np.asarray(qd, dtype=dtype)
+    qdda = np.zeros_like(qa) if qdd is None else np.asarray(qdd, dtype=dtype)
+    ar = _Arith(qa.shape[:-1], dtype, absolute)
+    wrap, one, zero = ar.wrap, ar.one, ar.zero
+    gravity = np.asarray(robot["gravity"], dtype=dtype)
+    base = {"R": [[one if r == c else zero for c in range(3)] for r in range(3)], "p": [zero] * 3, "w": [zero] * 3, "v": [zero] * 3,
+            "wd": [zero] * 3, "a": [zero - wrap(gravity[k]) * one for k in range(3)]}
     links = []
-    for i in range(d):
-        rot = [[wrap(par["rot"][i, r, c]) * one for c in range(3)] for r in range(3)]
-        k = [wrap(par["axis"][i, j]) * one for j in range(3)]
-        Rj = _mm(R, rot)
+    for i, parent in enumerate(parents_of(robot)):
+        assert -1 <= parent < i, (i, parent)
+        up = base if parent < 0 else links[parent]
+        R, w, wd, a = up["R"], up["w"], up["wd"], up["a"]
+        qi, qdi, qddi = wrap(qa[..., i]), wrap(qda[..., i]), wrap(qdda[..., i])
+        k = ar.vec(robot["axis"][i])
+        Rj = _mm(R, ar.mat(robot["rot"][i]))
         z = _mv(Rj, k)
-        r = _mv(R, [wrap(par["trans"][i, j]) * one for j in range(3)])
-        prismatic = int(chain["joint_type"][i]) == 1
+        r = _mv(R, ar.vec(robot["trans"][i]))
+        prismatic = int(robot["joint_type"][i]) == 1
         if prismatic:
             Rl = Rj
-            r = _add(r, _scale(z, qcols[i]))
+            r = _add(r, _scale(z, qi))
         else:
-            s, c = wrap(np.sin(qarr[..., i])), wrap(np.cos(qarr[..., i]))
-            Rl = _mm(Rj, _rodrigues(k, s, c))
-        v_new = _add(v, _cross(w, r))
-        if dynamics:
-            a_new = _add(_add(a, _cross(wd, r)), _cross(w, _cross(w, r)))
+            Rl = _mm(Rj, _rodrigues(k, wrap(np.sin(qa[..., i])), wrap(np.cos(qa[..., i]))))
+        v_new = _add(up["v"], _cross(w, r))
+        a_new = _add(_add(a, _cross(wd, r)), _cross(w, _cross(w, r)))
         if prismatic:
-            v_new = _add(v_new, _scale(z, qd[i]))
-            w_new = w
-            if dynamics:
-                wd_new = wd
-                a_new = _add(_add(a_new, _scale(z, qdd[i])), _scale(_cross(w, z), 2 * qd[i]))
+            v_new = _add(v_new, _scale(z, qdi))
+            w_new, wd_new = w, wd
+            a_new = _add(_add(a_new, _scale(z, qddi)), _scale(_cross(w, z), 2 * qdi))
         else:
-            w_new = _add(w, _scale(z, qd[i]))
-            if dynamics:
-                wd_new = _add(_add(wd, _scale(z, qdd[i])), _scale(_cross(w, z), qd[i]))
-        p = _add(p, r)
-        R, w, v = Rl, w_new, v_new
+            w_new = _add(w, _scale(z, qdi))
+            wd_new = _add(_add(wd, _scale(z, qddi)), _scale(_cross(w, z), qdi))
+        L = {"parent": parent, "R": Rl, "p": _add(up["p"], r), "z": z, "w": w_new, "v": v_new, "wd": wd_new, "a": a_new,
+             "prismatic": prismatic}
         if dynamics:
-            wd, a = wd_new, a_new
-        links.append({"R": R, "p": p, "z": z, "w": w, "v": v, "wd": wd, "a": a, "prismatic": prismatic})
-    return links
+            com = _mv(Rl, ar.vec(robot["com"][i]))
+            ac = _add(_add(a_new, _cross(wd_new, com)), _cross(w_new, _cross(w_new, com)))
+            inertia = ar.inertia(Rl, robot["inertia"][i])
+            L["F"] = _scale(ac, wrap(np.asarray(robot["mass"], dtype=dtype)[i]))
+            L["N"] = _add(inertia(wd_new), _cross(w_new, inertia(w_new)))
+            L["c"] = com
+        links.append(L)
+    return links, ar
 
 
-def rnea(chain, q, qd, qdd, dtype=np.float64, absolute=False):
-    """tau(q, qd, qdd), arrays [..., d]."""
-    wrap, (qa, qda, qdda), (qc, qdc, qddc), par, one, zero, lead = _prepare(chain, (q, qd, qdd), dtype, absolute)
-    links = _walk(chain, qa, qc, qdc, qddc, par, wrap, one, zero, True)
+def backward(links, ar):
+    """The way down: per link the (f, n) its parent exerts on it through its joint, in world axes, n about the link's own origin.
+    A link hands (f, n about the parent's origin) down; a parent adds its children in descending child number."""
     d = len(links)
-    for i, L in enumerate(links):
-        com = _mv(L["R"], [wrap(par["com"][i, j]) * one for j in range(3)])
-        ac = _add(_add(L["a"], _cross(L["wd"], com)), _cross(L["w"], _cross(L["w"], com)))
-        I = par["inertia"][i]
-        Il = [[wrap(I[0]), wrap(I[3]), wrap(I[4])], [wrap(I[3]), wrap(I[1]), wrap(I[5])], [wrap(I[4]), wrap(I[5]), wrap(I[2])]]
-        inertia = lambda x, L=L, Il=Il: _mv(L["R"], _mv(Il, _mtv(L["R"], x)))  # noqa: E731
-        L["F"] = _scale(ac, wrap(par["mass"][i]))
-        L["N"] = _add(inertia(L["wd"]), _cross(L["w"], inertia(L["w"])))
-        L["c"] = com
-    f, n = [zero] * 3, [zero] * 3
-    tau = [None] * d
+    handed, out = [None] * d, [None] * d
     for i in range(d - 1, -1, -1):
         L = links[i]
-        if i + 1 < d:
-            lever = [links[i + 1]["p"][k] - L["p"][k] for k in range(3)]
-            n = _add(n, _cross(lever, f))
+        f, n = handed[i] if handed[i] is not None else ([ar.zero] * 3, [ar.zero] * 3)
         f = _add(L["F"], f)
         n = _add(_add(L["N"], _cross(L["c"], L["F"])), n)
-        tau[i] = _dot(L["z"], f) if L["prismatic"] else _dot(L["z"], n)
-    return np.stack([t.v if absolute else t for t in tau], -1)
+        out[i] = (f, n)
+        p = L["parent"]
+        if p >= 0:
+            lever = [L["p"][k] - links[p]["p"][k] for k in range(3)]
+            give = (f, _add(n, _cross(lever, f)))
+            handed[p] = give if handed[p] is None else (_add(handed[p][0], give[0]), _add(handed[p][1], give[1]))
+    return out
+
+
+def rnea(robot, q, qd, qdd, dtype=np.float64, absolute=False):
+    """tau(q, qd, qdd), arrays [..., d]; a chain or a tree dict."""
+    links, ar = forward(robot, q, qd, qdd, dtype, absolute, dynamics=True)
+    return ar.stack([_dot(L["z"], f) if L["prismatic"] else _dot(L["z"], n) for L, (f, n) in zip(links, backward(links, ar))])
 
 
 def tool_velocity(chain, q, qd, dtype=np.float64, absolute=False):
     """(v, w) [..., 3] each: the tool point's linear and angular velocity in world axes for joint velocities qd."""
-    wrap, (qa, qda), (qc, qdc), par, one, zero, lead = _prepare(chain, (q, qd), dtype, absolute)
-    L = _walk(chain, qa, qc, qdc, None, par, wrap, one, zero, False)[-1]
-    tool = _mv(L["R"], [wrap(par["tool"][j]) * one for j in range(3)])
-    v = _add(L["v"], _cross(L["w"], tool))
+    links, ar = forward(chain, q, qd, None, dtype, absolute)
+    L = links[-1]
+    v = _add(L["v"], _cross(L["w"], _mv(L["R"], ar.vec(chain["tool"]))))
     return v, L["w"]
 
 

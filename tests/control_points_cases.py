@@ -95,19 +95,9 @@ def point_speeds(chain, links, offsets, q, qs, dtype=np.float64, absolute=False)
 def reference_of(chain, links, offsets, q, qs, qss):
     """float64 references of speed2, wa, wb with their magnitudes (name + "_mag") and, under "yardstick", the error each shows
     against np.longdouble in the metric."""
-    ref = {"yardstick": {}}
-    ref["speed2"] = point_speeds(chain, links, offsets, q, qs)
-    ref["speed2_mag"] = point_speeds(chain, links, offsets, q, qs, absolute=True)
-    ref["yardstick"]["speed2"] = cc._own_error(ref["speed2"], point_speeds(chain, links, offsets, q, qs, dtype=np.longdouble), ref["speed2_mag"])
-    for name, args in evaluations(q, qs, qss).items():
-        ref[name] = point_accelerations(chain, links, offsets, *args)
-        ref[name + "_mag"] = point_accelerations(chain, links, offsets, *args, absolute=True)
-        ref["yardstick"][name] = cc._own_error(ref[name], point_accelerations(chain, links, offsets, *args, dtype=np.longdouble),
-                                               ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    quantities = {"speed2": (point_speeds, (chain, links, offsets, q, qs))}
+    quantities.update({name: (point_accelerations, (chain, links, offsets) + args) for name, args in evaluations(q, qs, qss).items()})
+    return cc.references(quantities)
 
 
 @functools.lru_cache(maxsize=None)
@@ -122,5 +112,4 @@ def bound(d, which, name):
 
 def accuracy_table():
     """{"<dof><set>": {quantity: {"yardstick", "bound"}}}: what profiles/control_points_accuracy.json records."""
-    return {"%d%s" % (d, w): {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in reference(d, w)["yardstick"].items()}
-            for d, w in CASES}
+    return cc.table({"%d%s" % (d, w): reference(d, w)["yardstick"] for d, w in CASES})

@@ -19,7 +19,7 @@ import functools
 import numpy as np
 
 from tests import base_wrench_cases as bc, chain_cases as cc, chain_ref, joint_load_ref, tree_cases as tc
-from tests.base_wrench_ref import parents_of
+from tests.chain_ref import parents_of
 
 BOUND_FACTOR, metric = cc.BOUND_FACTOR, cc.metric
 DOFS, NAMES = cc.DOFS, tc.NAMES
@@ -80,19 +80,8 @@ def by_sets(key, call):
 def reference_of(robot, sec, q, qs, qss):
     """float64 references of w0, wa, wb, wrench [B, N+1, S, 6] with their magnitudes (name + "_mag") and, under "yardstick", the
     error each shows against np.longdouble in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        if name == "wrench":
-            ref["wrench"], ref["wrench_mag"], ref["yardstick"]["wrench"] = ref["wb"], ref["wb_mag"], ref["yardstick"]["wb"]
-            continue
-        ref[name] = joint_load_ref.joint_wrenches(robot, *args, sections=sec)
-        ref[name + "_mag"] = joint_load_ref.joint_wrenches(robot, *args, sections=sec, absolute=True)
-        ref["yardstick"][name] = cc._own_error(ref[name], joint_load_ref.joint_wrenches(robot, *args, sections=sec, dtype=np.longdouble),
-                                               ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    fn, ev = functools.partial(joint_load_ref.joint_wrenches, sections=sec), evaluations(q, qs, qss)
+    return cc.alias(cc.references({name: (fn, (robot,) + ev[name]) for name in ("w0", "wa", "wb")}), "wrench", "wb")
 
 
 @functools.lru_cache(maxsize=None)
@@ -124,5 +113,8 @@ def worst_restatement(gravity):
 
 def accuracy_table():
     """{case: {quantity: {"yardstick", "bound", "restatement"}}}: what profiles/joint_load_accuracy.json records."""
-    return {str(k): {n: {"yardstick": v, "bound": BOUND_FACTOR * v, "restatement": restatement_fractions(k)[n]}
-                     for n, v in reference(k)["yardstick"].items()} for k in CASES}
+    table = cc.table({str(k): reference(k)["yardstick"] for k in CASES})
+    for k in CASES:
+        for n, entry in table[str(k)].items():
+            entry["restatement"] = restatement_fractions(k)[n]
+    return table

@@ -1,7 +1,7 @@
 """Plain numpy reference for the joint wrenches of include/toppra_hip.h (tpr_tree_joint_wrench_*): the full 6-D wrench the parent
 side exerts ON link i through joint i, reported in a section frame fixed to link i.  joint_wrenches is written the textbook way:
-tests/base_wrench_ref.py's way up and way down in WORLD coordinates, every link's handed-down (f, n) kept, and only at the end
-turned into the link's frame and from there into the section's.  ``dtype`` and ``absolute`` as in tests/tree_ref.py.
+tests/chain_ref.py's way up and way down in WORLD coordinates, every link's (f, n) kept, and only at the end turned into the
+link's frame and from there into the section's.  ``dtype`` and ``absolute`` as in tests/tree_ref.py.
 
 Beside it, local_joint_wrenches: a float64 RESTATEMENT of the order the kernels use -- the link-local recursion of
 toppra_amd/csrc/tpr_chain_rnea.hip.inc on tpr_tree.hip.inc's walk (the children i != j + 1 of a fork summed in descending number,
@@ -14,8 +14,7 @@ are a dict: link [S] (resolved, 0 .. d-1), rot [S, 3, 3] (columns = the section 
 """
 import numpy as np
 
-from tests.base_wrench_ref import parents_of
-from tests.chain_ref import _Mag, _add, _cross, _mm, _mtv, _mv, _rodrigues, _scale
+from tests.chain_ref import _add, _cross, _mm, _mtv, _mv, _rodrigues, _scale, backward, forward, parents_of
 
 
 def default_sections(links):
@@ -29,84 +28,22 @@ def subset(sections, index):
 
 
 def link_wrenches(robot, q, qd, qdd, dtype=np.float64, absolute=False):
-    """Per link i: (f, n, R) -- the wrench ON link i through joint i in WORLD axes, the moment about link i's origin, and the link
-    frame's rotation; lists of 3 (3 x 3) arrays over the leading shape."""
-    wrap = (lambda x: _Mag(x)) if absolute else (lambda x: x)
-    qa, qda, qdda = (np.asarray(a, dtype=dtype) for a in (q, qd, qdd))
-    lead = qa.shape[:-1]
-    par = {k: np.asarray(robot[k], dtype=dtype) for k in ("axis", "rot", "trans", "mass", "com", "inertia", "gravity")}
-    parent = parents_of(robot)
-    d = len(parent)
-    one, zero = wrap(np.ones(lead, dtype=dtype)), wrap(np.zeros(lead, dtype=dtype))
-    vec = lambda x: [wrap(x[j]) * one for j in range(3)]  # noqa: E731
-    base = {"R": [[one if r == c else zero for c in range(3)] for r in range(3)], "p": [zero] * 3, "w": [zero] * 3,
-            "wd": [zero] * 3, "a": [zero - wrap(par["gravity"][k]) * one for k in range(3)]}
-    links = []
-    for i in range(d):  # (base_wrench_ref's way up)
-        assert -1 <= parent[i] < i, (i, parent[i])
-        up = base if parent[i] < 0 else links[parent[i]]
-        R, w, wd, a = up["R"], up["w"], up["wd"], up["a"]
-        qi, qdi, qddi = wrap(qa[..., i]), wrap(qda[..., i]), wrap(qdda[..., i])
-        rot = [[wrap(par["rot"][i, r, c]) * one for c in range(3)] for r in range(3)]
-        k = vec(par["axis"][i])
-        Rj = _mm(R, rot)
-        z = _mv(Rj, k)
-        r = _mv(R, vec(par["trans"][i]))
-        prismatic = int(robot["joint_type"][i]) == 1
-        if prismatic:
-            Rl = Rj
-            r = _add(r, _scale(z, qi))
-        else:
-            Rl = _mm(Rj, _rodrigues(k, wrap(np.sin(qa[..., i])), wrap(np.cos(qa[..., i]))))
-        a_new = _add(_add(a, _cross(wd, r)), _cross(w, _cross(w, r)))
-        if prismatic:
-            w_new, wd_new = w, wd
-            a_new = _add(_add(a_new, _scale(z, qddi)), _scale(_cross(w, z), 2 * qdi))
-        else:
-            w_new = _add(w, _scale(z, qdi))
-            wd_new = _add(_add(wd, _scale(z, qddi)), _scale(_cross(w, z), qdi))
-        L = {"R": Rl, "p": _add(up["p"], r), "w": w_new, "wd": wd_new, "a": a_new}
-        com = _mv(Rl, vec(par["com"][i]))
-        ac = _add(_add(L["a"], _cross(L["wd"], com)), _cross(L["w"], _cross(L["w"], com)))
-        I = par["inertia"][i]
-        Il = [[wrap(I[0]), wrap(I[3]), wrap(I[4])], [wrap(I[3]), wrap(I[1]), wrap(I[5])], [wrap(I[4]), wrap(I[5]), wrap(I[2])]]
-        inertia = lambda x, Rl=Rl, Il=Il: _mv(Rl, _mv(Il, _mtv(Rl, x)))  # noqa: E731
-        L["F"] = _scale(ac, wrap(par["mass"][i]))
-        L["N"] = _add(inertia(L["wd"]), _cross(L["w"], inertia(L["w"])))
-        L["c"] = com
-        links.append(L)
-    handed = [None] * d
-    out = [None] * d
-    for i in range(d - 1, -1, -1):  # the way down: (force, moment about the receiving link's origin)
-        L = links[i]
-        f, n = handed[i] if handed[i] is not None else ([zero] * 3, [zero] * 3)
-        f = _add(L["F"], f)
-        n = _add(_add(L["N"], _cross(L["c"], L["F"])), n)
-        out[i] = (f, n, L["R"])
-        p = parent[i]
-        if p >= 0:
-            lever = [L["p"][k] - links[p]["p"][k] for k in range(3)]
-            give = (f, _add(n, _cross(lever, f)))
-            handed[p] = give if handed[p] is None else (_add(handed[p][0], give[0]), _add(handed[p][1], give[1]))
-    return out, wrap, one
-
-
-def _in_section(f, n, sections, k, wrap, one, dtype):
-    """[Rk' f; Rk' (n - ok x f)] of (f, n) in link axes."""
-    Rk = [[wrap(np.asarray(sections["rot"], dtype=dtype)[k, r, c]) * one for c in range(3)] for r in range(3)]
-    ok = [wrap(np.asarray(sections["origin"], dtype=dtype)[k, j]) * one for j in range(3)]
-    shift = _cross(ok, f)
-    return _mtv(Rk, f) + _mtv(Rk, [n[j] - shift[j] for j in range(3)])
+    """(per link i: (f, n, R), ar) -- the wrench ON link i through joint i in WORLD axes, the moment about link i's origin, and the
+    link frame's rotation, lists of 3 (3 x 3) arrays over the leading shape; and the evaluation's arithmetic."""
+    links, ar = forward(robot, q, qd, qdd, dtype, absolute, dynamics=True)
+    return [(f, n, L["R"]) for L, (f, n) in zip(links, backward(links, ar))], ar
 
 
 def joint_wrenches(robot, q, qd, qdd, sections, dtype=np.float64, absolute=False):
     """w(q, qd, qdd) [..., S, 6]: per section [force; moment about its origin] in its axes; arrays [..., d]."""
-    per_link, wrap, one = link_wrenches(robot, q, qd, qdd, dtype=dtype, absolute=absolute)
+    per_link, ar = link_wrenches(robot, q, qd, qdd, dtype=dtype, absolute=absolute)
     rows = []
     for k, i in enumerate(np.asarray(sections["link"]).tolist()):
         f, n, R = per_link[i]
-        six = _in_section(_mtv(R, f), _mtv(R, n), sections, k, wrap, one, dtype)
-        rows.append(np.stack([t.v if absolute else t for t in six], -1))
+        f, n = _mtv(R, f), _mtv(R, n)  # in link axes; then [Rk' f; Rk' (n - ok x f)]
+        Rk = ar.mat(np.asarray(sections["rot"])[k])
+        shift = _cross(ar.vec(np.asarray(sections["origin"])[k]), f)
+        rows.append(ar.stack(_mtv(Rk, f) + _mtv(Rk, [n[j] - shift[j] for j in range(3)])))
     return np.stack(rows, -2)
 
 

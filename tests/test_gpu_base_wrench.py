@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from tests import base_wrench_cases as bw, base_wrench_ref as bwr, chain_cases as cc, chain_ref, second_order_ref as sor
-from tests import test_gpu_chain as tgc, tree_cases as tc, tree_ref
+from tests import rigid_support as rs, tree_cases as tc, tree_ref
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +25,6 @@ I3, Z3 = np.eye(3), np.zeros((3, 3))
 F_BOTH = np.block([[I3, Z3], [-I3, Z3], [Z3, I3], [Z3, -I3]])
 GRAVITY = np.array([0.0, 0.0, -9.81])
 BADARG, UNSUPPORTED = -1, -3
-
-
-def _check(key, got):
-    ref = bw.reference(key)
-    for name, val in got.items():
-        err, bound = bw.metric(val, ref[name], ref[name + "_mag"]), bw.bound(key, name)
-        print("%s %s: error %.3g, bound %.3g (%.2f of it)" % (key, name, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (key, name, err, bound)
 
 
 @pytest.mark.parametrize("key", bw.CASES)
@@ -45,7 +37,7 @@ def test_kernels_against_the_numpy_reference(gpu, key):
     w0, wa, wb = model.base_wrench_terms(q, qs, qss, mount)
     single = model.base_wrench(q, qs, qss, mount)
     assert w0.shape == wa.shape == wb.shape == single.shape == q.shape[:2] + (6,)
-    _check(key, {"w0": w0, "wa": wa, "wb": wb, "wrench": single})
+    rs.check(bw, key, {"w0": w0, "wa": wa, "wb": wb, "wrench": single}, label="%s")
     zero = np.zeros_like(q)
     assert np.array_equal(w0, model.base_wrench(q, zero, zero, mount)) and np.array_equal(wa, model.base_wrench(q, zero, qs, mount))
     assert np.array_equal(wb, single)
@@ -123,7 +115,7 @@ def test_joint_0_identity_against_the_tree_kernels(gpu, key):
 @pytest.mark.parametrize("key", (1, 7, 32, "nested", "comb32"))
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, key):
     """(6) torch tensors on the device, contiguous and as a non-contiguous view, a flattened shape, a single point."""
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     robot, q, qs, qss = bw.case(key)
     d = q.shape[-1]
     model, mount = bwr.robot_of(robot), bwr.mount_of(bw.MOUNT)
@@ -146,14 +138,6 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, key):
 
 # ---- the constraint ---------------------------------------------------------------------------------------------------------
 
-def _instance(source, data, args, cons):
-    from toppra_amd import algorithm, batch
-    if source == "spline":
-        return algorithm.BatchTOPPRA(*args, constraints=cons)
-    pe = batch.path_eval_batch(*args[:3])
-    return algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"], constraints=cons)
-
-
 def _robot(kind):
     """A robot dict under gravity along -z: the 7-dof chain, or the torso with two 7-dof arms."""
     base = cc.case(7)[0] if kind == "chain" else tc.case("torso")[0]
@@ -169,15 +153,8 @@ def _peak(robot, mount, args):
 
 def _compare(source, data, args, ours, F, g, DT):
     """The constraint against BatchSecondOrderConstraint(robot.base_wrench with the mount bound, F, g): rows and all five passes."""
-    from toppra_amd import constraint
     robot, mount = ours.robot, ours.mount
-    theirs = constraint.BatchSecondOrderConstraint(lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount), F, g, discretization_scheme=DT)
-    results = [tgc._run_passes(_instance(source, data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
-    assert np.isfinite(results[0]["rows"][0]).all()
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(results[0][k]["status"] == 0), k  # the limits leave every trajectory feasible
-    return results[0]
+    return rs.compare(source, data, args, ours, lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount), F, g, DT)
 
 
 @pytest.mark.parametrize("scheme", ["Collocation", "Interpolation"])
@@ -189,7 +166,7 @@ def test_the_constraint_equals_the_callback_route(gpu, scheme, source, kind, per
     robot = _robot(kind)
     d = len(robot["mass"])
     model, mount = bwr.robot_of(robot), bwr.mount_of(bw.MOUNT)
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     peak = _peak(robot, bw.MOUNT, args)
     hi = 1.5 * peak[:3] * (1.0 + np.random.default_rng(9).random((cc.B, 3) if per_traj else 3))
     force, moment = np.stack([-1.25 * hi, hi], -1), 2.0 * peak[3:].max()
@@ -222,7 +199,7 @@ def test_the_contact_cone_equals_the_callback_route(gpu, kind, source):
     from toppra_amd import constraint
     robot = _robot(kind)
     d = len(robot["mass"])
-    data, args = tgc._problem(d, seed=6)
+    data, args = rs.problem(d, seed=6)
     mount, mu, half, F, g = _cart(robot, args)
     DT = constraint.DiscretizationType.Interpolation
     ours = constraint.BatchBaseWrenchConstraint.surface_contact(bwr.robot_of(robot), mu, half, mount=bwr.mount_of(mount))
@@ -238,14 +215,14 @@ def test_beside_a_torque_constraint_on_the_same_robot(gpu):
     robot = _robot("tree")
     d = len(robot["mass"])
     model, mount = bwr.robot_of(robot), bwr.mount_of(bw.MOUNT)
-    data, args = tgc._problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     taumax = np.abs(model.torque_terms(pe["q"], pe["qs"], pe["qss"])[0]).max() + 20.0
     peak = _peak(robot, bw.MOUNT, args)
     cons = [constraint.BatchJointTorqueConstraint(model, np.tile([-taumax, taumax], (d, 1)), np.zeros(d)),
             constraint.BatchBaseWrenchConstraint(model, mount, force=1.5 * peak[:3].max(), moment=1.5 * peak[3:].max())]
     inst = algorithm.BatchTOPPRA(*args, constraints=cons)
-    out = tgc._run_passes(inst)
+    out = rs.run_passes(inst)
     assert out["rows"][0].shape[-1] == 2 + 4 * d + 2 * d + 24 == 116 <= 122
     assert all(np.isfinite(out["rows"][k]).all() for k in range(3))
     for k in ("compute_parameterization", "compute_parameterization_sd"):

@@ -8,7 +8,7 @@ np.longdouble): at most 0.43 over w0 / wa / wb (32 dof), 0.66 over the tool velo
 import numpy as np
 import pytest
 
-from tests import chain_cases as cc, chain_ref, second_order_ref as sor
+from tests import chain_cases as cc, chain_ref, rigid_support as rs, second_order_ref as sor
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -17,36 +17,23 @@ PASSES = ("compute_parameterization", "compute_parameterization_sd", "compute_fe
           "compute_reachable_sets")
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _check(d, got, names):
-    ref = cc.reference(d)
-    for name, val in zip(names, got):
-        err, bound = cc.metric(val, ref[name], ref[name + "_mag"]), cc.bound(d, name)
-        print("d %d %s: error %.3g, bound %.3g (%.2f of it)" % (d, name, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (d, name, err, bound)
-
-
 @pytest.mark.parametrize("d", cc.DOFS)
 def test_kernels_against_the_numpy_reference(gpu, d):
     """All three entries, from numpy arrays; each fused output equals the single evaluation on the same arguments."""
     chain, q, qs, qss = cc.case(d)
     sc = chain_ref.serial_chain(chain)
     fused = sc.torque_terms(q, qs, qss)
-    _check(d, fused, ("w0", "wa", "wb"))
+    rs.check(cc, d, dict(zip(("w0", "wa", "wb"), fused)))
     for got, args in zip(fused, cc.evaluations(q, qs, qss).values()):
         assert np.array_equal(got, sc.inverse_dynamics(*args))
-    _check(d, (sc.tool_velocity_norm(q, qs), sc.tool_velocity_norm(q, qs, cc.S_FULL)), ("vsv", "vsv_S"))
+    rs.check(cc, d, {"vsv": sc.tool_velocity_norm(q, qs), "vsv_S": sc.tool_velocity_norm(q, qs, cc.S_FULL)})
     assert np.all(sc.tool_velocity_norm(q, qs)[2] == 0.0)  # the trajectory that stands still
 
 
 @pytest.mark.parametrize("d", cc.DOFS)
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     """torch tensors on the device, contiguous and as a non-contiguous view, any leading shape: the values of the numpy call."""
-    torch, dev = _torch()
+    torch, dev = rs.torch_device()
     chain, q, qs, qss = cc.case(d)
     sc = chain_ref.serial_chain(chain)
     host = sc.torque_terms(q, qs, qss)
@@ -66,45 +53,16 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     assert np.array_equal(sc.tool_velocity_norm(tq, tqs, S).cpu().numpy(), sc.tool_velocity_norm(q, qs, cc.S_FULL))
 
 
-def _problem(d, B=cc.B, N=cc.N, seed=5):
-    from toppra_amd import batch
-    data = batch.make_synthetic_batch(B, d, N, seed=seed)
-    return data, (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
-
-
-def _run_passes(inst):
-    out = {"rows": inst.dense_rows() if inst.constraints else inst.stage_boxes()}
-    out["compute_parameterization"] = inst.compute_parameterization()
-    out["compute_parameterization_sd"] = inst.compute_parameterization_sd(np.full(cc.B, 8.0))
-    out["compute_feasible_sets"] = inst.compute_feasible_sets()
-    out["compute_controllable_sets"] = inst.compute_controllable_sets(np.zeros(cc.B), np.full(cc.B, 0.3))
-    out["compute_reachable_sets"] = inst.compute_reachable_sets(np.zeros(cc.B), np.full(cc.B, 0.3))
-    return out
-
-
-def _same(a, b, what):
-    if isinstance(a, dict):
-        assert sorted(a) == sorted(b), what
-        for k in a:
-            _same(a[k], b[k], what + "." + k)
-    elif isinstance(a, (tuple, list)):
-        assert len(a) == len(b), what
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (what, i))
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True), what
-
-
 @pytest.mark.parametrize("scheme", ["Collocation", "Interpolation"])
 @pytest.mark.parametrize("source", ["spline", "samples"])
 @pytest.mark.parametrize("per_traj", [False, True])
 def test_a_chain_in_the_torque_constraint_equals_its_callback(gpu, scheme, source, per_traj):
     """BatchJointTorqueConstraint(chain, ...) against inv_dyn=chain.inverse_dynamics: the dense rows and every pass are equal."""
-    from toppra_amd import algorithm, batch, constraint
+    from toppra_amd import algorithm, constraint
     d = 7
     chain, q, _, _ = cc.case(d)
     sc = chain_ref.serial_chain(chain)
-    data, args = _problem(d)
+    data, args = rs.problem(d)
     hold = np.abs(cc.reference(d)["w0"]).max() + 5.0
     rng = np.random.default_rng(9)
     taumax = hold * (1.0 + rng.random((cc.B, d) if per_traj else d))
@@ -113,22 +71,12 @@ def test_a_chain_in_the_torque_constraint_equals_its_callback(gpu, scheme, sourc
     results = []
     for inv_dyn in (sc, sc.inverse_dynamics):
         cons = [constraint.BatchJointTorqueConstraint(inv_dyn, taulim, fric, discretization_scheme=DT)]
-        if source == "spline":
-            inst = algorithm.BatchTOPPRA(*args, constraints=cons)
-        else:
-            pe = batch.path_eval_batch(*args[:3])
-            inst = algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"],
-                                                           constraints=cons)
-        results.append(_run_passes(inst))
-    _same(results[0], results[1], "chain vs callback")
+        results.append(rs.run_passes(rs.instance(source, data, args, cons)))
+    rs.same(results[0], results[1], "chain vs callback")
     assert np.isfinite(results[0]["rows"][0]).all()
     if source == "spline":  # the second-order spelling of the same constraint takes a chain as well, and builds the same rows
         so = constraint.BatchSecondOrderConstraint.joint_torque_constraint(sc, taulim, fric, discretization_scheme=DT)
-        _same(algorithm.BatchTOPPRA(*args, constraints=[so]).dense_rows(), results[0]["rows"], "second-order spelling")
-
-
-def _fixture_chain(fx):
-    return {k: fx[k] for k in ("joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity", "tool")}
+        rs.same(algorithm.BatchTOPPRA(*args, constraints=[so]).dense_rows(), results[0]["rows"], "second-order spelling")
 
 
 @pytest.mark.parametrize("name", FIXTURES)
@@ -137,7 +85,7 @@ def test_against_the_reference_s_fixtures(gpu, name):
     tolerance (measured on the CPU: tools/make_chain_golden.py)."""
     from toppra_amd import algorithm, constraint
     fx = golden(name)
-    chain = _fixture_chain(fx)
+    chain = rs.fixture_chain(fx)
     sc = chain_ref.serial_chain(chain)
     B, d = fx["coef"].shape[0], fx["coef"].shape[3]
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
@@ -188,11 +136,11 @@ def test_tool_speed_constraint(gpu, S, kind):
     d = 7
     chain, _, _, _ = cc.case(d)
     sc = chain_ref.serial_chain(chain)
-    data, args = _problem(d, seed=6)
+    data, args = rs.problem(d, seed=6)
     S = None if S is None else cc.S_FULL
     limit = np.array([0.05, 0.1, 0.2, 0.4, 0.8])
     if kind == "torch":
-        torch, dev = _torch()
+        torch, dev = rs.torch_device()
         args = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in args)
     host = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else v  # noqa: E731
     pe = batch.path_eval_batch(*args[:3])
@@ -255,7 +203,7 @@ def test_chained_with_the_other_constraints(gpu):
     d = 7
     chain, _, _, _ = cc.case(d)
     sc = chain_ref.serial_chain(chain)
-    data, args = _problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     _, xbound = batch.chain_tool_bound_batch(sc, pe["q"], pe["qs"], 0.3)
     vgrid = np.broadcast_to(2.0 * data["vlim"][:, None], (cc.B, cc.N + 1, d, 2)).copy()
@@ -268,8 +216,8 @@ def test_chained_with_the_other_constraints(gpu):
     b = algorithm.BatchTOPPRA(*args, constraints=[constraint.BatchJointVelocityConstraintVarying(vgrid),
                                                   constraint.BatchBoundConstraint(xbound=xbound),
                                                   constraint.BatchBoundConstraint(ubound=ub), torque()])
-    _same(a.dense_rows(), b.dense_rows(), "rows")
-    _same(a.compute_parameterization(), b.compute_parameterization(), "parameterization")
+    rs.same(a.dense_rows(), b.dense_rows(), "rows")
+    rs.same(a.compute_parameterization(), b.compute_parameterization(), "parameterization")
     assert np.all(a.compute_parameterization()["status"] == 0)
 
 
@@ -317,7 +265,7 @@ def test_entries_refuse_bad_arguments_before_any_launch(gpu):
     codes = np.array([0, 2, 1], dtype=np.int32)
     assert calls(model(joint_type=codes.ctypes.data)) == (BADARG,) * 3
     assert b"joint type" in lib.tpr_last_error()
-    torch, dev = _torch()
+    torch, dev = rs.torch_device()
     on_device = torch.zeros(3, dtype=torch.int32, device=dev)
     assert calls(model(joint_type=on_device.data_ptr())) == (BADARG,) * 3
     assert b"host array" in lib.tpr_last_error()

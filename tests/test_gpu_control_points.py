@@ -13,7 +13,7 @@ reference's fixtures, whose sd they reproduce to 7.1e-15 / 6.3e-14 (tolerances 1
 import numpy as np
 import pytest
 
-from tests import chain_cases as cc, chain_ref, control_points_cases as cp, second_order_ref as sor, test_gpu_chain as tgc
+from tests import chain_cases as cc, chain_ref, control_points_cases as cp, rigid_support as rs, second_order_ref as sor
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -73,7 +73,7 @@ def test_every_point_equals_the_tool_kernels_on_the_cut_chain(gpu, d, which):
 @pytest.mark.parametrize("d,which", [(1, "c"), (7, "b"), (9, "d"), (32, "c")], ids=["1c", "7b", "9d", "32c"])
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d, which):
     """torch tensors on the device, contiguous and as a non-contiguous view, a flattened shape, a single point."""
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     chain, q, qs, qss = cc.case(d)
     sc, pts = chain_ref.serial_chain(chain), cp.control_points(d, which)
     P = pts.count
@@ -106,14 +106,6 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d, which):
     assert np.array_equal(xb.cpu().numpy(), batch.chain_points_speed_batch(sc, q, qs, pts, limit)[1])
 
 
-def _instance(source, data, args, cons):
-    from toppra_amd import algorithm, batch
-    if source == "spline":
-        return algorithm.BatchTOPPRA(*args, constraints=cons)
-    pe = batch.path_eval_batch(*args[:3])
-    return algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"], constraints=cons)
-
-
 def _peak(chain, links, offsets, args):
     """max |wb| per point [P] over the problem's gridpoints, from the CPU reference."""
     q, qs, qss = sor.path_samples(*args[:3])
@@ -139,7 +131,7 @@ def test_the_acceleration_constraint_equals_the_callback_route(gpu, scheme, sour
     links, offsets = cp.point_set(d, which)
     sc, pts = chain_ref.serial_chain(chain), cp.control_points(d, which)
     P = pts.count
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     # positive on both sides (standing still satisfies it) and a generous multiple of each point's largest |wb|
     hi = 2.0 * _peak(chain, links, offsets, args)[:, None] * (1.0 + np.random.default_rng(9).random((cc.B, P, 3) if per_traj else (P, 3)))
     linear = np.stack([-1.5 * hi, hi], -1)  # [P, 3, 2] or [B, P, 3, 2]
@@ -148,14 +140,8 @@ def test_the_acceleration_constraint_equals_the_callback_route(gpu, scheme, sour
     F = _signed_identity(P)
     g = np.concatenate((linear[..., 1], -linear[..., 0]), -1).reshape(linear.shape[:-3] + (6 * P,))
     assert np.array_equal(ours.F, F) and np.array_equal(ours.g, g)
-    theirs = constraint.BatchSecondOrderConstraint(_stacked_tool_accelerations(_cut_chains(chain, links, offsets)), F, g,
-                                                   discretization_scheme=DT)
-    results = [tgc._run_passes(_instance(source, data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
-    assert np.isfinite(results[0]["rows"][0]).all()
-    assert results[0]["rows"][0].shape[-1] == 2 + 4 * d + (12 if scheme == "Interpolation" else 6) * P
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(results[0][k]["status"] == 0), k
+    out = rs.compare(source, data, args, ours, _stacked_tool_accelerations(_cut_chains(chain, links, offsets)), F, g, DT)
+    assert out["rows"][0].shape[-1] == 2 + 4 * d + (12 if scheme == "Interpolation" else 6) * P
 
 
 def test_a_dense_F_equals_the_callback_route(gpu):
@@ -165,13 +151,13 @@ def test_a_dense_F_equals_the_callback_route(gpu):
     chain = cc.case(d)[0]
     links, offsets = cp.point_set(d, which)
     sc, pts = chain_ref.serial_chain(chain), cp.control_points(d, which)
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     F = np.random.default_rng(11).uniform(-1.0, 1.0, (5, 3 * pts.count))
     g = 2.0 * np.abs(F).reshape(5, pts.count, 3).sum(-1) @ _peak(chain, links, offsets, args)
     ours = constraint.BatchPointAccelerationConstraint(sc, pts, F=F, g=g)
     theirs = constraint.BatchSecondOrderConstraint(_stacked_tool_accelerations(_cut_chains(chain, links, offsets)), F, g)
-    results = [tgc._run_passes(_instance("spline", data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
+    results = [rs.run_passes(rs.instance("spline", data, args, [con])) for con in (ours, theirs)]
+    rs.same(results[0], results[1], "constraint vs callback")
     assert np.all(results[0]["compute_parameterization"]["status"] == 0)
 
 
@@ -185,7 +171,7 @@ def test_the_speed_constraint_equals_a_host_made_bound(gpu, kind, limits):
     chain = cc.case(d)[0]
     sc, pts = chain_ref.serial_chain(chain), cp.control_points(d, which)
     P = pts.count
-    data, args = tgc._problem(d, seed=6)
+    data, args = rs.problem(d, seed=6)
     limit = {"scalar": 0.2, "per_point": np.array([0.05, 0.4, 0.1]),
              "per_traj": np.random.default_rng(3).uniform(0.05, 0.8, (cc.B, P))}[limits]
     pe = batch.path_eval_batch(*args[:3])
@@ -196,7 +182,7 @@ def test_the_speed_constraint_equals_a_host_made_bound(gpu, kind, limits):
     host = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else v  # noqa: E731
     ours_limit = limit
     if kind == "torch":
-        torch, dev = tgc._torch()
+        torch, dev = rs.torch_device()
         args = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in args)
         xbound = torch.from_numpy(xbound).to(dev)
         if limits == "per_traj":
@@ -207,10 +193,10 @@ def test_the_speed_constraint_equals_a_host_made_bound(gpu, kind, limits):
         assert np.array_equal(host(a), host(b))
     results = []
     for inst in (ours, theirs):
-        out = tgc._run_passes(inst)
+        out = rs.run_passes(inst)
         results.append({k: ({n: host(x) for n, x in v.items()} if isinstance(v, dict) else [host(x) for x in v] if isinstance(v, (tuple, list))
                             else host(v)) for k, v in out.items()})
-    tgc._same(results[0], results[1], "constraint vs host-made bound")
+    rs.same(results[0], results[1], "constraint vs host-made bound")
     assert np.all(results[0]["compute_parameterization"]["status"] == 0)
     high = host(ours.stage_boxes()[1])
     assert (high[..., 1] < sor.velocity_box(host(pe["qs"]), data["vlim"])[1][..., 1]).any(), "the speed limit tightens no box"
@@ -254,7 +240,7 @@ def test_beside_the_other_chain_constraints(gpu):
     chain = cc.case(d)[0]
     links, offsets = cp.point_set(d, which)
     sc, pts = chain_ref.serial_chain(chain), cp.control_points(d, which)
-    data, args = tgc._problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     taumax = np.abs(sc.torque_terms(pe["q"], pe["qs"], pe["qss"])[0]).max() + 20.0
     body = Payload(0.5, com=(0.0, 0.0, 0.05))
@@ -267,7 +253,7 @@ def test_beside_the_other_chain_constraints(gpu):
               lambda: constraint.BatchToolWrenchConstraint(sc, body, force=fmax)]
     speeds = lambda: [constraint.BatchCartesianVelocityNormConstraint(sc, 0.3), constraint.BatchPointSpeedConstraint(sc, pts, 0.2)]  # noqa: E731
     inst = algorithm.BatchTOPPRA(*args, constraints=[m() for m in makers[:2]] + speeds()[:1] + [m() for m in makers[2:]] + speeds()[1:])
-    out = tgc._run_passes(inst)
+    out = rs.run_passes(inst)
     for k in ("compute_parameterization", "compute_parameterization_sd"):
         assert np.all(out[k]["status"] == 0), k
     for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
@@ -306,7 +292,7 @@ def test_against_the_reference_s_fixtures(gpu, name):
     from toppra_amd import algorithm, constraint
     from toppra_amd.chain import ControlPoints
     fx = golden(name)
-    chain = tgc._fixture_chain(fx)
+    chain = rs.fixture_chain(fx)
     sc, pts = chain_ref.serial_chain(chain), ControlPoints(fx["links"], fx["offsets"])
     B, d, P = fx["coef"].shape[0], fx["coef"].shape[3], len(fx["links"])
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
@@ -381,7 +367,7 @@ def test_entries_refuse_a_bad_chain_before_any_launch(gpu):
         assert calls(model(**{field: None})) == (BADARG,) * 3, field
     codes = np.array([0, 2, 1], dtype=np.int32)
     assert calls(model(joint_type=codes.ctypes.data)) == (BADARG,) * 3
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     on_device = torch.zeros(3, dtype=torch.int32, device=dev)
     assert calls(model(joint_type=on_device.data_ptr())) == (BADARG,) * 3
     assert calls(model(), B=1 << 20, N=(1 << 11) - 1) == (UNSUPPORTED,) * 3  # 2^31 points

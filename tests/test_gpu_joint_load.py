@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from tests import base_wrench_ref as bwr, chain_cases as cc, chain_ref, joint_load_cases as jc, joint_load_ref as jr
-from tests import second_order_ref as sor, test_gpu_chain as tgc, tree_cases as tc, tree_ref
+from tests import rigid_support as rs, second_order_ref as sor, tree_cases as tc, tree_ref
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -35,14 +35,6 @@ def _single(model, key, q, qd, qdd):
     return jc.by_sets(key, lambda sec: model.joint_wrenches(q, qd, qdd, jr.joint_sections_of(sec)))
 
 
-def _check(key, got):
-    ref = jc.reference(key)
-    for name, val in got.items():
-        err, bound = jc.metric(val, ref[name], ref[name + "_mag"]), jc.bound(key, name)
-        print("%s %s: error %.3g, bound %.3g (%.2f of it)" % (key, name, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (key, name, err, bound)
-
-
 @pytest.mark.parametrize("key", jc.CASES)
 def test_kernels_against_the_numpy_reference(gpu, key):
     """(1) Both entries, from numpy arrays; each fused output equals the single evaluation on the same arguments in every bit; no
@@ -53,7 +45,7 @@ def test_kernels_against_the_numpy_reference(gpu, key):
     w0, wa, wb = _terms(model, key, q, qs, qss)
     single = _single(model, key, q, qs, qss)
     assert w0.shape == wa.shape == wb.shape == single.shape == q.shape[:2] + (S, 6)
-    _check(key, {"w0": w0, "wa": wa, "wb": wb, "wrench": single})
+    rs.check(jc, key, {"w0": w0, "wa": wa, "wb": wb, "wrench": single}, label="%s")
     zero = np.zeros_like(q)
     assert np.array_equal(w0, _single(model, key, q, zero, zero)) and np.array_equal(wa, _single(model, key, q, zero, qs))
     assert np.array_equal(wb, single)
@@ -209,7 +201,7 @@ def test_joint_0_identity_against_the_base_reaction(gpu, key):
 @pytest.mark.parametrize("key", (1, 7, 32, "nested", "comb32"))
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, key):
     """(7) torch tensors on the device, contiguous and as a non-contiguous view, a flattened shape, a single point."""
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     robot, q, qs, qss = jc.case(key)
     d = q.shape[-1]
     model = bwr.robot_of(robot)
@@ -234,14 +226,6 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, key):
 
 # ---- the constraint ---------------------------------------------------------------------------------------------------------
 
-def _instance(source, data, args, cons):
-    from toppra_amd import algorithm, batch
-    if source == "spline":
-        return algorithm.BatchTOPPRA(*args, constraints=cons)
-    pe = batch.path_eval_batch(*args[:3])
-    return algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"], constraints=cons)
-
-
 def _robot(kind):
     """A robot dict under gravity along -z with its sections: the 7-dof chain (joint 1 and the last link), or the torso with two
     7-dof arms (the first joint of each arm)."""
@@ -262,20 +246,13 @@ def _peak(robot, sec, args):
 
 def _compare(source, data, args, ours, F, g, DT):
     """The constraint against BatchSecondOrderConstraint(robot.joint_wrenches flattened, F, g): rows and all five passes."""
-    from toppra_amd import constraint
     robot, sections = ours.robot, ours.sections
 
     def inv_dyn(q, qd, qdd):
         w = robot.joint_wrenches(q, qd, qdd, sections)
         return w.reshape(tuple(w.shape[:-2]) + (6 * sections.count,))
 
-    theirs = constraint.BatchSecondOrderConstraint(inv_dyn, F, g, discretization_scheme=DT)
-    results = [tgc._run_passes(_instance(source, data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
-    assert np.isfinite(results[0]["rows"][0]).all()
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(results[0][k]["status"] == 0), k  # the limits leave every trajectory feasible
-    return results[0]
+    return rs.compare(source, data, args, ours, inv_dyn, F, g, DT)
 
 
 def _box_rows(S):
@@ -296,7 +273,7 @@ def test_the_constraint_equals_the_callback_route(gpu, scheme, source, kind, per
     from toppra_amd import constraint
     robot, model, sections, sec = _robot(kind)
     d, S = len(robot["mass"]), sections.count
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     peak = _peak(robot, sec, args)
     hi = 1.5 * peak[:, :3] * (1.0 + np.random.default_rng(9).random((cc.B, S, 3) if per_traj else (S, 3)))
     force, moment = np.stack([-1.25 * hi, hi], -1), 2.0 * peak[:, 3:].max(-1)
@@ -317,7 +294,7 @@ def test_the_bearing_rows_equal_the_callback_route(gpu, kind, source, scheme):
     from toppra_amd import constraint
     robot, model, sections, sec = _robot(kind)
     d, S = len(robot["mass"]), sections.count
-    data, args = tgc._problem(d, seed=6)
+    data, args = rs.problem(d, seed=6)
     peak = _peak(robot, sec, args)
     sides = 6
     room = 1.5 * np.sqrt(2.0) / np.cos(np.pi / sides)
@@ -337,14 +314,14 @@ def test_beside_a_torque_constraint_on_the_same_robot(gpu):
     from toppra_amd import algorithm, batch, constraint
     robot, model, sections, sec = _robot("tree")
     d = len(robot["mass"])
-    data, args = tgc._problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     taumax = np.abs(model.torque_terms(pe["q"], pe["qs"], pe["qss"])[0]).max() + 20.0
     peak = _peak(robot, sec, args)
     cons = [constraint.BatchJointTorqueConstraint(model, np.tile([-taumax, taumax], (d, 1)), np.zeros(d)),
             constraint.BatchJointLoadConstraint(model, sections, moment=1.5 * peak[:, 3:].max(-1))]
     inst = algorithm.BatchTOPPRA(*args, constraints=cons)
-    out = tgc._run_passes(inst)
+    out = rs.run_passes(inst)
     assert out["rows"][0].shape[-1] == 2 + 4 * d + 2 * d + 24 == 116 <= 122
     assert all(np.isfinite(out["rows"][k]).all() for k in range(3))
     for k in ("compute_parameterization", "compute_parameterization_sd"):

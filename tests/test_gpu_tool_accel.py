@@ -10,21 +10,13 @@ bound on the reference's fixtures, whose sd they reproduce to 7.8e-16 / 3.8e-13 
 import numpy as np
 import pytest
 
-from tests import chain_cases as cc, chain_ref, second_order_ref as sor, test_gpu_chain as tgc, tool_accel_cases as tc, tool_accel_ref as tar
+from tests import chain_cases as cc, chain_ref, rigid_support as rs, second_order_ref as sor, tool_accel_cases as tc, tool_accel_ref as tar
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
 FIXTURES = ("tool_accel_d6_N40", "tool_accel_d3_N30_colloc")
 I3, Z3 = np.eye(3), np.zeros((3, 3))
 F_LINEAR, F_BOTH = np.block([[I3, Z3], [-I3, Z3]]), np.block([[I3, Z3], [-I3, Z3], [Z3, I3], [Z3, -I3]])
-
-
-def _check(d, got):
-    ref = tc.reference(d)
-    for name, val in got.items():
-        err, bound = cc.metric(val, ref[name], ref[name + "_mag"]), tc.bound(d, name)
-        print("d %d %s: error %.3g, bound %.3g (%.2f of it)" % (d, name, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (d, name, err, bound)
 
 
 @pytest.mark.parametrize("d", tc.DOFS)
@@ -35,7 +27,7 @@ def test_kernels_against_the_numpy_reference(gpu, d):
     wa, wb = sc.tool_acceleration_terms(q, qs, qss)
     acc = sc.tool_acceleration(q, qs, qss)
     assert wa.shape == wb.shape == acc.shape == (cc.B, cc.N + 1, 6)
-    _check(d, {"wa": wa, "wb": wb, "acc": acc})
+    rs.check(tc, d, {"wa": wa, "wb": wb, "acc": acc})
     zero = np.zeros_like(q)
     assert np.array_equal(wa, sc.tool_acceleration(q, zero, qs)) and np.array_equal(wb, acc)
     assert np.all(wa[2] == 0.0)  # the trajectory that stands still
@@ -49,7 +41,7 @@ def test_kernels_against_the_numpy_reference(gpu, d):
 @pytest.mark.parametrize("d", tc.DOFS)
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     """torch tensors on the device, contiguous and as a non-contiguous view, a flattened shape, a single point."""
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     chain, q, qs, qss = cc.case(d)
     sc = chain_ref.serial_chain(chain)
     host = sc.tool_acceleration_terms(q, qs, qss)
@@ -69,14 +61,6 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     assert np.array_equal(one[0], host[0][1, 3]) and np.array_equal(one[1], host[1][1, 3])
 
 
-def _instance(source, data, args, cons):
-    from toppra_amd import algorithm, batch
-    if source == "spline":
-        return algorithm.BatchTOPPRA(*args, constraints=cons)
-    pe = batch.path_eval_batch(*args[:3])
-    return algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"], constraints=cons)
-
-
 def _peak(chain, args):
     """max |wb| of the linear and of the angular part over the problem's gridpoints, from the CPU reference."""
     q, qs, qss = sor.path_samples(*args[:3])
@@ -86,15 +70,7 @@ def _peak(chain, args):
 
 def _compare(source, data, args, ours, F, g, DT):
     """The constraint against BatchSecondOrderConstraint(chain.tool_acceleration, F, g): the dense rows and all five passes."""
-    from toppra_amd import constraint
-    sc = ours.chain
-    theirs = constraint.BatchSecondOrderConstraint(sc.tool_acceleration, F, g, discretization_scheme=DT)
-    results = [tgc._run_passes(_instance(source, data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
-    assert np.isfinite(results[0]["rows"][0]).all()
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(results[0][k]["status"] == 0), k  # the limits leave every trajectory feasible
-    return results[0]
+    return rs.compare(source, data, args, ours, ours.chain.tool_acceleration, F, g, DT)
 
 
 @pytest.mark.parametrize("scheme", ["Collocation", "Interpolation"])
@@ -105,7 +81,7 @@ def test_the_constraint_equals_the_callback_route(gpu, scheme, source, per_traj)
     d = 7
     chain = cc.case(d)[0]
     sc = chain_ref.serial_chain(chain)
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     # positive on both sides (standing still satisfies it) and a generous multiple of the largest |wb|
     hi = 2.0 * _peak(chain, args)[0] * (1.0 + np.random.default_rng(9).random((cc.B, 3) if per_traj else 3))
     linear = np.stack([-1.5 * hi, hi], -1)  # [3, 2] or [B, 3, 2]
@@ -120,7 +96,7 @@ def test_linear_and_angular_limits_equal_the_callback_route(gpu):
     d = 7
     chain = cc.case(d)[0]
     sc = chain_ref.serial_chain(chain)
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     lin, ang = _peak(chain, args)
     DT = constraint.DiscretizationType.Interpolation
     ours = constraint.BatchCartesianAccelerationConstraint(sc, linear=2.0 * lin, angular=3.0 * ang)
@@ -133,7 +109,7 @@ def test_a_dense_F_equals_the_callback_route(gpu):
     d = 7
     chain = cc.case(d)[0]
     sc = chain_ref.serial_chain(chain)
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     F = np.random.default_rng(11).uniform(-1.0, 1.0, (5, 6))
     g = 2.0 * (np.abs(F[:, :3]).sum(-1) * _peak(chain, args)[0] + np.abs(F[:, 3:]).sum(-1) * _peak(chain, args)[1])
     DT = constraint.DiscretizationType.Interpolation
@@ -146,7 +122,7 @@ def test_against_the_reference_s_fixtures(gpu, name):
     return codes equal, sd within the stored end-to-end tolerance (tools/make_tool_accel_golden.py)."""
     from toppra_amd import algorithm, constraint
     fx = golden(name)
-    chain = tgc._fixture_chain(fx)
+    chain = rs.fixture_chain(fx)
     sc = chain_ref.serial_chain(chain)
     B, d = fx["coef"].shape[0], fx["coef"].shape[3]
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
@@ -199,13 +175,13 @@ def test_beside_the_other_chain_constraints(gpu):
     d = 7
     chain = cc.case(d)[0]
     sc = chain_ref.serial_chain(chain)
-    data, args = tgc._problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     taumax = np.abs(sc.torque_terms(pe["q"], pe["qs"], pe["qss"])[0]).max() + 20.0
     torque = lambda: constraint.BatchJointTorqueConstraint(sc, np.tile([-taumax, taumax], (d, 1)), np.zeros(d))  # noqa: E731
     accel = lambda: constraint.BatchCartesianAccelerationConstraint(sc, linear=2.0 * _peak(chain, args)[0])  # noqa: E731
     inst = algorithm.BatchTOPPRA(*args, constraints=[torque(), accel(), constraint.BatchCartesianVelocityNormConstraint(sc, 0.3)])
-    out = tgc._run_passes(inst)
+    out = rs.run_passes(inst)
     for k in ("compute_parameterization", "compute_parameterization_sd"):
         assert np.all(out[k]["status"] == 0), k
     for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
@@ -252,7 +228,7 @@ def test_entries_refuse_bad_arguments_before_any_launch(gpu):
     codes = np.array([0, 2, 1], dtype=np.int32)
     assert calls(model(joint_type=codes.ctypes.data)) == (BADARG,) * 2
     assert b"joint type" in lib.tpr_last_error()
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     on_device = torch.zeros(3, dtype=torch.int32, device=dev)
     assert calls(model(joint_type=on_device.data_ptr())) == (BADARG,) * 2
     assert b"host array" in lib.tpr_last_error()

@@ -10,7 +10,7 @@ bound on the reference's fixtures, whose sd they reproduce to 5.3e-15 / 2.7e-13 
 import numpy as np
 import pytest
 
-from tests import chain_cases as cc, chain_ref, second_order_ref as sor, test_gpu_chain as tgc, tool_wrench_cases as tw, tool_wrench_ref as twr
+from tests import chain_cases as cc, chain_ref, rigid_support as rs, second_order_ref as sor, tool_wrench_cases as tw, tool_wrench_ref as twr
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +21,6 @@ F_BOTH = np.block([[I3, Z3], [-I3, Z3], [Z3, I3], [Z3, -I3]])
 GRAVITY = np.array([0.3, -0.2, -9.81])
 
 
-def _check(d, got):
-    ref = tw.reference(d)
-    for name, val in got.items():
-        err, bound = cc.metric(val, ref[name], ref[name + "_mag"]), tw.bound(d, name)
-        print("d %d %s: error %.3g, bound %.3g (%.2f of it)" % (d, name, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (d, name, err, bound)
-
-
 @pytest.mark.parametrize("d", tw.DOFS)
 def test_kernels_against_the_numpy_reference(gpu, d):
     """Both entries, from numpy arrays; each fused output equals the single evaluation on the same arguments in every bit."""
@@ -37,7 +29,7 @@ def test_kernels_against_the_numpy_reference(gpu, d):
     w0, wa, wb = sc.tool_wrench_terms(q, qs, qss, obj)
     single = sc.tool_wrench(q, qs, qss, obj)
     assert w0.shape == wa.shape == wb.shape == single.shape == (cc.B, cc.N + 1, 6)
-    _check(d, {"w0": w0, "wa": wa, "wb": wb, "wrench": single})
+    rs.check(tw, d, {"w0": w0, "wa": wa, "wb": wb, "wrench": single})
     zero = np.zeros_like(q)
     assert np.array_equal(w0, sc.tool_wrench(q, zero, zero, obj)) and np.array_equal(wa, sc.tool_wrench(q, zero, qs, obj))
     assert np.array_equal(wb, single)
@@ -83,7 +75,7 @@ def test_a_zero_payload_gives_positive_zeros(gpu, d):
 @pytest.mark.parametrize("d", tw.DOFS)
 def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     """torch tensors on the device, contiguous and as a non-contiguous view, a flattened shape, a single point."""
-    torch, dev = tgc._torch()
+    torch, dev = rs.torch_device()
     chain, q, qs, qss = cc.case(d)
     sc, obj = chain_ref.serial_chain(chain), twr.payload_of(tw.PAYLOAD, chain)
     host = sc.tool_wrench_terms(q, qs, qss, obj)
@@ -103,14 +95,6 @@ def test_device_tensors_and_views_give_the_host_call_s_bits(gpu, d):
     assert all(np.array_equal(one[k], host[k][1, 3]) for k in range(3))
 
 
-def _instance(source, data, args, cons):
-    from toppra_amd import algorithm, batch
-    if source == "spline":
-        return algorithm.BatchTOPPRA(*args, constraints=cons)
-    pe = batch.path_eval_batch(*args[:3])
-    return algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"], constraints=cons)
-
-
 def _case7():
     """The 7-dof chain under gravity (the shared case has it switched off), its SerialChain and the payload."""
     chain = dict(cc.case(7)[0], gravity=GRAVITY)
@@ -126,15 +110,8 @@ def _peak(chain, args):
 
 def _compare(source, data, args, ours, F, g, DT):
     """The constraint against BatchSecondOrderConstraint(chain.tool_wrench with the payload bound, F, g): rows and all five passes."""
-    from toppra_amd import constraint
     sc, obj = ours.chain, ours.payload
-    theirs = constraint.BatchSecondOrderConstraint(lambda q, qd, qdd: sc.tool_wrench(q, qd, qdd, obj), F, g, discretization_scheme=DT)
-    results = [tgc._run_passes(_instance(source, data, args, [con])) for con in (ours, theirs)]
-    tgc._same(results[0], results[1], "constraint vs callback")
-    assert np.isfinite(results[0]["rows"][0]).all()
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(results[0][k]["status"] == 0), k  # the limits leave every trajectory feasible
-    return results[0]
+    return rs.compare(source, data, args, ours, lambda q, qd, qdd: sc.tool_wrench(q, qd, qdd, obj), F, g, DT)
 
 
 @pytest.mark.parametrize("scheme", ["Collocation", "Interpolation"])
@@ -145,7 +122,7 @@ def test_the_constraint_equals_the_callback_route(gpu, scheme, source, per_traj)
     from toppra_amd import constraint
     d = 7
     chain, sc, obj = _case7()
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     rng = np.random.default_rng(11)
     F = rng.uniform(-1.0, 1.0, (5, 6))
     g = 1.5 * (np.abs(F) @ _peak(chain, args))
@@ -161,7 +138,7 @@ def test_force_and_moment_boxes_equal_their_explicit_rows(gpu, per_traj):
     from toppra_amd import constraint
     d = 7
     chain, sc, obj = _case7()
-    data, args = tgc._problem(d)
+    data, args = rs.problem(d)
     peak = _peak(chain, args)
     hi = 1.5 * peak[:3] * (1.0 + np.random.default_rng(9).random((cc.B, 3) if per_traj else 3))
     force, moment = np.stack([-1.25 * hi, hi], -1), 2.0 * peak[3:].max()
@@ -182,7 +159,7 @@ def test_against_the_reference_s_fixtures(gpu, name):
     (tools/make_tool_wrench_golden.py)."""
     from toppra_amd import algorithm, constraint
     fx = golden(name)
-    chain, payload = tgc._fixture_chain(fx), _fixture_payload(fx)
+    chain, payload = rs.fixture_chain(fx), _fixture_payload(fx)
     sc, obj = chain_ref.serial_chain(chain), twr.payload_of(payload, chain)
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     ev = tw.evaluations(q, qs, qss)
@@ -215,7 +192,7 @@ def test_beside_the_other_chain_constraints(gpu):
     d = 7
     chain, sc, obj = _case7()
     loaded = sc.with_payload(obj)
-    data, args = tgc._problem(d, seed=8)
+    data, args = rs.problem(d, seed=8)
     pe = batch.path_eval_batch(*args[:3])
     taumax = np.abs(loaded.torque_terms(pe["q"], pe["qs"], pe["qss"])[0]).max() + 20.0
     acc = np.abs(sc.tool_acceleration_terms(pe["q"], pe["qs"], pe["qss"])[1][..., :3]).max()
@@ -225,7 +202,7 @@ def test_beside_the_other_chain_constraints(gpu):
             constraint.BatchToolWrenchConstraint(sc, obj, force=1.5 * peak[:3].max(), moment=1.5 * peak[3:].max()),
             constraint.BatchCartesianVelocityNormConstraint(sc, 0.3)]
     inst = algorithm.BatchTOPPRA(*args, constraints=cons)
-    out = tgc._run_passes(inst)
+    out = rs.run_passes(inst)
     assert out["rows"][0].shape[-1] == 2 + 4 * d + 2 * d + 12 + 24 <= 122
     assert all(np.isfinite(out["rows"][k]).all() for k in range(3))
     for k in ("compute_parameterization", "compute_parameterization_sd"):

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests import chain_ref, second_order_ref as sor, tree_cases as tc, tree_ref
+from tests import chain_ref, rigid_support as rs, second_order_ref as sor, tree_cases as tc, tree_ref
 from tests.helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -91,13 +91,10 @@ def test_fused_equals_single_and_both_meet_the_reference(gpu, name):
     tests/tree_ref.py (where the magnitude is zero the values agree exactly)."""
     tree, q, qs, qss = tc.case(name)
     kt = tree_ref.kinematic_tree(tree)
-    ref = tc.reference(name)
-    fused = kt.torque_terms(q, qs, qss)
-    for key, got, args in zip(("w0", "wa", "wb"), fused, tc.evaluations(q, qs, qss).values()):
-        assert np.array_equal(got, kt.inverse_dynamics(*args)), (name, key)
-        err, bound = tc.metric(got, ref[key], ref[key + "_mag"]), tc.bound(name, key)
-        print("%s %s: error %.3g, bound %.3g (%.2f of it)" % (name, key, err, bound, err / bound if bound else 0.0))
-        assert err <= bound, (name, key, err, bound)
+    fused = dict(zip(("w0", "wa", "wb"), kt.torque_terms(q, qs, qss)))
+    for key, args in tc.evaluations(q, qs, qss).items():
+        assert np.array_equal(fused[key], kt.inverse_dynamics(*args)), (name, key)
+    rs.check(tc, name, fused, label="%s")
 
 
 def test_relabelling_the_arms(gpu):
@@ -145,19 +142,6 @@ def _run_passes(inst):
     return out
 
 
-def _same(a, b, what):
-    if isinstance(a, dict):
-        assert sorted(a) == sorted(b), what
-        for k in a:
-            _same(a[k], b[k], what + "." + k)
-    elif isinstance(a, (tuple, list)):
-        assert len(a) == len(b), what
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (what, i))
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True), what
-
-
 @pytest.mark.parametrize("scheme", ["Collocation", "Interpolation"])
 @pytest.mark.parametrize("source", ["spline", "samples"])
 @pytest.mark.parametrize("per_traj", [False, True])
@@ -185,11 +169,11 @@ def test_a_tree_in_the_torque_constraint_equals_its_callback(gpu, scheme, source
             inst = algorithm.BatchTOPPRA.from_path_samples(data["grid"], pe["q"], pe["qs"], pe["qss"], data["vlim"], data["alim"],
                                                            interpolation=False, constraints=cons)
         results.append(_run_passes(inst))
-    _same(results[0], results[1], "tree vs callback")
+    rs.same(results[0], results[1], "tree vs callback")
     assert sorted(results[0]) == sorted(PASSES + ("rows",)) and np.isfinite(results[0]["rows"][0]).all()
     if source == "spline":  # the second-order spelling of the same constraint takes a tree as well, and builds the same rows
         so = constraint.BatchSecondOrderConstraint.joint_torque_constraint(kt, taulim, fric, discretization_scheme=DT)
-        _same(algorithm.BatchTOPPRA(*args, interpolation=False, constraints=[so]).dense_rows(), results[0]["rows"], "second-order spelling")
+        rs.same(algorithm.BatchTOPPRA(*args, interpolation=False, constraints=[so]).dense_rows(), results[0]["rows"], "second-order spelling")
 
 
 @pytest.mark.parametrize("name", FIXTURES)

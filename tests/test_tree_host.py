@@ -168,18 +168,6 @@ def test_the_reference_sums_a_fork_s_branches():
     assert np.all(np.abs(both[..., 0] - (2.0 * one[..., 0] - trunk[..., 0])) <= 64 * np.finfo(float).eps * scale)
 
 
-def test_accuracy_table_is_the_committed_one():
-    import json
-    with open(os.path.join(ROOT, "profiles", "tree_dynamics_accuracy.json")) as fh:
-        stored = json.load(fh)["cases"]
-    table = tc.accuracy_table()
-    assert sorted(stored) == sorted(table)
-    for name in table:  # (to 1 %: a yardstick is the distance to an np.longdouble evaluation, whose sine and cosine are the host library's)
-        for key, rec in table[name].items():
-            assert stored[name][key]["yardstick"] == pytest.approx(rec["yardstick"], rel=1e-2), (name, key)
-            assert stored[name][key]["bound"] == pytest.approx(tc.BOUND_FACTOR * stored[name][key]["yardstick"], rel=1e-12), (name, key)
-
-
 def test_import_works_without_the_reference():
     """toppra_amd and a KinematicTree need neither the reference package nor the CPU restatement beside the tests."""
     code = ("import sys\n"

@@ -26,19 +26,8 @@ def evaluations(q, qs, qss):
 def reference_of(chain, q, qs, qss):
     """float64 references of wa, wb, acc with their magnitudes (name + "_mag") and, under "yardstick", the error each shows
     against np.longdouble in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        if name == "acc":
-            ref["acc"], ref["acc_mag"], ref["yardstick"]["acc"] = ref["wb"], ref["wb_mag"], ref["yardstick"]["wb"]
-            continue
-        ref[name] = tool_accel_ref.tool_acceleration(chain, *args)
-        ref[name + "_mag"] = tool_accel_ref.tool_acceleration(chain, *args, absolute=True)
-        ref["yardstick"][name] = cc._own_error(ref[name], tool_accel_ref.tool_acceleration(chain, *args, dtype=np.longdouble),
-                                               ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    ev = evaluations(q, qs, qss)
+    return cc.alias(cc.references({name: (tool_accel_ref.tool_acceleration, (chain,) + ev[name]) for name in ("wa", "wb")}), "acc", "wb")
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,4 +41,4 @@ def bound(d, name):
 
 def accuracy_table():
     """{dof: {quantity: {"yardstick", "bound"}}}: what profiles/tool_accel_accuracy.json records."""
-    return {str(d): {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in reference(d)["yardstick"].items()} for d in DOFS}
+    return cc.table({str(d): reference(d)["yardstick"] for d in DOFS})

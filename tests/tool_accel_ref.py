@@ -1,6 +1,6 @@
 """Plain numpy reference for the tool point's acceleration of the serial chain (include/toppra_hip.h:
-tpr_chain_tool_acceleration_batch), in WORLD coordinates: the forward recursion of tests/chain_ref.py (``_walk`` with
-``dynamics=True``) with the gravity parameter set to zero -- the base is at rest, this is kinematics -- plus the tool offset:
+tpr_chain_tool_acceleration_batch), in WORLD coordinates: the forward recursion of tests/chain_ref.py (``forward``) with the
+gravity parameter set to zero -- the base is at rest, this is kinematics -- plus the tool offset:
 
     lin = a_d + wd_d x t + w_d x (w_d x t),   ang = wd_d,   t = R_d tool
 
@@ -16,9 +16,8 @@ from tests.chain_ref import _add, _cross, _mv
 
 def tool_acceleration(chain, q, qd, qdd, dtype=np.float64, absolute=False):
     """acc(q, qd, qdd) [..., 6] = [lin; ang] in world axes; arrays [..., d]."""
-    at_rest = dict(chain, gravity=np.zeros(3))
-    wrap, (qa, _, _), (qc, qdc, qddc), par, one, zero, lead = chain_ref._prepare(at_rest, (q, qd, qdd), dtype, absolute)
-    L = chain_ref._walk(at_rest, qa, qc, qdc, qddc, par, wrap, one, zero, True)[-1]
-    tool = _mv(L["R"], [wrap(par["tool"][j]) * one for j in range(3)])
+    links, ar = chain_ref.forward(dict(chain, gravity=np.zeros(3)), q, qd, qdd, dtype, absolute)
+    L = links[-1]
+    tool = _mv(L["R"], ar.vec(chain["tool"]))
     lin = _add(_add(L["a"], _cross(L["wd"], tool)), _cross(L["w"], _cross(L["w"], tool)))
-    return np.stack([t.v if absolute else t for t in lin + L["wd"]], -1)
+    return ar.stack(lin + L["wd"])

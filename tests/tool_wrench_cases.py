@@ -43,19 +43,9 @@ def evaluations(q, qs, qss):
 def reference_of(chain, payload, q, qs, qss):
     """float64 references of w0, wa, wb, wrench with their magnitudes (name + "_mag") and, under "yardstick", the error each
     shows against np.longdouble in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        if name == "wrench":
-            ref["wrench"], ref["wrench_mag"], ref["yardstick"]["wrench"] = ref["wb"], ref["wb_mag"], ref["yardstick"]["wb"]
-            continue
-        ref[name] = tool_wrench_ref.tool_wrench(chain, payload, *args)
-        ref[name + "_mag"] = tool_wrench_ref.tool_wrench(chain, payload, *args, absolute=True)
-        ref["yardstick"][name] = cc._own_error(ref[name], tool_wrench_ref.tool_wrench(chain, payload, *args, dtype=np.longdouble),
-                                               ref[name + "_mag"])
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    ev = evaluations(q, qs, qss)
+    return cc.alias(cc.references({name: (tool_wrench_ref.tool_wrench, (chain, payload) + ev[name]) for name in ("w0", "wa", "wb")}),
+                    "wrench", "wb")
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,4 +59,4 @@ def bound(d, name):
 
 def accuracy_table():
     """{dof: {quantity: {"yardstick", "bound"}}}: what profiles/tool_wrench_accuracy.json records."""
-    return {str(d): {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in reference(d)["yardstick"].items()} for d in DOFS}
+    return cc.table({str(d): reference(d)["yardstick"] for d in DOFS})

@@ -1,7 +1,6 @@
 """Plain numpy reference for the wrench a serial chain's last link transmits to a carried body (include/toppra_hip.h:
-tpr_chain_tool_wrench_batch), written in WORLD coordinates from the forward recursion of tests/chain_ref.py (``_walk`` with
-``dynamics=True`` and the chain's own gravity: the base accelerates by -gravity).  With R, w, wd, a the last link's rotation,
-angular velocity, angular acceleration and origin acceleration in the world, and the payload (mass m, centre of mass c, inertia
+tpr_chain_tool_wrench_batch), written in WORLD coordinates from the forward recursion of tests/chain_ref.py (``forward`` with the
+chain's own gravity: the base accelerates by -gravity).  With R, w, wd, a the last link's rotation, angular velocity, angular acceleration and origin acceleration in the world, and the payload (mass m, centre of mass c, inertia
 I about c, contact frame Rc at p, all in the last link's frame):
 
     cw = R c,  Fw = m (a + wd x cw + w x (w x cw)),  Nw = R I R' wd + w x (R I R' w)
@@ -20,23 +19,19 @@ from tests.chain_ref import _add, _cross, _mtv, _mv, _scale
 
 def tool_wrench(chain, payload, q, qd, qdd, dtype=np.float64, absolute=False):
     """wrench(q, qd, qdd) [..., 6] = [f; n] in contact-frame axes; arrays [..., d]."""
-    wrap, (qa, _, _), (qc, qdc, qddc), par, one, zero, lead = chain_ref._prepare(chain, (q, qd, qdd), dtype, absolute)
-    L = chain_ref._walk(chain, qa, qc, qdc, qddc, par, wrap, one, zero, True)[-1]
-    body = {k: np.asarray(payload[k], dtype=dtype) for k in ("mass", "com", "inertia", "rot", "origin")}
-    vec = lambda x: [wrap(x[j]) * one for j in range(3)]  # noqa: E731
+    links, ar = chain_ref.forward(chain, q, qd, qdd, dtype, absolute)
+    L = links[-1]
     R, w, wd = L["R"], L["w"], L["wd"]
-    cw = _mv(R, vec(body["com"]))
+    com, origin = ar.vec(payload["com"]), ar.vec(payload["origin"])
+    cw = _mv(R, com)
     ac = _add(_add(L["a"], _cross(wd, cw)), _cross(w, _cross(w, cw)))
-    Fw = _scale(ac, wrap(body["mass"]) * one)
-    I = body["inertia"]
-    Il = [[wrap(I[0]), wrap(I[3]), wrap(I[4])], [wrap(I[3]), wrap(I[1]), wrap(I[5])], [wrap(I[4]), wrap(I[5]), wrap(I[2])]]
-    inertia = lambda x: _mv(R, _mv(Il, _mtv(R, x)))  # noqa: E731
+    Fw = _scale(ac, ar.scalar(payload["mass"]))
+    inertia = ar.inertia(R, payload["inertia"])
     Nw = _add(inertia(wd), _cross(w, inertia(w)))
-    arm = _mv(R, [wrap(body["com"][j]) * one - wrap(body["origin"][j]) * one for j in range(3)])
+    arm = _mv(R, [com[j] - origin[j] for j in range(3)])
     nw = _add(Nw, _cross(arm, Fw))
-    Rc = [[wrap(body["rot"][r, c]) * one for c in range(3)] for r in range(3)]
-    out = _mtv(Rc, _mtv(R, Fw)) + _mtv(Rc, _mtv(R, nw))
-    return np.stack([t.v if absolute else t for t in out], -1)
+    Rc = ar.mat(payload["rot"])
+    return ar.stack(_mtv(Rc, _mtv(R, Fw)) + _mtv(Rc, _mtv(R, nw)))
 
 
 def payload_of(p, chain):

@@ -17,7 +17,7 @@ import functools
 
 import numpy as np
 
-from tests import tree_ref
+from tests import chain_cases as cc, tree_ref
 from tests.chain_cases import BOUND_FACTOR, evaluations, metric  # noqa: F401  (the tests take them from here)
 
 B, N = 3, 22
@@ -79,17 +79,7 @@ def case(name):
 def reference_of(tree, q, qs, qss):
     """float64 references of w0, wa, wb with their magnitudes (name + "_mag"), and under "yardstick" the error each shows
     against the same recursion in np.longdouble, in the metric."""
-    ref = {"yardstick": {}}
-    for name, args in evaluations(q, qs, qss).items():
-        val, mag = tree_ref.rnea(tree, *args), tree_ref.rnea(tree, *args, absolute=True)
-        ld = tree_ref.rnea(tree, *args, dtype=np.longdouble)
-        live = mag > 0
-        ref[name], ref[name + "_mag"] = val, mag
-        ref["yardstick"][name] = float(np.max(np.abs(val - ld)[live] / mag[live])) if live.any() else 0.0
-    for v in ref.values():
-        if isinstance(v, np.ndarray):
-            v.flags.writeable = False
-    return ref
+    return cc.references({name: (tree_ref.rnea, (tree,) + args) for name, args in evaluations(q, qs, qss).items()})
 
 
 @functools.lru_cache(maxsize=None)
@@ -104,4 +94,4 @@ def bound(name, quantity):
 
 def accuracy_table():
     """{shape: {quantity: {"yardstick", "bound"}}}: what profiles/tree_dynamics_accuracy.json records."""
-    return {n: {k: {"yardstick": v, "bound": BOUND_FACTOR * v} for k, v in reference(n)["yardstick"].items()} for n in NAMES}
+    return cc.table({n: reference(n)["yardstick"] for n in NAMES})

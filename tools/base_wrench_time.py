@@ -17,13 +17,12 @@ timed the fused outputs are compared with the single entry bit for bit.  Prints 
 --out.  The two expectations are comparisons within the run, each with the run's spread as its allowance:
   fused_vs_callback   wrench_terms / callback: at most 1 + the two spreads
   fused_vs_torque     wrench_terms / torque_terms: at most 1 + the two spreads"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,25 +45,14 @@ def mount():
 
 def main():
     import torch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=7, reps=5).parse_args()
     B, N = args.batch, args.grid
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: nothing is measured")
-    dev = torch.device("cuda", 0)
+    dev = timing.device()
     frame = mount()
     results = []
     for name, robot in models():
         d = robot.dof
-        gen = torch.Generator(device=dev).manual_seed(d)
-        q = 6.0 * torch.rand((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen) - 3.0
-        qs = torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
-        qss = 2.0 * torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
+        q, qs, qss = timing.inputs(dev, B, N, d)
         zero = torch.zeros_like(q)
 
         def callback():
@@ -73,47 +61,27 @@ def main():
                 "wrench": lambda: batch.base_wrench_batch(robot, q, qs, qss, frame),
                 "callback": callback,
                 "torque_terms": lambda: robot.torque_terms(q, qs, qss)}
-        outs = {k: fn() for k, fn in runs.items()}  # warm-up of every shape, and the values
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         for k, what in enumerate(("w0", "wa", "wb")):
             assert torch.equal(outs["wrench_terms"][k], outs["callback"][k]), (name, "fused %s vs the single entry" % what)
         assert torch.equal(outs["wrench_terms"][2], outs["wrench"]) and bool(torch.isfinite(outs["wrench"]).all())
         del outs
         torch.cuda.empty_cache()
-        ms = {k: [] for k in runs}
-        for _ in range(args.rounds):
-            for k, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1) / args.reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         points = B * (N + 1)
-        rec = {"model": name, "forks": len(getattr(robot, "forks", ())), "B": B, "N": N, "d": d, "rounds": args.rounds, "reps": args.reps,
-               "date": time.strftime("%Y-%m-%d"),
-               "wrench_terms_bytes": points * (3 * d + 18) * 8, "wrench_bytes": points * (3 * d + 6) * 8,
-               "callback_bytes": 3 * points * (3 * d + 6) * 8, "torque_terms_bytes": points * 6 * d * 8}
-        for k, v in ms.items():
-            med = float(np.median(v))
-            rec[k + "_ms"] = round(med, 4)
-            rec[k + "_spread"] = round((max(v) - min(v)) / med, 4)
-            rec[k + "_GBps"] = round(rec[k + "_bytes"] / med / 1e6, 1)
+        rec = dict({"model": name, "forks": len(getattr(robot, "forks", ()))}, **timing.header(args, d))
+        rec.update({"wrench_terms_bytes": points * (3 * d + 18) * 8, "wrench_bytes": points * (3 * d + 6) * 8,
+                    "callback_bytes": 3 * points * (3 * d + 6) * 8, "torque_terms_bytes": points * 6 * d * 8})
+        timing.record(rec, ms, gbps=True)
         rec["wrench_terms_Mpoints_per_s"] = round(points / rec["wrench_terms_ms"] / 1e3, 1)
         rec["fused_vs_callback"] = round(rec["wrench_terms_ms"] / rec["callback_ms"], 3)
         rec["fused_vs_torque"] = round(rec["wrench_terms_ms"] / rec["torque_terms_ms"], 3)
         rec["not_slower_than_callback"] = bool(rec["fused_vs_callback"] <= 1.0 + rec["wrench_terms_spread"] + rec["callback_spread"])
         rec["not_slower_than_torque_terms"] = bool(rec["fused_vs_torque"] <= 1.0 + rec["wrench_terms_spread"] + rec["torque_terms_spread"])
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del q, qs, qss, zero
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
-            fh.write("\n")
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,12 @@ variants are timed in turn, each timing `--reps` calls between two events on the
 takes seconds); the figure is the median over the rounds and the spread their (max - min) / median.  The fused outputs are
 compared with the singles bit for bit and with the torch recursion to rounding before anything is timed.  Prints one JSON line
 per dof and writes them to --out."""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -92,23 +91,13 @@ def torch_inverse_dynamics(chain, device):
 
 def main():
     import torch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--dofs", type=int, nargs="+", default=[7, 12, 20])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=5, reps=3, dofs=(7, 12, 20)).parse_args()
     B, N = args.batch, args.grid
-    dev = torch.device("cuda", 0)
+    dev = timing.device()
     results = []
     for d in args.dofs:
         chain = random_chain(d, 20240924 + d)
-        gen = torch.Generator(device=dev).manual_seed(d)
-        q = 6.0 * torch.rand((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen) - 3.0
-        qs = torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
-        qss = 2.0 * torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
+        q, qs, qss = timing.inputs(dev, B, N, d)
         zero = torch.zeros_like(q)
         taulim = np.tile([-1e3, 1e3], (d, 1))
         con = constraint.BatchJointTorqueConstraint(torch_inverse_dynamics(chain, dev), taulim, np.zeros(d))
@@ -127,32 +116,19 @@ def main():
         def tool():
             return batch.chain_tool_bound_batch(chain, q, qs, 0.25)
 
-        runs = {"fused": (fused, args.reps), "singles": (singles, args.reps), "torch": (torch_block, 1), "tool": (tool, args.reps)}
-        outs = {name: fn() for name, (fn, _) in runs.items()}  # warm-up of every shape, and the values
-        torch.cuda.synchronize()
+        runs = {"fused": fused, "singles": singles, "torch": (torch_block, 1), "tool": tool}  # (the torch callback once per round)
+        outs = timing.warm_up(runs)
         for x, y in zip(outs["fused"], outs["singles"]):
             assert torch.equal(x, y), (d, "fused vs singles")
         worst = max(float(((x - y).abs().max() / y.abs().max())) for x, y in zip(outs["fused"], outs["torch"]))
         assert worst < 1e-9, (d, "fused vs the torch recursion", worst)
         del outs
         torch.cuda.empty_cache()
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, (fn, reps) in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         points = B * (N + 1)
-        rec = {"B": B, "N": N, "d": d, "rounds": args.rounds, "reps": args.reps, "date": time.strftime("%Y-%m-%d"),
-               "fused_bytes": 6 * points * d * 8, "tool_bytes": 2 * points * d * 8 + 24 * points, "fused_vs_torch_max_rel": worst}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
+        rec = timing.header(args, d)
+        rec.update({"fused_bytes": 6 * points * d * 8, "tool_bytes": 2 * points * d * 8 + 24 * points, "fused_vs_torch_max_rel": worst})
+        timing.record(rec, ms)
         rec["fused_GBps"] = round(rec["fused_bytes"] / rec["fused_ms"] / 1e6, 1)
         rec["fused_Mpoints_per_s"] = round(points / rec["fused_ms"] / 1e3, 1)
         rec["tool_GBps"] = round(rec["tool_bytes"] / rec["tool_ms"] / 1e6, 1)
@@ -160,14 +136,10 @@ def main():
         rec["torch_over_fused"] = round(rec["torch_ms"] / rec["fused_ms"], 2)
         rec["fused_faster_than_singles"] = bool(rec["fused_ms"] * (1 + rec["fused_spread"]) < rec["singles_ms"] * (1 - rec["singles_spread"]))
         rec["fused_faster_than_torch"] = bool(rec["fused_ms"] * (1 + rec["fused_spread"]) < rec["torch_ms"] * (1 - rec["torch_spread"]))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del q, qs, qss, zero
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
+    timing.write(results, args.out)
     if not all(r["fused_faster_than_singles"] and r["fused_faster_than_torch"] for r in results):
         raise SystemExit("the fused kernel is not faster than its alternatives")
 

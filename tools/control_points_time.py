@@ -18,13 +18,13 @@ the rounds and the spread their (max - min) / median.  Before anything is timed 
 kernels' bit for bit.  Prints one JSON line per dof and writes them to --out.  `terms_ratio` / `speed_ratio` are the fused launch
 over the P launches: above 1 the new kernel takes longer than what it replaces; `*_not_slower` allows the run's own spread (the
 larger of the two variants')."""
-import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,19 +35,11 @@ from toppra_amd.chain import ControlPoints  # noqa: E402
 def main():
     import torch
     from tests import chain_ref, control_points_cases as cp
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--dofs", type=int, nargs="+", default=[7, 12, 20])
+    ap = timing.parser(rounds=7, reps=5, dofs=(7, 12, 20))
     ap.add_argument("--points", type=int, default=4)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     B, N, P = args.batch, args.grid, args.points
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: nothing is measured")
-    dev = torch.device("cuda", 0)
+    dev = timing.device()
     results = []
     for d in args.dofs:
         model = chain_ref.random_chain(d, 20240924 + d, prismatic_every=4)
@@ -56,10 +48,7 @@ def main():
         offsets = np.random.default_rng(d).uniform(-0.25, 0.25, (P, 3))
         points = ControlPoints(links, offsets)
         cuts = [(k, chain_ref.serial_chain(cp.truncated(model, k, r))) for k, r in zip(links, offsets)]
-        gen = torch.Generator(device=dev).manual_seed(d)
-        q = 6.0 * torch.rand((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen) - 3.0
-        qs = torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
-        qss = 2.0 * torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
+        q, qs, qss = timing.inputs(dev, B, N, d)
         limit = torch.full((B, P), 0.25, dtype=torch.float64, device=dev)
 
         def tool_terms():
@@ -76,8 +65,7 @@ def main():
                 "tool_terms_xP": tool_terms,
                 "points_speed": lambda: batch.chain_points_speed_batch(chain, q, qs, points, limit),
                 "tool_speed_xP": tool_speed}
-        outs = {name: fn() for name, fn in runs.items()}  # warm-up of every shape, and the values
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         for p in range(P):
             for i in range(2):
                 assert torch.equal(outs["points_terms"][i][..., p, :], outs["tool_terms_xP"][p][i][..., :3]), (d, p, "terms")
@@ -89,37 +77,20 @@ def main():
         for fn in runs.values():  # once more, untimed: the outputs' memory comes back from the allocator's cache, not the driver
             fn()
         torch.cuda.synchronize()
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         npoints = B * (N + 1)
         rec = {"B": B, "N": N, "d": d, "P": P, "links": links, "rounds": args.rounds, "reps": args.reps, "date": time.strftime("%Y-%m-%d"),
                "points_terms_bytes": npoints * (3 * (max(links) + 1) + 6 * P) * 8, "points_speed_bytes": npoints * (2 * (max(links) + 1) + P + 2) * 8}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
+        timing.record(rec, ms)
         for fused, many, key in (("points_terms", "tool_terms_xP", "terms"), ("points_speed", "tool_speed_xP", "speed")):
             rec[fused + "_GBps"] = round(rec[fused + "_bytes"] / rec[fused + "_ms"] / 1e6, 1)
             rec[key + "_ratio"] = round(rec[fused + "_ms"] / rec[many + "_ms"], 3)
             spread = max(rec[fused + "_spread"], rec[many + "_spread"])
             rec[key + "_not_slower"] = bool(rec[fused + "_ms"] <= rec[many + "_ms"] * (1.0 + spread))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del q, qs, qss
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
-            fh.write("\n")
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":

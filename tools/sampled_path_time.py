@@ -11,13 +11,12 @@ Protocol: device tensors, warm-up of every shape, then `--rounds` rounds in whic
 all three alike), each timing `--reps` calls between two events on the stream; the figure is the median over the rounds and the
 spread their (max - min) / median.  The three results are compared bit for bit before anything is timed.  Prints one JSON line
 per dof and writes them to --out."""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import timing
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from toppra_amd import batch  # noqa: E402
@@ -25,14 +24,7 @@ from toppra_amd import batch  # noqa: E402
 
 def main():
     import torch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--dofs", type=int, nargs="+", default=[7, 12, 20])
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=7, reps=3, dofs=(7, 12, 20)).parse_args()
     B, N = args.batch, args.grid
     results = []
     for d in args.dofs:
@@ -54,39 +46,22 @@ def main():
             return batch.solve_dense_batch(*[rows[k] for k in keys])
 
         runs = {"sampled": sampled, "rows+dense": rows_dense, "dense": dense}
-        outs = {name: fn() for name, fn in runs.items()}  # warm-up of every shape, and the bits
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         for name in ("rows+dense", "dense"):
             for key in ("sd2", "u", "K", "status"):
                 assert torch.equal(outs["sampled"][key].view(torch.int64 if key != "status" else torch.int32),
                                    outs[name][key].view(torch.int64 if key != "status" else torch.int32)), (d, name, key)
         del outs
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
-        rec = {"B": B, "N": N, "d": d, "rounds": args.rounds, "reps": args.reps, "date": time.strftime("%Y-%m-%d"),
-               "bytes_samples": 2 * 8 * B * (N + 1) * d, "bytes_rows": 3 * 8 * B * (N + 1) * (2 + 4 * d)}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
+        ms = timing.measure(runs, args.rounds, args.reps)
+        rec = timing.header(args, d)
+        rec.update({"bytes_samples": 2 * 8 * B * (N + 1) * d, "bytes_rows": 3 * 8 * B * (N + 1) * (2 + 4 * d)})
+        timing.record(rec, ms)
         rec["sampled_not_slower_than_rows+dense"] = bool(
             rec["sampled_ms"] <= rec["rows+dense_ms"] * (1 + max(rec["sampled_spread"], rec["rows+dense_spread"])))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del dev, pe, rows, sargs
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":

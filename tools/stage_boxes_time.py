@@ -16,13 +16,12 @@ Protocol (that of tools/sampled_path_time.py): device tensors, warm-up of every 
 variants are timed in turn (so that drift hits all alike), each timing `--reps` calls between two events on the stream; the
 figure is the median over the rounds and the spread their (max - min) / median.  Results are compared bit for bit before
 anything is timed.  Prints one JSON line per dof and writes them to --out."""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import timing
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from toppra_amd import batch  # noqa: E402
@@ -30,14 +29,7 @@ from toppra_amd import batch  # noqa: E402
 
 def main():
     import torch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--dofs", type=int, nargs="+", default=[7, 12, 20])
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=7, reps=3, dofs=(7, 12, 20)).parse_args()
     B, N = args.batch, args.grid
     results = []
 
@@ -83,43 +75,26 @@ def main():
 
         runs = {"boxes": boxes, "params": params, "boxes+boxed": boxes_boxed, "rows+dense": rows_dense, "boxed_const": boxed_const,
                 "sampled_const": sampled_const}
-        outs = {name: fn() for name, fn in runs.items()}  # warm-up of every shape, and the bits
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         same(outs["boxes+boxed"], outs["rows+dense"], (d, "boxes+boxed vs rows+dense"))
         same(outs["boxed_const"], outs["sampled_const"], (d, "boxed vs sampled, constant limits"))
         params_bytes = sum(v.numel() * 8 for v in outs["params"].values())
         ok = int((outs["boxes+boxed"]["status"] == 0).sum())
         del outs
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         boxes_bytes = (8 * 3 * d + 32) * B * (N + 1)
-        rec = {"B": B, "N": N, "d": d, "rounds": args.rounds, "reps": args.reps, "date": time.strftime("%Y-%m-%d"), "ok": ok,
-               "boxes_bytes": boxes_bytes, "params_bytes": params_bytes}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
+        rec = timing.header(args, d)
+        rec.update({"ok": ok, "boxes_bytes": boxes_bytes, "params_bytes": params_bytes})
+        timing.record(rec, ms)
         rec["boxes_GBps"] = round(boxes_bytes / rec["boxes_ms"] / 1e6, 1)
         rec["params_GBps"] = round(params_bytes / rec["params_ms"] / 1e6, 1)
         rec["boxes+boxed_not_slower_than_rows+dense"] = bool(
             rec["boxes+boxed_ms"] <= rec["rows+dense_ms"] * (1 + max(rec["boxes+boxed_spread"], rec["rows+dense_spread"])))
         rec["boxed_const_over_sampled_const"] = round(rec["boxed_const_ms"] / rec["sampled_const_ms"], 4)
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del dev, pe, qs, qss, vgrid, low_c, high_c, low_v, high_v
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -16,13 +16,12 @@ single entry bit for bit.  Prints one JSON line per dof and writes them to --out
 the run, each with the run's spread as its allowance:
   fused_vs_callback        wrench_terms / callback: at most 1 + the two spreads
   fused_vs_accel_scaled    wrench_terms / (1.5 accel_terms), the yardstick scaled for the third evaluation: at most 1 + the two spreads"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -44,26 +43,14 @@ def payload():
 
 def main():
     import torch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--dofs", type=int, nargs="+", default=[7, 12, 20])
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=7, reps=5, dofs=(7, 12, 20)).parse_args()
     B, N = args.batch, args.grid
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: nothing is measured")
-    dev = torch.device("cuda", 0)
+    dev = timing.device()
     obj = payload()
     results = []
     for d in args.dofs:
         chain = random_chain(d, 20240924 + d)
-        gen = torch.Generator(device=dev).manual_seed(d)
-        q = 6.0 * torch.rand((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen) - 3.0
-        qs = torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
-        qss = 2.0 * torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
+        q, qs, qss = timing.inputs(dev, B, N, d)
         zero = torch.zeros_like(q)
 
         def callback():
@@ -72,46 +59,27 @@ def main():
                 "wrench": lambda: batch.chain_tool_wrench_batch(chain, q, qs, qss, obj),
                 "callback": callback,
                 "accel_terms": lambda: batch.chain_tool_acceleration_terms_batch(chain, q, qs, qss)}
-        outs = {name: fn() for name, fn in runs.items()}  # warm-up of every shape, and the values
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         for k, what in enumerate(("w0", "wa", "wb")):
             assert torch.equal(outs["wrench_terms"][k], outs["callback"][k]), (d, "fused %s vs the single entry" % what)
         assert torch.equal(outs["wrench_terms"][2], outs["wrench"]) and bool(torch.isfinite(outs["wrench"]).all())
         del outs
         torch.cuda.empty_cache()
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         points = B * (N + 1)
-        rec = {"B": B, "N": N, "d": d, "rounds": args.rounds, "reps": args.reps, "date": time.strftime("%Y-%m-%d"),
-               "wrench_terms_bytes": points * (3 * d + 18) * 8, "wrench_bytes": points * (3 * d + 6) * 8,
-               "callback_bytes": 3 * points * (3 * d + 6) * 8, "accel_terms_bytes": points * (3 * d + 12) * 8}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
-            rec[name + "_GBps"] = round(rec[name + "_bytes"] / med / 1e6, 1)
+        rec = timing.header(args, d)
+        rec.update({"wrench_terms_bytes": points * (3 * d + 18) * 8, "wrench_bytes": points * (3 * d + 6) * 8,
+                    "callback_bytes": 3 * points * (3 * d + 6) * 8, "accel_terms_bytes": points * (3 * d + 12) * 8})
+        timing.record(rec, ms, gbps=True)
         rec["wrench_terms_Mpoints_per_s"] = round(points / rec["wrench_terms_ms"] / 1e3, 1)
         rec["fused_vs_callback"] = round(rec["wrench_terms_ms"] / rec["callback_ms"], 3)
         rec["fused_vs_accel_scaled"] = round(rec["wrench_terms_ms"] / (1.5 * rec["accel_terms_ms"]), 3)
         rec["not_slower_than_callback"] = bool(rec["fused_vs_callback"] <= 1.0 + rec["wrench_terms_spread"] + rec["callback_spread"])
         rec["within_scaled_accel_terms"] = bool(rec["fused_vs_accel_scaled"] <= 1.0 + rec["wrench_terms_spread"] + rec["accel_terms_spread"])
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del q, qs, qss, zero
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
-            fh.write("\n")
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,13 @@ Protocol (that of tools/chain_dynamics_time.py): device tensors, warm-up of ever
 variants are timed in turn, each timing `--reps` calls between two events on the stream; the figure is the median over the
 rounds and the spread their (max - min) / median.  Before anything is timed the chain-shaped tree's outputs are compared with
 the chain's bit for bit.  Prints one JSON line per dof and writes them to --out."""
-import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,65 +31,38 @@ from toppra_amd.chain import KinematicTree  # noqa: E402
 def main():
     import torch
     from tests import chain_ref, tree_cases, tree_ref
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--grid", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = timing.parser(rounds=5, reps=3).parse_args()
     B, N = args.batch, args.grid
-    dev = torch.device("cuda", 0)
+    dev = timing.device()
     results = []
     for d, shape in ((15, "torso"), (18, "y18")):
         links = chain_ref.random_chain(d, 20240924 + d, prismatic_every=4)
         chain = chain_ref.serial_chain(links)
         branched = tree_ref.kinematic_tree(dict(links, parent=np.array(tree_cases.SHAPES[shape], dtype=np.int32)))
         straight = KinematicTree.from_chain(chain)
-        gen = torch.Generator(device=dev).manual_seed(d)
-        q = 6.0 * torch.rand((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen) - 3.0
-        qs = torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
-        qss = 2.0 * torch.randn((B, N + 1, d), dtype=torch.float64, device=dev, generator=gen)
+        q, qs, qss = timing.inputs(dev, B, N, d)
         runs = {"tree_" + shape: lambda: batch.tree_torque_terms_batch(branched, q, qs, qss),
                 "tree_chain": lambda: batch.tree_torque_terms_batch(straight, q, qs, qss),
                 "chain": lambda: batch.chain_torque_terms_batch(chain, q, qs, qss)}
-        outs = {name: fn() for name, fn in runs.items()}  # warm-up of every shape, and the values
-        torch.cuda.synchronize()
+        outs = timing.warm_up(runs)
         for x, y in zip(outs["tree_chain"], outs["chain"]):
             assert torch.equal(x, y), (d, "chain-shaped tree vs chain")
         assert all(bool(torch.isfinite(x).all()) for x in outs["tree_" + shape])
         del outs
         torch.cuda.empty_cache()
-        ms = {name: [] for name in runs}
-        for _ in range(args.rounds):
-            for name, fn in runs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
+        ms = timing.measure(runs, args.rounds, args.reps)
         points = B * (N + 1)
         rec = {"B": B, "N": N, "d": d, "shape": shape, "forks": len(branched.forks), "rounds": args.rounds, "reps": args.reps,
                "date": time.strftime("%Y-%m-%d"), "bytes": 6 * points * d * 8}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            rec[name + "_ms"] = round(med, 4)
-            rec[name + "_spread"] = round((max(v) - min(v)) / med, 4)
+        timing.record(rec, ms)
         rec["tree_%s_over_chain" % shape] = round(rec["tree_%s_ms" % shape] / rec["chain_ms"], 3)
         rec["tree_chain_over_chain"] = round(rec["tree_chain_ms"] / rec["chain_ms"], 3)
         rec["chain_GBps"] = round(rec["bytes"] / rec["chain_ms"] / 1e6, 1)
         rec["tree_%s_GBps" % shape] = round(rec["bytes"] / rec["tree_%s_ms" % shape] / 1e6, 1)
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
+        timing.emit(rec, results)
         del q, qs, qss
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            json.dump(results, fh, indent=1)
-            fh.write("\n")
+    timing.write(results, args.out)
 
 
 if __name__ == "__main__":
