@@ -32,7 +32,7 @@ def test_exactly_three_joint_kernels(kernels):
         assert sum(key in n for n in mine) == 1, (key, mine)
     # the chain and tree tests pick their kernels by "chain_" and "tree_": neither may answer to them, argument types included
     assert not any("chain_" in n or "tree_" in n for n in mine), mine
-    # ... and the unit brings no second copy of a tree kernel with the banks it takes from tpr_tree.hip.inc
+    # ... and the unit brings no second copy of a tree kernel with the banks it takes from tpr_tree_walk.hip.inc
     for name in ("tree_inverse_dynamics_kernel", "tree_torque_terms_kernelILb1E", "tree_torque_terms_kernelILb0E"):
         assert sum(name in n for n in kernels) == 1, name
 

@@ -41,6 +41,24 @@ __device__ __forceinline__ void chain_rows_load(double *b0, double *b1, double *
         if (c >= d) { c -= d; ++r; }
     }
 }
+// A block's q, q', q'' staged at the head of its LDS, and where this lane reads them: g0 = the block's first point, npts = its
+// points, bq / b1 / b2 = the three areas, row = where this lane's row begins in each; lanes past the last point of the batch take
+// the last point's lane.  Ends with the block in step: every row is in place.
+struct ChainStage {
+    size_t g0;
+    int npts, lane, row;
+    const double *bq, *b1, *b2;
+};
+__device__ __forceinline__ ChainStage chain_stage(double *lds, const double *s0, const double *s1, const double *s2, int npoints, int d) {
+    const int pitch = d | 1;
+    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
+    const int left = npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
+    double *bq = lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    chain_rows_load(bq, b1, b2, s0, s1, s2, g0, npts, d, pitch);
+    __syncthreads();
+    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    return {g0, npts, lane, row, bq, b1, b2};
+}
 // ... and a block's outputs [npts][6] from LDS at pitch 7.
 __device__ __forceinline__ void chain_accel_rows_store(const double *buf, double *dst, size_t g0, int npts) {
     for (int k = threadIdx.x; k < npts * 6; k += kChainBlock) dst[g0 * 6 + k] = buf[(k / 6) * 7 + (k % 6)];
@@ -173,14 +191,12 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_velocity_kernel
 //   angular acceleration, world axes; no gravity.  Per evaluation the state is (w, wd, a) of the current link, W is shared.
 // Every output passes through "+ 0.0": a zero leaves as +0 whatever the signs of the vanishing products were, so the fused
 // outputs equal the single evaluation's in every bit and acc(q, 0, 0) is the +0 a constraint's w0 is given as.
-// How a block's rows pass through LDS (chain_accel_lds_bytes, chain_rows_load, chain_accel_rows_store) is at the head of this file.
+// How a block's rows pass through LDS (chain_accel_lds_bytes, chain_stage, chain_accel_rows_store) is at the head of this file.
 template <int Level>
 __device__ __forceinline__ void chain_tool_accel_put(const M3 &W, const ChainKin &K, V3 tool, double *o) {
     V3 al = K.a + cross(K.wd, tool);
     if (Level >= 2) al = al + cross(K.w, cross(K.w, tool));
-    const V3 lin = mul(W, al), ang = mul(W, K.wd);
-    o[0] = lin.x + 0.0; o[1] = lin.y + 0.0; o[2] = lin.z + 0.0;
-    o[3] = ang.x + 0.0; o[4] = ang.y + 0.0; o[5] = ang.z + 0.0;
+    chain_put6(mul(W, al), mul(W, K.wd), o);
 }
 
 // Lanes past the last point of the batch work on the last point's row again and rewrite its LDS row with its values (no lane is
@@ -188,48 +204,38 @@ __device__ __forceinline__ void chain_tool_accel_put(const M3 &W, const ChainKin
 static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_kernel(ChainAccelArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
-    chain_rows_load(bq, b1, b2, A.q, A.qd, A.qdd, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qd, A.qdd, A.npoints, d);
     const V3 zero{0.0, 0.0, 0.0};
     ChainKin K{zero, zero, zero};
     M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
 #pragma nounroll
     for (int i = 0; i < d; ++i) {
         const ChainLink L = chain_link(M, i);
-        const double qi = bq[row + i];
+        const double qi = B.bq[B.row + i];
         const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
-        chain_kinematics<2>(L, J, K, b1[row + i], b2[row + i]);
+        chain_kinematics<2>(L, J, K, B.b1[B.row + i], B.b2[B.row + i]);
         W = mul(W, J.E);
     }
     __syncthreads();
-    chain_tool_accel_put<2>(W, K, load3(M.tool), chain_lds + lane * 7);
+    chain_tool_accel_put<2>(W, K, load3(M.tool), chain_lds + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(chain_lds, A.acc, g0, npts);
+    chain_accel_rows_store(chain_lds, A.acc, B.g0, B.npts);
 }
 
 // wa = acc(q, 0, qs), wb = acc(q, qs, qss) in one pass: level 1 leaves out the products with the zero velocity.
 static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_terms_kernel(ChainAccelTermsArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
-    chain_rows_load(bq, b1, b2, A.q, A.qs, A.qss, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qs, A.qss, A.npoints, d);
     const V3 zero{0.0, 0.0, 0.0};
     ChainKin K1{zero, zero, zero}, K2 = K1;
     M3 W{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
 #pragma nounroll
     for (int i = 0; i < d; ++i) {
         const ChainLink L = chain_link(M, i);
-        const double qi = bq[row + i], v1 = b1[row + i], v2 = b2[row + i];
+        const double qi = B.bq[B.row + i], v1 = B.b1[B.row + i], v2 = B.b2[B.row + i];
         const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
         chain_kinematics<1>(L, J, K1, 0.0, v1);
         chain_kinematics<2>(L, J, K2, v1, v2);
@@ -238,11 +244,11 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_accel_terms_ker
     const V3 tool = load3(M.tool);
     double *oa = chain_lds, *ob = chain_lds + kChainBlock * 7;
     __syncthreads();
-    chain_tool_accel_put<1>(W, K1, tool, oa + lane * 7);
-    chain_tool_accel_put<2>(W, K2, tool, ob + lane * 7);
+    chain_tool_accel_put<1>(W, K1, tool, oa + B.lane * 7);
+    chain_tool_accel_put<2>(W, K2, tool, ob + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(oa, A.wa, g0, npts);
-    chain_accel_rows_store(ob, A.wb, g0, npts);
+    chain_accel_rows_store(oa, A.wa, B.g0, B.npts);
+    chain_accel_rows_store(ob, A.wb, B.g0, B.npts);
 }
 
 // ---- the wrench at the tool: what the last link transmits to a body it carries, any dof, state in registers -------------------
@@ -286,9 +292,7 @@ __device__ __forceinline__ void chain_tool_wrench_put(ChainPayloadWords P, const
         if (Level >= 2) Nl = Nl + cross(K.w, payload_inertia_mul(P + 4, K.w));
         n = Nl + n;
     }
-    const V3 f = mul_t(Rc, Fl), t = mul_t(Rc, n);
-    o[0] = f.x + 0.0; o[1] = f.y + 0.0; o[2] = f.z + 0.0;
-    o[3] = t.x + 0.0; o[4] = t.y + 0.0; o[5] = t.z + 0.0;
+    chain_put6(mul_t(Rc, Fl), mul_t(Rc, n), o);
 }
 
 // Lanes past the last point of the batch work on the last point's row again and rewrite its LDS row with its values (no lane is
@@ -296,45 +300,35 @@ __device__ __forceinline__ void chain_tool_wrench_put(ChainPayloadWords P, const
 static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_kernel(ChainWrenchArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
-    chain_rows_load(bq, b1, b2, A.q, A.qd, A.qdd, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qd, A.qdd, A.npoints, d);
     const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
     ChainKin K{zero, zero, {-g.x, -g.y, -g.z}};
 #pragma nounroll
     for (int i = 0; i < d; ++i) {
         const ChainLink L = chain_link(M, i);
-        const double qi = bq[row + i];
+        const double qi = B.bq[B.row + i];
         const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
-        chain_kinematics<2>(L, J, K, b1[row + i], b2[row + i]);
+        chain_kinematics<2>(L, J, K, B.b1[B.row + i], B.b2[B.row + i]);
     }
     __syncthreads();
-    chain_tool_wrench_put<2>(chain_payload_words<ChainWrenchArgs>(), K, chain_lds + lane * 7);
+    chain_tool_wrench_put<2>(chain_payload_words<ChainWrenchArgs>(), K, chain_lds + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(chain_lds, A.wrench, g0, npts);
+    chain_accel_rows_store(chain_lds, A.wrench, B.g0, B.npts);
 }
 
 // w0 = wrench(q, 0, 0), wa = wrench(q, 0, qs), wb = wrench(q, qs, qss) in one pass over the links.
 static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_terms_kernel(ChainWrenchTermsArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
-    chain_rows_load(bq, b1, b2, A.q, A.qs, A.qss, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qs, A.qss, A.npoints, d);
     const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
     ChainKin K0{zero, zero, {-g.x, -g.y, -g.z}}, K1 = K0, K2 = K0;
 #pragma nounroll
     for (int i = 0; i < d; ++i) {
         const ChainLink L = chain_link(M, i);
-        const double qi = bq[row + i], v1 = b1[row + i], v2 = b2[row + i];
+        const double qi = B.bq[B.row + i], v1 = B.b1[B.row + i], v2 = B.b2[B.row + i];
         const ChainJoint J = chain_joint(L, L.prismatic ? qi : sin(qi), cos(qi));
         chain_kinematics<0>(L, J, K0, 0.0, 0.0);
         chain_kinematics<1>(L, J, K1, 0.0, v1);
@@ -343,13 +337,13 @@ static __global__ void __launch_bounds__(kChainBlock) chain_tool_wrench_terms_ke
     double *o0 = chain_lds, *oa = o0 + kChainBlock * 7, *ob = oa + kChainBlock * 7;
     __syncthreads();
     const ChainPayloadWords P = chain_payload_words<ChainWrenchTermsArgs>();
-    chain_tool_wrench_put<0>(P, K0, o0 + lane * 7);
-    chain_tool_wrench_put<1>(P, K1, oa + lane * 7);
-    chain_tool_wrench_put<2>(P, K2, ob + lane * 7);
+    chain_tool_wrench_put<0>(P, K0, o0 + B.lane * 7);
+    chain_tool_wrench_put<1>(P, K1, oa + B.lane * 7);
+    chain_tool_wrench_put<2>(P, K2, ob + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(o0, A.w0, g0, npts);
-    chain_accel_rows_store(oa, A.wa, g0, npts);
-    chain_accel_rows_store(ob, A.wb, g0, npts);
+    chain_accel_rows_store(o0, A.w0, B.g0, B.npts);
+    chain_accel_rows_store(oa, A.wa, B.g0, B.npts);
+    chain_accel_rows_store(ob, A.wb, B.g0, B.npts);
 }
 
 // ---- control points on any link: speed and linear acceleration of up to 16 points in one pass over the links -------------------

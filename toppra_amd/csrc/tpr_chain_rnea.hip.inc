@@ -168,6 +168,19 @@ struct ChainLdsState {
     __device__ __forceinline__ double &at(int i, int s) { return base[(i * Slots + s) * kChainBlock]; }
 };
 __device__ __forceinline__ void chain_put(V3 v, double &a, double &b, double &c) { a = v.x; b = v.y; c = v.z; }
+// A lane's banks in LDS, [bank][slot][lane] -- ChainLdsState's layout -- read and written three doubles at a time: what the tree and
+// joint-load kernels (TreeBanks) and the base-reaction kernels (MountBanks) keep a fork's state in.
+template <int Doubles>
+struct ChainLaneBanks : ChainLdsState<Doubles> {
+    using ChainLdsState<Doubles>::at;
+    __device__ __forceinline__ V3 get(int b, int s) { return {at(b, s), at(b, s + 1), at(b, s + 2)}; }
+    __device__ __forceinline__ void put(int b, int s, V3 v) { at(b, s) = v.x; at(b, s + 1) = v.y; at(b, s + 2) = v.z; }
+};
+// Six outputs, each through "+ 0.0": a zero leaves as +0 whatever the signs of the vanishing products were.
+__device__ __forceinline__ void chain_put6(V3 a, V3 b, double *o) {
+    o[0] = a.x + 0.0; o[1] = a.y + 0.0; o[2] = a.z + 0.0;
+    o[3] = b.x + 0.0; o[4] = b.y + 0.0; o[5] = b.z + 0.0;
+}
 
 // One point.  Fused: o0 = tau(q, 0, 0), o1 = tau(q, 0, v1), o2 = tau(q, v1, v2).  Otherwise o2 = tau(q, v1, v2) alone, where a
 // null v1 / v2 stands for zeros.  q, v1, v2, o* are this point's rows.  D = 0: runtime dof M.d.
@@ -226,9 +239,10 @@ __device__ __forceinline__ void chain_rnea(const ChainModel &M, State &St, const
 
 // Lanes past the last point of the batch evaluate the last point again and store the very same values where its own lane
 // does: no lane is ever masked out, nothing is written outside [npoints][d].
-__device__ __forceinline__ size_t chain_row(int npoints, int d) {
+__device__ __forceinline__ size_t chain_point(int npoints) {
     const size_t g = (size_t)blockIdx.x * kChainBlock + threadIdx.x;
-    return (g < (size_t)npoints ? g : (size_t)npoints - 1) * (size_t)d;
+    return g < (size_t)npoints ? g : (size_t)npoints - 1;
 }
+__device__ __forceinline__ size_t chain_row(int npoints, int d) { return chain_point(npoints) * (size_t)d; }
 
 }  // namespace tpr

@@ -1,9 +1,11 @@
 // tpr_joint.hip.inc -- the wrench ACROSS any joint of a rigid-body tree: what a gearbox's output bearing, a linear guide's
 // carriage or a slender link's flange carries beside the joint's own torque -- tilting moment, axial and radial force -- at every
 // gridpoint of every trajectory, for a set of up to 8 sections in one launch.  The model and the walk are the tree kernels'
-// (tpr_tree.hip.inc: a serial chain is the tree parent = -1, 0, 1, ...); chain_link, chain_joint and chain_forward<Level> are used
-// as they are, and the way down uses chain_backward_wrench<Level>, chain_backward's sibling that hands out the pair (f, n) the
-// torque kernels project on the joint axis and drop.
+// (tpr_tree.hip.inc: a serial chain is the tree parent = -1, 0, 1, ...), on the banks and slots of tpr_tree_walk.hip.inc;
+// chain_link, chain_joint and chain_forward<Level> are used as they are, and the way down uses chain_backward_wrench<Level>,
+// chain_backward's sibling that hands out the pair (f, n) the torque kernels project on the joint axis and drop.  joint_rnea repeats
+// tree_rnea's walk in its own text: written on walk functions shared with tree_rnea the single kernel was 2 % slower on the MI355X
+// (profiles/rigid_body_kernel_refactor.md).
 //
 // The quantity.  (f_i, n_i) of the recursion: the force the parent side exerts ON link i through joint i and its moment about
 // link i's origin, in link i's axes, gravity included (at rest f is the support of the weight of everything that hangs on the
@@ -31,8 +33,7 @@
 // and section: no staging, no LDS of their own.  Lanes past the last point of the batch evaluate the last point again and store
 // the very same values where its own lane does.
 #pragma once
-#define TPR_TREE_WALK_ONLY  // (TreeBanks; none of the tree kernels)
-#include "tpr_tree.hip.inc"
+#include "tpr_tree_walk.hip.inc"
 #include "tpr_joint_args.hpp"
 
 namespace tpr {
@@ -42,9 +43,7 @@ __device__ __forceinline__ void joint_put(const JointSections &S, int k, V3 f, V
     M3 R;
 #pragma unroll
     for (int j = 0; j < 9; ++j) R.m[j] = S.rot[k][j];
-    const V3 fo = mul_t(R, f), no = mul_t(R, n + cross(f, V3{S.origin[k][0], S.origin[k][1], S.origin[k][2]}));
-    o[0] = fo.x + 0.0; o[1] = fo.y + 0.0; o[2] = fo.z + 0.0;
-    o[3] = no.x + 0.0; o[4] = no.y + 0.0; o[5] = no.z + 0.0;
+    chain_put6(mul_t(R, f), mul_t(R, n + cross(f, V3{S.origin[k][0], S.origin[k][1], S.origin[k][2]})), o);
 }
 
 // One point, as tree_rnea<Fused>: o0 = w(q, 0, 0), o1 = w(q, 0, v1), o2 = w(q, v1, v2), or o2 alone; o* = this point's [count][6].
@@ -52,10 +51,8 @@ __device__ __forceinline__ void joint_put(const JointSections &S, int k, V3 f, V
 template <bool Fused, class State>
 __device__ __forceinline__ void joint_rnea(const ChainModel &M, const TreeTables &T, const JointSections &S, State &St, double *banks,
                                            const double *q, const double *v1, const double *v2, double *o0, double *o1, double *o2) {
-    constexpr int kFull = Fused ? 11 : 2;     // first slot of the level-2 evaluation's F, N
-    constexpr int kBank2 = Fused ? 9 : 0;     // first bank slot of the level-2 evaluation, forward
-    constexpr int kWrench2 = Fused ? 12 : 0;  // ... and backward
-    TreeBanks<Fused ? kTreeBankFused : kTreeBankSingle> Bk{banks};
+    constexpr int kFull = TreeSlots<Fused>::kFull, kBank2 = TreeSlots<Fused>::kBank2, kWrench2 = TreeSlots<Fused>::kWrench2;
+    typename TreeSlots<Fused>::Banks Bk{banks};
     const int d = M.d;
     const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
     const ChainKin base{zero, zero, {-g.x, -g.y, -g.z}};
@@ -151,15 +148,9 @@ __device__ __forceinline__ void joint_rnea(const ChainModel &M, const TreeTables
     }
 }
 
-// This lane's point: lanes past the last point of the batch take the last point (chain_row's rule).
-__device__ __forceinline__ size_t joint_point(int npoints) {
-    const size_t g = (size_t)blockIdx.x * kChainBlock + threadIdx.x;
-    return g < (size_t)npoints ? g : (size_t)npoints - 1;
-}
-
 static __global__ void __launch_bounds__(kChainBlock) joint_wrench_kernel(JointWrenchArgs A) {
     extern __shared__ double chain_lds[];
-    const size_t pt = joint_point(A.npoints), at = pt * (size_t)A.M.d, to = pt * (size_t)(6 * A.S.count);
+    const size_t pt = chain_point(A.npoints), at = pt * (size_t)A.M.d, to = pt * (size_t)(6 * A.S.count);
     ChainLdsState<kChainSlotsSingle> St{chain_lds + threadIdx.x};
     double *banks = chain_lds + A.M.d * kChainSlotsSingle * kChainBlock + threadIdx.x;
     joint_rnea<false>(A.M, A.T, A.S, St, banks, A.q + at, A.qd + at, A.qdd + at, nullptr, nullptr, A.wrench + to);
@@ -170,7 +161,7 @@ static __global__ void __launch_bounds__(kChainBlock) joint_wrench_kernel(JointW
 template <bool FusedState>
 static __global__ void __launch_bounds__(kChainBlock) joint_wrench_terms_kernel(JointWrenchTermsArgs A) {
     extern __shared__ double chain_lds[];
-    const size_t pt = joint_point(A.npoints), at = pt * (size_t)A.M.d, to = pt * (size_t)(6 * A.S.count);
+    const size_t pt = chain_point(A.npoints), at = pt * (size_t)A.M.d, to = pt * (size_t)(6 * A.S.count);
     if constexpr (FusedState) {
         ChainLdsState<kChainSlotsFused> St{chain_lds + threadIdx.x};
         double *banks = chain_lds + A.M.d * kChainSlotsFused * kChainBlock + threadIdx.x;

@@ -36,7 +36,7 @@
 // (chain_accel_rows_store).  Lanes past the last point of the batch work on the last point's row again and rewrite its LDS row
 // with its values (no lane is masked out); only npts rows leave.  Dynamic LDS: mount_lds_bytes.
 #pragma once
-#define TPR_CHAIN_STAGING_ONLY  // (chain_accel_lds_bytes, chain_rows_load, chain_accel_rows_store; none of the chain kernels)
+#define TPR_CHAIN_STAGING_ONLY  // (chain_accel_lds_bytes, chain_stage, chain_accel_rows_store; none of the chain kernels)
 #include "tpr_chain.hip.inc"
 #include "tpr_mount_args.hpp"
 
@@ -83,11 +83,8 @@ static_assert(offsetof(MountWrenchArgs, T) % 4 == 0 && offsetof(MountWrenchTerms
 
 // This lane's banks: [fork][slot][lane].
 template <int Doubles>
-struct MountBanks {
-    double *base;
-    __device__ __forceinline__ double &at(int b, int s) { return base[(b * Doubles + s) * kChainBlock]; }
-    __device__ __forceinline__ V3 get(int b, int s) { return {at(b, s), at(b, s + 1), at(b, s + 2)}; }
-    __device__ __forceinline__ void put(int b, int s, V3 v) { at(b, s) = v.x; at(b, s + 1) = v.y; at(b, s + 2) = v.z; }
+struct MountBanks : ChainLaneBanks<Doubles> {
+    using ChainLaneBanks<Doubles>::at;
     __device__ __forceinline__ M3 frame(int b) {
         M3 W;
 #pragma unroll
@@ -115,9 +112,7 @@ __device__ __forceinline__ void mount_put(MountWords P, const MountSum &G, const
     M3 Rm;
 #pragma unroll
     for (int k = 0; k < 9; ++k) Rm.m[k] = P[k];
-    const V3 fo = mul_t(Rm, f), no = mul_t(Rm, n + cross(f, V3{P[9], P[10], P[11]}));
-    o[0] = fo.x + 0.0; o[1] = fo.y + 0.0; o[2] = fo.z + 0.0;
-    o[3] = no.x + 0.0; o[4] = no.y + 0.0; o[5] = no.z + 0.0;
+    chain_put6(mul_t(Rm, f), mul_t(Rm, n + cross(f, V3{P[9], P[10], P[11]})), o);
 }
 
 // This lane's walk over the links.  G: the weight's part, platform included.  Fused: S1, S2 = the dynamic parts of w(q, 0, v1) and
@@ -195,47 +190,37 @@ __device__ __forceinline__ void mount_walk(const ChainModel &M, const TreeTables
 static __global__ void __launch_bounds__(kChainBlock) mount_wrench_kernel(MountWrenchArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qd, A.qdd, A.npoints, d);
     double *banks = chain_lds + chain_accel_lds_bytes(d, 1) / sizeof(double) + threadIdx.x;
-    chain_rows_load(bq, b1, b2, A.q, A.qd, A.qdd, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
     MountSum G, S1, S2;
-    mount_walk<false, MountWrenchArgs>(M, A.T, banks, bq + row, b1 + row, b2 + row, G, S1, S2);
+    mount_walk<false, MountWrenchArgs>(M, A.T, banks, B.bq + B.row, B.b1 + B.row, B.b2 + B.row, G, S1, S2);
     __syncthreads();
-    mount_put(mount_words<MountWrenchArgs>(), G, S2, chain_lds + lane * 7);
+    mount_put(mount_words<MountWrenchArgs>(), G, S2, chain_lds + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(chain_lds, A.wrench, g0, npts);
+    chain_accel_rows_store(chain_lds, A.wrench, B.g0, B.npts);
 }
 
 // w0 = w(q, 0, 0), wa = w(q, 0, qs), wb = w(q, qs, qss) in one pass over the links.
 static __global__ void __launch_bounds__(kChainBlock) mount_wrench_terms_kernel(MountWrenchTermsArgs A) {
     extern __shared__ double chain_lds[];
     const ChainModel &M = A.M;
-    const int d = M.d, pitch = d | 1;
-    const size_t g0 = (size_t)blockIdx.x * kChainBlock;
-    const int left = A.npoints - (int)g0, npts = left < kChainBlock ? left : kChainBlock;
-    double *bq = chain_lds, *b1 = bq + kChainBlock * pitch, *b2 = b1 + kChainBlock * pitch;
+    const int d = M.d;
+    const ChainStage B = chain_stage(chain_lds, A.q, A.qs, A.qss, A.npoints, d);
     double *banks = chain_lds + chain_accel_lds_bytes(d, 3) / sizeof(double) + threadIdx.x;
-    chain_rows_load(bq, b1, b2, A.q, A.qs, A.qss, g0, npts, d, pitch);
-    __syncthreads();
-    const int lane = (int)threadIdx.x < npts ? (int)threadIdx.x : npts - 1, row = lane * pitch;
     MountSum G, S1, S2;
-    mount_walk<true, MountWrenchTermsArgs>(M, A.T, banks, bq + row, b1 + row, b2 + row, G, S1, S2);
+    mount_walk<true, MountWrenchTermsArgs>(M, A.T, banks, B.bq + B.row, B.b1 + B.row, B.b2 + B.row, G, S1, S2);
     double *o0 = chain_lds, *oa = o0 + kChainBlock * 7, *ob = oa + kChainBlock * 7;
     __syncthreads();
     const MountWords P = mount_words<MountWrenchTermsArgs>();
     const V3 zero{0.0, 0.0, 0.0};
-    mount_put(P, G, MountSum{zero, zero}, o0 + lane * 7);
-    mount_put(P, G, S1, oa + lane * 7);
-    mount_put(P, G, S2, ob + lane * 7);
+    mount_put(P, G, MountSum{zero, zero}, o0 + B.lane * 7);
+    mount_put(P, G, S1, oa + B.lane * 7);
+    mount_put(P, G, S2, ob + B.lane * 7);
     __syncthreads();
-    chain_accel_rows_store(o0, A.w0, g0, npts);
-    chain_accel_rows_store(oa, A.wa, g0, npts);
-    chain_accel_rows_store(ob, A.wb, g0, npts);
+    chain_accel_rows_store(o0, A.w0, B.g0, B.npts);
+    chain_accel_rows_store(oa, A.wa, B.g0, B.npts);
+    chain_accel_rows_store(ob, A.wb, B.g0, B.npts);
 }
 
 }  // namespace tpr

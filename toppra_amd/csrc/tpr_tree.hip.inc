@@ -1,7 +1,8 @@
 // tpr_tree.hip.inc -- recursive Newton-Euler inverse dynamics of a kinematic TREE (a branched robot: two arms on a torso, an arm
 // beside a pan-tilt head, a forest of robots on one base) at every gridpoint of every trajectory.  The model is tpr_chain's with
 // a parent table beside it; the recursion is tpr_chain_rnea.hip.inc's -- chain_link, chain_joint, chain_forward<Level> and
-// chain_backward<Level> are used as they are -- and what is new is the walk around them.
+// chain_backward<Level> are used as they are -- and what is new is the walk around them.  The banks and the slots of state and banks
+// are tpr_tree_walk.hip.inc's, shared with the joint-load kernels (tpr_joint.hip.inc), whose joint_rnea repeats tree_rnea's walk.
 //
 // The walk.  Links are numbered topologically (parent[i] < i), so one loop up and one loop down visit every link after (before)
 // its parent.  Forward, link i takes the parent's (w, wd, a):
@@ -33,38 +34,16 @@
 // d * 17 * 512 + forks * 18 * 512.  Lanes past the last point of the batch evaluate the last point again and store the very same
 // values where its own lane does.
 #pragma once
-#include "tpr_chain_rnea.hip.inc"
-#include "tpr_tree_args.hpp"
+#include "tpr_tree_walk.hip.inc"
 
 namespace tpr {
 
-// This lane's banks: [fork][slot][lane].
-template <int Doubles>
-struct TreeBanks {
-    double *base;
-    __device__ __forceinline__ double &at(int b, int s) { return base[(b * Doubles + s) * kChainBlock]; }
-    __device__ __forceinline__ V3 get(int b, int s) { return {at(b, s), at(b, s + 1), at(b, s + 2)}; }
-    __device__ __forceinline__ void put(int b, int s, V3 v) { at(b, s) = v.x; at(b, s + 1) = v.y; at(b, s + 2) = v.z; }
-    __device__ __forceinline__ ChainWrench wrench(int b, int s) { return {get(b, s), get(b, s + 3)}; }
-    // the first contribution is stored; a later one is added to what the bank holds (bank on the left)
-    __device__ __forceinline__ void hand_up(int b, int s, const ChainWrench &C, bool first) {
-        if (first) {
-            put(b, s, C.f); put(b, s + 3, C.n);
-        } else {
-            put(b, s, get(b, s) + C.f); put(b, s + 3, get(b, s + 3) + C.n);
-        }
-    }
-};
-
 // One point, as chain_rnea<0, Fused>: o0 = tau(q, 0, 0), o1 = tau(q, 0, v1), o2 = tau(q, v1, v2), or o2 alone.
-// Bank slots, forward: fused a0 | wd1 a1 | w2 wd2 a2 at 0, 3, 9; single w wd a.  Backward: (f, n) per level at 0, 6, 12; single at 0.
 template <bool Fused, class State>
 __device__ __forceinline__ void tree_rnea(const ChainModel &M, const TreeTables &T, State &St, double *banks, const double *q,
                                           const double *v1, const double *v2, double *o0, double *o1, double *o2) {
-    constexpr int kFull = Fused ? 11 : 2;         // first slot of the level-2 evaluation's F, N
-    constexpr int kBank2 = Fused ? 9 : 0;         // first bank slot of the level-2 evaluation, forward
-    constexpr int kWrench2 = Fused ? 12 : 0;      // ... and backward
-    TreeBanks<Fused ? kTreeBankFused : kTreeBankSingle> Bk{banks};
+    constexpr int kFull = TreeSlots<Fused>::kFull, kBank2 = TreeSlots<Fused>::kBank2, kWrench2 = TreeSlots<Fused>::kWrench2;
+    typename TreeSlots<Fused>::Banks Bk{banks};
     const int d = M.d;
     const V3 g = load3(M.gravity), zero{0.0, 0.0, 0.0};
     const ChainKin base{zero, zero, {-g.x, -g.y, -g.z}};
@@ -147,7 +126,6 @@ __device__ __forceinline__ void tree_rnea(const ChainModel &M, const TreeTables 
     }
 }
 
-#ifndef TPR_TREE_WALK_ONLY  // (tpr_joint.hip.inc takes TreeBanks and the walk's conventions from here, and no copy of the kernels)
 static __global__ void __launch_bounds__(kChainBlock) tree_inverse_dynamics_kernel(TreeDynArgs A) {
     extern __shared__ double chain_lds[];
     const size_t at = chain_row(A.npoints, A.M.d);
@@ -173,6 +151,5 @@ static __global__ void __launch_bounds__(kChainBlock) tree_torque_terms_kernel(T
         tree_rnea<false>(A.M, A.T, St, banks, A.q + at, A.qs + at, A.qss + at, nullptr, nullptr, A.wb + at);
     }
 }
-#endif  // TPR_TREE_WALK_ONLY
 
 }  // namespace tpr
