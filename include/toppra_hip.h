@@ -634,6 +634,36 @@ int tpr_tree_joint_wrench_terms_batch(const tpr_chain *links, const int32_t *par
                                       const double *q, const double *qs, const double *qss, double *w0, double *wa, double *wb,
                                       int flags, void *stream);
 
+/* ---- momentum and kinetic energy: how much motion a set of a robot's links carries, for a batch --------------------------------
+ * What a collaborative robot's safety controller caps beside force and speed: the momentum of the moving structure (kg m / s) and
+ * the kinetic energy it can transfer on contact.  Both are first order in the path velocity: with qd = q' sd the momentum is
+ * h(q, q') sd and the energy 1/2 q'' M(q) q' sd^2, so each limit is an upper bound on x = sd^2 per gridpoint.  Per unit of path
+ * velocity (qd = qs), with W_i the link frame's rotation and p_i its origin in base coordinates, v_i and w_i the velocity of that
+ * origin and the angular velocity in link axes (the recursion of tpr_chain_tool_velocity_batch), m_i, c_i, I_i the link's mass,
+ * centre of mass and inertia about it, and vc_i = v_i + w_i x c_i:
+ *   h_i = (W_i vc_i) m_i
+ *   P   = sum_i h_i                                           linear momentum, base axes
+ *   L   = sum_i [ W_i (I_i w_i) + (p_i + W_i c_i) x h_i ]     angular momentum about the base origin, base axes
+ *   T2  = sum_i [ m_i (vc_i . vc_i) + w_i . (I_i w_i) ]       = qs' M(q) qs: twice the kinetic energy per sd^2
+ *   P'  = rot' P,   L' = rot' (L - origin x P)                in the mount frame (the mount's mass and com do not move: not read)
+ * The sums run over the links of link_mask (bit i = link i) in ascending number, the sum on the left, (((0 + t_0) + t_1) + ...),
+ * then the mount frame; every output passes through "+ 0.0": a standstill gives +0.  Links outside the set are skipped, not
+ * multiplied by zero, and the walk ends after the highest link of the set; the result equals, in every bit, the full sum on the
+ * robot whose other links have mass 0 and inertia 0.
+ *   momentum [B][N+1][6] = [P'; L'];   energy2 [B][N+1] = T2;
+ *   xbound [B][N+1][2] = (0, min(limit[b][0] / |P'|^2, limit[b][1] / |L'|^2, limit[b][2] / T2)),  |a|^2 = (a_x a_x + a_y a_y) + a_z a_z,
+ *   limit [B][3] = (p_max^2, L_max^2, 2 E_max), each > 0 (the caller's responsibility, as for tpr_chain_tool_velocity_batch);
+ *   +inf switches a term off.  The divisions are IEEE on the outputs as they leave: a standstill gives +inf -- the array a
+ *   TPR_BOUND_X source of tpr_stage_boxes_batch takes, where the box then keeps its 1e8.
+ * Any of momentum, energy2, xbound may be NULL, not all; each output is the same whichever others are asked for.  Forward only, a
+ * point's state in registers at any dof.  One wave of 64 points per block; dynamic LDS stages a block's q, qs rows and its outputs
+ * (one row of 9 doubles per point) and keeps one bank of 18 doubles per lane and fork: at most 33 792 + 4 * 18 * 512 = 70 656 bytes.
+ * Refused before any launch, in this order: B, N; what tpr_tree_base_wrench_batch refuses of links, parent and the mount; an empty
+ * link_mask, a bit at or above d (TPR_E_BADARG); a NULL q or qs; all three outputs NULL; xbound without limit.               */
+int tpr_tree_momentum_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, uint32_t link_mask, int B, int N,
+                            const double *q, const double *qs, const double *limit, double *momentum, double *energy2,
+                            double *xbound, int flags, void *stream);
+
 /* Replaces seidelWrapper.solve_stagewise_optim (cy_seidel_solverwrapper.pyx:549-697) for ONE
  * stage of each of B trajectories (the compatibility entry; 1 LP per call per trajectory).
  *   stage [B]; g [B][2]; xb [B][4] = x_min, x_max, x_next_min, x_next_max (NaN = absent);

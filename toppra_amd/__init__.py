@@ -19,7 +19,7 @@ from . import algorithm, batch, chain, constants, constraint, exceptions, interp
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
 from .chain import ControlPoints, JointSections, KinematicTree, Mount, Payload, SerialChain
-from .constraint import BatchBaseWrenchConstraint, BatchJointLoadConstraint, BatchToolWrenchConstraint
+from .constraint import BatchBaseWrenchConstraint, BatchJointLoadConstraint, BatchMomentumConstraint, BatchToolWrenchConstraint
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
@@ -27,4 +27,4 @@ logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 __all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
            "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint", "ControlPoints", "KinematicTree",
-           "Mount", "BatchBaseWrenchConstraint", "JointSections", "BatchJointLoadConstraint"]
+           "Mount", "BatchBaseWrenchConstraint", "JointSections", "BatchJointLoadConstraint", "BatchMomentumConstraint"]

@@ -142,6 +142,7 @@ EXPORTS = (
     "tpr_tree_inverse_dynamics_batch", "tpr_tree_torque_terms_batch",
     "tpr_mount_bytes", "tpr_tree_base_wrench_batch", "tpr_tree_base_wrench_terms_batch",
     "tpr_joint_sections_bytes", "tpr_tree_joint_wrench_batch", "tpr_tree_joint_wrench_terms_batch",
+    "tpr_tree_momentum_batch",
 )
 
 _lib = None
@@ -280,7 +281,8 @@ def load():
                 "tpr_tree_base_wrench_batch": [CP, V, MP, LL, V, V, V, V],
                 "tpr_tree_base_wrench_terms_batch": [CP, V, MP, I, I, V, V, V, V, V, V],
                 "tpr_tree_joint_wrench_batch": [CP, V, JP, LL, V, V, V, V],
-                "tpr_tree_joint_wrench_terms_batch": [CP, V, JP, I, I, V, V, V, V, V, V]}.items()})
+                "tpr_tree_joint_wrench_terms_batch": [CP, V, JP, I, I, V, V, V, V, V, V],
+                "tpr_tree_momentum_batch": [CP, V, MP, C.c_uint32, I, I, V, V, V, V, V, V]}.items()})
         for name, argtypes in signatures.items():
             entry = getattr(L, name)
             entry.restype, entry.argtypes = C.c_int, argtypes

@@ -28,7 +28,7 @@ __all__ = ["solve_batch", "controllable_sets_batch", "feasible_sets_batch", "rea
            "chain_tool_wrench_batch", "chain_tool_wrench_terms_batch",
            "chain_points_speed_batch", "chain_points_acceleration_batch", "chain_points_acceleration_terms_batch",
            "tree_inverse_dynamics_batch", "tree_torque_terms_batch", "base_wrench_batch", "base_wrench_terms_batch",
-           "joint_wrench_batch", "joint_wrench_terms_batch"]
+           "joint_wrench_batch", "joint_wrench_terms_batch", "momentum_batch", "momentum_bound_batch", "link_mask"]
 
 
 def _stream_ptr(like):
@@ -857,6 +857,86 @@ def base_wrench_terms_batch(robot, q, qs, qss, mount=None):
     constraint on the base reaction builds its rows from (w0 is the static reaction: not zero under gravity).  Each equals
     :func:`base_wrench_batch` on the same arguments in every bit."""
     return tuple(_base_wrench_call(robot, "tpr_tree_base_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, mount, by_grid=True))
+
+
+# momentum and kinetic energy of a set of links of a chain or tree (include/toppra_hip.h: tpr_tree_momentum_batch)
+
+def link_mask(robot, links=None):
+    """The link set ``links`` of ``robot`` as the mask the momentum entry takes, bit i = link i: None = every link, otherwise an
+    iterable of link numbers in -d .. d-1 (negative numbers count from the end: -1 is the last link).  ValueError for anything
+    else, an empty set and a link outside the robot -- before any launch."""
+    d = int(robot.dof)
+    if links is None:
+        return (1 << d) - 1
+    if isinstance(links, (str, bytes)) or not hasattr(links, "__iter__"):
+        raise ValueError("links must be an iterable of link numbers (or None = every link), got %r" % (links,))
+    mask = 0
+    for link in links:
+        if isinstance(link, (bool, np.bool_)) or not isinstance(link, (int, np.integer)):
+            raise ValueError("links must hold integers, got %r" % (link,))
+        link = int(link)
+        if not -d <= link < d:
+            raise ValueError("link %d is outside the robot's links 0..%d" % (link, d - 1))
+        mask |= 1 << (link % d)
+    if mask == 0:
+        raise ValueError("links is empty: the sum needs at least one link")
+    return mask
+
+
+def _momentum_call(robot, q, qs, mount, links, limit, tails):
+    """One call of tpr_tree_momentum_batch; ``tails`` = the last axes of (momentum, energy2, xbound), None = not asked for."""
+    if mount is None:
+        from .chain import Mount
+        mount = Mount()
+    if not (hasattr(mount, "c_struct") and hasattr(mount, "rotation")):
+        raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+    mask = C.c_uint32(link_mask(robot, links))
+    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
+
+    def limits(q, shape, npoints):
+        if limit is None:
+            return (mask, npoints, 0), (None,), tails
+        dev = _capi.is_torch_cuda(q)
+
+        def convert(lim, B):
+            if dev:
+                import torch
+                if not (hasattr(lim, "is_cuda") and lim.is_cuda):
+                    lim = torch.as_tensor(np.asarray(lim, dtype=np.float64), device=q.device)
+                _capi.check_tensor("limit", lim, q)
+            else:
+                lim = np.asarray(lim, dtype=np.float64)
+            if tuple(lim.shape) not in ((3,), (B, 3)):
+                raise ValueError("limit must have shape [3] or [B, 3] = [%d, 3] (p_max^2, L_max^2, 2 E_max), got %s" % (B, tuple(lim.shape)))
+            return lim.expand(B, 3).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(lim, (B, 3)))
+
+        B, N, lim = _bound_limits(limit, shape, convert)
+        return (mask, B, N), (lim,), tails
+
+    return _rigid_call(tree, "tpr_tree_momentum_batch", (q, qs), ("q", "qs"), None, structs=[mount], by_grid=True, limits=limits)
+
+
+def momentum_batch(robot, q, qs, mount=None, links=None, limit=None):
+    """How much motion ``robot`` (a :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``) carries per unit of path velocity
+    (qd = qs): ``(momentum, energy2)`` with ``momentum`` [..., 6] = [linear; angular about the mount frame's origin] in
+    mount-frame axes and ``energy2`` [...] = qs' M(q) qs, TWICE the kinetic energy -- summed over the links of ``links`` (None =
+    all; :func:`link_mask`), in ascending link number (include/toppra_hip.h: tpr_tree_momentum_batch).  ``mount``: a
+    :class:`toppra_amd.chain.Mount`, None = the base frame; its platform does not move and plays no part.
+
+    With ``limit`` ([3] or [B, 3] = (p_max^2, L_max^2, 2 E_max), each > 0, +inf = no limit on that term; q must be [B, N+1, d]
+    then) also the one bound on x = sd^2 the three imply: ``(momentum, energy2, xbound)`` with xbound [B, N+1, 2] =
+    (0, min(limit_0 / |P|^2, limit_1 / |L|^2, limit_2 / energy2)) -- +inf at a standstill -- the array a ``("xbound", ...)``
+    source of :func:`stage_boxes_batch` takes."""
+    out = _momentum_call(robot, q, qs, mount, links, limit, [(6,), (), None if limit is None else (2,)])
+    return tuple(out[:2]) if limit is None else tuple(out)
+
+
+def momentum_bound_batch(robot, q, qs, limit, mount=None, links=None):
+    """``xbound`` [B, N+1, 2] of :func:`momentum_batch` alone -- the same launch with the other two outputs left out, the same
+    bits: what :class:`toppra_amd.constraint.BatchMomentumConstraint` hands to the stage boxes."""
+    if limit is None:
+        raise ValueError("the bound needs limit: [3] or [B, 3] = (p_max^2, L_max^2, 2 E_max)")
+    return _momentum_call(robot, q, qs, mount, links, limit, [None, None, (2,)])[2]
 
 
 # the wrench across any joint of a chain or tree (include/toppra_hip.h: tpr_tree_joint_wrench_*; the set is toppra_amd.chain.JointSections)

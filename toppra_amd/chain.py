@@ -481,6 +481,18 @@ class SerialChain(object):
         reaction needs; the first is the static reaction, which gravity keeps from being zero."""
         return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
 
+    def momentum(self, q, qd, mount=None, links=None):
+        """The momentum [..., 6] = [linear; angular] the robot carries at velocity ``qd``: the sum over the links of ``links`` (an
+        iterable of link numbers, -1 = the last; None = every link) of each link's linear momentum and of its angular momentum
+        about the origin of ``mount``'s frame (a :class:`Mount`, None = the base frame), both in that frame's axes -- kg m / s
+        and kg m^2 / s.  The mount's platform does not move and plays no part."""
+        return _batch.momentum_batch(self, q, qd, mount, links)[0]
+
+    def kinetic_energy(self, q, qd, links=None):
+        """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
+        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
+        return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
+
     def joint_wrenches(self, q, qd, qdd, sections):
         """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section
         [force; moment about its origin] in its axes -- what the parent side exerts ON the section's link through its joint,
@@ -593,6 +605,18 @@ class KinematicTree(object):
         """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
         reaction needs; the first is the static reaction, which gravity keeps from being zero."""
         return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
+
+    def momentum(self, q, qd, mount=None, links=None):
+        """The momentum [..., 6] = [linear; angular] the robot carries at velocity ``qd``: the sum over the links of ``links`` (an
+        iterable of link numbers, -1 = the last; None = every link) of each link's linear momentum and of its angular momentum
+        about the origin of ``mount``'s frame (a :class:`Mount`, None = the base frame), both in that frame's axes -- kg m / s
+        and kg m^2 / s.  The mount's platform does not move and plays no part."""
+        return _batch.momentum_batch(self, q, qd, mount, links)[0]
+
+    def kinetic_energy(self, q, qd, links=None):
+        """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
+        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
+        return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
 
     def joint_wrenches(self, q, qd, qdd, sections):
         """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section

@@ -1196,6 +1196,70 @@ class BatchPointSpeedConstraint(_BatchChainBound):
         return [("xbound", _batch.chain_points_speed_batch(self.chain, q, like, self.points, limit)[1])]
 
 
+class BatchMomentumConstraint(_BatchChainBound):
+    """Limits on how much motion a robot carries, for a batch -- what a collaborative robot's safety controller caps beside
+    force and point speeds:  |P| sd <= linear,  |L| sd <= angular,  1/2 q'' M(q) q' sd^2 <= energy  at every gridpoint, where
+    P and L are the linear and the angular momentum per unit of path velocity (qd = q') of the links of ``links``, L about the
+    origin of ``mount``'s frame (:meth:`toppra_amd.chain.SerialChain.momentum`, ``kinetic_energy``).  The kinetic energy bounds
+    what the structure can transfer on contact for every contact point and direction at once.
+
+    ``robot``: a :class:`toppra_amd.chain.SerialChain` or :class:`toppra_amd.chain.KinematicTree`; ``mount``: a
+    :class:`toppra_amd.chain.Mount`, None = the base frame (its platform does not move and plays no part); ``links``: an iterable
+    of link numbers, -1 = the last ("everything beyond the shoulder", "the left arm"), None = every link.
+
+    ``linear``, ``angular``, ``energy``: each None (no limit), a scalar or [B], > 0; at least one is given.  They are in PHYSICAL
+    UNITS, the way a safety configuration states them -- kg m / s, kg m^2 / s and J: ``linear=5`` holds the momentum to
+    5 kg m / s.  This is unlike the speed constraints (:class:`BatchCartesianVelocityNormConstraint`,
+    :class:`BatchPointSpeedConstraint`), whose ``limit`` is the SQUARE of a speed; here the class squares and doubles on the host
+    (``linear * linear``, ``angular * angular``, ``2.0 * energy``) and hands the kernel what it divides.
+
+    The bound (0, min(linear^2 / |P|^2, angular^2 / |L|^2, 2 energy / q'' M q')) comes from one launch and is ONE ``xbound`` source
+    of the stage boxes; a term that vanishes drops out of the minimum, and where the robot stands still the box keeps its 1e8.
+    Needs the path positions: a ``from_path_samples`` batch must be given ``q``.  Per-trajectory robots or mounts, a floating
+    base, power limits and the effective mass at a contact point are out of scope."""
+    no_q = "a momentum or energy limit evaluates the robot at q: give the path positions"
+
+    def __init__(self, robot, linear=None, angular=None, energy=None, mount=None, links=None):
+        super(BatchMomentumConstraint, self).__init__()
+        if not isinstance(robot, (SerialChain, KinematicTree)):
+            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
+        if mount is None:
+            mount = Mount()
+        if not isinstance(mount, Mount):
+            raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+        if linear is None and angular is None and energy is None:
+            raise ValueError("no limit given: one of linear, angular, energy is required")
+        if links is not None:
+            links = tuple(links) if hasattr(links, "__iter__") and not isinstance(links, (str, bytes)) else links
+        _batch.link_mask(robot, links)  # (ValueError for a set that is not one of this robot's)
+        self.robot, self.mount, self.links = robot, mount, links
+        self.linear, self.angular, self.energy = linear, angular, energy
+        self.dof = robot.dof
+        self._limit_batch, parts = None, []
+        for name, value, scale in (("linear", linear, None), ("angular", angular, None), ("energy", energy, 2.0)):
+            if value is None:
+                parts.append(np.array(np.inf))
+                continue
+            host = _host(value)
+            if host.ndim > 1:
+                raise ValueError("%s must be a scalar or have shape [B], got %s" % (name, list(host.shape)))
+            if not np.all(host > 0):
+                raise ValueError("%s must be > 0 (NaN is refused; 0 / 0 at a standstill would be a NaN bound)" % name)
+            if host.ndim == 1:
+                if self._limit_batch not in (None, host.shape[0]):
+                    raise ValueError("the limits are given per trajectory for %d and %d trajectories" % (self._limit_batch, host.shape[0]))
+                self._limit_batch = int(host.shape[0])
+            parts.append(host * host if scale is None else scale * host)
+        lead = () if self._limit_batch is None else (self._limit_batch,)
+        # what the kernel divides: (p_max^2, L_max^2, 2 E_max), [3] or [B, 3]
+        self.limit = np.ascontiguousarray(np.stack([np.broadcast_to(part, lead) for part in parts], -1))
+        self._format_string = "    Batched momentum / kinetic-energy limit, %d dof\n" % self.dof
+
+    def bound_sources(self, gridpoints, B, N, d, like, q=None):
+        limit = self._limit_like(B, N, d, like, q)
+        return [("xbound", _batch.momentum_bound_batch(self.robot, q, like, limit, self.mount, self.links))]
+
+
 class ConicConstraint(Constraint):
     """Base class of canonical conic constraints (conic_constraint.py:6-44)."""
 

@@ -1607,11 +1607,12 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
 }  // extern "C"
 
 // ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip;
-// tpr_mount.hip.inc, tpr_mount_tu.hip; tpr_joint.hip.inc, tpr_joint_tu.hip) ------------------------------------------------------
+// tpr_mount.hip.inc, tpr_mount_tu.hip; tpr_joint.hip.inc, tpr_joint_tu.hip; tpr_momentum.hip.inc, tpr_momentum_tu.hip) -------------
 // One host path for the family: an entry is its argument checks, in an order that is its own and is behaviour (which refusal
 // wins when two arguments are bad: tests/test_rigid_refusal_order.py), then run_rigid() with what it stages and what it launches.
 #include "tpr_mount_args.hpp"
 #include "tpr_joint_args.hpp"
+#include "tpr_momentum_args.hpp"
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
@@ -1628,6 +1629,7 @@ __attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_launch(const tpr::
 __attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_terms_launch(const tpr::MountWrenchTermsArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_launch(const tpr::JointWrenchArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_terms_launch(const tpr::JointWrenchTermsArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_momentum_launch(const tpr::MomentumArgs *, int forks, hipStream_t);
 }
 namespace {
 // The gridpoints of a batch given as (B, N).
@@ -1754,6 +1756,12 @@ tpr::MountFrame stage_mount(const tpr_mount *m) {
     tpr::MountFrame P{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}, 0.0, {0.0, 0.0, 0.0}};
     if (m) std::memcpy(&P, m, sizeof(P));
     return P;
+}
+// A link set is a mask, bit i = link i: at least one link, none outside the robot.
+int check_link_mask(const tpr_chain *links, uint32_t mask, const char *who) {
+    if (mask == 0) return fail(TPR_E_BADARG, std::string(who) + ": the link set is empty (link_mask = 0)");
+    if (links->d < 32 && (mask >> links->d) != 0) return fail(TPR_E_BADARG, std::string(who) + ": the link set names a link outside the robot");
+    return TPR_E_OK;
 }
 // A section set is a host struct: read here, handed to the kernels by value with the mask of its links and the lowest of them.
 // Its frames are held to what a mount's is: orthonormal with determinant +1, to 1e-12.
@@ -2110,5 +2118,41 @@ int tpr_tree_joint_wrench_terms_batch(const tpr_chain *links, const int32_t *par
         stage_outputs(S, 6 * (size_t)sections->count * (size_t)npoints, {{&A.w0, w0}, {&A.wa, wa}, {&A.wb, wb}});
         return A;
     }, [forks](const tpr::JointWrenchTermsArgs *A, hipStream_t stream) { return tpr_tu_joint_wrench_terms_launch(A, forks, stream); });
+}
+
+int tpr_tree_momentum_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, uint32_t link_mask, int B, int N,
+                            const double *q, const double *qs, const double *limit, double *momentum, double *energy2, double *xbound,
+                            int flags, void *stream_) {
+    const char *who = "tpr_tree_momentum_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_mount(mount, who)) return rc;
+    if (int rc = check_link_mask(links, link_mask, who)) return rc;
+    if (int rc = required(q && qs, who, "q, qs")) return rc;
+    if (!momentum && !energy2 && !xbound) return fail(TPR_E_BADARG, "tpr_tree_momentum_batch: one of momentum, energy2, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, "tpr_tree_momentum_batch: xbound needs limit");
+    // the walk ends after the highest link of the set; of the forks, it reaches those below that link (their banks are the first)
+    int nlinks = 0;
+    for (int i = 0; i < links->d; ++i)
+        if (link_mask >> i & 1u) nlinks = i + 1;
+    int reached = 0;
+    for (int i = 0; i < nlinks; ++i) reached += (int)(T.forks >> i & 1u);
+    return run_rigid(flags, momentum ? momentum : energy2 ? energy2 : xbound, stream_, npoints,
+                     "tpr_tree_momentum_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::MomentumArgs>(links, npoints, S, false);
+        A.T = T;
+        A.P = stage_mount(mount);
+        A.mask = link_mask;
+        A.n1 = N + 1;
+        A.nlinks = nlinks;
+        stage_inputs(S, (size_t)npoints * (size_t)links->d, {{&A.q, q}, {&A.qs, qs}});
+        A.limit = xbound ? S.in(limit, 3 * (size_t)B) : nullptr;
+        A.momentum = S.out(momentum, 6 * (size_t)npoints); A.energy2 = S.out(energy2, (size_t)npoints);
+        A.xbound = S.out(xbound, 2 * (size_t)npoints);
+        return A;
+    }, [reached](const tpr::MomentumArgs *A, hipStream_t stream) { return tpr_tu_momentum_launch(A, reached, stream); });
 }
 }  // extern "C"
