@@ -6,12 +6,12 @@ where they are needed, and a link's parameters are fetched in two parts), no sta
 and outputs and keeps the forks' banks), at most the as-built register count plus 10 %, and the launch's LDS arithmetic."""
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers, val
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator)
 AS_BUILT = {"mount_wrench_kernel": 134, "mount_wrench_terms_kernel": 162}
@@ -19,10 +19,7 @@ AS_BUILT = {"mount_wrench_kernel": 134, "mount_wrench_terms_kernel": 162}
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return kr.kernels()
+    return built_kernels()
 
 
 def test_exactly_two_mount_kernels(kernels):
@@ -40,17 +37,13 @@ def test_exactly_two_mount_kernels(kernels):
 @pytest.mark.parametrize("key", sorted(AS_BUILT))
 def test_state_in_registers(kernels, key):
     (r,) = [r for n, r in kernels.items() if key in n]
-    assert r["scratch"] == 0, (key, "scratch bytes per lane", r["scratch"])
-    assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, (key, r)
-    assert r["lds"] == 0, (key, "static LDS bytes", r["lds"])  # (their LDS is dynamic, sized by the launch)
-    assert r["agpr"] == 0 and r["vgpr"] <= int(1.1 * AS_BUILT[key]), (key, "registers", r["vgpr"], AS_BUILT[key])
+    in_registers(r, AS_BUILT[key], key)
 
 
 def test_the_launch_s_lds_fits_the_cu():
     """Staging -- 3 arrays x 64 rows x (d | 1) doubles, or the outputs at pitch 7 where that is more -- plus forks x bank x 512
     bytes: at most 50 688 + 4 * 27 * 512 = 105 984 bytes (93 696 for the single evaluation), under the 160 KB of a CU; above 64 KB
     the launcher asks for the attribute."""
-    val = lambda name, src: sum(int(x) for x in re.search(name + r" = ([0-9+ ]+)[,;]", src).group(1).split("+"))  # noqa: E731
     args = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_mount_args.hpp")).read()
     tree = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_tree_args.hpp")).read()
     chain = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_chain_args.hpp")).read()

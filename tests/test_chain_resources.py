@@ -8,12 +8,12 @@ the fully unrolled links without fences between them (the scheduler starts every
 a store of the outputs under a condition (it draws the whole backward pass into its branch, past the fences)."""
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, val
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator) and static LDS bytes per block, per dof
 SINGLE = {1: (44, 1536), 2: (87, 4608), 3: (104, 4608), 4: (123, 7680), 5: (142, 7680), 6: (162, 10752), 7: (181, 10752), 8: (204, 13824)}
@@ -25,10 +25,7 @@ RUNTIME = {"chain_inverse_dynamics_lds_kernel": 95, "chain_torque_terms_lds_kern
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return {n: r for n, r in kr.kernels().items() if "chain_" in n}
+    return built_kernels("chain_")
 
 
 @pytest.mark.parametrize("kernel,table", [("chain_inverse_dynamics_kernel", SINGLE), ("chain_torque_terms_kernel", FUSED)])
@@ -58,7 +55,7 @@ def test_the_launch_s_lds_fits_the_cu():
     """d * slots * 64 lanes * 8 bytes: the single evaluation fits 160 KB up to 32 dof, the fused state up to 18 dof (the
     launcher switches to one evaluation after the other above), as csrc/tpr_chain_args.hpp states it."""
     text = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_chain_args.hpp")).read()
-    single, fused = (sum(int(x) for x in re.search(name + r" = ([0-9+ ]+)[,;]", text).group(1).split("+")) for name in ("kChainSlotsSingle", "kChainSlotsFused"))
+    single, fused = val("kChainSlotsSingle", text), val("kChainSlotsFused", text)
     assert (single, fused) == (8, 17)
     assert 32 * single * 64 * 8 <= 160 * 1024
     assert 18 * fused * 64 * 8 <= 160 * 1024 < 19 * fused * 64 * 8

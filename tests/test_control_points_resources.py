@@ -5,12 +5,12 @@ and holds its outputs for contiguous global accesses), and at most the as-built 
 tests/test_chain_resources.py.  The dynamic LDS is checked against the 64 KB a kernel may take without asking."""
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator), static LDS bytes per block
 AS_BUILT = {"chain_points_speed_kernel": (124, 0), "chain_points_accel_kernel": (126, 0), "chain_points_accel_terms_kernel": (138, 0)}
@@ -18,10 +18,7 @@ AS_BUILT = {"chain_points_speed_kernel": (124, 0), "chain_points_accel_kernel": 
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return {n: r for n, r in kr.kernels().items() if "chain_" in n}
+    return built_kernels("chain_")
 
 
 @pytest.mark.parametrize("key", sorted(AS_BUILT))
@@ -29,10 +26,7 @@ def test_state_in_registers(kernels, key):
     regs, lds = AS_BUILT[key]
     rs = [r for n, r in kernels.items() if key in n]
     assert len(rs) == 1, (key, sorted(kernels))
-    assert rs[0]["scratch"] == 0, (key, "scratch bytes per lane", rs[0]["scratch"])
-    assert rs[0]["lds"] == lds, (key, "LDS bytes", rs[0]["lds"])
-    assert rs[0]["vgpr"] + rs[0]["agpr"] <= int(1.1 * regs), (key, "registers", rs[0]["vgpr"], rs[0]["agpr"], regs)
-    assert rs[0]["vgpr_spill"] == 0 and rs[0]["sgpr_spill"] == 0, (key, rs[0])
+    in_registers(rs[0], regs, key, static_lds=lds)
 
 
 def test_the_new_names_leave_the_older_tests_their_kernels(kernels):

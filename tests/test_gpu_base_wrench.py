@@ -224,12 +224,7 @@ def test_beside_a_torque_constraint_on_the_same_robot(gpu):
     inst = algorithm.BatchTOPPRA(*args, constraints=cons)
     out = rs.run_passes(inst)
     assert out["rows"][0].shape[-1] == 2 + 4 * d + 2 * d + 24 == 116 <= 122
-    assert all(np.isfinite(out["rows"][k]).all() for k in range(3))
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(out[k]["status"] == 0), k
-    for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
-        sets = out[k] if isinstance(out[k], (tuple, list)) else (out[k],)
-        assert all(not np.isnan(np.asarray(s)).any() for s in sets), k
+    rs.passes_ran(out)
     alone = algorithm.BatchTOPPRA(*args, constraints=[cons[1]]).dense_rows()
     for k in range(3):
         assert np.array_equal(out["rows"][k][..., -24:], alone[k][..., -24:])
@@ -239,35 +234,23 @@ def test_beside_a_torque_constraint_on_the_same_robot(gpu):
 def test_against_the_reference_s_fixtures(gpu, name):
     """(9) w0 / wa / wb within the stored accuracy bound, return codes equal, sd within the stored end-to-end tolerance
     (tools/make_base_wrench_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     fx = golden(name)
-    robot = {k: fx[k] for k in ("joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity", "parent")}
+    robot = rs.fixture_tree(fx)
     mount = {k: fx["mount_" + k] for k in ("rot", "origin", "mass", "com")}
     model, frame = tree_ref.kinematic_tree(robot), bwr.mount_of(mount)
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     ev = bw.evaluations(q, qs, qss)
     got = dict(zip(NAMES, model.base_wrench_terms(q, qs, qss, frame)))
-    for i, k in enumerate(NAMES):
-        err = bw.metric(got[k], fx[k], bwr.base_wrench(robot, *ev[k], mount=mount, absolute=True))
-        print("%s %s: error %.3g, bound %.3g" % (name, k, err, fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    interp = bool(int(fx["scheme"]))
-    DT = constraint.DiscretizationType.Interpolation if interp else constraint.DiscretizationType.Collocation
+    rs.fixture_accuracy(name, fx, got, {k: bwr.base_wrench(robot, *ev[k], mount=mount, absolute=True) for k in NAMES})
+    interp, DT = rs.fixture_scheme(fx)
     if "mu" in fx:
         con = constraint.BatchBaseWrenchConstraint.surface_contact(model, float(fx["mu"]), tuple(fx["half_extents"]), mount=frame,
                                                                    discretization_scheme=DT)
         assert np.array_equal(con.F, fx["F"]) and np.array_equal(np.broadcast_to(con.g, fx["g"].shape), fx["g"])
     else:
         con = constraint.BatchBaseWrenchConstraint(model, frame, F=fx["F"], g=fx["g"], discretization_scheme=DT)
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True, constraints=[con])
-    rows = inst.dense_rows()
-    assert rows[0].shape[-1] == 2 + 4 * q.shape[-1] + (2 if interp else 1) * fx["F"].shape[0]
-    assert np.array_equal(rows[3], fx["low"]) and np.array_equal(rows[4], fx["high"])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("%s sd: deviation %.3g, tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
+    rs.fixture_solve(name, fx, con, interp)
 
 
 # ---- the entries' refusals --------------------------------------------------------------------------------------------------

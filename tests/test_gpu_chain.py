@@ -83,7 +83,7 @@ def test_a_chain_in_the_torque_constraint_equals_its_callback(gpu, scheme, sourc
 def test_against_the_reference_s_fixtures(gpu, name):
     """w0 / wa / wb and the torque rows within the stored accuracy bound, return codes equal, sd within the stored end-to-end
     tolerance (measured on the CPU: tools/make_chain_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     fx = golden(name)
     chain = rs.fixture_chain(fx)
     sc = chain_ref.serial_chain(chain)
@@ -91,15 +91,9 @@ def test_against_the_reference_s_fixtures(gpu, name):
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     mags = {k: chain_ref.rnea(chain, *args, absolute=True) for k, args in cc.evaluations(q, qs, qss).items()}
     got = dict(zip(("w0", "wa", "wb"), sc.torque_terms(q, qs, qss)))
-    for i, k in enumerate(("w0", "wa", "wb")):
-        err = cc.metric(got[k], fx[k], mags[k])
-        print("%s %s: error %.3g, bound %.3g" % (name, k, err, fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    interp = bool(int(fx["torque_scheme"]))
-    DT = constraint.DiscretizationType.Interpolation if interp else constraint.DiscretizationType.Collocation
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True,
-                                 constraints=[constraint.BatchJointTorqueConstraint(sc, fx["taulim"], fx["fric"], discretization_scheme=DT)])
-    rows = inst.dense_rows()
+    rs.fixture_accuracy(name, fx, got, mags)
+    interp, DT = rs.fixture_scheme(fx, "torque_scheme")
+    rows = rs.fixture_solve(name, fx, constraint.BatchJointTorqueConstraint(sc, fx["taulim"], fx["fric"], discretization_scheme=DT), interp)
     # The rows' allowance, composed from the per-quantity bounds through the rows' own assembly: a = wa - w0 may be off by
     # bound_wa mag_wa + bound_w0 mag_w0, b = wb - w0 alike, c = w0 + friction sign(q') - g by bound_w0 mag_w0, and under
     # Interpolation the second half a_{i+1} + 2 delta_i b_{i+1}, b_{i+1}, c_{i+1} by the same sums of its parts.  On top, the
@@ -121,12 +115,6 @@ def test_against_the_reference_s_fixtures(gpu, name):
         worst = float(np.max(np.abs(block - stored) / tol))
         print("%s rows %s: largest error / allowance %.3g" % (name, k, worst))
         assert worst <= 1.0, (name, k, worst)
-    assert np.array_equal(rows[3], fx["low"]) and np.array_equal(rows[4], fx["high"])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("%s sd: deviation %.3g, tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
 
 
 @pytest.mark.parametrize("S", [None, "full"])

@@ -254,11 +254,7 @@ def test_beside_the_other_chain_constraints(gpu):
     speeds = lambda: [constraint.BatchCartesianVelocityNormConstraint(sc, 0.3), constraint.BatchPointSpeedConstraint(sc, pts, 0.2)]  # noqa: E731
     inst = algorithm.BatchTOPPRA(*args, constraints=[m() for m in makers[:2]] + speeds()[:1] + [m() for m in makers[2:]] + speeds()[1:])
     out = rs.run_passes(inst)
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(out[k]["status"] == 0), k
-    for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
-        sets = out[k] if isinstance(out[k], (tuple, list)) else (out[k],)
-        assert all(not np.isnan(np.asarray(s)).any() for s in sets), k
+    rs.passes_ran(out)
     first = 2 + 4 * d
     widths = [2 * d, 12, 12 * pts.count, 12]  # (torque: Collocation; the others: Interpolation)
     assert out["rows"][0].shape[-1] == first + sum(widths)
@@ -289,7 +285,7 @@ def test_kernels_against_the_numpy_reference(gpu, d, which):
 def test_against_the_reference_s_fixtures(gpu, name):
     """wa / wb within the stored accuracy bound, the constraint's rows within the allowance composed from it, low / high and
     return codes equal, sd within the stored end-to-end tolerance (tools/make_control_points_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     from toppra_amd.chain import ControlPoints
     fx = golden(name)
     chain = rs.fixture_chain(fx)
@@ -299,16 +295,11 @@ def test_against_the_reference_s_fixtures(gpu, name):
     ev = cp.evaluations(q, qs, qss)
     mags = {k: cp.point_accelerations(chain, fx["links"], fx["offsets"], *ev[k], absolute=True).reshape(B, -1, 3 * P) for k in ("wa", "wb")}
     got = dict(zip(("wa", "wb"), (w.reshape(B, -1, 3 * P) for w in sc.point_acceleration_terms(q, qs, qss, pts))))
-    for i, k in enumerate(("wa", "wb")):
-        err = cc.metric(got[k], fx[k], mags[k])
-        print("ACCURACY fixture %s %s error %.3g bound %.3g fraction %.2f" % (name, k, err, fx["acc_bound"][i], err / fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    interp = bool(int(fx["scheme"]))
-    DT = constraint.DiscretizationType.Interpolation if interp else constraint.DiscretizationType.Collocation
+    rs.fixture_accuracy(name, fx, got, mags)
+    interp, DT = rs.fixture_scheme(fx)
     con = constraint.BatchPointAccelerationConstraint(sc, pts, linear=fx["linear"], discretization_scheme=DT)
     assert np.array_equal(con.F, fx["F"]) and np.array_equal(con.g, fx["g"])
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True, constraints=[con])
-    rows = inst.dense_rows()
+    rows = rs.fixture_solve(name, fx, con, interp)
     # The rows' allowance, composed as for the tool-acceleration fixtures (tests/test_gpu_tool_accel.py) through the rows' own
     # assembly: w0 is an exact zero on both sides, a = F wa may be off by |F| (bound_wa mag_wa), b = F wb alike, under
     # Interpolation the second half by the same sums of its parts; c = -g has no allowance from the kernels.  On top, 4 eps of the
@@ -329,12 +320,6 @@ def test_against_the_reference_s_fixtures(gpu, name):
         worst = float(np.max(np.abs(block - stored)[tol > 0] / tol[tol > 0]))
         print("ACCURACY fixture %s rows_%s error_over_allowance %.3g" % (name, k, worst))
         assert not bad.any(), (name, k, worst)
-    assert np.array_equal(rows[3], fx["low"]) and np.array_equal(rows[4], fx["high"])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("ACCURACY fixture %s sd deviation %.3g tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
 
 
 def test_entries_refuse_a_bad_chain_before_any_launch(gpu):

@@ -374,23 +374,20 @@ def test_beside_second_order_constraints_and_a_point_speed_limit(gpu):
 def test_against_the_reference_s_fixtures(gpu, name):
     """The kernel's outputs within the stored accuracy bound; high[..., 1] within that bound composed through the division; every
     other box entry, and the return codes, equal; sd within the stored end-to-end tolerance (tools/make_momentum_golden.py)."""
-    from toppra_amd import algorithm, batch, constraint
+    from toppra_amd import batch, constraint
     from toppra_amd.chain import Mount
     fx = golden(name)
-    robot = {k: fx[k] for k in ("joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity", "parent")}
+    robot = rs.fixture_tree(fx)
     model, frame = tree_ref.kinematic_tree(robot), Mount(rotation=fx["mount_rot"], origin=fx["mount_origin"])
     links = [int(i) for i in fx["links"]]
     q, qs, _ = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     h, e2, xb = batch.momentum_batch(model, q, qs, frame, links, fx["limit"])
-    for i, (k, got) in enumerate((("momentum", h), ("energy2", e2))):
-        err = mc.metric(got, fx[k], fx[k + "_mag"])
-        print("ACCURACY fixture %s %s error %.3g bound %.3g fraction %.2f" % (name, k, err, fx["acc_bound"][i], err / fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
+    rs.fixture_accuracy(name, fx, {"momentum": h, "energy2": e2}, {k: fx[k + "_mag"] for k in ("momentum", "energy2")})
     limits = {k: fx["limit_" + k] for k in KINDS if "limit_" + k in fx}
     assert len(limits) == 2 and all(v.shape == (q.shape[0],) for v in limits.values())
     con = constraint.BatchMomentumConstraint(model, mount=frame, links=links, **limits)
     assert np.array_equal(con.limit, fx["limit"])  # (the class squares and doubles as the generator did)
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True, constraints=[con])
+    inst = rs.fixture_instance(fx, con)
     low, high = inst.stage_boxes()
     tol = mr.xbound_tolerance(fx["momentum"], fx["momentum_mag"], fx["energy2"], fx["energy2_mag"], fx["limit"], *fx["acc_bound"])
     assert np.array_equal(low, fx["low"]) and np.array_equal(high[..., 0], fx["high"][..., 0])
@@ -398,8 +395,4 @@ def test_against_the_reference_s_fixtures(gpu, name):
     print("ACCURACY fixture %s high error_over_allowance %.3g" % (name, float(np.max(off[tol > 0] / tol[tol > 0]))))
     assert np.all(off <= tol)
     assert (fx["high"][..., 1] == fx["xbound"][..., 1]).sum(-1).min() >= (q.shape[1] + 3) // 4  # the bound, not the velocity box
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("ACCURACY fixture %s sd deviation %.3g tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
+    rs.fixture_sd(name, fx, inst)

@@ -120,7 +120,7 @@ def test_a_dense_F_equals_the_callback_route(gpu):
 def test_against_the_reference_s_fixtures(gpu, name):
     """wa / wb within the stored accuracy bound, the constraint's rows within the allowance composed from it, low / high and
     return codes equal, sd within the stored end-to-end tolerance (tools/make_tool_accel_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     fx = golden(name)
     chain = rs.fixture_chain(fx)
     sc = chain_ref.serial_chain(chain)
@@ -129,16 +129,11 @@ def test_against_the_reference_s_fixtures(gpu, name):
     ev = tc.evaluations(q, qs, qss)
     mags = {k: tar.tool_acceleration(chain, *ev[k], absolute=True) for k in ("wa", "wb")}
     got = dict(zip(("wa", "wb"), sc.tool_acceleration_terms(q, qs, qss)))
-    for i, k in enumerate(("wa", "wb")):
-        err = cc.metric(got[k], fx[k], mags[k])
-        print("%s %s: error %.3g, bound %.3g" % (name, k, err, fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    interp = bool(int(fx["scheme"]))
-    DT = constraint.DiscretizationType.Interpolation if interp else constraint.DiscretizationType.Collocation
+    rs.fixture_accuracy(name, fx, got, mags)
+    interp, DT = rs.fixture_scheme(fx)
     con = constraint.BatchCartesianAccelerationConstraint(sc, linear=fx["linear"], angular=fx.get("angular"), discretization_scheme=DT)
     assert np.array_equal(con.F, fx["F"]) and np.array_equal(con.g, fx["g"])
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True, constraints=[con])
-    rows = inst.dense_rows()
+    rows = rs.fixture_solve(name, fx, con, interp)
     # The rows' allowance, composed as for the torque fixtures (tests/test_gpu_chain.py) through the rows' own assembly: w0 is an
     # exact zero on both sides and contributes nothing, so a = F wa may be off by |F| (bound_wa mag_wa), b = F wb alike, and
     # under Interpolation the second half a_{i+1} + 2 delta_i b_{i+1}, b_{i+1} by the same sums of its parts; c = F 0 - g = -g
@@ -160,12 +155,6 @@ def test_against_the_reference_s_fixtures(gpu, name):
         worst = float(np.max(np.abs(block - stored)[tol > 0] / tol[tol > 0]))
         print("%s rows %s: largest error / allowance %.3g" % (name, k, worst))
         assert not bad.any(), (name, k, worst)
-    assert np.array_equal(rows[3], fx["low"]) and np.array_equal(rows[4], fx["high"])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("%s sd: deviation %.3g, tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
 
 
 def test_beside_the_other_chain_constraints(gpu):
@@ -182,11 +171,7 @@ def test_beside_the_other_chain_constraints(gpu):
     accel = lambda: constraint.BatchCartesianAccelerationConstraint(sc, linear=2.0 * _peak(chain, args)[0])  # noqa: E731
     inst = algorithm.BatchTOPPRA(*args, constraints=[torque(), accel(), constraint.BatchCartesianVelocityNormConstraint(sc, 0.3)])
     out = rs.run_passes(inst)
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(out[k]["status"] == 0), k
-    for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
-        sets = out[k] if isinstance(out[k], (tuple, list)) else (out[k],)
-        assert all(not np.isnan(np.asarray(s)).any() for s in sets), k
+    rs.passes_ran(out)
     first, nt, na = 2 + 4 * d, 2 * d, 12  # (x_next pair and acceleration block; torque: Collocation; tool acceleration: Interpolation)
     assert out["rows"][0].shape[-1] == first + nt + na
     alone_t = algorithm.BatchTOPPRA(*args, constraints=[torque()]).dense_rows()

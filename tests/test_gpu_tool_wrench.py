@@ -157,32 +157,21 @@ def _fixture_payload(fx):
 def test_against_the_reference_s_fixtures(gpu, name):
     """w0 / wa / wb within the stored accuracy bound, return codes equal, sd within the stored end-to-end tolerance
     (tools/make_tool_wrench_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     fx = golden(name)
     chain, payload = rs.fixture_chain(fx), _fixture_payload(fx)
     sc, obj = chain_ref.serial_chain(chain), twr.payload_of(payload, chain)
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     ev = tw.evaluations(q, qs, qss)
     got = dict(zip(NAMES, sc.tool_wrench_terms(q, qs, qss, obj)))
-    for i, k in enumerate(NAMES):
-        err = cc.metric(got[k], fx[k], twr.tool_wrench(chain, payload, *ev[k], absolute=True))
-        print("%s %s: error %.3g, bound %.3g" % (name, k, err, fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    interp = bool(int(fx["scheme"]))
-    DT = constraint.DiscretizationType.Interpolation if interp else constraint.DiscretizationType.Collocation
+    rs.fixture_accuracy(name, fx, got, {k: twr.tool_wrench(chain, payload, *ev[k], absolute=True) for k in NAMES})
+    interp, DT = rs.fixture_scheme(fx)
     if "mu" in fx:
         con = constraint.BatchToolWrenchConstraint.surface_contact(sc, obj, float(fx["mu"]), tuple(fx["half_extents"]), discretization_scheme=DT)
         assert np.array_equal(con.F, fx["F"]) and np.array_equal(np.broadcast_to(con.g, fx["g"].shape), fx["g"])
     else:
         con = constraint.BatchToolWrenchConstraint(sc, obj, F=fx["F"], g=fx["g"], discretization_scheme=DT)
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=True, constraints=[con])
-    rows = inst.dense_rows()
-    assert np.array_equal(rows[3], fx["low"]) and np.array_equal(rows[4], fx["high"])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("%s sd: deviation %.3g, tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
+    rs.fixture_solve(name, fx, con, interp)
 
 
 def test_beside_the_other_chain_constraints(gpu):
@@ -204,12 +193,7 @@ def test_beside_the_other_chain_constraints(gpu):
     inst = algorithm.BatchTOPPRA(*args, constraints=cons)
     out = rs.run_passes(inst)
     assert out["rows"][0].shape[-1] == 2 + 4 * d + 2 * d + 12 + 24 <= 122
-    assert all(np.isfinite(out["rows"][k]).all() for k in range(3))
-    for k in ("compute_parameterization", "compute_parameterization_sd"):
-        assert np.all(out[k]["status"] == 0), k
-    for k in ("compute_feasible_sets", "compute_controllable_sets", "compute_reachable_sets"):
-        sets = out[k] if isinstance(out[k], (tuple, list)) else (out[k],)
-        assert all(not np.isnan(np.asarray(s)).any() for s in sets), k
+    rs.passes_ran(out)
     # the wrench block is the last one, with the rows of that constraint alone
     alone = algorithm.BatchTOPPRA(*args, constraints=[cons[2]]).dense_rows()
     for k in range(3):

@@ -180,24 +180,15 @@ def test_a_tree_in_the_torque_constraint_equals_its_callback(gpu, scheme, source
 def test_against_the_reference_s_fixtures(gpu, name):
     """w0 / wa / wb within the stored accuracy bound, return codes equal, sd within the stored end-to-end tolerance (both computed
     on the CPU by tools/make_tree_golden.py)."""
-    from toppra_amd import algorithm, constraint
+    from toppra_amd import constraint
     fx = golden(name)
-    tree = {k: fx[k] for k in ("parent", "joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity")}
+    tree = rs.fixture_tree(fx)
     kt = tree_ref.kinematic_tree(tree)
     q, qs, qss = sor.path_samples(fx["coef"], fx["breaks"], fx["grid"])
     mags = {k: tree_ref.rnea(tree, *args, absolute=True) for k, args in tc.evaluations(q, qs, qss).items()}
-    for i, (k, got) in enumerate(zip(("w0", "wa", "wb"), kt.torque_terms(q, qs, qss))):
-        err = tc.metric(got, fx[k], mags[k])
-        print("%s %s: error %.3g, bound %.3g" % (name, k, err, fx["acc_bound"][i]))
-        assert err <= fx["acc_bound"][i], (name, k, err, fx["acc_bound"][i])
-    DT = constraint.DiscretizationType.Interpolation if int(fx["torque_scheme"]) else constraint.DiscretizationType.Collocation
-    inst = algorithm.BatchTOPPRA(fx["coef"], fx["breaks"], fx["grid"], fx["vlim"], fx["alim"], interpolation=bool(int(fx["accel_scheme"])),
-                                 constraints=[constraint.BatchJointTorqueConstraint(kt, fx["taulim"], fx["fric"], discretization_scheme=DT)])
-    out = inst.compute_parameterization()
-    assert np.array_equal(out["status"], fx["status"]) and np.all(fx["status"] == 0)
-    dev = float(np.max(np.abs(out["sd"] - fx["sd"])))
-    print("%s sd: deviation %.3g, tolerance %.3g" % (name, dev, float(fx["sd_tol"])))
-    assert dev <= float(fx["sd_tol"]), (name, dev, float(fx["sd_tol"]))
+    rs.fixture_accuracy(name, fx, dict(zip(("w0", "wa", "wb"), kt.torque_terms(q, qs, qss))), mags)
+    con = constraint.BatchJointTorqueConstraint(kt, fx["taulim"], fx["fric"], discretization_scheme=rs.fixture_scheme(fx, "torque_scheme")[1])
+    rs.fixture_sd(name, fx, rs.fixture_instance(fx, con, interpolation=bool(int(fx["accel_scheme"]))))
 
 
 def _c_call(gpu, kt, parent, q, terms):

@@ -6,12 +6,12 @@ against the struct sizes."""
 import ctypes
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers, val
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator)
 AS_BUILT = {"joint_wrench_kernelE": 91, "joint_wrench_terms_kernelILb1E": 121, "joint_wrench_terms_kernelILb0E": 143}
@@ -19,10 +19,7 @@ AS_BUILT = {"joint_wrench_kernelE": 91, "joint_wrench_terms_kernelILb1E": 121, "
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return kr.kernels()
+    return built_kernels()
 
 
 def test_exactly_three_joint_kernels(kernels):
@@ -40,15 +37,12 @@ def test_exactly_three_joint_kernels(kernels):
 @pytest.mark.parametrize("key", sorted(AS_BUILT))
 def test_no_scratch_no_static_lds_and_registers_under_the_ceiling(kernels, key):
     (r,) = [r for n, r in kernels.items() if key in n]
-    assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (key, r)
-    assert r["lds"] == 0, (key, "static LDS bytes", r["lds"])  # (their LDS is dynamic, sized by the launch)
-    assert r["agpr"] == 0 and r["vgpr"] <= int(1.1 * AS_BUILT[key]), (key, "registers", r["vgpr"], AS_BUILT[key])
+    in_registers(r, AS_BUILT[key], key, parked_scalars=True)
 
 
 def test_the_launch_s_lds_fits_the_cu():
     """d * slots * 512 + forks * bank * 512 bytes, the tree kernels': the single state serves 32 dof with 4 forks within 160 KB
     (149 504 bytes: the sequential mode), the fused state a chain to 18 dof and one fork to 17; the outputs take no LDS."""
-    val = lambda name, src: sum(int(x) for x in re.search(name + r" = ([0-9+ ]+)[,;]", src).group(1).split("+"))  # noqa: E731
     tree = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_tree_args.hpp")).read()
     chain = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_chain_args.hpp")).read()
     args = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_joint_args.hpp")).read()

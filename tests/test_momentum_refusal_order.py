@@ -9,32 +9,10 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import base_wrench_cases as bw, base_wrench_ref as bwr, chain_ref
+from tests import base_wrench_cases as bw, base_wrench_ref as bwr
+from tests.rigid_support import BADARG, BUF as _BUF, UNSUPPORTED, c_model as _model, parent_table as _parent
 
-BADARG, UNSUPPORTED = -1, -3
 NAME = "tpr_tree_momentum_batch"
-
-_BUF = np.zeros(64)
-_KEEP = []
-
-
-def _model(d=3, joint_type=None, dof=None):
-    sc = chain_ref.serial_chain(chain_ref.random_chain(d, 5))
-    model, keep = sc.c_struct(_BUF)
-    _KEEP.append((sc, keep))
-    if joint_type is not None:
-        codes = np.array(joint_type, dtype=np.int32)
-        _KEEP.append(codes)
-        model.joint_type = codes.ctypes.data
-    if dof is not None:
-        model.d = dof
-    return sc, model
-
-
-def _parent(d=3, table=None):
-    table = np.array(np.arange(d) - 1 if table is None else table, dtype=np.int32)
-    _KEEP.append(table)
-    return table
 
 
 def _call(model, parent, mount=None, mask=0b111, B=1, N=1, q=True, qs=True, limit=True, outputs=(True, True, True)):

@@ -7,12 +7,12 @@ stages a block's inputs and outputs and keeps the forks' banks), at most the as-
 LDS arithmetic."""
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers, val
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 KEY = "momentum_kernel"
 AS_BUILT = 116  # registers (vector + accumulator), read from the library as built
@@ -20,14 +20,11 @@ AS_BUILT = 116  # registers (vector + accumulator), read from the library as bui
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return kr.kernels()
+    return built_kernels()
 
 
 def test_exactly_one_momentum_kernel(kernels):
-    import kernel_resources as kr
+    import kernel_resources as kr  # (tools/ is on the path: tests/resource_support.py)
     mine = [n for n in kernels if KEY in n]
     assert len(mine) == 1 and "MomentumArgs" in mine[0], mine
     plain = kr.demangle(mine)[mine[0]]  # (the name itself where no demangler is installed)
@@ -43,17 +40,13 @@ def test_exactly_one_momentum_kernel(kernels):
 
 def test_state_in_registers(kernels):
     (r,) = [r for n, r in kernels.items() if KEY in n]
-    assert r["scratch"] == 0, ("scratch bytes per lane", r["scratch"])
-    assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, r
-    assert r["lds"] == 0, ("static LDS bytes", r["lds"])  # (its LDS is dynamic, sized by the launch)
-    assert r["agpr"] == 0 and r["vgpr"] <= int(1.1 * AS_BUILT), ("registers", r["vgpr"], AS_BUILT)
+    in_registers(r, AS_BUILT, KEY)
 
 
 def test_the_launch_s_lds_fits_the_cu():
     """Staging -- 2 arrays x 64 rows x (d | 1) doubles, or the 64 output rows of 9 doubles where that is more -- plus forks x 18 x
     512 bytes: at most 33 792 + 4 * 18 * 512 = 70 656 bytes, under the 160 KB of a CU; above 64 KB the launcher asks for the
     attribute -- only the widest tree does."""
-    val = lambda name, src: sum(int(x) for x in re.search(name + r" = ([0-9+ ]+)[,;]", src).group(1).split("+"))  # noqa: E731
     csrc = os.path.join(ROOT, "toppra_amd", "csrc")
     args = open(os.path.join(csrc, "tpr_momentum_args.hpp")).read()
     tree = open(os.path.join(csrc, "tpr_tree_args.hpp")).read()

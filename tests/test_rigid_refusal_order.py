@@ -14,9 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import chain_ref
-
-BADARG, UNSUPPORTED = -1, -3
+from tests.rigid_support import BADARG, BUF as _BUF, UNSUPPORTED, c_model as _model, parent_table
 
 # name: (what follows the chain, the size arguments, inputs, outputs, the refusal of a null q, the refusal of null outputs)
 ENTRIES = {
@@ -39,23 +37,6 @@ PAYLOAD_ENTRIES = [n for n in NAMES if ENTRIES[n][0] == "payload"]
 TREE_ENTRIES = [n for n in NAMES if ENTRIES[n][0] == "parent"]
 BN_FIRST_ENTRIES = [n for n in NAMES if ENTRIES[n][1] == "BN" and ENTRIES[n][0] != "points"]
 
-_BUF = np.zeros(64)
-_KEEP = []
-
-
-def _model(d=3, joint_type=None, dof=None):
-    """A tpr_chain of host arrays: ``joint_type`` in place of its own codes, ``dof`` in place of its own d."""
-    sc = chain_ref.serial_chain(chain_ref.random_chain(d, 5))
-    model, keep = sc.c_struct(_BUF)
-    _KEEP.append((sc, keep))
-    if joint_type is not None:
-        codes = np.array(joint_type, dtype=np.int32)
-        _KEEP.append(codes)
-        model.joint_type = codes.ctypes.data
-    if dof is not None:
-        model.d = dof
-    return sc, model
-
 
 def _extra(kind, sc, parent=None):
     """A valid second argument of an entry of ``kind`` on the chain ``sc``."""
@@ -65,9 +46,7 @@ def _extra(kind, sc, parent=None):
     if kind == "points":
         return ControlPoints([0, sc.dof - 1], np.ones((2, 3))).c_struct(sc)
     if kind == "parent":
-        table = np.array(np.arange(sc.dof) - 1 if parent is None else parent, dtype=np.int32)
-        _KEEP.append(table)
-        return table
+        return parent_table(sc.dof, parent)
     return None
 
 

@@ -4,12 +4,12 @@ registers at any dof: no scratch, no static LDS (the dynamic LDS only stages a b
 global accesses), and at most the as-built register count plus 10 %, the convention of tests/test_chain_resources.py.  The
 staging area's size is checked against the 64 KB a kernel may take without asking."""
 import os
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator), static LDS bytes per block (the staging area is dynamic LDS, sized by the launch)
 AS_BUILT = {"chain_tool_accel_kernel": (98, 0), "chain_tool_accel_terms_kernel": (118, 0)}
@@ -17,10 +17,7 @@ AS_BUILT = {"chain_tool_accel_kernel": (98, 0), "chain_tool_accel_terms_kernel":
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return {n: r for n, r in kr.kernels().items() if "chain_" in n}
+    return built_kernels("chain_")
 
 
 @pytest.mark.parametrize("key", sorted(AS_BUILT))
@@ -28,10 +25,7 @@ def test_state_in_registers(kernels, key):
     regs, lds = AS_BUILT[key]
     rs = [r for n, r in kernels.items() if key in n]
     assert len(rs) == 1, (key, sorted(kernels))
-    assert rs[0]["scratch"] == 0, (key, "scratch bytes per lane", rs[0]["scratch"])
-    assert rs[0]["lds"] == lds, (key, "LDS bytes", rs[0]["lds"])
-    assert rs[0]["vgpr"] <= int(1.1 * regs), (key, "registers", rs[0]["vgpr"], regs)
-    assert rs[0]["vgpr_spill"] == 0 and rs[0]["sgpr_spill"] == 0, (key, rs[0])
+    in_registers(rs[0], regs, key, static_lds=lds)
 
 
 def test_the_staging_area_needs_no_permission():

@@ -8,12 +8,12 @@ vector register; the compiler parks 3 / 3 / 5 scalar registers in lanes of a vec
 runtime-dof kernels park 8), which costs no memory traffic."""
 import os
 import re
-import sys
 
 import pytest
 
+from tests.resource_support import built_kernels, in_registers, val
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # as built: registers (vector + accumulator)
 TREE = {"tree_inverse_dynamics_kernel": 95, "tree_torque_terms_kernelILb1E": 129, "tree_torque_terms_kernelILb0E": 143}
@@ -21,10 +21,7 @@ TREE = {"tree_inverse_dynamics_kernel": 95, "tree_torque_terms_kernelILb1E": 129
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_resources as kr
-    from toppra_amd import build
-    build.build()
-    return kr.kernels()
+    return built_kernels()
 
 
 def test_exactly_three_tree_kernels(kernels):
@@ -39,15 +36,12 @@ def test_exactly_three_tree_kernels(kernels):
 def test_no_scratch_no_static_lds_and_registers_under_the_ceiling(kernels):
     for key, regs in TREE.items():
         (r,) = [r for n, r in kernels.items() if key in n]
-        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (key, r)
-        assert r["lds"] == 0, (key, r)  # (their LDS is dynamic: at most 160 KB, checked at launch)
-        assert r["agpr"] == 0 and r["vgpr"] <= int(1.1 * regs), (key, r["vgpr"], regs)
+        in_registers(r, regs, key, parked_scalars=True)  # (their LDS is dynamic: at most 160 KB, checked at launch)
 
 
 def _constants():
     text = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_tree_args.hpp")).read()
     chain = open(os.path.join(ROOT, "toppra_amd", "csrc", "tpr_chain_args.hpp")).read()
-    val = lambda name, src: sum(int(x) for x in re.search(name + r" = ([0-9+ ]+)[,;]", src).group(1).split("+"))  # noqa: E731
     return {"slots": (val("kChainSlotsSingle", chain), val("kChainSlotsFused", chain)), "bank": (val("kTreeBankSingle", text), val("kTreeBankFused", text)),
             "forks": val("kTreeMaxForks", text), "lds": eval(re.search(r"kChainLdsBytes = ([0-9* ]+);", chain).group(1))}
 

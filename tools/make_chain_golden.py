@@ -1,130 +1,36 @@
 #!/usr/bin/env python
-"""Generate the chain fixtures tests/golden/chain_torque_*.npz by running the REAL reference (hungpham2511/toppra):
-its JointTorqueConstraint and TOPPRA(solver_wrapper="seidel") with inv_dyn taken from tests/chain_ref.py (the numpy
-recursion, one gridpoint per call as the reference calls it), and profiles/chain_dynamics_accuracy.json.
+"""Generate the chain fixtures tests/golden/chain_torque_*.npz by running the REAL reference (hungpham2511/toppra): its
+JointTorqueConstraint and TOPPRA(solver_wrapper="seidel") with inv_dyn taken from tests/chain_ref.py (the numpy recursion), and
+profiles/chain_dynamics_accuracy.json.  The recipe, and how the two tolerances are made, is tools/rigid_golden.py's.
 
     python tools/make_chain_golden.py        # needs the reference; builds oracle/_ref on demand
 
-Each fixture holds data only: the chain's parameters, the paths' waypoints and coefficient tables, grid and limits; the reference's w0, wa,
-wb, the dense rows of its torque constraint (the columns after the acceleration block), sd, u, K and return codes; and the
-two tolerances of the GPU tests --
-  acc_yardstick / acc_bound [3]: the error of the float64 chain_ref against np.longdouble on the fixture's own w0, wa, wb, in
-      the metric of tests/chain_cases.py, and 16 x that;
-  sd_tol: 4 x the largest change of sd over 20 seeds when w0, wa, wb are disturbed by noise of the size of the accuracy
-      bound (each of the three uniform in +- its acc_bound x its magnitude) and the problem is solved by the CPU restatement under oracle/.
-      The disturbance is what the accuracy bound ALLOWS, not what the kernel shows: the bound is relative to the all-absolute
-      magnitude, which stands orders above the values for a 6-dof chain (tests/chain_cases.py), so noise of its size is
-      about 1e-12 relative to w0 and moves sd of about 0.4 by up to 5e-9 near the switching points: sd_tol = 2e-8 for the
-      6-dof fixture, 5e-14 for the 3-dof one.  It is the issue's procedure followed to the letter and errs on the loose side.
-Every trajectory must be feasible in the reference: asserted here.
+Stored beside the recipe's arrays: the chain, taulim ([d, 2] shared, or [B, d, 2]), fric, w0, wa, wb, torque_scheme.
+  chain_torque_d6_N40: 6 dof, Collocation, one set of torque limits.
+  chain_torque_d3_N30_interp: 3 dof, Interpolation, limits per trajectory.
+The accuracy bound is relative to the all-absolute magnitude, which stands orders above the values for a 6-dof chain
+(tests/chain_cases.py), so noise of its size is about 1e-12 relative to w0 and moves sd of about 0.4 by up to 5e-9 near the
+switching points: sd_tol = 2e-8 for the 6-dof fixture, 5e-14 for the 3-dof one.
 """
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "tests", "golden")
-
-from oracle import oracle as orc, ref_loader  # noqa: E402
-from tests import chain_cases, chain_ref, second_order_ref as sor  # noqa: E402
-
-ta = ref_loader.load()
-if ta is None:
-    raise SystemExit("reference not available")
-import toppra.algorithm as algo  # noqa: E402
-import toppra.constraint as constraint  # noqa: E402
-from toppra.algorithm.algorithm import ParameterizationReturnCode as RC  # noqa: E402
-
-STATUS = {RC.Ok: 0, RC.FailUncontrollable: 1, RC.ErrUnknown: 2}
-CHAIN_KEYS = ("joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity", "tool")
+import rigid_golden as rg
+from tests import chain_cases, chain_ref
 
 
 def fixture(name, B, d, N, seed, torque_scheme, per_traj_limits):
     rng = np.random.default_rng(seed)
     chain = chain_ref.random_chain(d, seed=seed + 1, gravity=True, prismatic_every=4)
     inv_dyn = lambda q, qd, qdd: chain_ref.rnea(chain, q, qd, qdd)  # noqa: E731
-    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
-    way = rng.uniform(-1.5, 1.5, (B, 5, d))
-    vmax, amax = 2.0 + 2.0 * rng.random((B, d)), 6.0 + 4.0 * rng.random((B, d))
-    vlim, alim = np.stack([-vmax, vmax], -1), np.stack([-amax, amax], -1)
-    fric = 0.05 * rng.random(d)
-    paths = [ta.SplineInterpolator(knots, way[b]) for b in range(B)]
-    q, qs, qss = (np.stack([p(grid, k) for p in paths]) for k in (0, 1, 2))
-    zero = np.zeros(d)
-    w0 = np.array([[inv_dyn(q_, zero, zero) for q_ in q[b]] for b in range(B)])
-    wa = np.array([[inv_dyn(q_, zero, s_) for q_, s_ in zip(q[b], qs[b])] for b in range(B)])
-    wb = np.array([[inv_dyn(q_, s_, ss_) for q_, s_, ss_ in zip(q[b], qs[b], qss[b])] for b in range(B)])
-    # limits that leave every trajectory feasible: the torque of standing still anywhere on the paths, and headroom to move
-    hold = np.abs(w0).max(axis=(0, 1))
-    taumax = 1.2 * hold + 1.0 + rng.random((B, d) if per_traj_limits else d)
-    taulim = np.stack([-taumax, taumax], -1)  # [d, 2] shared or [B, d, 2]
+    p = rg.draw_paths(rng, B, d, N)
+    constraint = rg.reference().constraint
     DT = constraint.DiscretizationType(torque_scheme)
-    out = {k: [] for k in ("rows_a", "rows_b", "rows_c", "low", "high", "K", "sd", "u", "status")}
-    from toppra_amd.solverwrapper import dense_rows
-    for b in range(B):
-        lim = taulim[b] if per_traj_limits else taulim
-        cons = [constraint.JointVelocityConstraint(vlim[b]),
-                constraint.JointAccelerationConstraint(alim[b], discretization_scheme=constraint.DiscretizationType.Interpolation),
-                constraint.JointTorqueConstraint(inv_dyn, lim, fric, discretization_scheme=DT)]
-        inst = algo.TOPPRA(cons, paths[b], gridpoints=grid, solver_wrapper="seidel")
-        sdd, sd, _, K = inst.compute_parameterization(0, 0, return_data=True)
-        st = STATUS[inst.problem_data.return_code]
-        assert st == 0 and sd is not None, "%s: trajectory %d is not feasible in the reference (status %d)" % (name, b, st)
-        rows = dense_rows(cons, paths[b], grid)
-        first = 2 + 4 * d  # (the x_next pair, the acceleration block under Interpolation)
-        for k in "abc":
-            out["rows_" + k].append(rows[k][:, first:])
-        out["low"].append(rows["low"]); out["high"].append(rows["high"])
-        out["K"].append(K); out["sd"].append(sd); out["u"].append(sdd); out["status"].append(st)
-        # the constraint's own parameters are chain_ref's values through the reference's expressions
-        a, bb, c = cons[2].compute_constraint_params(paths[b], grid)[:3]
-        if torque_scheme == 0:
-            assert np.array_equal(a, wa[b] - w0[b]) and np.array_equal(bb, wb[b] - w0[b])
-    rec = {k: np.stack(v) for k, v in out.items()}
-    rec["status"] = rec["status"].astype(np.int32)
-    coef = np.stack([np.asarray(p.cspl.c) for p in paths])
-    breaks = np.asarray(paths[0].cspl.x)
-
-    # the accuracy yardstick on the fixture's own inputs
-    ref = chain_cases.reference_of(chain, q, qs, qss)
-    assert all(np.array_equal(ref[k], v) for k, v in (("w0", w0), ("wa", wa), ("wb", wb))), "batched chain_ref differs from per-point calls"
-    yard = np.array([ref["yardstick"][k] for k in ("w0", "wa", "wb")])
-    bound = chain_cases.BOUND_FACTOR * yard
-
-    # the end-to-end tolerance of sd: the CPU restatement on rows from disturbed w0, wa, wb
-    block = {"F": None, "g": np.concatenate((taulim[..., 1], -taulim[..., 0]), -1), "friction": fric,
-             "interpolation": bool(torque_scheme)}
-
-    def solve(v0, va, vb):
-        rows = sor.dense_problem(coef, breaks, grid, vlim, alim, True, [dict(block, w0=v0, wa=va, wb=vb)])
-        return orc.solve_dense_batch(*(rows[k] for k in ("a", "b", "c", "low", "high", "deltas")))
-    base = solve(w0, wa, wb)
-    assert np.array_equal(base["status"], rec["status"]) and np.array_equal(base["sd"], rec["sd"]), "the restatement differs from the reference"
-    worst = 0.0
-    for s in range(20):
-        nrng = np.random.default_rng(1000 + s)
-        noisy = [v + bd * ref[k + "_mag"] * nrng.uniform(-1.0, 1.0, v.shape) for bd, (k, v) in zip(bound, (("w0", w0), ("wa", wa), ("wb", wb)))]
-        got = solve(*noisy)
-        assert np.array_equal(got["status"], rec["status"])
-        worst = max(worst, float(np.max(np.abs(got["sd"] - base["sd"]))))
-    rec.update({k: np.asarray(chain[k]) for k in CHAIN_KEYS})
-    rec.update(knots=knots, way=way, coef=coef, breaks=breaks, grid=grid, vlim=vlim, alim=alim, taulim=taulim, fric=fric, w0=w0, wa=wa, wb=wb,
-               torque_scheme=np.array(torque_scheme), acc_yardstick=yard, acc_bound=bound, sd_tol=np.array(4.0 * worst))
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
-    print(name, "torque rows", rec["rows_a"].shape, "status", np.bincount(rec["status"], minlength=3), "acc_bound", bound,
-          "sd_tol %.3g" % (4.0 * worst), "%.0f KB" % (os.path.getsize(os.path.join(OUT, name + ".npz")) / 1024))
-    return {"yardstick": dict(zip(("w0", "wa", "wb"), yard.tolist())), "bound": dict(zip(("w0", "wa", "wb"), bound.tolist())),
-            "sd_tol": 4.0 * worst}
+    return rg.torque_fixture(name, rng, p, chain, rg.CHAIN_KEYS, inv_dyn, chain_cases.reference_of(chain, p.q, p.qs, p.qss),
+                             lambda lim, fric: constraint.JointTorqueConstraint(inv_dyn, lim, fric, discretization_scheme=DT),
+                             torque_scheme, 1, per_traj_limits)
 
 
 if __name__ == "__main__":
     fixtures = {"chain_torque_d6_N40": fixture("chain_torque_d6_N40", 4, 6, 40, 311, 0, False),
                 "chain_torque_d3_N30_interp": fixture("chain_torque_d3_N30_interp", 4, 3, 30, 312, 1, True)}
-    with open(os.path.join(ROOT, "profiles", "chain_dynamics_accuracy.json"), "w") as fh:
-        json.dump({"metric": "|got - ref| / (|ref| with every product and sum in absolute value); yardstick = float64 chain_ref "
-                             "against np.longdouble on the same inputs; bound = %g x yardstick" % chain_cases.BOUND_FACTOR,
-                   "cases": chain_cases.accuracy_table(), "fixtures": fixtures}, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    rg.write_profile("chain_dynamics", "float64 chain_ref", chain_cases.accuracy_table(), fixtures)

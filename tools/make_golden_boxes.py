@@ -34,6 +34,7 @@ OUT = os.path.join(ROOT, "tests", "golden")
 
 from oracle import ref_loader  # noqa: E402
 from tests import stage_boxes_ref as sbr  # noqa: E402
+from tools.rigid_golden import reference_boxes  # noqa: E402  (it lives there, where importing it runs nothing)
 
 ta = ref_loader.load()
 if ta is None:
@@ -42,20 +43,9 @@ import toppra.algorithm as algo  # noqa: E402
 import toppra.constraint as constraint  # noqa: E402
 import toppra.parametrizer as tparam  # noqa: E402
 from toppra.algorithm.algorithm import ParameterizationReturnCode as RC  # noqa: E402
-from toppra.solverwrapper.cy_seidel_solverwrapper import seidelWrapper  # noqa: E402
 
 STATUS = {RC.Ok: 0, RC.FailUncontrollable: 1, RC.ErrUnknown: 2}
 B = 4
-
-
-def reference_boxes(cons, path, grid):
-    """low_arr, high_arr [N+1, 2] of the reference's wrapper on the first-order constraints of ``cons``."""
-    first = [c for c in cons if c.compute_constraint_params(path, grid)[0] is None]
-    w = seidelWrapper(first, path, grid)
-    nan = float("nan")
-    low = np.array([w.solve_stagewise_optim(i, None, np.array([1.0, 1.0]), nan, nan, nan, nan) for i in range(len(grid))])
-    high = np.array([w.solve_stagewise_optim(i, None, np.array([-1.0, -1.0]), nan, nan, nan, nan) for i in range(len(grid))])
-    return low, high
 
 
 def solve(cons, path, grid, s0, s1, cls=algo.TOPPRA, desired=None):

@@ -1,62 +1,23 @@
 #!/usr/bin/env python
 """Generate the tool-wrench fixtures tests/golden/tool_wrench_*.npz by running the REAL reference (hungpham2511/toppra): its
-SecondOrderConstraint with inv_dyn = the numpy wrench of tests/tool_wrench_ref.py (one gridpoint per call, as the reference
-calls it) in [JointVelocityConstraint, JointAccelerationConstraint, that] through TOPPRA(solver_wrapper="seidel"), one trajectory
-at a time; and profiles/tool_wrench_accuracy.json.
+SecondOrderConstraint with inv_dyn = the numpy wrench of tests/tool_wrench_ref.py; and profiles/tool_wrench_accuracy.json.  The
+recipe, and how the two tolerances are made, is tools/rigid_golden.py's.
 
     python tools/make_tool_wrench_golden.py        # needs the reference; builds oracle/_ref on demand
 
-It follows tools/make_tool_accel_golden.py: B = 4; data only -- the chain's and the payload's parameters, waypoints, coefficient
-tables, grid and limits; the reference's w0, wa, wb, the dense rows of its constraint (the columns after the acceleration block),
-low, high, sd, u, K and return codes; and the two tolerances of the GPU tests --
-  acc_yardstick / acc_bound [3]: the error of the float64 reference against np.longdouble on the fixture's own w0, wa, wb, in the
-      metric of tests/chain_cases.py, and 16 x that;
-  sd_tol: 4 x the largest change of sd over 20 seeds when w0, wa, wb are disturbed by noise of the size of the accuracy bound
-      (each uniform in +- its acc_bound x its magnitude) and the problem is solved by the CPU restatement under oracle/.
-Two fixtures:
-  tool_wrench_d6_N40: a random chain, a dense F (five rows that mix force and moment), Interpolation.  g is chosen here, on the
-      CPU, per trajectory: the largest static value F w0 along the path plus half of the largest dynamic part F (w - w0) along
-      the reference's own solution WITHOUT the constraint -- standing still satisfies it with room, and it is active.
+Stored beside the recipe's arrays: the chain, the payload (payload_*), F, g, w0, wa, wb, scheme (and mu, half_extents).
+  tool_wrench_d6_N40: a random chain, a dense F (five rows that mix force and moment), Interpolation.  g is chosen per
+      trajectory: the largest static value F w0 along the path plus half of the largest dynamic part F (w - w0) along the
+      reference's own solution WITHOUT the constraint -- standing still satisfies it with room, and it is active.
   tool_wrench_d4_N30_colloc: a SCARA-like arm (vertical revolute axes, a vertical prismatic joint: the tray stays level) that
       carries a box on a tray, BatchToolWrenchConstraint.surface_contact's 16 rows, Collocation.
-Feasibility of every trajectory and that the constraint is active (the reference's sd differs from its sd without it) are asserted.
 """
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "tests", "golden")
+import rigid_golden as rg
+from tests import chain_ref, tool_wrench_cases, tool_wrench_ref
 
-from oracle import oracle as orc, ref_loader  # noqa: E402
-from tests import chain_cases, chain_ref, second_order_ref as sor, tool_wrench_cases, tool_wrench_ref  # noqa: E402
-
-ta = ref_loader.load()
-if ta is None:
-    raise SystemExit("reference not available")
-import toppra.algorithm as algo  # noqa: E402
-import toppra.constraint as constraint  # noqa: E402
-from toppra.algorithm.algorithm import ParameterizationReturnCode as RC  # noqa: E402
-
-STATUS = {RC.Ok: 0, RC.FailUncontrollable: 1, RC.ErrUnknown: 2}
-CHAIN_KEYS = ("joint_type", "axis", "rot", "trans", "mass", "com", "inertia", "gravity", "tool")
 PAYLOAD_KEYS = ("mass", "com", "inertia", "rot", "origin")
-NAMES = ("w0", "wa", "wb")
-
-
-def scara():
-    """Two vertical revolute joints, a vertical prismatic joint, a vertical wrist: the last link keeps its z axis up."""
-    d = 4
-    eye = np.tile(np.eye(3), (d, 1, 1))
-    return {"joint_type": np.array([0, 0, 1, 0], dtype=np.int32), "axis": np.tile([0.0, 0.0, 1.0], (d, 1)), "rot": eye,
-            "trans": np.array([[0.0, 0.0, 0.4], [0.35, 0.0, 0.0], [0.3, 0.0, 0.0], [0.0, 0.0, -0.1]]),
-            "mass": np.array([6.0, 4.0, 1.5, 0.5]), "com": np.array([[0.17, 0.0, 0.0], [0.15, 0.0, 0.0], [0.0, 0.0, -0.1], [0.0, 0.0, 0.0]]),
-            "inertia": np.array([[0.02, 0.08, 0.08, 0, 0, 0], [0.01, 0.04, 0.04, 0, 0, 0], [0.005, 0.005, 0.001, 0, 0, 0],
-                                 [0.0005, 0.0005, 0.0005, 0, 0, 0]], dtype=np.float64),
-            "gravity": np.array([0.0, 0.0, -9.81]), "tool": np.array([0.05, 0.0, 0.02])}
 
 
 def box_on_tray(tool):
@@ -70,121 +31,31 @@ def box_on_tray(tool):
 def fixture(name, B, d, N, seed, scheme, contact):
     rng = np.random.default_rng(seed)
     if contact:
-        chain = scara()
+        chain = rg.scara()
         payload = box_on_tray(chain["tool"])
     else:
         chain = chain_ref.random_chain(d, seed=seed + 1, gravity=True, prismatic_every=4)
         payload = dict(tool_wrench_cases.PAYLOAD)
     inv_dyn = lambda q, qd, qdd: tool_wrench_ref.tool_wrench(chain, payload, q, qd, qdd)  # noqa: E731
-    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
-    way = rng.uniform(-1.5, 1.5, (B, 5, d))
+    p = rg.draw_paths(rng, B, d, N, rg.SCARA_WAY if contact else 1.0)
+    terms = rg.gridpoint_terms(inv_dyn, p)
+    free = rg.free_solutions(p)
     if contact:
-        way[..., 2] *= 0.1  # (the lift: +- 15 cm)
-    vmax, amax = 2.0 + 2.0 * rng.random((B, d)), 6.0 + 4.0 * rng.random((B, d))
-    vlim, alim = np.stack([-vmax, vmax], -1), np.stack([-amax, amax], -1)
-    paths = [ta.SplineInterpolator(knots, way[b]) for b in range(B)]
-    q, qs, qss = (np.stack([p(grid, k) for p in paths]) for k in (0, 1, 2))
-    zero = np.zeros(d)
-    w0 = np.array([[inv_dyn(q_, zero, zero) for q_ in q[b]] for b in range(B)])
-    wa = np.array([[inv_dyn(q_, zero, s_) for q_, s_ in zip(q[b], qs[b])] for b in range(B)])
-    wb = np.array([[inv_dyn(q_, s_, ss_) for q_, s_, ss_ in zip(q[b], qs[b], qss[b])] for b in range(B)])
-    DT = constraint.DiscretizationType(scheme)
-    acc_dt = constraint.DiscretizationType.Interpolation
-
-    def base_constraints(b):
-        return [constraint.JointVelocityConstraint(vlim[b]), constraint.JointAccelerationConstraint(alim[b], discretization_scheme=acc_dt)]
-
-    # the reference without the constraint, and the dynamic part of the wrench along its solution
-    free_sd, along = [], []
-    for b in range(B):
-        inst = algo.TOPPRA(base_constraints(b), paths[b], gridpoints=grid, solver_wrapper="seidel")
-        sdd, sd, _ = inst.compute_parameterization(0, 0)
-        assert sd is not None
-        free_sd.append(sd)
-        along.append((wa[b, :-1] - w0[b, :-1]) * sdd[:, None] + (wb[b, :-1] - w0[b, :-1]) * (sd[:-1] ** 2)[:, None])
-    extra = {}
-    if contact:
-        from toppra_amd.constraint import BatchToolWrenchConstraint
-        mu, half = 0.1, (0.05, 0.03)
-        F, g1 = BatchToolWrenchConstraint.surface_contact_rows(mu, half)
-        g = np.broadcast_to(g1, (B, F.shape[0])).copy()
-        extra = {"mu": np.array(mu), "half_extents": np.array(half)}
+        F, g, extra = rg.surface_contact(B, 0.1, (0.05, 0.03))
     else:
-        F = rng.uniform(-1.0, 1.0, (5, 6))
-        static = np.einsum("mk,bnk->bnm", F, w0).max(1)  # [B, m]
-        dynamic = np.stack([np.abs(np.einsum("mk,nk->nm", F, along[b])).max(0) for b in range(B)])
+        F, extra = rng.uniform(-1.0, 1.0, (5, 6)), {}
+        static = np.einsum("mk,bnk->bnm", F, terms["w0"]).max(1)  # [B, m]
+        dynamic = np.stack([np.abs(np.einsum("mk,nk->nm", F, rg.along(terms, free, b))).max(0) for b in range(B)])
         g = static + 0.5 * dynamic
-    assert np.all(np.einsum("mk,bnk->bnm", F, w0) < g[:, None, :]), "%s: standing still violates the limits" % name
-
-    out = {k: [] for k in ("rows_a", "rows_b", "rows_c", "low", "high", "K", "sd", "u", "status")}
-    from toppra_amd.solverwrapper import dense_rows
-    for b in range(B):
-        cons = base_constraints(b) + [constraint.SecondOrderConstraint(inv_dyn, lambda q_: F, lambda q_, b=b: g[b], dof=d,
-                                                                       discretization_scheme=DT)]
-        inst = algo.TOPPRA(cons, paths[b], gridpoints=grid, solver_wrapper="seidel")
-        sdd, sd, _, K = inst.compute_parameterization(0, 0, return_data=True)
-        st = STATUS[inst.problem_data.return_code]
-        assert st == 0 and sd is not None, "%s: trajectory %d is not feasible in the reference (status %d)" % (name, b, st)
-        assert not np.array_equal(sd, free_sd[b]), "%s: the constraint is not active in trajectory %d" % (name, b)
-        print("%s trajectory %d: largest sd %.4f, without the constraint %.4f" % (name, b, sd.max(), free_sd[b].max()))
-        rows = dense_rows(cons, paths[b], grid)
-        first = 2 + 4 * d  # (the x_next pair, the acceleration block under Interpolation)
-        for k in "abc":
-            out["rows_" + k].append(rows[k][:, first:])
-        out["low"].append(rows["low"]); out["high"].append(rows["high"])
-        out["K"].append(K); out["sd"].append(sd); out["u"].append(sdd); out["status"].append(st)
-    rec = {k: np.stack(v) for k, v in out.items()}
-    rec["status"] = rec["status"].astype(np.int32)
-    coef = np.stack([np.asarray(p.cspl.c) for p in paths])
-    breaks = np.asarray(paths[0].cspl.x)
-
-    # the accuracy yardstick on the fixture's own inputs
-    ref = tool_wrench_cases.reference_of(chain, payload, q, qs, qss)
-    assert all(np.array_equal(ref[k], v) for k, v in zip(NAMES, (w0, wa, wb))), "batched reference differs from per-point calls"
-    yard = np.array([ref["yardstick"][k] for k in NAMES])
-    bound = chain_cases.BOUND_FACTOR * yard
-
-    # the end-to-end tolerance of sd: the CPU restatement on rows from disturbed w0, wa, wb
-    block = {"F": F, "g": g, "friction": None, "interpolation": bool(scheme)}
-
-    def solve(v0, va, vb):
-        rows = sor.dense_problem(coef, breaks, grid, vlim, alim, True, [dict(block, w0=v0, wa=va, wb=vb)])
-        return orc.solve_dense_batch(*(rows[k] for k in ("a", "b", "c", "low", "high", "deltas")))
-    base = solve(w0, wa, wb)
-    # (F is dense here: the reference forms F a, F b, F c with numpy's dot, whose summation order is the BLAS's, the restatement and
-    # the kernels sum a row in index order -- the rows agree to rounding, not in bits, and so does sd; the gap must vanish in sd_tol)
-    gap = float(np.max(np.abs(base["sd"] - rec["sd"])))
-    assert np.array_equal(base["status"], rec["status"]), "the restatement's return codes differ from the reference's"
-    worst = 0.0
-    for s in range(20):
-        nrng = np.random.default_rng(1000 + s)
-        noisy = [v + bd * ref[k + "_mag"] * nrng.uniform(-1.0, 1.0, v.shape) for bd, k, v in zip(bound, NAMES, (w0, wa, wb))]
-        got = solve(*noisy)
-        assert np.array_equal(got["status"], rec["status"])
-        worst = max(worst, float(np.max(np.abs(got["sd"] - base["sd"]))))
-    print("%s: restatement vs reference sd %.3g, sd_tol %.3g" % (name, gap, 4.0 * worst))
-    assert gap <= worst, "%s: the restatement differs from the reference by more than the disturbance moves it" % name
-    rec.update({k: np.asarray(chain[k]) for k in CHAIN_KEYS})
-    rec.update({"payload_" + k: np.asarray(payload[k], dtype=np.float64) for k in PAYLOAD_KEYS})
-    rec.update(knots=knots, way=way, coef=coef, breaks=breaks, grid=grid, vlim=vlim, alim=alim, F=F, g=g, w0=w0, wa=wa, wb=wb,
-               scheme=np.array(scheme), acc_yardstick=yard, acc_bound=bound, sd_tol=np.array(4.0 * worst), **extra)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
-    print(name, "rows", rec["rows_a"].shape, "status", np.bincount(rec["status"], minlength=3), "acc_bound", bound,
-          "sd_tol %.3g" % (4.0 * worst), "%.0f KB" % (os.path.getsize(os.path.join(OUT, name + ".npz")) / 1024))
-    return {"yardstick": dict(zip(NAMES, yard.tolist())), "bound": dict(zip(NAMES, bound.tolist())), "sd_tol": 4.0 * worst}
+    constraint = rg.reference().constraint
+    DT = constraint.DiscretizationType(scheme)
+    return rg.second_order_fixture(
+        name, p, free, lambda b: constraint.SecondOrderConstraint(inv_dyn, lambda q_: F, lambda q_: g[b], dof=d, discretization_scheme=DT),
+        F, g, scheme, terms, ("w0", "wa", "wb"), tool_wrench_cases.reference_of(chain, payload, p.q, p.qs, p.qss), False, chain,
+        rg.CHAIN_KEYS, {"payload_" + k: np.asarray(payload[k], dtype=np.float64) for k in PAYLOAD_KEYS}, extra=extra)
 
 
 if __name__ == "__main__":
     fixtures = {"tool_wrench_d6_N40": fixture("tool_wrench_d6_N40", 4, 6, 40, 511, 1, False),
                 "tool_wrench_d4_N30_colloc": fixture("tool_wrench_d4_N30_colloc", 4, 4, 30, 512, 0, True)}
-    path = os.path.join(ROOT, "profiles", "tool_wrench_accuracy.json")
-    measured = {}
-    if os.path.exists(path):  # (what the kernels were measured to use is written by the GPU run, not here: keep it)
-        with open(path) as fh:
-            measured = json.load(fh).get("measured", {})
-    with open(path, "w") as fh:
-        json.dump({"metric": "|got - ref| / (|ref| with every product and sum in absolute value); yardstick = float64 "
-                             "tests/tool_wrench_ref.py against np.longdouble on the same inputs; bound = %g x yardstick"
-                             % chain_cases.BOUND_FACTOR,
-                   "cases": tool_wrench_cases.accuracy_table(), "fixtures": fixtures, "measured": measured}, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    rg.write_profile("tool_wrench", "float64 tests/tool_wrench_ref.py", tool_wrench_cases.accuracy_table(), fixtures)
