@@ -98,8 +98,7 @@ def _raw(model, q, qs, mount, mask, limit, want):
     """The C entry on host arrays with any subset of its outputs: (momentum, energy2, xbound), None where not asked for."""
     from toppra_amd import _capi, batch
     lib = _capi.load()
-    tree = model if hasattr(model, "parents") else batch._AsTree(model)
-    links, parent, keep = tree.c_struct(q)
+    links, parent, keep = model.as_tree(q)
     B, n1, d = q.shape
     q, qs = np.ascontiguousarray(q), np.ascontiguousarray(qs)
     outs = [np.full(shape, np.nan) if given else None for given, shape in zip(want, ((B, n1, 6), (B, n1), (B, n1, 2)))]

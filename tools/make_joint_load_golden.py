@@ -39,7 +39,7 @@ def scara_with_a_linear_guide():
 
 
 def fixture(name, B, N, seed, scheme, bearing):
-    from toppra_amd.constraint import BatchJointLoadConstraint, _section_limits
+    from toppra_amd.constraint import BatchJointLoadConstraint, _box_limits
     rng = np.random.default_rng(seed)
     robot, sec = torso_with_shoulder_bearings() if bearing else scara_with_a_linear_guide()
     d, S = len(robot["parent"]), len(sec["link"])
@@ -67,7 +67,7 @@ def fixture(name, B, N, seed, scheme, bearing):
         dynamic = np.stack([np.abs(m - static[b, :-1]).max(0) for b, m in enumerate(moving)])
         hi = rest + 0.5 * dynamic
         force, moment = np.stack([-hi[..., :3], hi[..., :3]], -1), np.stack([-hi[..., 3:], hi[..., 3:]], -1)  # [B, S, 3, 2]
-        F, g, _ = _section_limits(S, force, moment, None, None)
+        F, g, _ = _box_limits(S, 6, (("force", force, 0), ("moment", moment, 3)), "S", None, None)
         extra = {"force": force, "moment": moment}
     constraint = rg.reference().constraint
     DT = constraint.DiscretizationType(scheme)

@@ -657,7 +657,8 @@ def _rigid_call(model, entry, arrays, names, tails, structs=(), by_grid=False, l
         size, more, tails = limits(q, shape, npoints)
         arrays = arrays + list(more)
     _prepare(q)
-    links = model.c_struct(q)  # (tpr_chain, what it points to) of a chain; a tree's host parent array between the two
+    # (tpr_chain, what it points to) for a chain entry; a tree-walking one takes the host parent array between the two
+    links = model.as_tree(q) if entry.startswith("tpr_tree_") else model.c_struct(q)
     head = [C.byref(links[0])] + [parent.ctypes.data for parent in links[1:-1]] + [C.byref(s) for s in structs]
     outs = [None if tail is None else _empty(q, shape[:-1] + tuple(tail)) for tail in tails]
     _capi.check(getattr(_capi.load(), entry)(*head, *size, *[_capi.ptr(a) for a in arrays + outs],
@@ -675,6 +676,38 @@ def _bound_limits(limit, shape, convert):
     if isinstance(limit, np.ndarray) and not np.all(limit > 0):  # (device limits are not read back: the caller's, as NaN limits are)
         raise ValueError("limit must be > 0 (0 / 0 at a standstill would be a NaN bound, which the box fold drops silently)")
     return B, N, limit
+
+
+def _per_traj_limit(name, limit, q, B, tails, words):
+    """The limit ``limit`` of a bound function as the contiguous fp64 array [B, *tails[-1]] its entry reads, of the kind of q.
+    ``tails``: the shapes accepted for the whole batch, the last of them also after a leading B; ``words``: those shapes, for the
+    refusal.  A limit on q's device stays there and is never read back; a host limit goes where q is."""
+    dev, full = _capi.is_torch_cuda(q), (B,) + tuple(tails[-1])
+    if dev:
+        import torch
+        if not (hasattr(limit, "is_cuda") and limit.is_cuda):
+            limit = torch.as_tensor(np.asarray(limit, dtype=np.float64), device=q.device)
+        _capi.check_tensor(name, limit, q)
+    else:
+        limit = np.asarray(limit, dtype=np.float64)
+    if tuple(limit.shape) not in tuple(tails) + (full,):
+        raise ValueError("%s must %s, got %s" % (name, words, tuple(limit.shape)))
+    return limit.expand(*full).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(limit, full))
+
+
+def _need(value, name, *kinds):
+    """``value``, which must be one of the classes ``kinds`` of :mod:`toppra_amd.chain` (named: that module imports this one, so
+    they are looked up here): ValueError for anything else."""
+    from . import chain
+    if not isinstance(value, tuple(getattr(chain, kind) for kind in kinds)):
+        raise ValueError("%s must be a toppra_amd.chain.%s, got %s" % (name, " or ".join(kinds), type(value).__name__))
+    return value
+
+
+def _mount(mount):
+    """``mount`` as a :class:`toppra_amd.chain.Mount`: None = the base frame without a platform; ValueError for anything else."""
+    from .chain import Mount
+    return _need(Mount() if mount is None else mount, "mount", "Mount")
 
 
 def chain_inverse_dynamics_batch(chain, q, qd, qdd):
@@ -748,9 +781,7 @@ def chain_tool_wrench_terms_batch(chain, q, qs, qss, payload):
 def _control_points(chain, points):
     """The tpr_chain_points of ``points`` (a :class:`toppra_amd.chain.ControlPoints`) on ``chain``: ValueError for anything else,
     and for a link outside the chain -- before any launch."""
-    if not (hasattr(points, "c_struct") and hasattr(points, "count")):
-        raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
-    return points.c_struct(chain)
+    return _need(points, "points", "ControlPoints").c_struct(chain)
 
 
 def chain_points_speed_batch(chain, q, qs, points, limit=None):
@@ -765,21 +796,8 @@ def chain_points_speed_batch(chain, q, qs, points, limit=None):
     def limits(q, shape, npoints):
         if limit is None:
             return (npoints, 0), (None,), [(P,), None]
-        dev = _capi.is_torch_cuda(q)
-
-        def convert(lim, B):
-            if dev:
-                import torch
-                if not (hasattr(lim, "is_cuda") and lim.is_cuda):
-                    lim = torch.as_tensor(np.asarray(lim, dtype=np.float64), device=q.device)
-                _capi.check_tensor("limit", lim, q)
-            else:
-                lim = np.asarray(lim, dtype=np.float64)
-            if tuple(lim.shape) not in ((), (P,), (B, P)):
-                raise ValueError("limit must be a scalar or have shape [P] = [%d] or [B, P] = [%d, %d], got %s" % (P, B, P, tuple(lim.shape)))
-            return lim.expand(B, P).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(lim, (B, P)))
-
-        B, N, lim = _bound_limits(limit, shape, convert)
+        B, N, lim = _bound_limits(limit, shape, lambda lim, B: _per_traj_limit(
+            "limit", lim, q, B, ((), (P,)), "be a scalar or have shape [P] = [%d] or [B, P] = [%d, %d]" % (P, B, P)))
         return (B, N), (lim,), [(P,), (2,)]
 
     speed2, xbound = _rigid_call(chain, "tpr_chain_points_speed_batch", (q, qs), ("q", "qs"), None, structs=[pts], by_grid=True,
@@ -822,41 +840,20 @@ def tree_torque_terms_batch(tree, q, qs, qss):
 
 # the base reaction of a chain or tree (include/toppra_hip.h: tpr_tree_base_wrench_*; the frame is toppra_amd.chain.Mount)
 
-class _AsTree(object):
-    """A :class:`toppra_amd.chain.SerialChain` as the tree-walking entries take it: its links with the parent table -1, 0, 1, ..."""
-
-    def __init__(self, chain):
-        self.dof, self._chain = chain.dof, chain
-        self.parents = (np.arange(chain.dof) - 1).astype(np.int32)
-
-    def c_struct(self, like):
-        model, keep = self._chain.c_struct(like)
-        return model, self.parents, (keep, self.parents)
-
-
-def _base_wrench_call(robot, entry, arrays, names, count, mount, **kwargs):
-    if mount is None:
-        from .chain import Mount
-        mount = Mount()
-    if not (hasattr(mount, "c_struct") and hasattr(mount, "rotation")):
-        raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
-    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
-    return _rigid_call(tree, entry, arrays, names, [(6,)] * count, structs=[mount], **kwargs)
-
-
 def base_wrench_batch(robot, q, qd, qdd, mount=None):
     """The base reaction of ``robot`` (a :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``) at every point: three arrays
     [..., d] in, [..., 6] = [force; moment about the mount frame's origin] in mount-frame axes out -- the wrench the mount exerts
     on the robot, every link of every root summed, gravity included.  ``mount``: a :class:`toppra_amd.chain.Mount`, None = the
     base frame without a platform (include/toppra_hip.h: tpr_tree_base_wrench_batch)."""
-    return _base_wrench_call(robot, "tpr_tree_base_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), 1, mount)[0]
+    return _rigid_call(robot, "tpr_tree_base_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(6,)], structs=[_mount(mount)])[0]
 
 
 def base_wrench_terms_batch(robot, q, qs, qss, mount=None):
     """(w0, wa, wb) = (w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) [..., 6] of :func:`base_wrench_batch` in one launch: what a
     constraint on the base reaction builds its rows from (w0 is the static reaction: not zero under gravity).  Each equals
     :func:`base_wrench_batch` on the same arguments in every bit."""
-    return tuple(_base_wrench_call(robot, "tpr_tree_base_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, mount, by_grid=True))
+    return tuple(_rigid_call(robot, "tpr_tree_base_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(6,)] * 3,
+                             structs=[_mount(mount)], by_grid=True))
 
 
 # momentum and kinetic energy of a set of links of a chain or tree (include/toppra_hip.h: tpr_tree_momentum_batch)
@@ -885,35 +882,17 @@ def link_mask(robot, links=None):
 
 def _momentum_call(robot, q, qs, mount, links, limit, tails):
     """One call of tpr_tree_momentum_batch; ``tails`` = the last axes of (momentum, energy2, xbound), None = not asked for."""
-    if mount is None:
-        from .chain import Mount
-        mount = Mount()
-    if not (hasattr(mount, "c_struct") and hasattr(mount, "rotation")):
-        raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+    mount = _mount(mount)
     mask = C.c_uint32(link_mask(robot, links))
-    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
 
     def limits(q, shape, npoints):
         if limit is None:
             return (mask, npoints, 0), (None,), tails
-        dev = _capi.is_torch_cuda(q)
-
-        def convert(lim, B):
-            if dev:
-                import torch
-                if not (hasattr(lim, "is_cuda") and lim.is_cuda):
-                    lim = torch.as_tensor(np.asarray(lim, dtype=np.float64), device=q.device)
-                _capi.check_tensor("limit", lim, q)
-            else:
-                lim = np.asarray(lim, dtype=np.float64)
-            if tuple(lim.shape) not in ((3,), (B, 3)):
-                raise ValueError("limit must have shape [3] or [B, 3] = [%d, 3] (p_max^2, L_max^2, 2 E_max), got %s" % (B, tuple(lim.shape)))
-            return lim.expand(B, 3).contiguous() if dev else np.ascontiguousarray(np.broadcast_to(lim, (B, 3)))
-
-        B, N, lim = _bound_limits(limit, shape, convert)
+        B, N, lim = _bound_limits(limit, shape, lambda lim, B: _per_traj_limit(
+            "limit", lim, q, B, ((3,),), "have shape [3] or [B, 3] = [%d, 3] (p_max^2, L_max^2, 2 E_max)" % B))
         return (mask, B, N), (lim,), tails
 
-    return _rigid_call(tree, "tpr_tree_momentum_batch", (q, qs), ("q", "qs"), None, structs=[mount], by_grid=True, limits=limits)
+    return _rigid_call(robot, "tpr_tree_momentum_batch", (q, qs), ("q", "qs"), None, structs=[mount], by_grid=True, limits=limits)
 
 
 def momentum_batch(robot, q, qs, mount=None, links=None, limit=None):
@@ -941,12 +920,10 @@ def momentum_bound_batch(robot, q, qs, limit, mount=None, links=None):
 
 # the wrench across any joint of a chain or tree (include/toppra_hip.h: tpr_tree_joint_wrench_*; the set is toppra_amd.chain.JointSections)
 
-def _joint_wrench_call(robot, entry, arrays, names, count, sections, **kwargs):
-    if not (hasattr(sections, "c_struct") and hasattr(sections, "joints")):
-        raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
-    set_ = sections.c_struct(robot)  # (a link outside the robot: ValueError, before anything else)
-    tree = robot if hasattr(robot, "parents") else _AsTree(robot)
-    return _rigid_call(tree, entry, arrays, names, [(int(set_.count), 6)] * count, structs=[set_], **kwargs)
+def _joint_sections(robot, sections):
+    """The tpr_joint_sections of ``sections`` (a :class:`toppra_amd.chain.JointSections`) on ``robot``: ValueError for anything
+    else, and for a joint outside the robot -- before any launch."""
+    return _need(sections, "sections", "JointSections").c_struct(robot)
 
 
 def joint_wrench_batch(robot, q, qd, qdd, sections):
@@ -954,14 +931,17 @@ def joint_wrench_batch(robot, q, qd, qdd, sections):
     :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``) at every point: three arrays [..., d] in, [..., S, 6] out in the
     set's order -- per section [force; moment about its origin] in its axes: the wrench the parent side exerts ON the section's
     link through its joint, gravity included (include/toppra_hip.h: tpr_tree_joint_wrench_batch)."""
-    return _joint_wrench_call(robot, "tpr_tree_joint_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), 1, sections)[0]
+    set_ = _joint_sections(robot, sections)
+    return _rigid_call(robot, "tpr_tree_joint_wrench_batch", (q, qd, qdd), ("q", "qd", "qdd"), [(int(set_.count), 6)], structs=[set_])[0]
 
 
 def joint_wrench_terms_batch(robot, q, qs, qss, sections):
     """(w0, wa, wb) = (w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) [..., S, 6] of :func:`joint_wrench_batch` in one launch: what a
     constraint on joint loads builds its rows from (w0 is the static load: not zero under gravity).  Each equals
     :func:`joint_wrench_batch` on the same arguments in every bit."""
-    return tuple(_joint_wrench_call(robot, "tpr_tree_joint_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), 3, sections, by_grid=True))
+    set_ = _joint_sections(robot, sections)
+    return tuple(_rigid_call(robot, "tpr_tree_joint_wrench_terms_batch", (q, qs, qss), ("q", "qs", "qss"), [(int(set_.count), 6)] * 3,
+                             structs=[set_], by_grid=True))
 
 
 def spline_coefficients(knots, waypoints, bc_type="not-a-knot"):

@@ -31,6 +31,39 @@ def _inertia33(I):
     return np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
 
 
+def _arrays(values, want, infix="", words=None, convert=None, fold=None):
+    """``values`` (name -> what was given) as finite float64 arrays of the shapes ``want`` (name -> shape): {name: array}, a
+    ValueError that names the argument otherwise.  Every value is converted before any shape is looked at, then each is checked
+    for its shape and its content in the order of ``want``.  ``infix`` goes after the wanted shape in the message and ``words``
+    (name -> text) in that shape's place; ``convert`` (name -> f(value, name)) stands in for ``np.array`` and its "symmetric"
+    refusal passes through; ``fold(arrays)`` runs between the two passes."""
+    arr = dict(values)
+    for name in arr:
+        special = (convert or {}).get(name)
+        try:
+            arr[name] = np.array(arr[name], dtype=np.float64) if special is None else special(arr[name], name)
+        except (TypeError, ValueError) as exc:
+            if "symmetric" in str(exc):
+                raise
+            raise ValueError("%s is not an array of numbers" % name)
+    if fold is not None:
+        fold(arr)
+    for name, shape in want.items():
+        if name not in arr:
+            continue
+        if arr[name].shape != tuple(shape):
+            raise ValueError("%s must have shape %s%s, got %s" % (name, (words or {}).get(name, list(shape)), infix, list(arr[name].shape)))
+        if not np.all(np.isfinite(arr[name])):
+            raise ValueError("%s holds a value that is not finite" % name)
+    return arr
+
+
+def _need_rotation(rot, name):
+    """ValueError unless ``rot`` -- [3, 3], or a stack [K, 3, 3] -- is orthonormal with determinant +1 (to 1e-12)."""
+    if np.any(np.abs(np.swapaxes(rot, -1, -2) @ rot - np.eye(3)) > 1e-12) or np.any(np.abs(np.linalg.det(rot) - 1.0) > 1e-12):
+        raise ValueError("%s must be orthonormal with determinant +1 (to 1e-12)" % name)
+
+
 def _with_payload_on(masses, coms, inertias, link, payload):
     """Copies of (masses, coms, inertias) with ``payload`` (a :class:`Payload` fixed in the frame of ``link``) merged into that
     link's mass, centre of mass and inertia (parallel-axis theorem)."""
@@ -68,26 +101,13 @@ class Payload(object):
                "frame_rotation": np.eye(3) if frame_rotation is None else frame_rotation}
         if frame_origin is not None:
             arr["frame_origin"] = frame_origin
-        for name in arr:
-            try:
-                arr[name] = _inertia6(arr[name], name) if name == "inertia" else np.array(arr[name], dtype=np.float64)
-            except (TypeError, ValueError) as exc:
-                if "symmetric" in str(exc):
-                    raise
-                raise ValueError("%s is not an array of numbers" % name)
-        want = {"mass": (), "com": (3,), "inertia": (6,), "frame_rotation": (3, 3), "frame_origin": (3,)}
-        for name, value in arr.items():
-            if value.shape != want[name]:
-                raise ValueError("%s must have shape %s, got %s" % (name, list(want[name]), list(value.shape)))
-            if not np.all(np.isfinite(value)):
-                raise ValueError("%s holds a value that is not finite" % name)
+        arr = _arrays(arr, {"mass": (), "com": (3,), "inertia": (6,), "frame_rotation": (3, 3), "frame_origin": (3,)},
+                      convert={"inertia": _inertia6})
         if arr["mass"] < 0:
             raise ValueError("mass must be >= 0")
-        rot = arr["frame_rotation"]
-        if np.any(np.abs(rot.T @ rot - np.eye(3)) > 1e-12) or abs(np.linalg.det(rot) - 1.0) > 1e-12:
-            raise ValueError("frame_rotation must be orthonormal with determinant +1 (to 1e-12)")
+        _need_rotation(arr["frame_rotation"], "frame_rotation")
         self.mass = float(arr["mass"])
-        self.com, self.inertia, self.frame_rotation = arr["com"], arr["inertia"], rot
+        self.com, self.inertia, self.frame_rotation = arr["com"], arr["inertia"], arr["frame_rotation"]
         self.frame_origin = arr.get("frame_origin")
         for value in (self.com, self.inertia, self.frame_rotation, self.frame_origin):
             if value is not None:
@@ -126,25 +146,13 @@ class Mount(object):
     """
 
     def __init__(self, rotation=None, origin=(0.0, 0.0, 0.0), mass=0.0, com=(0.0, 0.0, 0.0)):
-        arr = {"rotation": np.eye(3) if rotation is None else rotation, "origin": origin, "mass": mass, "com": com}
-        for name in arr:
-            try:
-                arr[name] = np.array(arr[name], dtype=np.float64)
-            except (TypeError, ValueError):
-                raise ValueError("%s is not an array of numbers" % name)
-        want = {"rotation": (3, 3), "origin": (3,), "mass": (), "com": (3,)}
-        for name, value in arr.items():
-            if value.shape != want[name]:
-                raise ValueError("%s must have shape %s, got %s" % (name, list(want[name]), list(value.shape)))
-            if not np.all(np.isfinite(value)):
-                raise ValueError("%s holds a value that is not finite" % name)
+        arr = _arrays({"rotation": np.eye(3) if rotation is None else rotation, "origin": origin, "mass": mass, "com": com},
+                      {"rotation": (3, 3), "origin": (3,), "mass": (), "com": (3,)})
         if arr["mass"] < 0:
             raise ValueError("mass must be >= 0")
-        rot = arr["rotation"]
-        if np.any(np.abs(rot.T @ rot - np.eye(3)) > 1e-12) or abs(np.linalg.det(rot) - 1.0) > 1e-12:
-            raise ValueError("rotation must be orthonormal with determinant +1 (to 1e-12)")
+        _need_rotation(arr["rotation"], "rotation")
         self.mass = float(arr["mass"])
-        self.rotation, self.origin, self.com = rot, arr["origin"], arr["com"]
+        self.rotation, self.origin, self.com = arr["rotation"], arr["origin"], arr["com"]
         for value in (self.rotation, self.origin, self.com):
             value.flags.writeable = False
 
@@ -160,7 +168,47 @@ class Mount(object):
         return frame
 
 
-class ControlPoints(object):
+class _LinkSet(object):
+    """What :class:`ControlPoints` and :class:`JointSections` share: K entries, each fixed to a link of a robot that is named only
+    where the set is used -- the index checks of the constructor, the length, the resolution of -1 and read-only storage.  A
+    subclass names its index argument (``_index``, also the attribute), its cap, and its words: the letter of its count, what it
+    is a set of, and its refusal of a link outside the robot."""
+    _index = _cap = _letter = _holds = _sits = None
+
+    def _indices(self, given):
+        """``given`` as the integer array [K] of the set, 1 <= K <= the cap (the range waits for :meth:`_store`)."""
+        try:
+            raw = np.array(given)
+        except (TypeError, ValueError):
+            raise ValueError("%s is not an array of integers" % self._index)
+        if raw.ndim != 1 or not 1 <= raw.shape[0] <= self._cap:
+            raise ValueError("a %s: %s must have shape [%s], got %s"
+                             % (self._holds % self._cap, self._index, self._letter, list(raw.shape)))
+        if raw.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers (link indices 0 .. d-1, or -1 for the last link), got %r" % (self._index, given))
+        return raw
+
+    def _store(self, raw, **payload):
+        """Keeps the indices (-1 .. MAX_DOF-1, as int32) and the checked per-entry arrays ``payload``, all read-only."""
+        if np.any(raw.astype(np.int64) < -1) or np.any(raw.astype(np.int64) >= _capi.MAX_DOF):
+            raise ValueError("%s must lie in -1 .. %d, got %r" % (self._index, _capi.MAX_DOF - 1, raw.tolist()))
+        self.count = int(raw.shape[0])
+        for name, value in dict(payload, **{self._index: raw.astype(np.int32)}).items():
+            value.flags.writeable = False
+            setattr(self, name, value)
+
+    def __len__(self):
+        return self.count
+
+    def _on(self, robot):
+        links = getattr(self, self._index)
+        links = np.where(links < 0, robot.dof - 1, links).astype(np.int32)
+        if np.any(links >= robot.dof):
+            raise ValueError(self._sits % (int(links.max()), robot.dof - 1))
+        return links
+
+
+class ControlPoints(_LinkSet):
     """Points fixed to ANY links of a chain -- an elbow, a camera bracket, a cable carrier: what the whole-arm speed and
     acceleration limits are set on.
 
@@ -173,43 +221,20 @@ class ControlPoints(object):
     P is 1 .. 16 (several sets may be used side by side).  The given order is the order of every output.  The links are checked
     against a chain where the set is used with one (:meth:`c_struct`).
     """
+    _index, _cap, _letter = "links", _capi.CHAIN_MAX_POINTS, "P"
+    _holds, _sits = "control-point set holds 1..%d points", "a control point sits on link %d, the chain has links 0..%d"
 
     def __init__(self, links, offsets):
-        try:
-            raw = np.array(links)
-        except (TypeError, ValueError):
-            raise ValueError("links is not an array of integers")
-        if raw.ndim != 1 or not 1 <= raw.shape[0] <= _capi.CHAIN_MAX_POINTS:
-            raise ValueError("a control-point set holds 1..%d points: links must have shape [P], got %s"
-                             % (_capi.CHAIN_MAX_POINTS, list(raw.shape)))
-        if raw.dtype.kind not in "iu":
-            raise ValueError("links must hold integers (link indices 0 .. d-1, or -1 for the last link), got %r" % (links,))
-        try:
-            off = np.array(offsets, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("offsets is not an array of numbers")
-        if off.shape != (raw.shape[0], 3):
-            raise ValueError("offsets must have shape [P, 3] = [%d, 3], got %s" % (raw.shape[0], list(off.shape)))
-        if not np.all(np.isfinite(off)):
-            raise ValueError("offsets holds a value that is not finite")
-        if np.any(raw.astype(np.int64) < -1) or np.any(raw.astype(np.int64) >= _capi.MAX_DOF):
-            raise ValueError("links must lie in -1 .. %d, got %r" % (_capi.MAX_DOF - 1, raw.tolist()))
-        self.links, self.offsets = raw.astype(np.int32), off
-        self.count = int(raw.shape[0])
-        self.links.flags.writeable = self.offsets.flags.writeable = False
-
-    def __len__(self):
-        return self.count
+        raw = self._indices(links)
+        P = raw.shape[0]
+        self._store(raw, **_arrays({"offsets": offsets}, {"offsets": (P, 3)}, words={"offsets": "[P, 3] = [%d, 3]" % P}))
 
     def __repr__(self):
         return "ControlPoints(%d points on links %s)" % (self.count, self.links.tolist())
 
     def on(self, chain):
         """The link of every point on ``chain`` ([P], -1 resolved to its last link); ValueError for a link outside it."""
-        links = np.where(self.links < 0, chain.dof - 1, self.links).astype(np.int32)
-        if np.any(links >= chain.dof):
-            raise ValueError("a control point sits on link %d, the chain has links 0..%d" % (int(links.max()), chain.dof - 1))
-        return links
+        return self._on(chain)
 
     def c_struct(self, chain):
         """The tpr_chain_points of a call on ``chain`` (a host struct, passed to the kernels by value)."""
@@ -220,7 +245,7 @@ class ControlPoints(object):
         return pts
 
 
-class JointSections(object):
+class JointSections(_LinkSet):
     """Cuts across joints of a robot -- a gearbox's output bearing, a linear guide's carriage, a slender link's flange: where the
     joint-load limits are set (:class:`toppra_amd.constraint.BatchJointLoadConstraint`).
 
@@ -237,41 +262,17 @@ class JointSections(object):
     The given order is the order of every output.  The links are checked against a robot where the set is used with one
     (:meth:`on`, :meth:`c_struct`).  :meth:`on_axes` builds sections along joint axes.
     """
+    _index, _cap, _letter = "joints", _capi.JOINT_MAX_SECTIONS, "S"
+    _holds, _sits = "section set holds 1..%d sections", "a section sits on joint %d, the robot has joints 0..%d"
 
     def __init__(self, joints, origins=None, rotations=None):
-        try:
-            raw = np.array(joints)
-        except (TypeError, ValueError):
-            raise ValueError("joints is not an array of integers")
-        if raw.ndim != 1 or not 1 <= raw.shape[0] <= _capi.JOINT_MAX_SECTIONS:
-            raise ValueError("a section set holds 1..%d sections: joints must have shape [S], got %s"
-                             % (_capi.JOINT_MAX_SECTIONS, list(raw.shape)))
-        if raw.dtype.kind not in "iu":
-            raise ValueError("joints must hold integers (link indices 0 .. d-1, or -1 for the last link), got %r" % (joints,))
+        raw = self._indices(joints)
         S = int(raw.shape[0])
-        arr = {"origins": np.zeros((S, 3)) if origins is None else origins,
-               "rotations": np.broadcast_to(np.eye(3), (S, 3, 3)) if rotations is None else rotations}
-        for name in arr:
-            try:
-                arr[name] = np.array(arr[name], dtype=np.float64)
-            except (TypeError, ValueError):
-                raise ValueError("%s is not an array of numbers" % name)
-        for name, shape in (("origins", (S, 3)), ("rotations", (S, 3, 3))):
-            if arr[name].shape != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, list(shape), list(arr[name].shape)))
-            if not np.all(np.isfinite(arr[name])):
-                raise ValueError("%s holds a value that is not finite" % name)
-        rot = arr["rotations"]
-        if np.any(np.abs(np.swapaxes(rot, 1, 2) @ rot - np.eye(3)) > 1e-12) or np.any(np.abs(np.linalg.det(rot) - 1.0) > 1e-12):
-            raise ValueError("rotations must be orthonormal with determinant +1 (to 1e-12)")
-        if np.any(raw.astype(np.int64) < -1) or np.any(raw.astype(np.int64) >= _capi.MAX_DOF):
-            raise ValueError("joints must lie in -1 .. %d, got %r" % (_capi.MAX_DOF - 1, raw.tolist()))
-        self.joints, self.origins, self.rotations = raw.astype(np.int32), arr["origins"], rot
-        self.count = S
-        self.joints.flags.writeable = self.origins.flags.writeable = self.rotations.flags.writeable = False
-
-    def __len__(self):
-        return self.count
+        arr = _arrays({"origins": np.zeros((S, 3)) if origins is None else origins,
+                       "rotations": np.broadcast_to(np.eye(3), (S, 3, 3)) if rotations is None else rotations},
+                      {"origins": (S, 3), "rotations": (S, 3, 3)})
+        _need_rotation(arr["rotations"], "rotations")
+        self._store(raw, **arr)
 
     def __repr__(self):
         return "JointSections(%d sections on joints %s)" % (self.count, self.joints.tolist())
@@ -307,10 +308,7 @@ class JointSections(object):
 
     def on(self, robot):
         """The link of every section on ``robot`` ([S], -1 resolved to its last link); ValueError for a link outside it."""
-        links = np.where(self.joints < 0, robot.dof - 1, self.joints).astype(np.int32)
-        if np.any(links >= robot.dof):
-            raise ValueError("a section sits on joint %d, the robot has joints 0..%d" % (int(links.max()), robot.dof - 1))
-        return links
+        return self._on(robot)
 
     def c_struct(self, robot):
         """The tpr_joint_sections of a call on ``robot`` (a host struct, passed to the kernels by value)."""
@@ -322,7 +320,67 @@ class JointSections(object):
         return sec
 
 
-class SerialChain(object):
+class _Robot(object):
+    """What :class:`SerialChain` and :class:`KinematicTree` share: the evaluations that walk any robot as a tree -- base reaction,
+    momentum, joint loads -- and the joint torques, which each class takes from the entries of its own family (``_family``)."""
+    _family = None  # "chain" / "tree": the prefix of toppra_amd.batch's torque functions
+
+    def as_tree(self, like):
+        """(tpr_chain of the links, the host parent array [d] int32, what they point to): how the robot presents itself to the
+        tree-walking entries, for a call whose arrays are of the kind of ``like`` (see :meth:`SerialChain.c_struct`).  A tree's
+        ``c_struct`` is that; a chain adds its parent table -1, 0, 1, ..."""
+        return self.c_struct(like)
+
+    def inverse_dynamics(self, q, qd, qdd):
+        """Joint torques / forces tau(q, qd, qdd) by recursive Newton-Euler: arrays [..., d] in, [..., d] out (numpy in ->
+        numpy out, torch-ROCm tensors in -> a tensor out on the current stream).  A valid ``inv_dyn`` callback of the
+        torque constraints."""
+        return getattr(_batch, self._family + "_inverse_dynamics_batch")(self, q, qd, qdd)
+
+    def torque_terms(self, q, qs, qss):
+        """(tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: the three evaluations a torque constraint needs."""
+        return getattr(_batch, self._family + "_torque_terms_batch")(self, q, qs, qss)
+
+    def base_wrench(self, q, qd, qdd, mount=None):
+        """The base reaction [..., 6] = [force; moment]: the wrench the mount exerts ON the robot, summed over every link,
+        gravity included -- at rest the force holds up the weight.  ``mount`` (a :class:`Mount`, None = the base frame, no
+        platform) gives the frame: the moment is about its origin, both parts are in its axes.  With the mount bound
+        (``lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount)``) a valid batched ``inv_dyn`` of
+        :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
+        return _batch.base_wrench_batch(self, q, qd, qdd, mount)
+
+    def base_wrench_terms(self, q, qs, qss, mount=None):
+        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
+        reaction needs; the first is the static reaction, which gravity keeps from being zero."""
+        return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
+
+    def momentum(self, q, qd, mount=None, links=None):
+        """The momentum [..., 6] = [linear; angular] the robot carries at velocity ``qd``: the sum over the links of ``links`` (an
+        iterable of link numbers, -1 = the last; None = every link) of each link's linear momentum and of its angular momentum
+        about the origin of ``mount``'s frame (a :class:`Mount`, None = the base frame), both in that frame's axes -- kg m / s
+        and kg m^2 / s.  The mount's platform does not move and plays no part."""
+        return _batch.momentum_batch(self, q, qd, mount, links)[0]
+
+    def kinetic_energy(self, q, qd, links=None):
+        """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
+        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
+        return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
+
+    def joint_wrenches(self, q, qd, qdd, sections):
+        """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section
+        [force; moment about its origin] in its axes -- what the parent side exerts ON the section's link through its joint,
+        gravity included (at rest the force is the support of the weight of everything that hangs on the joint).  With the
+        sections bound and the result flattened to [..., 6 S], a valid batched ``inv_dyn`` of
+        :class:`toppra_amd.constraint.BatchSecondOrderConstraint`."""
+        return _batch.joint_wrench_batch(self, q, qd, qdd, sections)
+
+    def joint_wrench_terms(self, q, qs, qss, sections):
+        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`joint_wrenches` in one launch: the evaluations a limit on joint
+        loads needs; the first is the static load, which gravity keeps from being zero."""
+        return _batch.joint_wrench_terms_batch(self, q, qs, qss, sections)
+
+
+class SerialChain(_Robot):
     """A fixed-base serial chain of 1 .. 32 revolute / prismatic joints.
 
     Links are i = 0 .. d-1; the parent of link i is link i-1, the parent of link 0 the fixed base (the world frame).
@@ -343,6 +401,8 @@ class SerialChain(object):
     with the constraints (``fs_coef`` / ``friction``).  The model is uploaded to a device once per object, on first use there.
     """
 
+    _family = "chain"
+
     def __init__(self, joint_types, axes, rotations, translations, masses, coms, inertias, gravity=(0.0, 0.0, -9.81),
                  tool=(0.0, 0.0, 0.0)):
         try:
@@ -352,35 +412,27 @@ class SerialChain(object):
         d = len(codes)
         if not 1 <= d <= _capi.MAX_DOF:
             raise ValueError("a chain has 1..%d joints, got %d" % (_capi.MAX_DOF, d))
-        arr = {"axis": axes, "rot": rotations, "trans": translations, "mass": masses, "com": coms, "inertia": inertias,
-               "gravity": gravity, "tool": tool}
-        for name in arr:
-            try:
-                arr[name] = np.array(arr[name], dtype=np.float64)
-            except (TypeError, ValueError):
-                raise ValueError("%s is not an array of numbers" % name)
-        if arr["inertia"].shape == (d, 3, 3):
+
+        def fold(arr):  # inertias given as [d, 3, 3]
             full = arr["inertia"]
-            if not np.array_equal(full, np.swapaxes(full, 1, 2)):
-                raise ValueError("inertia matrices must be symmetric")
-            arr["inertia"] = np.stack([full[:, 0, 0], full[:, 1, 1], full[:, 2, 2], full[:, 0, 1], full[:, 0, 2], full[:, 1, 2]], -1)
-        want = {"axis": (d, 3), "rot": (d, 3, 3), "trans": (d, 3), "mass": (d,), "com": (d, 3), "inertia": (d, 6),
-                "gravity": (3,), "tool": (3,)}
-        for name, shape in want.items():
-            if arr[name].shape != shape:
-                raise ValueError("%s must have shape %s for %d joints, got %s" % (name, list(shape), d, list(arr[name].shape)))
-            if not np.all(np.isfinite(arr[name])):
-                raise ValueError("%s holds a value that is not finite" % name)
+            if full.shape == (d, 3, 3):
+                if not np.array_equal(full, np.swapaxes(full, 1, 2)):
+                    raise ValueError("inertia matrices must be symmetric")
+                arr["inertia"] = np.stack([full[:, 0, 0], full[:, 1, 1], full[:, 2, 2], full[:, 0, 1], full[:, 0, 2], full[:, 1, 2]], -1)
+
+        arr = _arrays({"axis": axes, "rot": rotations, "trans": translations, "mass": masses, "com": coms, "inertia": inertias,
+                       "gravity": gravity, "tool": tool},
+                      {"axis": (d, 3), "rot": (d, 3, 3), "trans": (d, 3), "mass": (d,), "com": (d, 3), "inertia": (d, 6),
+                       "gravity": (3,), "tool": (3,)}, infix=" for %d joints" % d, fold=fold)
         if np.any(np.abs(np.sqrt((arr["axis"] ** 2).sum(-1)) - 1.0) > 1e-12):
             raise ValueError("axes must be unit vectors (to 1e-12)")
-        rot = arr["rot"]
-        if np.any(np.abs(np.swapaxes(rot, 1, 2) @ rot - np.eye(3)) > 1e-12) or np.any(np.abs(np.linalg.det(rot) - 1.0) > 1e-12):
-            raise ValueError("rotations must be orthonormal with determinant +1 (to 1e-12)")
+        _need_rotation(arr["rot"], "rotations")
         if np.any(arr["mass"] < 0):
             raise ValueError("masses must be >= 0")
         self.dof = d
         self.joint_types = [PRISMATIC if c == _capi.JOINT_PRISMATIC else REVOLUTE for c in codes]
         self._codes = np.array(codes, dtype=np.int32)
+        self._parents = (np.arange(d) - 1).astype(np.int32)  # the chain as a tree: -1, 0, 1, ...
         # one packed buffer: a single upload per device, the struct's pointers are offsets into it
         self._offsets, parts, at = {}, [], 0
         for name, _ in _capi.CHAIN_ARRAYS:
@@ -414,15 +466,9 @@ class SerialChain(object):
             setattr(model, name, base + 8 * self._offsets[name])
         return model, (buf, self._codes)
 
-    def inverse_dynamics(self, q, qd, qdd):
-        """Joint torques / forces tau(q, qd, qdd) by recursive Newton-Euler: arrays [..., d] in, [..., d] out (numpy in ->
-        numpy out, torch-ROCm tensors in -> a tensor out on the current stream).  A valid ``inv_dyn`` callback of the
-        torque constraints."""
-        return _batch.chain_inverse_dynamics_batch(self, q, qd, qdd)
-
-    def torque_terms(self, q, qs, qss):
-        """(tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: the three evaluations a torque constraint needs."""
-        return _batch.chain_torque_terms_batch(self, q, qs, qss)
+    def as_tree(self, like):
+        model, keep = self.c_struct(like)
+        return model, self._parents, (keep, self._parents)
 
     def tool_velocity_norm(self, q, qs, S=None):
         """v' S v of the tool point for qd = qs, shape [...]: [v; w] are its linear and angular velocity in world axes, ``S``
@@ -468,44 +514,6 @@ class SerialChain(object):
         limit on the points' accelerations needs; acc(q, 0, 0) is an exact zero."""
         return _batch.chain_points_acceleration_terms_batch(self, q, qs, qss, points)
 
-    def base_wrench(self, q, qd, qdd, mount=None):
-        """The base reaction [..., 6] = [force; moment]: the wrench the mount exerts ON the robot, summed over every link,
-        gravity included -- at rest the force holds up the weight.  ``mount`` (a :class:`Mount`, None = the base frame, no
-        platform) gives the frame: the moment is about its origin, both parts are in its axes.  With the mount bound
-        (``lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount)``) a valid batched ``inv_dyn`` of
-        :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
-        return _batch.base_wrench_batch(self, q, qd, qdd, mount)
-
-    def base_wrench_terms(self, q, qs, qss, mount=None):
-        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
-        reaction needs; the first is the static reaction, which gravity keeps from being zero."""
-        return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
-
-    def momentum(self, q, qd, mount=None, links=None):
-        """The momentum [..., 6] = [linear; angular] the robot carries at velocity ``qd``: the sum over the links of ``links`` (an
-        iterable of link numbers, -1 = the last; None = every link) of each link's linear momentum and of its angular momentum
-        about the origin of ``mount``'s frame (a :class:`Mount`, None = the base frame), both in that frame's axes -- kg m / s
-        and kg m^2 / s.  The mount's platform does not move and plays no part."""
-        return _batch.momentum_batch(self, q, qd, mount, links)[0]
-
-    def kinetic_energy(self, q, qd, links=None):
-        """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
-        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
-        return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
-
-    def joint_wrenches(self, q, qd, qdd, sections):
-        """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section
-        [force; moment about its origin] in its axes -- what the parent side exerts ON the section's link through its joint,
-        gravity included (at rest the force is the support of the weight of everything that hangs on the joint).  With the
-        sections bound and the result flattened to [..., 6 S], a valid batched ``inv_dyn`` of
-        :class:`toppra_amd.constraint.BatchSecondOrderConstraint`."""
-        return _batch.joint_wrench_batch(self, q, qd, qdd, sections)
-
-    def joint_wrench_terms(self, q, qs, qss, sections):
-        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`joint_wrenches` in one launch: the evaluations a limit on joint
-        loads needs; the first is the static load, which gravity keeps from being zero."""
-        return _batch.joint_wrench_terms_batch(self, q, qs, qss, sections)
-
     def with_payload(self, payload):
         """A new chain whose last link carries ``payload``: its mass, centre of mass and inertia merged into the last link's
         (parallel-axis theorem).  Host only; the contact frame plays no part.  Torque limits on the result load the joints
@@ -515,7 +523,7 @@ class SerialChain(object):
                            gravity=self.gravity, tool=self.tool)
 
 
-class KinematicTree(object):
+class KinematicTree(_Robot):
     """A fixed-base tree of 1 .. 32 revolute / prismatic joints: a branched robot -- two arms on a torso or a lifting column, an
     arm beside a pan-tilt head, an arm with an articulated gripper -- or several robots on one base planned as one path.
 
@@ -531,6 +539,8 @@ class KinematicTree(object):
     (``TPR_TREE_MAX_FORKS``).  ``parents = [-1, 0, 1, ...]`` is the serial chain and gives :class:`SerialChain`'s torques bit for
     bit.  Not modelled: floating bases, closed loops, rotor inertia, viscous damping.
     """
+
+    _family = "tree"
 
     def __init__(self, parents, joint_types, axes, rotations, translations, masses, coms, inertias, gravity=(0.0, 0.0, -9.81)):
         try:
@@ -587,49 +597,7 @@ class KinematicTree(object):
         """Joint torques / forces tau(q, qd, qdd) by recursive Newton-Euler over the tree: arrays [..., d] in, [..., d] out
         (numpy in -> numpy out, torch-ROCm tensors in -> a tensor out on the current stream).  A valid ``inv_dyn`` callback of
         the torque constraints."""
-        return _batch.tree_inverse_dynamics_batch(self, q, qd, qdd)
-
-    def torque_terms(self, q, qs, qss):
-        """(tau(q, 0, 0), tau(q, 0, qs), tau(q, qs, qss)) in one launch: the three evaluations a torque constraint needs."""
-        return _batch.tree_torque_terms_batch(self, q, qs, qss)
-
-    def base_wrench(self, q, qd, qdd, mount=None):
-        """The base reaction [..., 6] = [force; moment]: the wrench the mount exerts ON the robot, summed over every link,
-        gravity included -- at rest the force holds up the weight.  ``mount`` (a :class:`Mount`, None = the base frame, no
-        platform) gives the frame: the moment is about its origin, both parts are in its axes.  With the mount bound
-        (``lambda q, qd, qdd: robot.base_wrench(q, qd, qdd, mount)``) a valid batched ``inv_dyn`` of
-        :class:`toppra_amd.constraint.BatchSecondOrderConstraint` (p = 6)."""
-        return _batch.base_wrench_batch(self, q, qd, qdd, mount)
-
-    def base_wrench_terms(self, q, qs, qss, mount=None):
-        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`base_wrench` in one launch: the evaluations a limit on the base
-        reaction needs; the first is the static reaction, which gravity keeps from being zero."""
-        return _batch.base_wrench_terms_batch(self, q, qs, qss, mount)
-
-    def momentum(self, q, qd, mount=None, links=None):
-        """The momentum [..., 6] = [linear; angular] the robot carries at velocity ``qd``: the sum over the links of ``links`` (an
-        iterable of link numbers, -1 = the last; None = every link) of each link's linear momentum and of its angular momentum
-        about the origin of ``mount``'s frame (a :class:`Mount`, None = the base frame), both in that frame's axes -- kg m / s
-        and kg m^2 / s.  The mount's platform does not move and plays no part."""
-        return _batch.momentum_batch(self, q, qd, mount, links)[0]
-
-    def kinetic_energy(self, q, qd, links=None):
-        """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
-        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
-        return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
-
-    def joint_wrenches(self, q, qd, qdd, sections):
-        """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section
-        [force; moment about its origin] in its axes -- what the parent side exerts ON the section's link through its joint,
-        gravity included (at rest the force is the support of the weight of everything that hangs on the joint).  With the
-        sections bound and the result flattened to [..., 6 S], a valid batched ``inv_dyn`` of
-        :class:`toppra_amd.constraint.BatchSecondOrderConstraint`."""
-        return _batch.joint_wrench_batch(self, q, qd, qdd, sections)
-
-    def joint_wrench_terms(self, q, qs, qss, sections):
-        """(w(q, 0, 0), w(q, 0, qs), w(q, qs, qss)) of :meth:`joint_wrenches` in one launch: the evaluations a limit on joint
-        loads needs; the first is the static load, which gravity keeps from being zero."""
-        return _batch.joint_wrench_terms_batch(self, q, qs, qss, sections)
+        return super(KinematicTree, self).inverse_dynamics(q, qd, qdd)
 
     def path_to(self, link):
         """The links from the base to ``link``, in order: the joints that move it."""

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
-from .chain import ControlPoints, JointSections, KinematicTree, Mount, Payload, SerialChain
+from .chain import KinematicTree, SerialChain
 from .interpolator import path_samples, spline_tables
 
 
@@ -318,6 +318,14 @@ def _like(x, like):
     return np.asarray(x, dtype=np.float64)
 
 
+def _shape_of(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64)
+
+
 def _zeros_like(x):
     return np.zeros_like(x) if isinstance(x, np.ndarray) else x.new_zeros(tuple(x.shape))
 
@@ -326,6 +334,14 @@ def _check_chain_dof(inv_dyn, d):
     if isinstance(inv_dyn, (SerialChain, KinematicTree)) and inv_dyn.dof != d:
         raise ValueError("Wrong dimension: the {:s} has {:d} joints, the path {:d} dof".format(
             "tree" if isinstance(inv_dyn, KinematicTree) else "chain", inv_dyn.dof, d))
+
+
+def _check_leading(F_shape, g_shape, B, N):
+    """The axes of rows F [..., m, p] and g [..., m] before those (a shape; None = not an array): none, [B] or [B, N+1]."""
+    for name, shape, tail in (("F", F_shape, 2), ("g", g_shape, 1)):
+        if shape is not None and tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
+            raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
+                             % (name, tuple(shape[:-tail]), B, B, N + 1))
 
 
 class _BatchSecondOrder(LinearConstraint):
@@ -385,11 +401,11 @@ class BatchJointTorqueConstraint(_BatchSecondOrder):
         super(BatchJointTorqueConstraint, self).__init__()
         self.inv_dyn = inv_dyn
         self.tau_lim, self.fs_coef = tau_lim, fs_coef
-        shape = tuple(tau_lim.shape) if hasattr(tau_lim, "shape") else np.shape(tau_lim)
+        shape = _shape_of(tau_lim)
         if len(shape) not in (2, 3) or shape[-1] != 2:
             raise ValueError("tau_lim must have shape [d, 2] or [B, d, 2], got %s" % (shape,))
         self.dof = int(shape[-2])
-        fshape = tuple(fs_coef.shape) if hasattr(fs_coef, "shape") else np.shape(fs_coef)
+        fshape = _shape_of(fs_coef)
         if len(fshape) not in (1, 2) or fshape[-1] != self.dof:
             raise ValueError("fs_coef must have shape [d] or [B, d] with d = %d, got %s" % (self.dof, fshape))
         self._tau_batch = shape[0] if len(shape) == 3 else None
@@ -443,17 +459,17 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         self.F, self.g, self.friction = F, g, friction
         self.set_discretization_type(discretization_scheme)
         if F is not None and not callable(F):
-            shape = tuple(F.shape) if hasattr(F, "shape") else np.shape(F)
+            shape = _shape_of(F)
             if len(shape) not in (2, 3, 4):
                 raise ValueError("F must have shape [m, p], [B, m, p] or [B, N+1, m, p], got %s" % (shape,))
         if not callable(g):
-            gshape = tuple(g.shape) if hasattr(g, "shape") else np.shape(g)
+            gshape = _shape_of(g)
             if len(gshape) not in (1, 2, 3):
                 raise ValueError("g must have shape [m], [B, m] or [B, N+1, m], got %s" % (gshape,))
             if F is not None and not callable(F) and gshape[-1] != shape[-2]:
                 raise ValueError("g has %d entries per gridpoint, F has %d rows" % (gshape[-1], shape[-2]))
         if friction is not None:
-            fshape = tuple(friction.shape) if hasattr(friction, "shape") else np.shape(friction)
+            fshape = _shape_of(friction)
             if len(fshape) not in (1, 2):
                 raise ValueError("friction must have shape [d] or [B, d], got %s" % (fshape,))
         self._format_string = "    Kind: Batched generalized second-order constraint\n"
@@ -462,7 +478,7 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
     def joint_torque_constraint(cls, inv_dyn, taulim, joint_friction, **kwargs):
         """Joint torque bounds taulim [d, 2] or [B, d, 2] with dry friction joint_friction [d] or [B, d]
         (linear_second_order.py:100-140): the signed identity with g = [tau_max; -tau_min]."""
-        shape = tuple(taulim.shape) if hasattr(taulim, "shape") else np.shape(taulim)
+        shape = _shape_of(taulim)
         if len(shape) not in (2, 3) or shape[-1] != 2:
             raise ValueError("taulim must have shape [d, 2] or [B, d, 2], got %s" % (shape,))
         if hasattr(taulim, "detach"):
@@ -474,7 +490,7 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         return cls(inv_dyn, None, g, friction=joint_friction, **kwargs)
 
     def _shape(self, x):
-        return None if x is None or callable(x) else (tuple(x.shape) if hasattr(x, "shape") else np.shape(x))
+        return None if x is None or callable(x) else _shape_of(x)
 
     def rows_per_stage(self, d):
         F, g = self._shape(self.F), self._shape(self.g)
@@ -483,10 +499,7 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
 
     def check(self, B, N, d):
         _check_chain_dof(self.inv_dyn, d)
-        for name, shape, tail in (("F", self._shape(self.F), 2), ("g", self._shape(self.g), 1)):
-            if shape is not None and tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
-                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
-                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+        _check_leading(self._shape(self.F), self._shape(self.g), B, N)
         fr = self._shape(self.friction)
         if fr is not None and (fr[-1] != d or (len(fr) == 2 and fr[0] != B)):
             raise ValueError("friction must have shape [d] or [B, d] = [%d, %d], got %s" % (B, d, fr))
@@ -519,19 +532,16 @@ class BatchSecondOrderConstraint(_BatchSecondOrder):
         return {"w0": w0, "wa": wa, "wb": wb, "F": F, "g": g, "friction": fr, "interpolation": self._interp()}
 
 
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64)
-
-
 def _need_chain(chain):
-    if not isinstance(chain, SerialChain):
-        raise ValueError("chain must be a toppra_amd.chain.SerialChain, got %s" % type(chain).__name__)
+    _batch._need(chain, "chain", "SerialChain")
+
+
+def _need_robot(robot):
+    _batch._need(robot, "robot", "SerialChain", "KinematicTree")
 
 
 def _need_points(points, chain):
-    if not isinstance(points, ControlPoints):
-        raise ValueError("points must be a toppra_amd.chain.ControlPoints, got %s" % type(points).__name__)
-    points.on(chain)  # (a link outside the chain: ValueError)
+    _batch._need(points, "points", "ControlPoints").on(chain)  # (a link outside the chain: ValueError)
 
 
 def _row_limits(F, g, width, shapes):
@@ -551,45 +561,56 @@ def _row_limits(F, g, width, shapes):
     return F, g, None
 
 
-def _six_wide_limits(first, second, F, g):
-    """The limits of a constraint on a 6-wide quantity [first part; second part], given either as boxes on the parts --
-    (name, limit) each, a limit being None, a scalar, [3, 2] or [B, 3, 2] (lower, upper) -- or as rows F, g:
-    (F, g, the B of per-trajectory boxes or None).  Each box adds six rows, the signed identity on its part with
-    g = [upper; -lower], the first part's rows first."""
-    names = (first[0], second[0])
-    boxes, rows = first[1] is not None or second[1] is not None, F is not None or g is not None
+def _box_limits(count, width, parts, letter, F, g):
+    """The limits of a constraint on ``count`` units of ``width`` numbers each, unit-major -- one tool point or one wrench, S
+    sections, P points -- given either as boxes on 3-wide parts of a unit or as rows F, g: (F, g, the B of boxes given per
+    trajectory or None).  ``parts``: (name, limit, the part's first column in its unit) each; a limit is None, a scalar, [K] (a
+    magnitude per unit), [K, 3, 2] or [B, K, 3, 2] (lower, upper).  ``letter`` names K in the messages (S, P); None = a lone unit,
+    whose boxes are [3, 2] or [B, 3, 2] without the unit's axis and without the [K] spelling.  Each part given adds six rows per
+    unit, the signed identity [+I; -I] on that part with g = [upper; -lower]: the rows are unit-major, within a unit the parts
+    follow in their order, and g is laid out as the rows are."""
+    names = tuple(name for name, _, _ in parts)
+    boxes, rows = any(lim is not None for _, lim, _ in parts), F is not None or g is not None
     if boxes and rows:
-        raise ValueError("give the limits either as %s / %s or as F and g, not both" % names)
+        raise ValueError("give the limits either as %s or as F and g, not both" % " / ".join(names))
     if not boxes and not rows:
-        raise ValueError("no limit given: one of %s, %s, or F with g, is required" % names)
-    limit_batch = None
-    if boxes:
-        F_parts, g_parts = [], []
-        for (name, lim), at in ((first, 0), (second, 3)):
-            if lim is None:
-                continue
-            lim = _host(lim)
-            if lim.ndim == 0:
-                lim = np.stack([np.full(3, -float(lim)), np.full(3, float(lim))], -1)
-            if lim.ndim not in (2, 3) or lim.shape[-2:] != (3, 2):
-                raise ValueError("%s must be a scalar or have shape [3, 2] or [B, 3, 2], got %s" % (name, list(lim.shape)))
-            if not np.all(np.isfinite(lim)):
-                raise ValueError("%s holds a limit that is not finite" % name)
-            if np.any(lim[..., 0] > lim[..., 1]):
-                raise ValueError("%s holds a lower limit above its upper limit" % name)
-            if lim.ndim == 3:
-                if limit_batch not in (None, lim.shape[0]):
-                    raise ValueError("%s and %s are given per trajectory for %d and %d trajectories"
-                                     % (names + (limit_batch, lim.shape[0])))
-                limit_batch = int(lim.shape[0])
-            part = np.zeros((6, 6))
-            part[:3, at:at + 3], part[3:, at:at + 3] = np.eye(3), -np.eye(3)
-            F_parts.append(part)
-            g_parts.append(np.concatenate((lim[..., 1], -lim[..., 0]), -1))  # [upper; -lower]
-        if limit_batch is not None:
-            g_parts = [np.broadcast_to(p, (limit_batch, 6)) for p in g_parts]
-        return np.concatenate(F_parts, 0), np.ascontiguousarray(np.concatenate(g_parts, -1)), limit_batch
-    return _row_limits(F, g, 6, "[m, 6], [B, m, 6] or [B, N+1, m, 6]")
+        raise ValueError("no limit given: %s%s, or F with g, is required" % ("one of " if len(names) > 1 else "", ", ".join(names)))
+    if not boxes:
+        wide = "%d" % width if letter is None else "%d %s" % (width, letter)
+        shapes = "[m, %s], [B, m, %s] or [B, N+1, m, %s]" % (wide, wide, wide)
+        return _row_limits(F, g, width * count, shapes if letter is None else "%s with %s = %d" % (shapes, wide, width * count))
+    limit_batch, given = None, []
+    for name, lim, at in parts:
+        if lim is None:
+            continue
+        lim = _host(lim)
+        shape = lim.shape
+        if lim.ndim == 0 or (letter is not None and shape == (count,)):  # a magnitude: for every unit, or one per unit
+            lim = np.broadcast_to(lim, (count,))
+            lim = np.stack([np.repeat(-lim[:, None], 3, 1), np.repeat(lim[:, None], 3, 1)], -1)
+        elif letter is None and lim.ndim >= 2:
+            lim = lim.reshape(shape[:-2] + (1,) + shape[-2:])
+        if lim.ndim not in (3, 4) or lim.shape[-3:] != (count, 3, 2):
+            raise ValueError("%s must be a scalar or have shape %s, got %s" % (name, "[3, 2] or [B, 3, 2]" if letter is None else
+                             "[%s], [%s, 3, 2] or [B, %s, 3, 2] with %s = %d" % (letter, letter, letter, letter, count), list(shape)))
+        if not np.all(np.isfinite(lim)):
+            raise ValueError("%s holds a limit that is not finite" % name)
+        if np.any(lim[..., 0] > lim[..., 1]):
+            raise ValueError("%s holds a lower limit above its upper limit" % name)
+        if lim.ndim == 4:
+            if limit_batch not in (None, lim.shape[0]):
+                raise ValueError("%s and %s are given per trajectory for %d and %d trajectories" % (names + (limit_batch, lim.shape[0])))
+            limit_batch = int(lim.shape[0])
+        given.append((at, np.concatenate((lim[..., 1], -lim[..., 0]), -1)))  # [..., K, 6] = [upper; -lower] per unit
+    per = 6 * len(given)  # rows per unit
+    Fm = np.zeros((per * count, width * count))
+    for k in range(count):
+        for j, (at, _) in enumerate(given):
+            r, c = per * k + 6 * j, width * k + at
+            Fm[r:r + 3, c:c + 3], Fm[r + 3:r + 6, c:c + 3] = np.eye(3), -np.eye(3)
+    lead = () if limit_batch is None else (limit_batch,)
+    gm = np.concatenate([np.broadcast_to(gp, lead + (count, 6)) for _, gp in given], -1)  # [..., K, per]
+    return Fm, np.ascontiguousarray(gm.reshape(lead + (per * count,))), limit_batch
 
 
 class _BatchChainRows(_BatchSecondOrder):
@@ -618,10 +639,7 @@ class _BatchChainRows(_BatchSecondOrder):
             raise ValueError("Wrong dimension: the chain has {:d} joints, the path {:d} dof".format(self.dof, d))
         if self._limit_batch is not None and self._limit_batch != B:
             raise ValueError("the limits are given per trajectory for %d trajectories, the problem has %d" % (self._limit_batch, B))
-        for name, shape, tail in (("F", _shape_of(self.F), 2), ("g", _shape_of(self.g), 1)):
-            if tuple(shape[:-tail]) not in ((), (B,), (B, N + 1)):
-                raise ValueError("%s has leading shape %s: one for the batch, [B] = [%d] or [B, N+1] = [%d, %d] is expected"
-                                 % (name, tuple(shape[:-tail]), B, B, N + 1))
+        _check_leading(_shape_of(self.F), _shape_of(self.g), B, N)
 
     def block(self, q, qs, qss):
         B, n1, d = (int(v) for v in q.shape)
@@ -654,7 +672,7 @@ class BatchCartesianAccelerationConstraint(_BatchChainRows):
     def __init__(self, chain, linear=None, angular=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
         _need_chain(chain)
         super(BatchCartesianAccelerationConstraint, self).__init__(
-            chain, _six_wide_limits(("linear", linear), ("angular", angular), F, g), discretization_scheme,
+            chain, _box_limits(1, 6, (("linear", linear, 0), ("angular", angular, 3)), None, F, g), discretization_scheme,
             "tool acceleration limit, %d dof" % chain.dof)
         self.linear, self.angular = linear, angular
 
@@ -688,10 +706,9 @@ class BatchToolWrenchConstraint(_BatchChainRows):
 
     def __init__(self, chain, payload, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
         _need_chain(chain)
-        if not isinstance(payload, Payload):
-            raise ValueError("payload must be a toppra_amd.chain.Payload, got %s" % type(payload).__name__)
+        _batch._need(payload, "payload", "Payload")
         super(BatchToolWrenchConstraint, self).__init__(
-            chain, _six_wide_limits(("force", force), ("moment", moment), F, g), discretization_scheme,
+            chain, _box_limits(1, 6, (("force", force, 0), ("moment", moment, 3)), None, F, g), discretization_scheme,
             "tool wrench limit, %d dof" % chain.dof)
         self.payload = payload
         self.force, self.moment = force, moment
@@ -762,14 +779,10 @@ class BatchBaseWrenchConstraint(_BatchChainRows):
     Per-trajectory mounts, a floating base, a true (conic) friction cone and non-rectangular footprints are out of scope."""
 
     def __init__(self, robot, mount=None, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
-        if not isinstance(robot, (SerialChain, KinematicTree)):
-            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
-        if mount is None:
-            mount = Mount()
-        if not isinstance(mount, Mount):
-            raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+        _need_robot(robot)
+        mount = _batch._mount(mount)
         super(BatchBaseWrenchConstraint, self).__init__(
-            robot, _six_wide_limits(("force", force), ("moment", moment), F, g), discretization_scheme,
+            robot, _box_limits(1, 6, (("force", force, 0), ("moment", moment, 3)), None, F, g), discretization_scheme,
             "base wrench limit, %d dof" % robot.dof)
         self.robot, self.mount = robot, mount
         self.force, self.moment = force, moment
@@ -785,51 +798,6 @@ class BatchBaseWrenchConstraint(_BatchChainRows):
 
     def _terms(self, q, qs, qss):
         return self.robot.base_wrench_terms(q, qs, qss, self.mount)
-
-
-def _section_limits(count, force, moment, F, g):
-    """The limits of a constraint on the 6 S-wide wrenches of S sections, section-major, given either as boxes -- ``force`` /
-    ``moment``: None, a scalar, [S] (a magnitude per section), [S, 3, 2] or [B, S, 3, 2] (lower, upper) -- or as rows F, g:
-    (F, g, the B of per-trajectory boxes or None).  Each part given adds six rows per section, the signed identity on that
-    part with g = [upper; -lower]; the force's rows come first within a section, the sections follow in order."""
-    boxes, rows = force is not None or moment is not None, F is not None or g is not None
-    if boxes and rows:
-        raise ValueError("give the limits either as force / moment or as F and g, not both")
-    if not boxes and not rows:
-        raise ValueError("no limit given: one of force, moment, or F with g, is required")
-    width = 6 * count
-    if not boxes:
-        return _row_limits(F, g, width, "[m, 6 S], [B, m, 6 S] or [B, N+1, m, 6 S] with 6 S = %d" % width)
-    limit_batch, parts = None, []
-    for name, lim, at in (("force", force, 0), ("moment", moment, 3)):
-        if lim is None:
-            continue
-        lim = _host(lim)
-        if lim.ndim == 0:
-            lim = np.full(count, float(lim))
-        if lim.shape == (count,):
-            lim = np.stack([np.repeat(-lim[:, None], 3, 1), np.repeat(lim[:, None], 3, 1)], -1)
-        if lim.ndim not in (3, 4) or lim.shape[-3:] != (count, 3, 2):
-            raise ValueError("%s must be a scalar or have shape [S], [S, 3, 2] or [B, S, 3, 2] with S = %d, got %s"
-                             % (name, count, list(lim.shape)))
-        if not np.all(np.isfinite(lim)):
-            raise ValueError("%s holds a limit that is not finite" % name)
-        if np.any(lim[..., 0] > lim[..., 1]):
-            raise ValueError("%s holds a lower limit above its upper limit" % name)
-        if lim.ndim == 4:
-            if limit_batch not in (None, lim.shape[0]):
-                raise ValueError("force and moment are given per trajectory for %d and %d trajectories" % (limit_batch, lim.shape[0]))
-            limit_batch = int(lim.shape[0])
-        parts.append((at, np.concatenate((lim[..., 1], -lim[..., 0]), -1)))  # [..., S, 6] = [upper; -lower] per section
-    per = 6 * len(parts)  # rows per section
-    Fm = np.zeros((per * count, width))
-    for k in range(count):
-        for j, (at, _) in enumerate(parts):
-            r, c = per * k + 6 * j, 6 * k + at
-            Fm[r:r + 3, c:c + 3], Fm[r + 3:r + 6, c:c + 3] = np.eye(3), -np.eye(3)
-    lead = () if limit_batch is None else (limit_batch,)
-    gm = np.concatenate([np.broadcast_to(gp, lead + (count, 6)) for _, gp in parts], -1)  # [..., S, per]
-    return Fm, np.ascontiguousarray(gm.reshape(lead + (per * count,))), limit_batch
 
 
 class BatchJointLoadConstraint(_BatchChainRows):
@@ -863,13 +831,10 @@ class BatchJointLoadConstraint(_BatchChainRows):
     scope."""
 
     def __init__(self, robot, sections, force=None, moment=None, F=None, g=None, discretization_scheme=DiscretizationType.Interpolation):
-        if not isinstance(robot, (SerialChain, KinematicTree)):
-            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
-        if not isinstance(sections, JointSections):
-            raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
-        sections.on(robot)  # (a joint outside the robot: ValueError)
+        _need_robot(robot)
+        _batch._need(sections, "sections", "JointSections").on(robot)  # (a joint outside the robot: ValueError)
         super(BatchJointLoadConstraint, self).__init__(
-            robot, _section_limits(sections.count, force, moment, F, g), discretization_scheme,
+            robot, _box_limits(sections.count, 6, (("force", force, 0), ("moment", moment, 3)), "S", F, g), discretization_scheme,
             "joint load limit, %d dof, %d sections" % (robot.dof, sections.count))
         self.robot, self.sections = robot, sections
         self.force, self.moment = force, moment
@@ -922,8 +887,7 @@ class BatchJointLoadConstraint(_BatchChainRows):
         |(f_x, f_y)| <= ``radial`` as the polygon with ``sides`` sides INSCRIBED in the circle -- the rows never allow more than
         the data sheet does --, and the axial force -``axial`` <= f_z <= ``axial``.  Each limit: None, a scalar or [S].  The moment
         about the axis is the joint's torque and is left to the torque limit."""
-        if not isinstance(sections, JointSections):
-            raise ValueError("sections must be a toppra_amd.chain.JointSections, got %s" % type(sections).__name__)
+        _batch._need(sections, "sections", "JointSections")
         F, g = cls.bearing_rows(sections.count, tilting, axial, radial, sides)
         return cls(robot, sections, F=F, g=g, **kwargs)
 
@@ -931,38 +895,6 @@ class BatchJointLoadConstraint(_BatchChainRows):
         w0, wa, wb = self.robot.joint_wrench_terms(q, qs, qss, self.sections)
         flat = tuple(q.shape[:2]) + (6 * self.sections.count,)
         return w0.reshape(flat), wa.reshape(flat), wb.reshape(flat)
-
-
-def _point_limits(count, linear, F, g):
-    """The limits of a constraint on the 3 P linear accelerations of P control points, given either as boxes -- ``linear``: a
-    scalar, [P] (amax per point), [P, 3, 2] or [B, P, 3, 2] (lower, upper) -- or as rows F, g: (F, g, the B of per-trajectory
-    boxes or None).  A box gives six rows per point, the signed identity on that point's three components with
-    g = [upper; -lower], the points in order."""
-    rows = F is not None or g is not None
-    if linear is not None and rows:
-        raise ValueError("give the limits either as linear or as F and g, not both")
-    if linear is None and not rows:
-        raise ValueError("no limit given: linear, or F with g, is required")
-    width = 3 * count
-    if linear is not None:
-        lim = _host(linear)
-        if lim.ndim == 0:
-            lim = np.full(count, float(lim))
-        if lim.shape == (count,):
-            lim = np.stack([np.repeat(-lim[:, None], 3, 1), np.repeat(lim[:, None], 3, 1)], -1)
-        if lim.ndim not in (3, 4) or lim.shape[-3:] != (count, 3, 2):
-            raise ValueError("linear must be a scalar or have shape [P], [P, 3, 2] or [B, P, 3, 2] with P = %d, got %s"
-                             % (count, list(lim.shape)))
-        if not np.all(np.isfinite(lim)):
-            raise ValueError("linear holds a limit that is not finite")
-        if np.any(lim[..., 0] > lim[..., 1]):
-            raise ValueError("linear holds a lower limit above its upper limit")
-        Fm = np.zeros((2 * width, width))
-        for p in range(count):
-            Fm[6 * p:6 * p + 3, 3 * p:3 * p + 3], Fm[6 * p + 3:6 * p + 6, 3 * p:3 * p + 3] = np.eye(3), -np.eye(3)
-        gm = np.concatenate((lim[..., 1], -lim[..., 0]), -1)  # [..., P, 6] = [upper; -lower] per point
-        return Fm, np.ascontiguousarray(gm.reshape(gm.shape[:-2] + (2 * width,))), (int(lim.shape[0]) if lim.ndim == 4 else None)
-    return _row_limits(F, g, width, "[m, 3 P], [B, m, 3 P] or [B, N+1, m, 3 P] with 3 P = %d" % width)
 
 
 class BatchPointAccelerationConstraint(_BatchChainRows):
@@ -990,7 +922,7 @@ class BatchPointAccelerationConstraint(_BatchChainRows):
         _need_chain(chain)
         _need_points(points, chain)
         super(BatchPointAccelerationConstraint, self).__init__(
-            chain, _point_limits(points.count, linear, F, g), discretization_scheme,
+            chain, _box_limits(points.count, 3, (("linear", linear, 0),), "P", F, g), discretization_scheme,
             "control-point acceleration limit, %d dof, %d points" % (chain.dof, points.count))
         self.points = points
         self.linear = linear
@@ -1002,10 +934,6 @@ class BatchPointAccelerationConstraint(_BatchChainRows):
 
 
 # ---- batched first-order constraints: they only tighten a stage's variable box (BatchTOPPRA(..., constraints=[...])) -------
-
-def _shape_of(x):
-    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
-
 
 class _BatchFirstOrder(LinearConstraint):
     """Shared part of the batched constraints that produce only ``ubound`` / ``xbound``: they become bound sources of
@@ -1148,8 +1076,7 @@ class BatchCartesianVelocityNormConstraint(_BatchChainBound):
         if len(lshape) > 1:
             raise ValueError("limit must be a scalar or have shape [B], got %s" % (lshape,))
         self._limit_batch = lshape[0] if lshape else None
-        host_limit = limit.detach().cpu().numpy() if hasattr(limit, "detach") else np.asarray(limit, dtype=np.float64)
-        if not np.all(host_limit > 0):
+        if not np.all(_host(limit) > 0):
             raise ValueError("limit must be > 0 (NaN is refused; 0 / 0 at a standstill would be a NaN bound)")
         if S is not None:
             if _shape_of(S) != (6, 6):
@@ -1221,12 +1148,8 @@ class BatchMomentumConstraint(_BatchChainBound):
 
     def __init__(self, robot, linear=None, angular=None, energy=None, mount=None, links=None):
         super(BatchMomentumConstraint, self).__init__()
-        if not isinstance(robot, (SerialChain, KinematicTree)):
-            raise ValueError("robot must be a toppra_amd.chain.SerialChain or KinematicTree, got %s" % type(robot).__name__)
-        if mount is None:
-            mount = Mount()
-        if not isinstance(mount, Mount):
-            raise ValueError("mount must be a toppra_amd.chain.Mount, got %s" % type(mount).__name__)
+        _need_robot(robot)
+        mount = _batch._mount(mount)
         if linear is None and angular is None and energy is None:
             raise ValueError("no limit given: one of linear, angular, energy is required")
         if links is not None:
