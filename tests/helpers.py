@@ -3,6 +3,8 @@ import os
 
 import numpy as np
 
+from tests.solver_support import same_array
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -49,18 +51,15 @@ def fixture_problem(fx):
 
 
 def assert_same(got, want, what, atol=0.0):
-    """Bit-exact by default (NaNs must coincide); atol > 0 relaxes to |diff| <= atol."""
+    """Bit-exact by default (tests/solver_support.py::same_array: NaNs must coincide); atol > 0 relaxes to |diff| <= atol."""
+    if atol == 0.0:
+        return same_array(got, want, what)
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, (what, got.shape, want.shape)
     assert np.array_equal(np.isnan(got), np.isnan(want)), what + ": NaN pattern differs"
-    if atol == 0.0:
-        if not np.array_equal(got, want, equal_nan=True):
-            dev = np.nanmax(np.abs(got - want))
-            raise AssertionError("%s not bit-exact, max deviation %g" % (what, dev))
-    else:
-        m = np.isfinite(want)
-        dev = np.max(np.abs(got[m] - want[m])) if m.any() else 0.0
-        assert dev <= atol, "%s deviates by %g > %g" % (what, dev, atol)
+    m = np.isfinite(want)
+    dev = np.max(np.abs(got[m] - want[m])) if m.any() else 0.0
+    assert dev <= atol, "%s deviates by %g > %g" % (what, dev, atol)
 
 
 def path_from_tables(coef, breaks):

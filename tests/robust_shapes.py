@@ -4,9 +4,8 @@ tests/test_oracle_robust_independent.py (the CPU restatement of their method): n
 A problem is the tuple (coef, breaks, grid, vlim or None, alim, sd_start or None, sd_end or None)."""
 import numpy as np
 
-from tests import test_oracle_vs_reference as T
-from tests.test_gpu_instantiations import _problem
-from tests.test_gpu_slim_blocks import irregular_batch, own_breakpoints, same
+from tests.solver_support import (EXTREME_KINDS, extreme_limit_batch, instantiation_problem, irregular_batch, oracle_flags, own_breakpoints,
+                                  problem, same)
 from toppra_amd import batch
 
 ELL = [1e-3, 5e-2, 9e-3]  # examples/plot_robust_kinematics.py:26-28
@@ -15,8 +14,8 @@ ELL = [1e-3, 5e-2, 9e-3]  # examples/plot_robust_kinematics.py:26-28
 def restatement(oracle, prob, interp, want_X):
     """prob: (coef, breaks, grid, vlim or None, alim, sd_start or None, sd_end or None).  The whole batch, every host thread."""
     coef, breaks, grid, vlim, alim, sd0, sd1 = prob
-    flags = oracle.FLAG_ACC | (oracle.FLAG_VEL if vlim is not None else 0) | (oracle.FLAG_INTERP if interp else 0)
-    return oracle.robust_solve_batch(coef, breaks, grid, vlim, alim, ELL, sd0, sd1, flags=flags, want_X=want_X, nthreads=0)
+    return oracle.robust_solve_batch(coef, breaks, grid, vlim, alim, ELL, sd0, sd1, flags=oracle_flags(oracle, vlim is not None, interp),
+                                     want_X=want_X, nthreads=0)
 
 
 def keys(want_X):
@@ -28,8 +27,8 @@ def ok_share(ref):
 
 
 def instantiation_case(d, per_traj_grid):
-    """Part 1's batch: tests/test_gpu_instantiations.py::_problem (96 x d x 48; sd_start and sd_end non-zero on 30 %)."""
-    data, grid, sd0, sd1 = _problem(d, 1100 + d, per_traj_grid)
+    """Part 1's batch: that of tests/test_gpu_instantiations.py (96 x d x 48; sd_start and sd_end non-zero on 30 %)."""
+    data, grid, sd0, sd1 = instantiation_problem(96, d, 48, 1100 + d, per_traj_grid)
     return (data["coef"], data["breaks"], grid, data["vlim"], data["alim"], sd0, sd1)
 
 
@@ -83,7 +82,7 @@ def table_case(d, n_waypoints, own, B=64, N=24):
 def many_dof_case(d, B=64, N=24):
     """Part 4 / 6: the irregular batch at 17..32 dof, six waypoints."""
     data = irregular_batch(B, d, N, 6, seed=3000 + d)
-    return (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd0"], data["sd1"])
+    return problem(data) + (data["sd0"], data["sd1"])
 
 
 PARITY_CASES = ["per-trajectory grid, 10 dof", "long table, 7 dof, 43 waypoints", "20 dof"]
@@ -149,8 +148,8 @@ def check_relaxed_twins(solve, d, slow):
 
 def extreme_case(d, N):
     """Part 9: 16 rounds of the twelve kinds and the `plain` control; breakpoints and grid per trajectory."""
-    data = T.extreme_limit_batch(208, d, N, d)
-    return data, (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd0"], data["sd1"])
+    data = extreme_limit_batch(208, d, N, d)
+    return data, problem(data) + (data["sd0"], data["sd1"])
 
 
 EXTREME_SHAPES = [(7, 24), (12, 16), (3, 20)]
@@ -171,4 +170,4 @@ def check_extreme_counts(ref, twin, kinds):
     assert (ref["status"][ahuge][twin["status"][ahuge] == 0] == 0).all(), np.flatnonzero(ahuge & (twin["status"] == 0) & (ref["status"] != 0))
     assert (twin["status"][ahuge] == 0).sum() >= 8
     assert (ref["status"][kinds == "inverted"] == 1).all() and (ref["status"][kinds == "plain"] == 0).sum() >= 8
-    return {k: int((ref["status"][kinds == k] == 0).sum()) for k in T.EXTREME_KINDS + ("plain",)}
+    return {k: int((ref["status"][kinds == k] == 0).sum()) for k in EXTREME_KINDS + ("plain",)}

@@ -1,7 +1,7 @@
 """Limits at the edge of the number range on every kernel family: infinite, 1e38 / 1e300, subnormal-squared, one-sided and
-inverted limits, standing joints, shifted path parameters (tests/test_oracle_vs_reference.py::extreme_limit_problems -- the
+inverted limits, standing joints, shifted path parameters (tests/solver_support.py::extreme_limit_problems -- the
 generator whose problems the real reference solved for tests/golden/oracle_vs_reference_extreme.npz, and to whose outputs the
-CPU oracle is pinned bit for bit there).
+CPU oracle is pinned bit for bit in tests/test_oracle_vs_reference.py).
 
 The fp32 velocity bound exists in six restatements on the device (tpr_device.hpp, tpr_group / tpr_wave / tpr_pair / tpr_cert
 twice), four of them restructured around a running fp64 minimum, a wave-level ballot and a positive-lower-limit shortcut; the
@@ -16,45 +16,28 @@ in, and no tolerance appears anywhere in this module.
 Every entry that reads vlim / alim runs this family, including the robust one: robust_solve_batch has its own restatement in the
 oracle and takes it in tests/test_gpu_robust_shapes.py, part 9.
 """
-import csv
 import functools
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import test_oracle_vs_reference as T
+from tests import solver_support as T
+from tests.solver_support import CERT_FEASIBLE_FROM, CERT_SOLVE_FROM, PAIR_FROM, dispatches, oracle_flags, problem, same, same_array, traced
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B_SMALL = 64 * 3 + 37
 ACC_KINDS = ("ainf", "ainf_one", "ahuge", "inverted")
-# pick_variant (toppra_amd/csrc/tpr_kernels.hip): family 3 solves from 9216 trajectories up to 8 dof, computes feasible sets from
-# 8192, and family 5 serves 2560 .. 9215 trajectories up to 7 dof.  A change there must be copied here.
-CERT_SOLVE_FROM, CERT_FEASIBLE_FROM, PAIR_FROM = 9216, 8192, 2560
 
 
 # --------------------------------------------------------------------------------------------------------------------------
-# shared setup
+# shared setup (comparison, flags, the generator and the sizes of the automatic choice: tests/solver_support.py)
 
 @functools.lru_cache(maxsize=8)
 def extreme(B, d, N, seed=0, kinds=T.EXTREME_KINDS):
     return T.extreme_limit_batch(B, d, N, seed, kinds=kinds)
-
-
-def problem(data, vel=True):
-    return (data["coef"], data["breaks"], data["grid"], data["vlim"] if vel else None, data["alim"])
-
-
-def oracle_flags(oracle, vel, interp):
-    return oracle.FLAG_ACC | (oracle.FLAG_VEL if vel else 0) | (oracle.FLAG_INTERP if interp else 0)
 
 
 def oracle_solve(oracle, data, interp, vel=True):
@@ -69,25 +52,6 @@ def wrappers(oracle, data, interp, vel=True):
     coef, breaks, grid, vlim, alim = problem(data, vel)
     for b in range(coef.shape[0]):
         yield oracle.Wrapper(coef[b], breaks[b], grid[b], None if vlim is None else vlim[b], alim[b], flags=oracle_flags(oracle, vel, interp))
-
-
-def same(got, want, keys, what):
-    """Bit for bit on every key (NaNs must coincide), exact on status; names the first trajectories that differ and their kinds."""
-    kinds = what[0]["kinds"] if isinstance(what[0], dict) else None
-    what = what[1:] if kinds is not None else what
-    for k in ("status",) + tuple(keys):
-        if k == "status" and "status" not in want:
-            continue
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, (what, k, g.shape, w.shape)
-        if not np.array_equal(g, w, equal_nan=(k != "status")):
-            differs = ~((g == w) | ((g != g) & (w != w))).reshape(g.shape[0], -1).all(axis=1)
-            where = np.flatnonzero(differs)
-            raise AssertionError((what, k, int(differs.sum()), where[:8], None if kinds is None else sorted(set(kinds[where]))))
-
-
-def same_array(got, want, what):
-    same({"x": got}, {"x": want}, ("x",), what)
 
 
 def not_vacuous(ref, data, kinds=T.EXTREME_KINDS):
@@ -118,7 +82,7 @@ def test_solve_on_every_family(gpu, oracle, d, N, interp):
     not_vacuous(ref, data)
     for kw in solve_variants(d):
         got = batch.solve_batch(*problem(data), data["sd0"], data["sd1"], interp, want_sd=True, **kw)
-        same(got, ref, ("K", "sd2", "sd", "u"), (data, d, interp, kw))
+        same(got, ref, ("K", "sd2", "sd", "u"), (d, interp, kw), data["kinds"])
 
 
 @pytest.mark.parametrize("d,N", [(3, 40), (7, 50), (12, 30)])
@@ -130,7 +94,7 @@ def test_solve_with_acceleration_limits_alone(gpu, oracle, d, N):
         not_vacuous(ref, data, ACC_KINDS)
         for kw in solve_variants(d):
             got = batch.solve_batch(*problem(data, False), data["sd0"], data["sd1"], interp, want_sd=True, **kw)
-            same(got, ref, ("K", "sd2", "sd", "u"), (data, d, interp, kw))
+            same(got, ref, ("K", "sd2", "sd", "u"), (d, interp, kw), data["kinds"])
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -139,7 +103,7 @@ def test_solve_with_acceleration_limits_alone(gpu, oracle, d, N):
 _TRACED_CHILD = """
 import sys
 import numpy as np
-from tests import test_oracle_vs_reference as T
+from tests import solver_support as T
 from toppra_amd import batch
 out = {}
 for name, B, N in (("solve3", %d, 24), ("feasible3", %d, 24), ("solve5", %d, 24)):
@@ -160,39 +124,21 @@ def test_the_sizes_at_which_the_throughput_kernels_are_chosen(gpu, oracle):
     2560 + 37 (family 5 solves) -- made in a fresh child process under the kernel tracer (no counters), whose statistics say that
     the certified lane kernels and the two-trajectories-per-wave kernel are what ran, and whose outputs are compared with the oracle
     on every trajectory here."""
-    rp = shutil.which("rocprofv3")
-    assert rp, "rocprofv3 is not on PATH: the dispatch of the automatic choice cannot be traced (GPU tests do not skip here)"
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    with tempfile.TemporaryDirectory(prefix="tpr_trace_") as tmp:
-        npz = os.path.join(tmp, "out.npz")
-        cmd = ["timeout", "-k", "10", "240", rp, "--kernel-trace", "--stats", "-d", tmp, "-o", "run", "--output-format", "csv", "--",
-               sys.executable, "-c", _TRACED_CHILD, npz]
-        run = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert run.returncode == 0, (run.returncode, run.stdout[-3000:])
-        assert "traced child done" in run.stdout, run.stdout[-3000:]
-        stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats*.csv"), recursive=True)
-        assert stats, ([os.path.join(r, f) for r, _, fs in os.walk(tmp) for f in fs], run.stdout[-2000:])
-        calls = []  # (kernel name, dispatches)
-        for path in stats:
-            with open(path, newline="") as fh:
-                calls += [(r["Name"], int(r["Calls"])) for r in csv.DictReader(fh)]
-        with np.load(npz) as z:
+    with traced(_TRACED_CHILD, os.path.join("{tmp}", "out.npz")) as (calls, tmp):
+        with np.load(os.path.join(tmp, "out.npz")) as z:
             out = {k: z[k] for k in z.files}
-
-    def ran(kernel, d=None):  # demangled names, or ...<kernel>ILi<d>E...: the dof is the first template argument where there is one
-        return sum(c for n, c in calls if (kernel in n if d is None else (kernel + "<%d," % d in n or kernel + "ILi%dE" % d in n)))
-    seen = {k: ran(k, 7) for k in ("cert_solve_kernel", "cert_feasible_kernel", "group_solve_kernel", "group_feasible_kernel")}
-    seen.update({k: ran(k) for k in ("pair_solve_kernel", "wave_solve_kernel", "lane_solve_kernel")})
+    seen = {k: dispatches(calls, k, 7) for k in ("cert_solve_kernel", "cert_feasible_kernel", "group_solve_kernel", "group_feasible_kernel")}
+    seen.update({k: dispatches(calls, k) for k in ("pair_solve_kernel", "wave_solve_kernel", "lane_solve_kernel")})
     assert seen["cert_solve_kernel"] >= 1 and seen["cert_feasible_kernel"] >= 1 and seen["pair_solve_kernel"] >= 1, seen
     assert not (seen["group_solve_kernel"] or seen["group_feasible_kernel"] or seen["wave_solve_kernel"] or seen["lane_solve_kernel"]), seen
     for name, B in (("solve3", CERT_SOLVE_FROM), ("solve5", PAIR_FROM)):
         data = T.extreme_limit_batch(B + 37, 7, 24, 2)
         ref = oracle_solve(oracle, data, True)
         not_vacuous(ref, data)
-        same({k: out[name + "_" + k] for k in ("K", "sd2", "sd", "u", "status")}, ref, ("K", "sd2", "sd", "u"), (data, name))
+        same({k: out[name + "_" + k] for k in ("K", "sd2", "sd", "u", "status")}, ref, ("K", "sd2", "sd", "u"), (name,), data["kinds"])
     data = T.extreme_limit_batch(CERT_FEASIBLE_FROM + 37, 7, 24, 2)
     want = np.stack([w.compute_feasible_sets() for w in wrappers(oracle, data, True)])
-    same_array(out["feasible3_X"], want, (data, "feasible3"))
+    same_array(out["feasible3_X"], want, ("feasible3",), data["kinds"])
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -218,7 +164,7 @@ def test_controllable_sets(gpu, oracle, d, N):
             assert np.isnan(want).any() and not np.isnan(want[data["kinds"] == "plain"]).all()
             for kw in (dict(), dict(variant=1), dict(variant=2), dict(variant=3), dict(variant=4), dict(variant=2, strict=True)):
                 K = batch.controllable_sets_batch(*problem(data), sdmin, sdmax, interp, **kw)
-                same_array(K, want, (data, d, interp, bool(sdmax.any()), kw))
+                same_array(K, want, (d, interp, bool(sdmax.any()), kw), data["kinds"])
 
 
 @pytest.mark.parametrize("d,N", SET_SHAPES)
@@ -228,7 +174,7 @@ def test_feasible_sets(gpu, oracle, d, N):
         want = np.stack([w.compute_feasible_sets() for w in wrappers(oracle, data, interp)])
         kws = [dict(), dict(variant=1), dict(variant=2), dict(variant=3), dict(variant=4), dict(variant=2, strict=True)]
         for kw in kws + ([dict(variant=3, sound=True)] if interp else []):
-            same_array(batch.feasible_sets_batch(*problem(data), interp, **kw), want, (data, d, interp, kw))
+            same_array(batch.feasible_sets_batch(*problem(data), interp, **kw), want, (d, interp, kw), data["kinds"])
 
 
 @pytest.mark.parametrize("d,N", SET_SHAPES)
@@ -240,8 +186,8 @@ def test_reachable_sets(gpu, oracle, d, N):
         for sdmin, sdmax in ((lo, hi), (zero, zero)):
             want = [w.compute_reachable_sets(float(sdmin[b]), float(sdmax[b])) for b, w in enumerate(wrappers(oracle, data, interp))]
             L, X = batch.reachable_sets_batch(*problem(data), sdmin, sdmax, interp, want_X=True)
-            same_array(L, np.stack([w[0] for w in want]), (data, d, interp, "L"))
-            same_array(X, np.stack([w[1] for w in want]), (data, d, interp, "X"))
+            same_array(L, np.stack([w[0] for w in want]), (d, interp, "L"), data["kinds"])
+            same_array(X, np.stack([w[1] for w in want]), (d, interp, "X"), data["kinds"])
 
 
 @pytest.mark.parametrize("d,N", SET_SHAPES)
@@ -264,7 +210,7 @@ def test_desired_duration(gpu, oracle, d, N):
             ref["sd"] = np.sqrt(ref["sd2"])
         for variant in (0, 2, 3):
             got = batch.solve_desired_duration_batch(*problem(data), desired, data["sd0"], data["sd1"], variant=variant, interpolation=interp)
-            same(got, ref, ("K", "sd2", "sd", "u", "alpha"), (data, d, interp, variant))
+            same(got, ref, ("K", "sd2", "sd", "u", "alpha"), (d, interp, variant), data["kinds"])
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -289,13 +235,13 @@ def test_rows(gpu, oracle, d, N, interp):
     assert ((hi > 0) & (hi < T.FLT_MIN_NORMAL)).any()  # fp32 subnormals, as the reference's fixture holds them
     so = batch.second_order_rows_batch(*problem(data), [], interp)
     for k in ("a", "b", "c", "low", "high"):
-        same_array(so[k], rows[k], (data, d, interp, "second_order_rows_batch", k))
-    same_array(so["deltas"], np.diff(data["grid"], axis=1), (data, d, interp, "deltas"))
+        same_array(so[k], rows[k], (d, interp, "second_order_rows_batch", k), data["kinds"])
+    same_array(so["deltas"], np.diff(data["grid"], axis=1), (d, interp, "deltas"), data["kinds"])
     dense = (rows["a"], rows["b"], rows["c"], rows["low"], rows["high"], so["deltas"])
     fused = batch.solve_batch(*problem(data), data["sd0"], data["sd1"], interp, want_sd=True)
     got = batch.solve_dense_batch(*dense, data["sd0"], data["sd1"], want_sd=True)
-    same(got, fused, ("K", "sd2", "sd", "u"), (data, d, interp, "dense rows vs fused"))
-    same_array(batch.feasible_sets_dense_batch(*dense), batch.feasible_sets_batch(*problem(data), interp), (data, d, interp, "dense X"))
+    same(got, fused, ("K", "sd2", "sd", "u"), (d, interp, "dense rows vs fused"), data["kinds"])
+    same_array(batch.feasible_sets_dense_batch(*dense), batch.feasible_sets_batch(*problem(data), interp), (d, interp, "dense X"), data["kinds"])
 
 
 # --------------------------------------------------------------------------------------------------------------------------

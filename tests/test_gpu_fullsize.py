@@ -6,6 +6,7 @@ import pytest
 
 from toppra_amd import batch
 from tests.helpers import need_reference_solver
+from tests.solver_support import irregular_batch, near_parallel_family, oracle_flags, problem, same, same_array
 
 pytestmark = pytest.mark.gpu
 
@@ -40,26 +41,21 @@ def _invariants(data, out, N):
 @pytest.mark.parametrize("B,d,N", [(65536, 7, 200), (4096, 7, 200), (65536, 6, 500)])
 def test_full_size_properties(gpu, oracle, B, d, N):
     data = batch.make_synthetic_batch(B, d, N)
-    out = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    out = batch.solve_batch(*problem(data))
     _invariants(data, out, N)
     # idempotence: a second launch returns the same bits
-    again = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
-    for k in ("K", "sd2", "u", "status"):
-        assert np.array_equal(out[k], again[k], equal_nan=True)
+    same(batch.solve_batch(*problem(data)), out, ("K", "sd2", "u"), "a second launch")
     # exact oracle parity on a random sample (seconds on the host)
     idx = np.sort(np.random.default_rng(1).choice(B, size=1024 if N <= 200 else 256, replace=False))
     ref = oracle.solve_batch(data["coef"][idx], data["breaks"], data["grid"], data["vlim"][idx], data["alim"][idx],
                              nthreads=0)
-    assert np.array_equal(out["status"][idx], ref["status"])
-    for k in ("K", "sd2", "u"):
-        assert np.array_equal(out[k][idx], ref[k], equal_nan=True), k
+    same({k: out[k][idx] for k in ("K", "sd2", "u", "status")}, ref, ("K", "sd2", "u"), "oracle sample")
     # the kernel families agree bit for bit on a 4096 slice (the default is family 3 at 65536, family 4 at 4096)
     sl = slice(0, 4096)
     for variant in (1, 2, 4):
         v = batch.solve_batch(data["coef"][sl], data["breaks"], data["grid"], data["vlim"][sl], data["alim"][sl],
                               variant=variant)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(out[k][sl], v[k], equal_nan=True), (variant, k)
+        same(v, {k: out[k][sl] for k in ("K", "sd2", "u", "status")}, ("K", "sd2", "u"), (variant,))
 
 
 @pytest.mark.parametrize("B,d,N,seed", [(65536, 7, 200, 20240924), (32768, 6, 500, 3), (16384, 3, 100, 5),
@@ -81,8 +77,7 @@ def test_lower_bound_shortcut_is_exact(gpu, B, d, N, seed):
         # per wave (default for small batches)
         for variant in (2, 3, 4):
             fast = batch.solve_batch(*args, variant=variant)
-            for k in ("K", "sd2", "u", "status"):
-                assert np.array_equal(fast[k], full[k], equal_nan=True), (variant, k)
+            same(fast, full, ("K", "sd2", "u"), (variant,))
 
 
 @pytest.mark.parametrize("B,d,N,seed", [(65536, 7, 200, 21), (20480, 4, 120, 22), (16384, 8, 64, 23)])
@@ -101,8 +96,7 @@ def test_collocation_on_the_certified_lane_kernel(gpu, B, d, N, seed):
         full = batch.solve_batch(*args, strict=True)
         for kw in (dict(variant=3), dict()):
             fast = batch.solve_batch(*args, **kw)
-            for k in ("K", "sd2", "u", "status"):
-                assert np.array_equal(fast[k], full[k], equal_nan=True), (kw, k)
+            same(fast, full, ("K", "sd2", "u"), (kw,))
         assert (full["status"] == 0).any()
 
 
@@ -128,17 +122,13 @@ def test_certified_lane_kernel_all_dofs(gpu, oracle, d):
         full = batch.solve_batch(*args, strict=True, want_sd=True)
         got = batch.solve_batch(*args, variant=3, want_sd=True)
         auto = batch.solve_batch(*args)
-        for k in ("K", "sd2", "sd", "u", "status"):
-            assert np.array_equal(got[k], full[k], equal_nan=True), (ci, k)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(auto[k], full[k], equal_nan=True), (ci, k)
+        same(got, full, ("K", "sd2", "sd", "u"), (ci, "family 3"))
+        same(auto, full, ("K", "sd2", "u"), (ci, "automatic choice"))
     idx = np.arange(0, B, 7)
     ref = oracle.solve_batch(data["coef"][idx], data["breaks"], data["grid"], data["vlim"][idx], data["alim"][idx],
                              sd0[idx], sd1[idx], nthreads=0)
     got = batch.solve_batch(*cases[0], variant=3)
-    assert np.array_equal(got["status"][idx], ref["status"])
-    for k in ("K", "sd2", "u"):
-        assert np.array_equal(got[k][idx], ref[k], equal_nan=True), k
+    same({k: got[k][idx] for k in ("K", "sd2", "u", "status")}, ref, ("K", "sd2", "u"), "oracle sample")
 
 
 @pytest.mark.parametrize("B,d,N", [(40000, 7, 48), (700, 5, 60), (600, 12, 30)])
@@ -166,14 +156,11 @@ def test_certified_lane_kernel_edge_shapes(gpu, oracle, B, N):
     args = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], sd0, sd1)
     got = batch.solve_batch(*args, variant=3, want_sd=True)
     full = batch.solve_batch(*args, strict=True, want_sd=True)
-    for k in ("K", "sd2", "sd", "u", "status"):
-        assert np.array_equal(got[k], full[k], equal_nan=True), k
+    same(got, full, ("K", "sd2", "sd", "u"), "full iteration")
     n = min(B, 8)
     ref = oracle.solve_batch(data["coef"][:n], data["breaks"], data["grid"], data["vlim"][:n], data["alim"][:n],
                              sd0[:n], sd1[:n], nthreads=0)
-    for k in ("K", "sd2", "u"):
-        assert np.array_equal(got[k][:n], ref[k], equal_nan=True), k
-    assert np.array_equal(got["status"][:n], ref["status"])
+    same({k: got[k][:n] for k in ("K", "sd2", "u", "status")}, ref, ("K", "sd2", "u"), "oracle")
 
 
 @pytest.mark.parametrize("B,d,N", [(300, 7, 50), (200, 12, 40), (129, 2, 33)])
@@ -201,11 +188,9 @@ def test_feasible_sets_on_the_certified_lane_kernel(gpu, oracle, interp):
     args = (coef, data["breaks"], data["grid"], data["vlim"], data["alim"], interp)
     full = batch.feasible_sets_batch(*args, variant=2, strict=True)
     for kw in (dict(), dict(variant=3), dict(variant=3, sound=True)):   # (auto picks family 3 at this size)
-        X = batch.feasible_sets_batch(*args, **kw)
-        assert np.array_equal(X, full, equal_nan=True), kw
+        same_array(batch.feasible_sets_batch(*args, **kw), full, (kw,))
     for b in range(0, B, 4099):
-        flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if interp else 0)
-        w = oracle.Wrapper(coef[b], data["breaks"], data["grid"], data["vlim"][b], data["alim"][b], flags=flags)
+        w = oracle.Wrapper(coef[b], data["breaks"], data["grid"], data["vlim"][b], data["alim"][b], flags=oracle_flags(oracle, True, interp))
         assert np.array_equal(full[b], w.compute_feasible_sets(), equal_nan=True), b
 
 
@@ -215,29 +200,13 @@ def test_headline_batch_oracle_parity_every_trajectory(gpu, oracle):
     against the oracle on every host thread: identical bits, trajectory by trajectory."""
     B, d, N = 65536, 7, 200
     data = batch.make_synthetic_batch(B, d, N)
-    cases = [(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, None)]
-    rng = np.random.default_rng(4242)
-    nw = 6
-    knots = np.concatenate([[0.0], np.sort(rng.random(nw - 2)) * 0.9 + 0.05, [1.0]])
-    way = rng.standard_normal((B, nw, d))
-    still = rng.random((B, d)) < 0.08
-    way = np.where(still[:, None, :], way[:, :1, :], way)
-    coef, breaks = batch.spline_coefficients(knots, way)
-    grid = 0.6 * np.concatenate([[0.0], np.sort(rng.random(N - 1)), [1.0]]) + 0.4 * np.linspace(0, 1, N + 1)
-    vhi = 5 + 25 * rng.random((B, d)); vlo = -(5 + 25 * rng.random((B, d)))
-    vlo = np.where(rng.random((B, d)) < 0.01, 0.05 * rng.random((B, d)), vlo)
-    ahi = 5 + 10 * rng.random((B, d)); alo = -(5 + 10 * rng.random((B, d)))
-    sd0 = np.where(rng.random(B) < 0.4, 0.3 * rng.random(B), 0.0)
-    sd1 = np.where(rng.random(B) < 0.4, 0.3 * rng.random(B), 0.0)
-    cases.append((coef, breaks, grid, np.ascontiguousarray(np.stack([vlo, vhi], -1)),
-                  np.ascontiguousarray(np.stack([alo, ahi], -1)), sd0, sd1))
+    irregular = irregular_batch(B, d, N, 6, seed=4242)
+    cases = [problem(data) + (None, None), problem(irregular) + (irregular["sd0"], irregular["sd1"])]
     for ci, args in enumerate(cases):
         got = batch.solve_batch(*args)
         ref = oracle.solve_batch(*args, nthreads=0)
-        assert np.array_equal(got["status"], ref["status"]), ci
         assert len(np.unique(ref["status"])) >= (1 if ci == 0 else 2)
-        for k in ("K", "sd2", "u"):
-            assert np.array_equal(got[k], ref[k], equal_nan=True), (ci, k)
+        same(got, ref, ("K", "sd2", "u"), (ci,))
 
 
 @pytest.mark.parametrize("B,d,N,seed", [(16384, 7, 120, 1), (16384, 4, 100, 2), (8192, 8, 80, 3)])
@@ -247,31 +216,12 @@ def test_near_parallel_rows_are_bit_exact(gpu, B, d, N, seed):
     either can bind.  This is where the reference's absolute 1e-10 / 1e-8 classifications bite (it declares
     some of these problems infeasible); the default path must return the full iteration's bits, failures
     included."""
-    rng = np.random.default_rng(900 + seed)
-    way = rng.standard_normal((B, 5, d))
-    eps = 10.0 ** rng.uniform(-14, -6, size=B)
-    scale = rng.choice([1.0, -1.0, 0.5, 2.0, 3.0], size=B)
-    src, dst = rng.integers(0, d, size=B), rng.integers(0, d, size=B)
-    dst = np.where(dst == src, (src + 1) % d, dst)
-    rows = np.arange(B)
-    way[rows, :, dst] = way[rows, :, src] * (scale * (1 + eps))[:, None]
-    twist = rng.random(B) < 0.5
-    way[rows[twist], :, dst[twist]] += eps[twist, None] * rng.standard_normal((twist.sum(), 5))
-    coef, breaks = batch.spline_coefficients(np.linspace(0, 1, 5), way)
-    vmax = 10 + 20 * rng.random((B, d))
-    amax = 10 + 2 * rng.random((B, d))
-    amax[rows, dst] = amax[rows, src] * np.abs(scale) * (1 + 0.02 * rng.standard_normal(B))
-    vmax[rows, dst] = vmax[rows, src] * np.abs(scale) * (1 + 0.02 * rng.standard_normal(B))
-    vlim = np.ascontiguousarray(np.stack([-vmax, vmax], -1))
-    alim = np.ascontiguousarray(np.stack([-amax, amax], -1))
-    sd1 = np.where(rng.random(B) < 0.3, 0.2 * rng.random(B), 0.0)
-    args = (coef, breaks, np.linspace(0, 1, N + 1), vlim, alim, None, sd1)
+    args = near_parallel_family(B, d, N, seed)
     full = batch.solve_batch(*args, strict=True)
     assert (full["status"] == 1).sum() >= 1  # the reference itself trips over some of them
     for variant, sound in ((2, False), (3, False), (4, False), (2, True), (3, True)):
         fast = batch.solve_batch(*args, variant=variant, sound=sound)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(fast[k], full[k], equal_nan=True), (variant, sound, k)
+        same(fast, full, ("K", "sd2", "u"), (variant, sound))
 
 
 @pytest.mark.parametrize("B,d,N,seed", [(16384, 7, 60, 1), (16384, 4, 50, 2), (16384, 3, 40, 3), (8192, 8, 48, 4)])
@@ -327,20 +277,14 @@ def test_concurrent_rows_and_sliver_pivots_are_bit_exact(gpu, B, d, N, seed):
         if variant == 3 and d > 13:
             continue
         got = batch.solve_batch(*args, variant=variant)
-        bad = got["status"] != full["status"]
-        for k in ("K", "sd2", "u"):
-            same = (got[k] == full[k]) | (np.isnan(got[k]) & np.isnan(full[k]))
-            bad |= ~same.reshape(B, -1).all(axis=1)
-        assert bad.sum() == 0, (variant, int(bad.sum()), np.flatnonzero(bad)[:4])
+        same(got, full, ("K", "sd2", "u"), (variant,))
         assert np.array_equal(batch.solve_batch(*args, variant=variant, sound=True)["K"], got["K"], equal_nan=True)  # the flag is a no-op
     # ... and `full` is not only the GPU's own full iteration: the first 512 trajectories against the CPU restatement of the
     # reference (oracle/, pinned to the reference's compiled solver), failures of the reference included
     from oracle import oracle as orc
     m = 512
     ref = orc.solve_batch(coef[:m], data["breaks"], grid, data["vlim"][:m], alim[:m], None, sd1[:m], nthreads=0)
-    assert np.array_equal(ref["status"], full["status"][:m])
-    for k in ("K", "sd2", "u"):
-        assert np.array_equal(ref[k], full[k][:m], equal_nan=True), k
+    same({k: full[k][:m] for k in ("K", "sd2", "u", "status")}, ref, ("K", "sd2", "u"), "oracle")
 
 
 def _tool(name):

@@ -9,6 +9,7 @@ import pytest
 
 from tests import kat_vectors as kat
 from tests.helpers import assert_same, batch_fixtures, fixture_problem, golden
+from tests.solver_support import oracle_flags
 from toppra_amd import _capi, batch
 
 pytestmark = pytest.mark.gpu
@@ -151,7 +152,7 @@ def test_reachable_sets_fixture(gpu, oracle, name):
     assert np.isnan(fx["L"]).any()
     assert_same(L, fx["L"], "L")
     assert_same(X, fx["X"], "X")
-    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if interp else 0)
+    flags = oracle_flags(oracle, True, interp)
     for b in (0, 3):
         w = oracle.Wrapper(fx["coef"][b], fx["breaks"], fx["grid"], fx["vlim"][b], fx["alim"][b], flags=flags)
         assert_same(w.compute_reachable_sets(float(fx["sdmin"][b]), float(fx["sdmax"][b]))[0], L[b], "oracle L")

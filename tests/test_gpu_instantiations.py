@@ -12,6 +12,7 @@ sequences of tpr_device.hpp) cannot pass it either.  What a failure here usually
 import numpy as np
 import pytest
 
+from tests.solver_support import instantiation_problem, oracle_flags, per_trajectory_grid, problem, same, same_array
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
@@ -19,56 +20,39 @@ B, N = 96, 48  # one full 64-lane block and a partial one
 
 
 def _problem(d, seed, per_traj_grid):
-    data = batch.make_synthetic_batch(B, d, N, seed=seed)
-    rng = np.random.default_rng(seed)
-    grid = data["grid"]
-    if per_traj_grid:  # TPR_GRID_PER_TRAJ: the grid is read from global memory instead of the block's LDS copy
-        inner = np.sort(rng.random((B, N - 1)), axis=1) * 0.8 + 0.1
-        grid = 0.5 * np.concatenate([np.zeros((B, 1)), inner, np.ones((B, 1))], axis=1) + 0.5 * np.linspace(0, 1, N + 1)[None, :]
-    sd0 = np.where(rng.random(B) < 0.3, np.round(0.1 * rng.random(B) * 1024) / 1024, 0.0)
-    sd1 = np.where(rng.random(B) < 0.3, np.round(0.2 * rng.random(B) * 1024) / 1024, 0.0)
-    return data, grid, sd0, sd1
+    """-> (coef, breaks, grid, vlim, alim), sd_start, sd_end"""
+    data, grid, sd0, sd1 = instantiation_problem(B, d, N, seed, per_traj_grid)
+    return problem(dict(data, grid=grid)), sd0, sd1
 
 
 @pytest.mark.parametrize("d", range(1, 16))
 def test_every_solve_instantiation(gpu, oracle, d):
     for per_traj_grid in (False, True):
-        data, grid, sd0, sd1 = _problem(d, 700 + d, per_traj_grid)
+        prob, sd0, sd1 = _problem(d, 700 + d, per_traj_grid)
         for interp in (True, False):
             for want_sd in (False, True):
-                args = (data["coef"], data["breaks"], grid, data["vlim"], data["alim"], sd0, sd1, interp)
-                want = batch.solve_batch(*args, want_sd=want_sd, variant=2)
-                got = batch.solve_batch(*args, want_sd=want_sd, variant=3)
+                want = batch.solve_batch(*prob, sd0, sd1, interp, want_sd=want_sd, variant=2)
+                got = batch.solve_batch(*prob, sd0, sd1, interp, want_sd=want_sd, variant=3)
                 what = (d, per_traj_grid, interp, want_sd)
-                assert np.array_equal(got["status"], want["status"]), what
-                for k in ("K", "sd2", "u") + (("sd",) if want_sd else ()):
-                    assert np.array_equal(got[k], want[k], equal_nan=True), what + (k,)
+                same(got, want, ("K", "sd2", "u") + (("sd",) if want_sd else ()), what)
                 assert (want["status"] == 0).mean() > 0.5, what
             if not per_traj_grid:  # ... and the rows-across-lanes answer against the CPU restatement of the reference
-                ref = oracle.solve_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], sd0, sd1,
-                                         flags=oracle.DEFAULT_FLAGS if interp else oracle.DEFAULT_FLAGS & ~oracle.FLAG_INTERP, nthreads=4)
-                assert np.array_equal(ref["status"], want["status"]), (d, interp, "oracle status")
-                for k in ("K", "sd2", "u"):
-                    assert np.array_equal(ref[k], want[k], equal_nan=True), (d, interp, "oracle", k)
+                ref = oracle.solve_batch(*prob, sd0, sd1, flags=oracle_flags(oracle, True, interp), nthreads=4)
+                same(want, ref, ("K", "sd2", "u"), (d, interp, "oracle"))
 
 
 @pytest.mark.parametrize("d", range(1, 16))
 def test_every_feasible_sets_and_toppra_sd_instantiation(gpu, d):
     for per_traj_grid in (False, True):
-        data, grid, sd0, sd1 = _problem(d, 800 + d, per_traj_grid)
+        prob, sd0, sd1 = _problem(d, 800 + d, per_traj_grid)
         desired = np.random.default_rng(d).uniform(0.5, 5.0, size=B)
         for interp in (True, False):
             what = (d, per_traj_grid, interp)
-            X2 = batch.feasible_sets_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], interp, variant=2)
-            X3 = batch.feasible_sets_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], interp, variant=3)
-            assert np.array_equal(X3, X2, equal_nan=True), what + ("X",)
-            a = batch.solve_desired_duration_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], desired, sd0, sd1,
-                                                   variant=2, interpolation=interp)
-            b = batch.solve_desired_duration_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], desired, sd0, sd1,
-                                                   variant=3, interpolation=interp)
-            assert np.array_equal(a["status"], b["status"]), what
-            for k in ("K", "sd2", "sd", "u", "alpha"):
-                assert np.array_equal(a[k], b[k], equal_nan=True), what + (k,)
+            X2 = batch.feasible_sets_batch(*prob, interp, variant=2)
+            same_array(batch.feasible_sets_batch(*prob, interp, variant=3), X2, what + ("X",))
+            a = batch.solve_desired_duration_batch(*prob, desired, sd0, sd1, variant=2, interpolation=interp)
+            b = batch.solve_desired_duration_batch(*prob, desired, sd0, sd1, variant=3, interpolation=interp)
+            same(b, a, ("K", "sd2", "sd", "u", "alpha"), what)
 
 
 def _tight_joint_problem(d, seed):
@@ -96,33 +80,22 @@ def _tight_joint_problem(d, seed):
 def test_every_joints_rows_bind_somewhere(gpu, oracle, d):
     data = _tight_joint_problem(d, 900 + d)
     desired = np.random.default_rng(50 + d).uniform(2.0, 40.0, size=4 * d)
-    rng = np.random.default_rng(60 + d)
-    inner = np.sort(rng.random((4 * d, N - 1)), axis=1) * 0.8 + 0.1
-    own_grids = 0.5 * np.concatenate([np.zeros((4 * d, 1)), inner, np.ones((4 * d, 1))], axis=1) + 0.5 * np.linspace(0, 1, N + 1)[None, :]
+    own_grids = per_trajectory_grid(np.random.default_rng(60 + d), 4 * d, N)
     # every instantiation: grid shared (in LDS up to 8 dof) / per trajectory, Interpolation / Collocation, with / without the sd output
     for grid, interp in ((data["grid"], True), (data["grid"], False), (own_grids, True), (own_grids, False)):
-        args = (data["coef"], data["breaks"], grid, data["vlim"], data["alim"], None, None, interp)
-        want = batch.solve_batch(*args, variant=2)
-        got = batch.solve_batch(*args, variant=3)
-        got_sd = batch.solve_batch(*args, want_sd=True, variant=3)
-        for k in ("status", "K", "sd2", "u"):
-            assert np.array_equal(got_sd[k], want[k], equal_nan=True), (d, interp, grid.ndim, "family 3 with sd output", k)
-        ref = oracle.solve_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], None, None,
-                                 flags=oracle.DEFAULT_FLAGS if interp else oracle.DEFAULT_FLAGS & ~oracle.FLAG_INTERP, nthreads=4)
+        prob = problem(dict(data, grid=grid))
+        want = batch.solve_batch(*prob, None, None, interp, variant=2)
+        got = batch.solve_batch(*prob, None, None, interp, variant=3)
+        got_sd = batch.solve_batch(*prob, None, None, interp, want_sd=True, variant=3)
+        same(got_sd, want, ("K", "sd2", "u"), (d, interp, grid.ndim, "family 3 with sd output"))
+        ref = oracle.solve_batch(*prob, None, None, flags=oracle_flags(oracle, True, interp), nthreads=4)
         assert (ref["status"] == 0).mean() > 0.5, (d, interp, grid.ndim)
-        for k in ("status", "K", "sd2", "u"):
-            assert np.array_equal(want[k], ref[k], equal_nan=True), (d, interp, "family 2 vs oracle", k)
-            assert np.array_equal(got[k], ref[k], equal_nan=True), (d, interp, "family 3 vs oracle", k)
+        same(want, ref, ("K", "sd2", "u"), (d, interp, "family 2 vs oracle"))
+        same(got, ref, ("K", "sd2", "u"), (d, interp, "family 3 vs oracle"))
         for v in (1, 4) + ((5,) if d <= 7 else ()):  # (the other families on the same batch: one trajectory per lane / wave, two per wave)
-            other = batch.solve_batch(*args, variant=v)
-            for k in ("status", "K", "sd2", "u"):
-                assert np.array_equal(other[k], ref[k], equal_nan=True), (d, interp, "family %d vs oracle" % v, k)
-        X2 = batch.feasible_sets_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], interp, variant=2)
-        X3 = batch.feasible_sets_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], interp, variant=3)
-        assert np.array_equal(X3, X2, equal_nan=True), (d, interp, "X")
-        a = batch.solve_desired_duration_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], desired, None, None,
-                                               variant=2, interpolation=interp)
-        b = batch.solve_desired_duration_batch(data["coef"], data["breaks"], grid, data["vlim"], data["alim"], desired, None, None,
-                                               variant=3, interpolation=interp)
-        for k in ("status", "K", "sd2", "sd", "u", "alpha"):
-            assert np.array_equal(a[k], b[k], equal_nan=True), (d, interp, "TOPPRAsd", k)
+            same(batch.solve_batch(*prob, None, None, interp, variant=v), ref, ("K", "sd2", "u"), (d, interp, "family %d vs oracle" % v))
+        X2 = batch.feasible_sets_batch(*prob, interp, variant=2)
+        same_array(batch.feasible_sets_batch(*prob, interp, variant=3), X2, (d, interp, "X"))
+        a = batch.solve_desired_duration_batch(*prob, desired, None, None, variant=2, interpolation=interp)
+        b = batch.solve_desired_duration_batch(*prob, desired, None, None, variant=3, interpolation=interp)
+        same(b, a, ("K", "sd2", "sd", "u", "alpha"), (d, interp, "TOPPRAsd"))

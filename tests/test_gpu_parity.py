@@ -9,6 +9,7 @@ import pytest
 
 from toppra_amd import batch
 from tests.helpers import need_reference_solver
+from tests.solver_support import oracle_flags, problem, same, same_array
 
 pytestmark = pytest.mark.gpu
 
@@ -22,8 +23,8 @@ def _compare(got, ref, exact=True):
         assert np.array_equal(np.isnan(g), np.isnan(r)), key
         dev = np.nanmax(np.abs(g - r)) if np.isfinite(r).any() else 0.0
         assert dev <= ATOL, (key, dev)
-        if exact:
-            assert np.array_equal(g, r, equal_nan=True), (key, "not bit-exact, max dev %g" % dev)
+    if exact:
+        same(got, ref, ("K", "sd2", "u"), "not bit-exact")
 
 
 @pytest.mark.parametrize("variant", [1, 2, 4])
@@ -31,9 +32,8 @@ def _compare(got, ref, exact=True):
                                    (40, 2, 33), (33, 4, 70), (50, 5, 101)])
 def test_solve_batch_matches_oracle(gpu, oracle, B, d, N, variant):
     data = batch.make_synthetic_batch(B, d, N, seed=1234 + d)
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"],
-                            variant=variant)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    got = batch.solve_batch(*problem(data), variant=variant)
+    ref = oracle.solve_batch(*problem(data))
     assert (ref["status"] == 0).mean() > 0.9
     _compare(got, ref)
 
@@ -44,24 +44,19 @@ def test_nonzero_boundary_velocities(gpu, oracle, variant):
     rng = np.random.default_rng(5)
     sd0, sd1 = 0.5 * rng.random(128), 0.5 * rng.random(128)
     sd0[::7] = 5.0  # some uncontrollable starts
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], sd0, sd1,
-                            variant=variant)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], sd0, sd1)
+    got = batch.solve_batch(*problem(data), sd0, sd1, variant=variant)
+    ref = oracle.solve_batch(*problem(data), sd0, sd1)
     assert set(np.unique(ref["status"])) >= {0, 1}
     _compare(got, ref)
 
 
 def test_collocation_and_single_constraint(gpu, oracle):
     data = batch.make_synthetic_batch(64, 5, 80, seed=11)
-    from oracle.oracle import FLAG_ACC, FLAG_VEL
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"],
-                            interpolation=False)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"],
-                             flags=FLAG_VEL | FLAG_ACC)
+    got = batch.solve_batch(*problem(data), interpolation=False)
+    ref = oracle.solve_batch(*problem(data), flags=oracle_flags(oracle, True, False))
     _compare(got, ref)
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], None, data["alim"])
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], None, data["alim"],
-                             flags=FLAG_ACC | 4)
+    got = batch.solve_batch(*problem(data, vel=False))
+    ref = oracle.solve_batch(*problem(data, vel=False), flags=oracle_flags(oracle, False, True))
     _compare(got, ref)
 
 
@@ -71,8 +66,8 @@ def test_collocation_and_single_constraint(gpu, oracle):
 def test_edge_shapes(gpu, oracle, B, d, N, nway, variant):
     """Smallest grids (N = 1), one spline segment, single trajectory, ragged batch sizes."""
     data = batch.make_synthetic_batch(B, d, N, seed=B + N, n_waypoints=nway)
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], variant=variant)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    got = batch.solve_batch(*problem(data), variant=variant)
+    ref = oracle.solve_batch(*problem(data))
     _compare(got, ref)
 
 
@@ -101,14 +96,13 @@ def test_dof_17_to_32_on_the_generic_kernel(gpu, oracle, B, d, N):
     data = batch.make_synthetic_batch(B, d, N, seed=d)
     rng = np.random.default_rng(d)
     sd1 = np.where(rng.random(B) < 0.3, 0.1 * rng.random(B), 0.0)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, sd1)
-    got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, sd1)
+    ref = oracle.solve_batch(*problem(data), None, sd1)
+    got = batch.solve_batch(*problem(data), None, sd1)
     _compare(got, ref)
     for variant in (1, 4):
-        _compare(batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, sd1,
-                                   variant=variant), ref)
-    X = batch.feasible_sets_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
-    K = batch.controllable_sets_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], sd1, sd1)
+        _compare(batch.solve_batch(*problem(data), None, sd1, variant=variant), ref)
+    X = batch.feasible_sets_batch(*problem(data))
+    K = batch.controllable_sets_batch(*problem(data), sd1, sd1)
     assert np.array_equal(K, ref["K"], equal_nan=True) and X.shape == K.shape
 
 
@@ -118,11 +112,11 @@ def test_wide_dof_and_long_splines(gpu, oracle, B, d, N, nway):
     """d = 9..16 run with 16 lanes per trajectory; paths with many spline segments keep the
     coefficient table in global memory instead of LDS.  Both against the oracle, both families."""
     data = batch.make_synthetic_batch(B, d, N, seed=d * 100 + nway, n_waypoints=nway)
-    ref = oracle.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    ref = oracle.solve_batch(*problem(data))
     for variant in (1, 2, 4):
-        got = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], variant=variant)
+        got = batch.solve_batch(*problem(data), variant=variant)
         _compare(got, ref)
-    strict = batch.solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], strict=True)
+    strict = batch.solve_batch(*problem(data), strict=True)
     _compare(strict, ref)
 
 
@@ -132,23 +126,20 @@ def test_fast_kernels_serve_every_constraint_set(gpu, oracle, B, d, N, mode):
     """Collocation and single-constraint problems run on the rows-across-lanes kernels (the missing
     acceleration blocks are disabled rows): identical bits to the generic lane kernel, to the full
     iteration and to the oracle, and the auto selection no longer falls back to the generic kernel."""
-    from oracle.oracle import FLAG_ACC, FLAG_INTERP, FLAG_VEL
     data = batch.make_synthetic_batch(B, d, N, seed=77 + d)
     rng = np.random.default_rng(d)
     sd1 = np.where(rng.random(B) < 0.3, 0.2 * rng.random(B), 0.0)
     vlim = None if mode in ("acc_only", "collocation_no_vel") else data["vlim"]
     alim = None if mode == "vel_only" else data["alim"]
     interp = mode == "acc_only"
-    flags = (FLAG_VEL if vlim is not None else 0) | (FLAG_ACC if alim is not None else 0) | (FLAG_INTERP if interp else 0)
+    flags = oracle_flags(oracle, vlim is not None, interp, acc=alim is not None)
     args = (data["coef"], data["breaks"], data["grid"], vlim, alim, None, sd1, interp)
     lane = batch.solve_batch(*args, variant=1)
     kws = [dict(variant=2), dict(variant=2, strict=True), dict(), dict(variant=4), dict(variant=4, strict=True)]
     if alim is not None and d <= 15:
         kws.append(dict(variant=3))  # the certified lane kernel: Interpolation and Collocation, velocity optional
     for kw in kws:
-        got = batch.solve_batch(*args, **kw)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(got[k], lane[k], equal_nan=True), (kw, k)
+        same(batch.solve_batch(*args, **kw), lane, ("K", "sd2", "u"), (kw,))
     idx = np.arange(0, B, max(1, B // 128))
     ref = oracle.solve_batch(data["coef"][idx], data["breaks"], data["grid"], None if vlim is None else vlim[idx],
                              None if alim is None else alim[idx], None, sd1[idx], flags=flags)
@@ -174,23 +165,18 @@ def test_certified_lane_kernel_above_8_dof(gpu, oracle, d):
         args = (data["coef"] * scale, data["breaks"], data["grid"], data["vlim"], data["alim"], sd0, sd1, interp)
         full = batch.solve_batch(*args, variant=2, strict=True)
         for kw in (dict(variant=3), dict(variant=3, sound=True), dict()):
-            got = batch.solve_batch(*args, **kw)
-            for k in ("K", "sd2", "u", "status"):
-                assert np.array_equal(got[k], full[k], equal_nan=True), (k, interp, kw)
+            same(batch.solve_batch(*args, **kw), full, ("K", "sd2", "u"), (interp, kw))
         # ... and the truth is not only another GPU kernel: the first 96 trajectories against the CPU restatement of the reference
         m = 96
-        flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if interp else 0)
-        ref = oracle.solve_batch(args[0][:m], args[1], args[2], args[3][:m], args[4][:m], sd0[:m], sd1[:m], flags=flags, nthreads=0)
-        assert np.array_equal(ref["status"], full["status"][:m]), interp
-        for k in ("K", "sd2", "u"):
-            assert np.array_equal(ref[k], full[k][:m], equal_nan=True), (k, interp)
+        ref = oracle.solve_batch(args[0][:m], args[1], args[2], args[3][:m], args[4][:m], sd0[:m], sd1[:m],
+                                 flags=oracle_flags(oracle, True, interp), nthreads=0)
+        same({k: full[k][:m] for k in ("K", "sd2", "u", "status")}, ref, ("K", "sd2", "u"), (interp, "oracle"))
         fargs = args[:5] + (interp,)
-        assert np.array_equal(batch.feasible_sets_batch(*fargs, variant=3), batch.feasible_sets_batch(*fargs, variant=2, strict=True), equal_nan=True)
+        same_array(batch.feasible_sets_batch(*fargs, variant=3), batch.feasible_sets_batch(*fargs, variant=2, strict=True), (interp, "X"))
         desired = rng.uniform(0.3, 6.0, size=B)
         want = batch.solve_desired_duration_batch(*args[:5], desired, sd0, sd1, variant=2, interpolation=interp)
         got = batch.solve_desired_duration_batch(*args[:5], desired, sd0, sd1, variant=3, interpolation=interp)
-        for k in ("K", "sd2", "u", "status", "alpha"):
-            assert np.array_equal(got[k], want[k], equal_nan=True), (k, interp)
+        same(got, want, ("K", "sd2", "u", "alpha"), (interp, "TOPPRAsd"))
 
 
 @pytest.mark.parametrize("B,d,N", [(1, 9, 7), (65, 13, 5), (3, 12, 2), (130, 10, 1)])
@@ -206,17 +192,13 @@ def test_slim_blocks_partial_and_tiny(gpu, oracle, B, d, N):
         args = (data["coef"] * scale, data["breaks"], data["grid"], data["vlim"], data["alim"], None, sd1, interp)
         full = batch.solve_batch(*args, variant=2, strict=True)
         got = batch.solve_batch(*args, variant=3)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(got[k], full[k], equal_nan=True), (k, interp)
-        flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if interp else 0)
-        ref = oracle.solve_batch(args[0], args[1], args[2], args[3], args[4], None, sd1, flags=flags, nthreads=0)  # (the CPU restatement)
-        assert np.array_equal(ref["status"], got["status"]), interp
-        for k in ("K", "sd2", "u"):
-            assert np.array_equal(ref[k], got[k], equal_nan=True), (k, interp)
+        same(got, full, ("K", "sd2", "u"), (interp, "full iteration"))
+        ref = oracle.solve_batch(*args[:5], None, sd1, flags=oracle_flags(oracle, True, interp), nthreads=0)  # (the CPU restatement)
+        same(got, ref, ("K", "sd2", "u"), (interp, "oracle"))
         fargs = args[:5] + (interp,)
-        assert np.array_equal(batch.feasible_sets_batch(*fargs, variant=3), batch.feasible_sets_batch(*fargs, variant=2, strict=True), equal_nan=True)
+        same_array(batch.feasible_sets_batch(*fargs, variant=3), batch.feasible_sets_batch(*fargs, variant=2, strict=True), (interp, "X"))
         K = batch.controllable_sets_batch(*args[:5], 0.0, sd1, interp, variant=3)
-        assert np.array_equal(K, batch.controllable_sets_batch(*args[:5], 0.0, sd1, interp, variant=2, strict=True), equal_nan=True)
+        same_array(K, batch.controllable_sets_batch(*args[:5], 0.0, sd1, interp, variant=2, strict=True), (interp, "controllable sets"))
 
 
 def test_violated_row_with_zero_normal_is_an_infeasible_stage(gpu, oracle):
@@ -239,8 +221,7 @@ def test_violated_row_with_zero_normal_is_an_infeasible_stage(gpu, oracle):
     assert (want["status"][hit] != 0).all() and (want["status"][~hit] == 0).all()
     for kw in (dict(variant=1), dict(variant=2), dict(variant=2, strict=True), dict(variant=3), dict(variant=4), dict()):
         got = batch.solve_batch(*args, **kw)
-        for k in ("K", "sd2", "u", "status"):
-            assert np.array_equal(got[k], want[k], equal_nan=True), (kw, k)
+        same(got, want, ("K", "sd2", "u"), (kw,))
         assert np.isnan(got["sd2"][hit]).all() and not np.isnan(got["sd2"][~hit]).any()
 
 

@@ -13,6 +13,7 @@ import pytest
 
 import toppra_amd as ta
 from tests.helpers import assert_same
+from tests.solver_support import oracle_flags, problem
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +29,13 @@ def test_kernel_is_self_consistent_with_its_restatement(gpu, oracle, B, d, N, in
     data = batch.make_synthetic_batch(B, d, N, seed=d)
     rng = np.random.default_rng(0)
     sd1 = np.where(rng.random(B) < 0.3, 0.2 * rng.random(B), 0.0)
-    got = batch.robust_solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], ELL,
-                                   None, sd1, interp, want_X=True)
-    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if interp else 0)
-    ref = oracle.robust_solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], ELL,
-                                    None, sd1, flags=flags, nthreads=0)
+    got = batch.robust_solve_batch(*problem(data), ELL, None, sd1, interp, want_X=True)
+    ref = oracle.robust_solve_batch(*problem(data), ELL, None, sd1, flags=oracle_flags(oracle, True, interp), nthreads=0)
     assert np.array_equal(got["status"], ref["status"]) and (ref["status"] == 0).mean() > 0.9
     for k in ("K", "X", "sd2", "u"):
         assert_same(got[k], ref[k], k)
     # without feasible sets the Interpolation case runs the rows-across-lanes kernel: same bits
-    fast = batch.robust_solve_batch(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], ELL,
-                                    None, sd1, interp)
+    fast = batch.robust_solve_batch(*problem(data), ELL, None, sd1, interp)
     assert np.array_equal(fast["status"], ref["status"])
     for k in ("K", "sd2", "u"):
         assert_same(fast[k], ref[k], k)

@@ -16,7 +16,7 @@ coinciding, no tolerance -- and the independent conic solver (oracle/robust_inde
 6. the independent solver on the new shape classes (CPU twin: tests/test_oracle_robust_independent.py, 1e-9);
 7. device tensors in, device tensors out;
 8. which kernel ran, from a kernel trace of a child process;
-9. limits at the edge of the number range (tests/test_oracle_vs_reference.py::extreme_limit_batch), and: acceleration limits
+9. limits at the edge of the number range (tests/solver_support.py::extreme_limit_batch), and: acceleration limits
    written as 1e300 x the ordinary ones give the bits of limits written as +-inf.
 
 Part 9 found a defect: rob_row_interval squared m = b x + c, which overflows from |m| ~ 1.3e154, and the +inf root turned a row that
@@ -39,26 +39,16 @@ and 0.39 s (part 1: 0.06 s at 2 dof .. 0.39 s at 16 dof -- its batches are 96 x 
 not touch what the tests compute: the problem builders now in tests/robust_shapes.py were part of this module, and part 4 had no
 bar on the solved share.  The module has not been timed since, nor beside the rest of `-m gpu`.
 """
-import csv
-import glob
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 
 from tests.robust_shapes import (ELL, EXTREME_SHAPES, RELAXED_CASES, as_checker_data, block_threads, check_extreme_counts, check_relaxed_twins,
                                  extreme_case, inf_twin, instantiation_case, keys, last_fitting_nseg, many_dof_case, ok_share, PARITY_CASES,
                                  parity_cases, restatement, table_case, table_fits_lds)
-from tests.test_gpu_slim_blocks import irregular_batch, same
+from tests.solver_support import dispatches, irregular_batch, problem, same, traced
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -104,7 +94,7 @@ def geometry_case(B, d, N, seed):
     data = batch.make_synthetic_batch(B, d, N, seed=seed)
     rng = np.random.default_rng(seed)
     sd1 = np.where(rng.random(B) < 0.3, 0.2 * rng.random(B), 0.0)
-    return (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, sd1)
+    return problem(data) + (None, sd1)
 
 
 @pytest.mark.parametrize("B,d,threads", GEOMETRIES)
@@ -122,7 +112,7 @@ def test_the_benchmarks_robust_batch(gpu, oracle):
     from 100 to 20."""
     assert block_threads(16384, 7, 4) == 128
     data = batch.make_synthetic_batch(16384, 7, 20)
-    prob = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], None, None)
+    prob = problem(data) + (None, None)
     assert ok_share(check(oracle, prob, True, False, ("C4",))) >= 0.9
 
 
@@ -172,7 +162,7 @@ def test_tiny_and_odd_shapes(gpu, oracle, B, d, N):
     """One trajectory, one and two stages, batches just past a whole number of blocks (a 64-thread block holds four trajectories
     at 16 lanes each: 130 = 32 blocks + 2 at 9 dof, 65 = 16 blocks + 1 at 13 dof)."""
     data = irregular_batch(B, d, N, 5, seed=10 * d + N)
-    prob = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd0"], data["sd1"])
+    prob = problem(data) + (data["sd0"], data["sd1"])
     for interp in (True, False):
         for want_X in (False, True):
             check(oracle, prob, interp, want_X, (B, d, N), variants=(0, 1))
@@ -222,7 +212,7 @@ def test_device_tensors_in_device_tensors_out(gpu):
 
 _TRACED_CHILD = """
 import numpy as np
-from tests.test_gpu_slim_blocks import irregular_batch
+from tests.solver_support import irregular_batch
 from toppra_amd import batch
 for d, n_waypoints in ((7, %d), (7, %d), (17, 6)):
     data = irregular_batch(64, d, 8, n_waypoints, seed=d)
@@ -236,24 +226,10 @@ def test_the_kernel_that_ran(gpu):
     """The C-ABI does not say which kernel it launched, and parts 3 and 4 pass whichever did.  A fresh child process under the
     kernel tracer (no counters) makes one automatic robust call at 7 dof with 41 segments, one with 42 and one at 17 dof: the
     rows-across-lanes kernel must be what ran for the first, the lane kernel for the other two."""
-    rp = shutil.which("rocprofv3")
-    assert rp, "rocprofv3 is not on PATH: the dispatch of the automatic choice cannot be traced (GPU tests do not skip here)"
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    with tempfile.TemporaryDirectory(prefix="tpr_trace_") as tmp:
-        cmd = ["timeout", "-k", "10", "240", rp, "--kernel-trace", "--stats", "-d", tmp, "-o", "run", "--output-format", "csv", "--",
-               sys.executable, "-c", _TRACED_CHILD]
-        run = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert run.returncode == 0, (run.returncode, run.stdout[-3000:])
-        assert "traced child done" in run.stdout, run.stdout[-3000:]
-        stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats*.csv"), recursive=True)
-        assert stats, ([os.path.join(r, f) for r, _, fs in os.walk(tmp) for f in fs], run.stdout[-2000:])
-        calls = []  # (kernel name, dispatches)
-        for path in stats:
-            with open(path, newline="") as fh:
-                calls += [(r["Name"], int(r["Calls"])) for r in csv.DictReader(fh)]
-    group = sum(c for n, c in calls if "group_robust_kernel" in n)
-    group7 = sum(c for n, c in calls if "group_robust_kernel<7," in n or "group_robust_kernelILi7E" in n)
-    lane = sum(c for n, c in calls if "robust_solve_kernel" in n)
+    with traced(_TRACED_CHILD) as (calls, _):
+        pass  # (the child leaves no files to read)
+    group, group7 = dispatches(calls, "group_robust_kernel"), dispatches(calls, "group_robust_kernel", 7)
+    lane = dispatches(calls, "robust_solve_kernel")
     assert (group, group7, lane) == (1, 1, 2), (group, group7, lane, [n for n, _ in calls])
 
 

@@ -10,6 +10,7 @@ fetch; the full block stride of the internal row numbering) and 9 dof (slim bloc
 import numpy as np
 import pytest
 
+from tests.solver_support import lattice_boundary_velocities, oracle_flags, per_trajectory_grid, problem, same, same_array
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
@@ -33,32 +34,20 @@ def _problem(B, d, N, seed, per_traj_grid=False, per_traj_breaks=False, one_segm
         breaks = np.ascontiguousarray(np.stack([fits[pick[b]][1] for b in range(B)]))
     else:
         coef, breaks = batch.spline_coefficients(np.linspace(0, 1, m), way, bc_type=bc)
-    grid = np.linspace(0, 1, N + 1)
-    if per_traj_grid:
-        inner = np.sort(rng.random((B, N - 1)), axis=1) * 0.8 + 0.1 if N > 1 else np.zeros((B, 0))
-        grid = 0.5 * np.concatenate([np.zeros((B, 1)), inner, np.ones((B, 1))], axis=1) + 0.5 * grid[None, :]
-    sd0 = sd1 = None
-    if boundary:
-        sd0 = np.where(rng.random(B) < 0.3, np.round(0.1 * rng.random(B) * 1024) / 1024, 0.0)
-        sd1 = np.where(rng.random(B) < 0.3, np.round(0.2 * rng.random(B) * 1024) / 1024, 0.0)
+    grid = per_trajectory_grid(rng, B, N) if per_traj_grid else np.linspace(0, 1, N + 1)
+    sd0, sd1 = lattice_boundary_velocities(rng, B, 0.1, 0.2) if boundary else (None, None)
     return {"coef": coef, "breaks": breaks, "grid": grid, "vlim": np.ascontiguousarray(np.stack([-vmax, vmax], axis=-1)),
             "alim": np.ascontiguousarray(np.stack([-amax, amax], axis=-1)), "sd0": sd0, "sd1": sd1}
 
 
 def _check(oracle, p, what, interp=True, want_sd=False, variants=(3,)):
-    args = (p["coef"], p["breaks"], p["grid"], p["vlim"], p["alim"], p["sd0"], p["sd1"], interp)
-    want = batch.solve_batch(*args, want_sd=want_sd, strict=True)
-    ref = oracle.solve_batch(p["coef"], p["breaks"], p["grid"], p["vlim"], p["alim"], p["sd0"], p["sd1"],
-                             flags=oracle.DEFAULT_FLAGS if interp else oracle.DEFAULT_FLAGS & ~oracle.FLAG_INTERP, nthreads=4)
+    args = problem(p) + (p["sd0"], p["sd1"])
+    want = batch.solve_batch(*args, interp, want_sd=want_sd, strict=True)
+    ref = oracle.solve_batch(*args, flags=oracle_flags(oracle, True, interp), nthreads=4)
     for v in variants:
-        got = batch.solve_batch(*args, want_sd=want_sd, variant=v)
-        for name, other in (("strict", want), ("oracle", ref)):
-            assert np.array_equal(got["status"], other["status"]), what + (v, name, "status")
-            for k in ("sd2", "u", "K"):
-                assert np.array_equal(np.isnan(got[k]), np.isnan(other[k])), what + (v, name, k, "NaN pattern")
-                assert np.array_equal(got[k], other[k], equal_nan=True), what + (v, name, k)
-        if want_sd:
-            assert np.array_equal(got["sd"], want["sd"], equal_nan=True), what + (v, "strict", "sd")
+        got = batch.solve_batch(*args, interp, want_sd=want_sd, variant=v)
+        same(got, want, ("sd2", "u", "K") + (("sd",) if want_sd else ()), what + (v, "strict"))
+        same(got, ref, ("sd2", "u", "K"), what + (v, "oracle"))
     return ref
 
 
@@ -144,12 +133,11 @@ def test_feasible_sets_and_toppra_sd_share_the_fetch(gpu, d):
     for N, B in ((5, 65), (13, 130)):
         for interp in (True, False):
             p = _problem(B, d, N, 700 + d + N)
-            args = (p["coef"], p["breaks"], p["grid"], p["vlim"], p["alim"])
+            args = problem(p)
             X2 = batch.feasible_sets_batch(*args, interp, variant=2)
             X3 = batch.feasible_sets_batch(*args, interp, variant=3)
-            assert np.array_equal(X3, X2, equal_nan=True), (d, N, B, interp, "X")
+            same_array(X3, X2, (d, N, B, interp, "X"))
             desired = np.random.default_rng(d).uniform(0.5, 5.0, size=B)
             a = batch.solve_desired_duration_batch(*args, desired, p["sd0"], p["sd1"], variant=2, interpolation=interp)
             b = batch.solve_desired_duration_batch(*args, desired, p["sd0"], p["sd1"], variant=3, interpolation=interp)
-            for k in ("status", "K", "sd2", "sd", "u", "alpha"):
-                assert np.array_equal(a[k], b[k], equal_nan=True), (d, N, B, interp, "TOPPRAsd", k)
+            same(b, a, ("K", "sd2", "sd", "u", "alpha"), (d, N, B, interp, "TOPPRAsd"))

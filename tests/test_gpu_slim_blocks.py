@@ -26,86 +26,19 @@ per case instead of four) the module took 49.7 s and 48.7 s in two runs -- 20.2 
 rest of the suite; parts 3 .. 6 and the session set-up are 24 s by themselves, so the module costs more than the earlier suite
 whatever parts 1 and 2 do, and part 1 was cut to the half fraction described at its test.
 """
-import csv
-import glob
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 
+from tests.solver_support import (CERT_AUTO_FROM, dispatches, irregular_batch, near_parallel_family, oracle_flags, own_breakpoints, problem, same,
+                                  same_array, traced)
 from toppra_amd import batch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# Batch size from which family 3 is the automatic choice above 8 dof: cert_auto_from(d), toppra_amd/csrc/tpr_kernels.hip:387,
-# documented in include/toppra_hip.h:150 (TOPPRAsd) and :178 (feasible sets) as "14336 .. 36864 at 9 .. 15 dof".  A change there
-# must be copied here: parts 3 and 6 sit on these numbers.
-CERT_AUTO_FROM = {9: 14336, 10: 14336, 11: 15360, 12: 17408, 13: 22528, 14: 27648, 15: 36864}
-
 
 # --------------------------------------------------------------------------------------------------------------------------
-# shared setup
-
-def irregular_batch(B, d, N, n_waypoints, seed):
-    """The irregular batch of tests/test_gpu_fullsize.py::test_headline_batch_oracle_parity_every_trajectory for any shape:
-    non-uniform knots and grid, standing joints (8 %), asymmetric velocity limits with a positive lower one on 1 % of the joints,
-    asymmetric acceleration limits, boundary velocities on 40 % of the trajectories at either end."""
-    rng = np.random.default_rng(seed)
-    nw = n_waypoints
-    knots = np.concatenate([[0.0], np.sort(rng.random(nw - 2)) * 0.9 + 0.05, [1.0]])
-    way = rng.standard_normal((B, nw, d))
-    still = rng.random((B, d)) < 0.08
-    way = np.where(still[:, None, :], way[:, :1, :], way)
-    coef, breaks = batch.spline_coefficients(knots, way)
-    grid = 0.6 * np.concatenate([[0.0], np.sort(rng.random(N - 1)), [1.0]]) + 0.4 * np.linspace(0, 1, N + 1)
-    vhi = 5 + 25 * rng.random((B, d)); vlo = -(5 + 25 * rng.random((B, d)))
-    vlo = np.where(rng.random((B, d)) < 0.01, 0.05 * rng.random((B, d)), vlo)
-    ahi = 5 + 10 * rng.random((B, d)); alo = -(5 + 10 * rng.random((B, d)))
-    sd0 = np.where(rng.random(B) < 0.4, 0.3 * rng.random(B), 0.0)
-    sd1 = np.where(rng.random(B) < 0.4, 0.3 * rng.random(B), 0.0)
-    return {"coef": coef, "breaks": breaks, "grid": grid, "vlim": np.ascontiguousarray(np.stack([vlo, vhi], -1)),
-            "alim": np.ascontiguousarray(np.stack([alo, ahi], -1)), "sd0": sd0, "sd1": sd1, "knots": knots, "waypoints": way}
-
-
-def own_breakpoints(data, seed):
-    """Per-trajectory breakpoints [B][nseg+1] for the paths of `data`: every trajectory's interior knots moved by up to a quarter of
-    the narrowest knot interval, and its spline fitted through the same waypoints on ITS knots (scipy's CubicSpline, one by one:
-    batch.spline_coefficients fits shared knots only).  -> (coef [B][4][nseg][d], breaks [B][nseg+1])"""
-    from scipy.interpolate import CubicSpline
-    knots, way = data["knots"], data["waypoints"]
-    B, nw, _ = way.shape
-    rng = np.random.default_rng(seed)
-    own = np.repeat(knots[None], B, axis=0)
-    own[:, 1:-1] += rng.uniform(-0.25, 0.25, size=(B, nw - 2)) * np.diff(knots).min()
-    coef = np.stack([CubicSpline(own[b], way[b]).c for b in range(B)])
-    return np.ascontiguousarray(coef), np.ascontiguousarray(own)
-
-
-def oracle_flags(oracle, vlim, interp):
-    return oracle.FLAG_ACC | (oracle.FLAG_VEL if vlim is not None else 0) | (oracle.FLAG_INTERP if interp else 0)
-
-
-def same(got, want, keys, what):
-    """Bit for bit on every key (NaNs must coincide), exact on status; names the first trajectories that differ."""
-    bad = np.asarray(got["status"]) != np.asarray(want["status"])
-    assert not bad.any(), (what, "status", int(bad.sum()), np.flatnonzero(bad)[:6])
-    for k in keys:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, (what, k, g.shape, w.shape)
-        if not np.array_equal(g, w, equal_nan=True):
-            differs = ~((g == w) | (np.isnan(g) & np.isnan(w))).reshape(g.shape[0], -1).all(axis=1)
-            raise AssertionError((what, k, int(differs.sum()), np.flatnonzero(differs)[:6]))
-
-
-def same_array(got, want, what):
-    same({"status": np.zeros(1), "x": got}, {"status": np.zeros(1), "x": want}, ("x",), what)
-
+# shared setup (the irregular batch, the comparison and CERT_AUTO_FROM -- cert_auto_from(d), on which parts 3 and 6 sit:
+# tests/solver_support.py)
 
 def block_sample(B, every=None):
     """Trajectories for the per-trajectory wrapper checks: every `every`-th one, or -- large batches -- at least 128 spread over all
@@ -126,7 +59,7 @@ def check_sets(oracle, coef, breaks, grid, vlim, alim, interp, sample, seed, wha
     """feasible_sets_batch and controllable_sets_batch (sdmin != sdmax: the backward scan alone) on family 3: the oracle's wrapper
     object on `sample`, the full iteration of family 2 on the whole batch."""
     B = coef.shape[0]
-    flags = oracle_flags(oracle, vlim, interp)
+    flags = oracle_flags(oracle, vlim is not None, interp)
     rng = np.random.default_rng(seed)
     sdmin = np.where(rng.random(B) < 0.5, 0.0, 0.2 * rng.random(B))
     sdmax = sdmin + 0.02 + 0.5 * rng.random(B)
@@ -146,7 +79,7 @@ def check_sets(oracle, coef, breaks, grid, vlim, alim, interp, sample, seed, wha
 def check_sd(oracle, coef, breaks, grid, vlim, alim, sd0, sd1, interp, desired, what, variants=(3,)):
     """TOPPRAsd through `variants`: the oracle on every trajectory (sd2, u, alpha, status), family 2 on the whole batch (K, sd).
     -> the oracle's output"""
-    ref = oracle.solve_batch_sd(coef, breaks, grid, vlim, alim, desired, sd0, sd1, flags=oracle_flags(oracle, vlim, interp), nthreads=0)
+    ref = oracle.solve_batch_sd(coef, breaks, grid, vlim, alim, desired, sd0, sd1, flags=oracle_flags(oracle, vlim is not None, interp), nthreads=0)
     f2 = batch.solve_desired_duration_batch(coef, breaks, grid, vlim, alim, desired, sd0, sd1, variant=2, interpolation=interp)
     same(f2, ref, ("sd2", "u", "alpha"), what + ("TOPPRAsd, family 2 vs oracle",))
     for variant in variants:
@@ -171,7 +104,7 @@ def check_solve(oracle, coef, breaks, grid, vlim, alim, sd0, sd1, interp, what):
     """solve_batch on family 3 with and without the sd output against the oracle on every trajectory (sd: against family 2's full
     iteration, itself held to the oracle here).  -> the oracle's output"""
     args = (coef, breaks, grid, vlim, alim, sd0, sd1)
-    ref = oracle.solve_batch(*args, flags=oracle_flags(oracle, vlim, interp), nthreads=0)
+    ref = oracle.solve_batch(*args, flags=oracle_flags(oracle, vlim is not None, interp), nthreads=0)
     f2 = batch.solve_batch(*args, interp, want_sd=True, variant=2, strict=True)
     same(f2, ref, ("K", "sd2", "u"), what + ("family 2 vs oracle",))
     same(batch.solve_batch(*args, interp, variant=3), ref, ("K", "sd2", "u"), what + ("family 3 vs oracle",))
@@ -236,8 +169,7 @@ def test_spline_table_cases_blend_and_saturate(oracle):
     for d in range(9, 16):
         for n_waypoints in TWS_WAYPOINTS:
             data = table_case(d, n_waypoints)
-            kinds += blend_kinds(oracle.solve_batch_sd(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["desired"],
-                                                       data["sd0"], data["sd1"], nthreads=0))
+            kinds += blend_kinds(oracle.solve_batch_sd(*problem(data), data["desired"], data["sd0"], data["sd1"], nthreads=0))
     assert kinds[0] > 0 and kinds[1] > 0, kinds
 
 
@@ -265,8 +197,7 @@ def test_stage_count_and_batch_size_edges(gpu, oracle, d, B, N):
     data = edge_case(d, B, N)
     assert np.all(data["sd0"] > 0) and np.all(data["sd1"] > 0)
     for interp in (True, False):
-        four_entries(oracle, data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd0"], data["sd1"], interp,
-                     data["desired"], seed=N, what=(d, B, N))
+        four_entries(oracle, *problem(data), data["sd0"], data["sd1"], interp, data["desired"], seed=N, what=(d, B, N))
 
 
 def test_edge_cases_blend_and_saturate(oracle):
@@ -275,8 +206,7 @@ def test_edge_cases_blend_and_saturate(oracle):
     for d in EDGE_DOFS:
         for B, N in EDGE_SHAPES:
             data = edge_case(d, B, N)
-            kinds += blend_kinds(oracle.solve_batch_sd(data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["desired"],
-                                                       data["sd0"], data["sd1"], nthreads=0))
+            kinds += blend_kinds(oracle.solve_batch_sd(*problem(data), data["desired"], data["sd0"], data["sd1"], nthreads=0))
     assert kinds[0] > 0 and kinds[1] > 0, kinds
 
 
@@ -290,7 +220,7 @@ def test_the_batch_sizes_the_kernel_is_chosen_for(gpu, oracle, d, offset):
     (just under it): the automatic choice, family 3 and family 2 against the oracle on every trajectory."""
     B, N = CERT_AUTO_FROM[d] + offset, 100
     data = irregular_batch(B, d, N, 6, seed=4242)  # (one set of knots for every dof: the conditions below hold on it, 13 .. 16 % blended)
-    prob = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    prob = problem(data)
     args = prob + (data["sd0"], data["sd1"])
     what = (d, B)
     ref = oracle.solve_batch(*args, nthreads=0)
@@ -298,28 +228,16 @@ def test_the_batch_sizes_the_kernel_is_chosen_for(gpu, oracle, d, offset):
     assert 0.25 < share < 0.75, (what, share)  # successful paths and the NaN filling of failed lanes in every block
     for kw in (dict(), dict(variant=3), dict(variant=2)):
         same(batch.solve_batch(*args, **kw), ref, ("K", "sd2", "u"), what + ("solve", kw))
-    # feasible sets: the automatic choice and family 3 against the full iteration of family 2, and that against the wrapper sample
-    full = batch.feasible_sets_batch(*prob, variant=2, strict=True)
-    for kw in (dict(), dict(variant=3)):
-        same_array(batch.feasible_sets_batch(*prob, **kw), full, what + ("X", kw))
+    # feasible sets and the backward scan alone: family 3 against the full iteration of family 2 and the wrapper sample, and the
+    # automatic choice of the feasible sets against that full iteration
     sample = block_sample(B)
     assert len(sample) >= 128 and {0, (B // 64 - 1) * 64, (B // 64) * 64, B - 1} <= set(sample.tolist())
-    for b in sample:
-        w = oracle.Wrapper(data["coef"][b], data["breaks"], data["grid"], data["vlim"][b], data["alim"][b])
-        assert np.array_equal(full[b], w.compute_feasible_sets(), equal_nan=True), what + ("X vs oracle", int(b))
+    check_sets(oracle, *prob, True, sample, seed=B, what=what)
+    same_array(batch.feasible_sets_batch(*prob), batch.feasible_sets_batch(*prob, variant=2, strict=True), what + ("X", "automatic choice"))
     # TOPPRAsd: the oracle on every trajectory
     sd = check_sd(oracle, *args, True, desired_durations(B, seed=d), what=what, variants=(0, 3))
     blended, saturated = blend_kinds(sd)
     assert blended >= 0.1 * B and saturated >= 0.1 * B, (what, blended, saturated)
-    # the backward scan alone
-    rng = np.random.default_rng(B)
-    sdmin = np.where(rng.random(B) < 0.5, 0.0, 0.2 * rng.random(B))
-    sdmax = sdmin + 0.02 + 0.5 * rng.random(B)
-    K = batch.controllable_sets_batch(*prob, sdmin, sdmax, variant=3)
-    same_array(K, batch.controllable_sets_batch(*prob, sdmin, sdmax, variant=2, strict=True), what + ("controllable sets vs family 2",))
-    for b in sample:
-        w = oracle.Wrapper(data["coef"][b], data["breaks"], data["grid"], data["vlim"][b], data["alim"][b])
-        assert np.array_equal(K[b], w.compute_controllable_sets(sdmin[b], sdmax[b]), equal_nan=True), what + ("controllable sets vs oracle", int(b))
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -330,7 +248,7 @@ def test_the_batches_the_readme_times(gpu, oracle, d):
     """make_synthetic_batch(65536, d, 200) -- what bench.py --dof d times -- through the automatic choice: every trajectory
     against the oracle."""
     data = batch.make_synthetic_batch(65536, d, 200)
-    args = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"])
+    args = problem(data)
     got = batch.solve_batch(*args)
     ref = oracle.solve_batch(*args, nthreads=0)
     assert (ref["status"] == 0).mean() > 0.99
@@ -345,7 +263,7 @@ def test_full_chip_launches_on_either_side_of_the_workspace_limit(gpu, oracle, n
     of this test)."""
     B, d, N = 65536, 15, 60
     data = irregular_batch(B, d, N, n_waypoints, seed=n_waypoints)
-    args = (data["coef"], data["breaks"], data["grid"], data["vlim"], data["alim"], data["sd0"], data["sd1"])
+    args = problem(data) + (data["sd0"], data["sd1"])
     ref = oracle.solve_batch(*args, nthreads=0)
     assert len(np.unique(ref["status"])) >= 2 and (ref["status"] == 0).mean() > 0.1
     for kw in (dict(), dict(variant=3)):
@@ -354,30 +272,6 @@ def test_full_chip_launches_on_either_side_of_the_workspace_limit(gpu, oracle, n
 
 # --------------------------------------------------------------------------------------------------------------------------
 # 5. adversarial families
-
-def near_parallel_family(B, d, N, seed):
-    """tests/test_gpu_fullsize.py::test_near_parallel_rows_are_bit_exact's generator: one joint a copy of another, scaled or tilted
-    by 1e-14 .. 1e-6, so that two non-twin rows are parallel to that accuracy at every gridpoint."""
-    rng = np.random.default_rng(900 + seed)
-    way = rng.standard_normal((B, 5, d))
-    eps = 10.0 ** rng.uniform(-14, -6, size=B)
-    scale = rng.choice([1.0, -1.0, 0.5, 2.0, 3.0], size=B)
-    src, dst = rng.integers(0, d, size=B), rng.integers(0, d, size=B)
-    dst = np.where(dst == src, (src + 1) % d, dst)
-    rows = np.arange(B)
-    way[rows, :, dst] = way[rows, :, src] * (scale * (1 + eps))[:, None]
-    twist = rng.random(B) < 0.5
-    way[rows[twist], :, dst[twist]] += eps[twist, None] * rng.standard_normal((twist.sum(), 5))
-    coef, breaks = batch.spline_coefficients(np.linspace(0, 1, 5), way)
-    vmax = 10 + 20 * rng.random((B, d))
-    amax = 10 + 2 * rng.random((B, d))
-    amax[rows, dst] = amax[rows, src] * np.abs(scale) * (1 + 0.02 * rng.standard_normal(B))
-    vmax[rows, dst] = vmax[rows, src] * np.abs(scale) * (1 + 0.02 * rng.standard_normal(B))
-    vlim = np.ascontiguousarray(np.stack([-vmax, vmax], -1))
-    alim = np.ascontiguousarray(np.stack([-amax, amax], -1))
-    sd1 = np.where(rng.random(B) < 0.3, 0.2 * rng.random(B), 0.0)
-    return coef, breaks, np.linspace(0, 1, N + 1), vlim, alim, None, sd1
-
 
 def sliver_family(B, d, N, seed):
     """tests/test_gpu_fullsize.py::test_concurrent_rows_and_sliver_pivots_are_bit_exact's generator: the acceleration limits of three
@@ -482,38 +376,19 @@ print("traced child done")
 """ % (CERT_AUTO_FROM[9], CERT_AUTO_FROM[15])
 
 
-def _dispatches(calls, kernel, d):
-    """Dispatches of tpr::<kernel><d, ...> in the tracer's (name, calls) statistics (demangled names, or ...<kernel>ILi<d>E...).
-    The dof is the FIRST template argument of all five kernels asked about here (cert_solve_kernel, cert_feasible_kernel,
-    group_solve_kernel, group_feasible_kernel, group_sd_forward_kernel): the match relies on that."""
-    return sum(c for n, c in calls if kernel + "<%d," % d in n or kernel + "ILi%dE" % d in n)
-
-
 @pytest.mark.parametrize("offset", [0, -1])
 def test_the_documented_thresholds_are_the_dispatched_ones(gpu, offset):
     """The C-ABI does not say which family it launched, and the parity tests above pass whichever did.  A fresh child process under
     the kernel tracer (no counters) makes one automatic solve_batch, feasible_sets_batch and solve_desired_duration_batch at 9 and 15
     dof, at cert_auto_from(d) (offset 0) or one trajectory below: the certified lane kernels must be what ran at the threshold
-    (pick_variant, tpr_kernels.hip:390-409; TOPPRAsd :694; feasible sets :936) and the rows-across-lanes kernels below it."""
-    rp = shutil.which("rocprofv3")
-    assert rp, "rocprofv3 is not on PATH: the dispatch of the automatic choice cannot be traced (GPU tests do not skip here)"
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    with tempfile.TemporaryDirectory(prefix="tpr_trace_") as tmp:
-        cmd = ["timeout", "-k", "10", "240", rp, "--kernel-trace", "--stats", "-d", tmp, "-o", "run", "--output-format", "csv", "--",
-               sys.executable, "-c", _TRACED_CHILD, str(offset)]
-        run = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert run.returncode == 0, (run.returncode, run.stdout[-3000:])
-        assert "traced child done" in run.stdout, run.stdout[-3000:]
-        stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats*.csv"), recursive=True)
-        assert stats, ([os.path.join(r, f) for r, _, fs in os.walk(tmp) for f in fs], run.stdout[-2000:])
-        calls = []  # (kernel name, dispatches)
-        for path in stats:
-            with open(path, newline="") as fh:
-                calls += [(r["Name"], int(r["Calls"])) for r in csv.DictReader(fh)]
+    (tpr_kernels.hip: pick_variant; tpr_solve_desired_duration_batch for TOPPRAsd; tpr_feasible_sets_batch) and the
+    rows-across-lanes kernels below it."""
+    with traced(_TRACED_CHILD, str(offset)) as (calls, _):
+        pass  # (the child leaves no files to read)
     cert = ("cert_solve_kernel", "cert_feasible_kernel")
     group = ("group_solve_kernel", "group_feasible_kernel", "group_sd_forward_kernel")
     for d in (9, 15):
-        ran = {k: _dispatches(calls, k, d) for k in cert + group}
+        ran = {k: dispatches(calls, k, d) for k in cert + group}
         if offset == 0:
             # the fused solve and the fused TOPPRAsd launch (another instantiation of cert_solve_kernel), the feasible sets -- and no
             # rows-across-lanes kernel at this dof for any of the three calls

@@ -44,7 +44,7 @@ def test_certificates_return_the_references_bits(harness, family, seed, B, min_u
 @pytest.mark.parametrize("seed,B", [(0, 39), (9, 52), (1, 65)])  # 7 dof N = 200, 12 dof N = 40, 3 dof N = 60
 def test_certificates_on_limits_at_the_edge_of_the_number_range(harness, seed, B, mode, minform):
     """Infinite, 1e300, subnormal-squared, one-sided and inverted limits (family `extreme`: every kind of
-    tests/test_oracle_vs_reference.py::extreme_limit_problems, round-robin, beside ordinary trajectories): rows with c = -inf or
+    tests/solver_support.py::extreme_limit_problems, round-robin, beside ordinary trajectories): rows with c = -inf or
     1e300 in every stage LP.  Whatever a certificate answers is the reference's bits, and it answers no LP the reference fails
     on -- in the solve and in the feasible-set mode, in both forms of the slides.  No acceptance floor: refusing is the right
     answer on infinite rows (0 .. 99 % of the LPs are certified, depending on the kind)."""

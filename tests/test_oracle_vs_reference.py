@@ -1,15 +1,18 @@
 """Pinning of the CPU oracle against the REAL reference on fresh seeds, bit-exact.  The problems are generated here
-(the functions below); the reference's outputs on exactly these problems are stored in
+(the functions below; those with limits at the edge of the number range, which the GPU tests run as well, in
+tests/solver_support.py); the reference's outputs on exactly these problems are stored in
 tests/golden/oracle_vs_reference_*.npz by tools/make_oracle_vs_reference_golden.py, which runs the reference on
 them -- so the pin holds wherever the suite runs, the reference itself being absent there."""
 import functools
 import hashlib
-import os
 
 import numpy as np
 import pytest
 
-from tests.helpers import GOLDEN, assert_same, torque_model
+from tests.helpers import assert_same, torque_model
+from tests.solver_support import (EXTREME_CASES, EXTREME_KINDS, FLT_MAX, FLT_MIN_NORMAL, case_id, extreme_limit_batch,  # noqa: F401
+                                  extreme_limit_problems, golden_path, oracle_flags, ordinary_problem as _problem, reference_outputs)
+# (noqa: tools/make_oracle_vs_reference_golden.py and tools/host_cert_hunt.py read the generators and the fixture's path here)
 
 PARAMETERIZATION_CASES = [(7, 200, 1, (0, 0)), (6, 500, 1, (0, 0)), (3, 60, 0, (0.1, 0.05)), (2, 40, 1, (3.0, 0.0)), (5, 77, 1, (0, 0.2))]
 IRREGULAR_CASES = [(6, 90, 9, 1), (7, 120, 6, 2), (9, 50, 7, 3), (14, 40, 5, 4), (3, 150, 4, 5)]
@@ -17,18 +20,7 @@ REACHABLE_CASES = [(7, 100, 1, (0.0, 0.0)), (5, 60, 1, (0.0, 0.3)), (3, 40, 0, (
 GENERAL_CASES = [0, 1]
 
 
-def case_id(*params):
-    return "_".join(str(p) for p in params)
-
-
 # ---- the problems (shared with tools/make_oracle_vs_reference_golden.py) ----
-
-def _problem(rng, d, nway=5):
-    way = rng.standard_normal((nway, d))
-    vmax = 10 + 20 * rng.random(d)
-    amax = 10 + 2 * rng.random(d)
-    return way, np.stack([-vmax, vmax], 1), np.stack([-amax, amax], 1)
-
 
 def parameterization_problems(d, N):
     """12 x (knots, grid, waypoints, vlim, alim)."""
@@ -55,122 +47,6 @@ def irregular_problems(d, N, nway, seed):
         sd0 = 0.3 * rng.random() if rng.random() < 0.5 else 0.0
         sd1 = 0.3 * rng.random() if rng.random() < 0.5 else 0.0
         yield knots, grid, way, vl, al, sd0, sd1
-
-
-EXTREME_KINDS = ("vinf", "ainf", "ainf_one", "vhuge", "ahuge", "vsub", "vtiny", "vneg", "inverted", "still", "shifted", "mix")
-EXTREME_CASES = [(1, 30, 1), (3, 40, 2), (7, 60, 3), (12, 36, 4)]
-EXTREME_TRIALS = 3
-FLT_MAX = float(np.finfo(np.float32).max)
-FLT_MIN_NORMAL = float(np.finfo(np.float32).tiny)  # 2^-126: fp32 values below it are subnormal
-
-
-def extreme_limit_problem(rng, kind, d, N, with_sd):
-    """One problem whose limits sit at the edge of the number range (the table of kinds: extreme_limit_problems), and the
-    ordinary problem it was made from: (knots, grid, waypoints, vlim, alim, sd_start, sd_end), (base waypoints, vlim, alim).
-    Kind 'plain' is the base problem itself, drawn from the same stream; with_sd: non-zero boundary velocities.  No NaN
-    anywhere."""
-    way, vl, al = _problem(rng, d)
-    base = (way.copy(), vl.copy(), al.copy())
-    knots, grid = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
-    hit = rng.random(d) < 0.35
-    hit[rng.integers(d)] = True                      # 30 - 40 % of the joints, at least one
-    one = int(rng.choice(np.flatnonzero(hit)))       # the joint of the one-joint kinds
-    # (every draw below is made for every kind, so that a kind's problem does not depend on the kinds before it)
-    expo = rng.uniform(-23, -19, size=d)
-    huge = np.where(rng.random(d) < 0.5, 1e38, 1e300)
-    side, frac, s0 = rng.random() < 0.5, 0.01 + 0.05 * rng.random(), (5.0, -3.0, 1e3)[int(rng.integers(3))]
-    order = rng.permutation(d)
-    lattice = [np.round(0.2 * rng.random() * 1024) / 1024 for _ in range(2)]  # 2^-10 lattice: the squares are exact
-    if kind == "vinf":
-        vl[hit] = [-np.inf, np.inf]
-    elif kind == "ainf":
-        al[hit] = [-np.inf, np.inf]
-    elif kind == "ainf_one":
-        al[hit, 1] = np.inf
-    elif kind == "vhuge":
-        vl[hit] *= huge[hit, None]
-    elif kind == "ahuge":
-        al[hit] *= 1e300
-    elif kind == "vsub":
-        vl *= 10.0 ** expo[:, None]
-    elif kind == "vtiny":
-        vl[hit] *= 1e-30
-    elif kind == "vneg":
-        vl[one] = [frac * vl[one, 1], vl[one, 1]] if side else [vl[one, 0], frac * vl[one, 0]]
-    elif kind == "inverted":
-        al[one] = al[one, ::-1]
-    elif kind == "still":
-        way[:, hit] = way[:1, hit]
-    elif kind == "shifted":
-        knots, grid = s0 + knots, s0 + grid
-    elif kind == "mix":
-        j = [int(order[i % d]) for i in range(4)]
-        vl[j[0]] = [-np.inf, np.inf]
-        al[j[1], 1] = np.inf
-        vl[j[2]] = base[1][j[2]] * 10.0 ** expo[j[2]]
-        al[j[3]] = al[j[3]] * 1e300
-    else:
-        assert kind == "plain", kind
-    sd0, sd1 = lattice if with_sd else (0.0, 0.0)
-    return (knots, grid, way, vl, al, float(sd0), float(sd1)), base
-
-
-def extreme_limit_problems(d, N, seed, trials=EXTREME_TRIALS):
-    """Limits at the edge of the number range, on the ordinary problem _problem(rng, d) with 30 - 40 % of the joints (at
-    least one) modified: `trials` x (kind, knots, grid, waypoints, vlim, alim, sd_start, sd_end) for every kind of
-
-      vinf      vlim = (-inf, +inf)                       ainf      alim = (-inf, +inf)
-      ainf_one  alim_hi = +inf only                       ahuge     alim x 1e300
-      vhuge     vlim x 1e38 and x 1e300: quotients vlim / q' beyond FLT_MAX
-      vsub      ALL vlim x 10^U(-23, -19): the fp32 square of sdmax is subnormal or underflows to 0
-      vtiny     vlim x 1e-30: the square underflows to 0, x is pinned to 0
-      vneg      vlim_hi < 0 or vlim_lo > 0 on one joint: a positive lower bound on sd, mostly infeasible
-      inverted  alim_lo and alim_hi swapped on one joint: every stage infeasible
-      still     the modified joints do not move (q' = q'' = 0: zero-normal rows, skipped in the velocity bound)
-      shifted   knots and grid on [s0, s0 + 1], s0 in {5, -3, 1e3}
-      mix       one joint each of vinf, ainf_one, vsub, ahuge in one trajectory
-
-    Every third trial of a kind carries non-zero boundary velocities on the 2^-10 lattice."""
-    rng = np.random.default_rng(31000 + seed)
-    for kind in EXTREME_KINDS:
-        for t in range(trials):
-            yield (kind,) + extreme_limit_problem(rng, kind, d, N, t % 3 == 2)[0]
-
-
-def extreme_limit_batch(B, d, N, seed, kinds=EXTREME_KINDS, shared_s0=None):
-    """The same problems as one batch, for the batched entries and for tools/host_cert_hunt.py: trajectory b is of kind
-    (kinds + ('plain',))[b % (len(kinds) + 1)] -- every 64-trajectory wave holds every kind next to ordinary trajectories, the
-    `plain` controls at a fixed stride -- and every third round of kinds carries non-zero boundary velocities.
-    dict(coef [B, 4, 4, d], breaks [B, 5], grid [B, N+1], vlim, alim [B, d, 2], sd0, sd1 [B], kinds [B], base): `base` holds
-    the unmodified problems (coef, breaks, grid, vlim, alim) in the same layout.  With shared_s0 (a number) breaks [5] and grid
-    [N+1] are one shifted set for the whole batch, and kind 'shifted' is an ordinary problem on it."""
-    from toppra_amd.batch import spline_coefficients
-    rng = np.random.default_rng(47000 + seed)
-    names = tuple(kinds) + ("plain",)
-    unit_k, unit_g = np.linspace(0, 1, 5), np.linspace(0, 1, N + 1)
-    kind = [names[b % len(names)] for b in range(B)]
-    out = {k: [] for k in ("knots", "grid", "way", "vlim", "alim", "sd0", "sd1")}
-    base = {k: [] for k in ("way", "vlim", "alim")}
-    for b in range(B):
-        prob, (bw, bv, ba) = extreme_limit_problem(rng, kind[b], d, N, (b // len(names)) % 3 == 2)
-        for k, v in zip(("knots", "grid", "way", "vlim", "alim", "sd0", "sd1"), prob):
-            out[k].append(v)
-        base["way"].append(bw); base["vlim"].append(bv); base["alim"].append(ba)
-    out = {k: np.array(v) for k, v in out.items()}
-    base = {k: np.array(v) for k, v in base.items()}
-    if shared_s0 is not None:
-        out["knots"], out["grid"] = shared_s0 + unit_k, shared_s0 + unit_g
-        out["coef"], _ = spline_coefficients(out["knots"], out["way"])
-        base.update(coef=spline_coefficients(out["knots"], base["way"])[0], breaks=out["knots"], grid=out["grid"])
-    else:
-        out["coef"] = np.empty((B, 4, 4, d))
-        for k0 in np.unique(out["knots"][:, 0]):   # one batched fit per set of knots
-            m = out["knots"][:, 0] == k0
-            out["coef"][m], _ = spline_coefficients(out["knots"][m][0], out["way"][m])
-        base.update(coef=spline_coefficients(unit_k, base["way"])[0], breaks=np.tile(unit_k, (B, 1)), grid=np.tile(unit_g, (B, 1)))
-    out["breaks"] = out.pop("knots")
-    out.update(kinds=np.array(kind), base=base)
-    return out
 
 
 def lp2d_problems():
@@ -255,31 +131,11 @@ def general_constraint_lists(mod, scheme, inv_dyn, taulim, fric, vfun):
             mod.SecondOrderConstraint.joint_torque_constraint(inv_dyn, 1.3 * taulim, fric, discretization_scheme=DT)]
 
 
-# ---- the reference's outputs ----
-
-def golden_path(test):
-    return os.path.join(GOLDEN, "oracle_vs_reference_%s.npz" % test)
-
-
-@functools.lru_cache(maxsize=None)
-def _golden(test):
-    with np.load(golden_path(test)) as z:
-        return {k: z[k] for k in z.files}
-
-
-def reference_outputs(test, case, trial):
-    """The reference's arrays for one trial: {name: array} from the stored key '<case>__<trial>__<name>'."""
-    prefix = "%s__%s__" % (case, trial)
-    out = {k[len(prefix):]: v for k, v in _golden(test).items() if k.startswith(prefix)}
-    assert out, "tests/golden/oracle_vs_reference_%s.npz holds nothing for %s" % (test, prefix)
-    return out
-
-
-# ---- the oracle against them ----
+# ---- the oracle against the reference's outputs (tests/solver_support.py::reference_outputs) ----
 
 @pytest.mark.parametrize("d,N,scheme,sd", PARAMETERIZATION_CASES)
 def test_parameterization_matches_reference(oracle, d, N, scheme, sd):
-    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
+    flags = oracle_flags(oracle, True, bool(scheme))
     for t, (knots, grid, way, vl, al) in enumerate(parameterization_problems(d, N)):
         ref = reference_outputs("parameterization", case_id(d, N, scheme, *sd), t)
         # the reference's own spline tables (path.cspl.c / .x) are the oracle's input
@@ -396,7 +252,7 @@ def test_velocity_bound_is_fp32(oracle):
 def test_reachable_sets_match_reference(oracle, d, N, scheme, sds):
     """compute_reachable_sets (reachability_algorithm.py:378-431) incl. its deltas[i-1] objective and the
     warm-start state carried over from the feasible-set pass it runs first."""
-    flags = oracle.FLAG_VEL | oracle.FLAG_ACC | (oracle.FLAG_INTERP if scheme else 0)
+    flags = oracle_flags(oracle, True, bool(scheme))
     for t, (knots, grid, way, vl, al) in enumerate(reachable_problems(d, N)):
         ref = reference_outputs("reachable", case_id(d, N, scheme, *sds), t)
         w = oracle.Wrapper(ref["c"], ref["x"], grid, vl, al, flags=flags)
