@@ -181,91 +181,44 @@ def load():
         L.tpr_device_count.restype = C.c_int
         L.tpr_last_error.restype = C.c_char_p
         L.tpr_version.restype = C.c_char_p
-        L.tpr_abi_sizes.restype = C.c_int
-        L.tpr_abi_sizes.argtypes = [C.POINTER(C.c_int32)] * 3
-        sizes = [C.c_int32(0), C.c_int32(0), C.c_int32(0)]
-        L.tpr_abi_sizes(*[C.byref(v) for v in sizes])
-        mine = [C.sizeof(tpr_problem), C.sizeof(tpr_result), C.sizeof(tpr_dense_problem)]
-        if [v.value for v in sizes] != mine:
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_problem / tpr_result / "
-                                 "tpr_dense_problem take %s bytes, this binding declares %s" % ([v.value for v in sizes], mine))
-        P, R, V = C.POINTER(tpr_problem), C.POINTER(tpr_result), C.c_void_p
-        L.tpr_solve_batch.restype = C.c_int
-        L.tpr_solve_batch.argtypes = [P, R, V]
-        L.tpr_solve_desired_duration_batch.restype = C.c_int
-        L.tpr_solve_desired_duration_batch.argtypes = [P, V, C.c_double, R, V, V]
-        L.tpr_robust_solve_batch.restype = C.c_int
-        L.tpr_robust_solve_batch.argtypes = [P, V, R, V, V]
-        L.tpr_solve_batch_timed.restype = C.c_int
-        L.tpr_solve_batch_timed.argtypes = [P, R, V, C.c_int, C.POINTER(C.c_float)]
-        L.tpr_controllable_sets_batch.restype = C.c_int
-        L.tpr_controllable_sets_batch.argtypes = [P, V, V, V, V]
-        L.tpr_reachable_sets_batch.restype = C.c_int
-        L.tpr_reachable_sets_batch.argtypes = [P, V, V, V, V, V]
-        L.tpr_feasible_sets_batch.restype = C.c_int
-        L.tpr_feasible_sets_batch.argtypes = [P, V, V]
-        L.tpr_constraint_params_batch.restype = C.c_int
-        L.tpr_constraint_params_batch.argtypes = [P, V, V, V, V, V, V, V, V, V]
-        L.tpr_solve_stagewise_batch.restype = C.c_int
-        L.tpr_solve_stagewise_batch.argtypes = [P, V, V, V, V, C.c_int, V, V]
-        L.tpr_spline_fit_batch.restype = C.c_int
-        L.tpr_spline_fit_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, C.c_int, V, C.c_int, C.c_int, V, V, V,
-                                           C.c_int, V]
-        L.tpr_const_accel_times_batch.restype = C.c_int
-        L.tpr_const_accel_times_batch.argtypes = [P, V, V, V, V]
-        L.tpr_const_accel_eval_batch.restype = C.c_int
-        L.tpr_const_accel_eval_batch.argtypes = [P, V, V, V, C.c_int, V, C.c_int, V, V]
-        L.tpr_param_spline_sample_batch.restype = C.c_int
-        L.tpr_param_spline_sample_batch.argtypes = [P, V, C.c_int, V, C.c_int, C.c_int, V, V, V, V, V]
-        L.tpr_param_spline_batch.restype = C.c_int
-        L.tpr_param_spline_batch.argtypes = [P, V, V, V, V, V]
-        L.tpr_ppoly_eval_batch.restype = C.c_int
-        L.tpr_ppoly_eval_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, V, V, C.c_int, V, C.c_int, V, C.c_int, V]
-        L.tpr_second_order_block_bytes.restype = C.c_int
-        L.tpr_second_order_block_bytes.argtypes = []
-        if L.tpr_second_order_block_bytes() != C.sizeof(tpr_second_order_block):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_second_order_block takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_second_order_block_bytes(), C.sizeof(tpr_second_order_block)))
-        L.tpr_path_eval_batch.restype = C.c_int
-        L.tpr_path_eval_batch.argtypes = [P, V, V, V, V]
-        L.tpr_second_order_rows_batch.restype = C.c_int
-        L.tpr_second_order_rows_batch.argtypes = [P, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V]
-        L.tpr_sampled_problem_bytes.restype = C.c_int
-        L.tpr_sampled_problem_bytes.argtypes = []
-        if L.tpr_sampled_problem_bytes() != C.sizeof(tpr_sampled_problem):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_sampled_problem takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_sampled_problem_bytes(), C.sizeof(tpr_sampled_problem)))
-        SP = C.POINTER(tpr_sampled_problem)
-        L.tpr_sampled_rows_batch.restype = C.c_int
-        L.tpr_sampled_rows_batch.argtypes = [SP, C.c_int, C.POINTER(tpr_second_order_block), V, V, V, V, V, V, V, V]
-        L.tpr_param_spline_samples_batch.restype = C.c_int
-        L.tpr_param_spline_samples_batch.argtypes = [SP, V, V, V, V, V]
-        L.tpr_bound_source_bytes.restype = C.c_int
-        L.tpr_bound_source_bytes.argtypes = []
-        if L.tpr_bound_source_bytes() != C.sizeof(tpr_bound_source):
-            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_bound_source takes %d bytes, this "
-                                 "binding declares %d" % (L.tpr_bound_source_bytes(), C.sizeof(tpr_bound_source)))
-        L.tpr_stage_boxes_batch.restype = C.c_int
-        L.tpr_stage_boxes_batch.argtypes = [C.c_int, C.c_int, C.c_int, V, C.c_int, C.POINTER(tpr_bound_source), C.c_int, V, V, V]
-        # the rigid-body family: five by-value structs with their size checks
-        for struct in (tpr_chain, tpr_payload, tpr_chain_points, tpr_mount, tpr_joint_sections):
-            size = getattr(L, struct.__name__ + "_bytes")
-            size.restype, size.argtypes = C.c_int, []
-            if size() != C.sizeof(struct):
-                raise ToppraHipError("libtoppra_hip.so was built from another header: its %s takes %d bytes, this "
-                                     "binding declares %d" % (struct.__name__, size(), C.sizeof(struct)))
+        I, LL, V = C.c_int, C.c_longlong, C.c_void_p
+        P, R, DP, SP = (C.POINTER(s) for s in (tpr_problem, tpr_result, tpr_dense_problem, tpr_sampled_problem))
+        SO, BS = C.POINTER(tpr_second_order_block), C.POINTER(tpr_bound_source)
         CP, PP, XP, MP = C.POINTER(tpr_chain), C.POINTER(tpr_payload), C.POINTER(tpr_chain_points), C.POINTER(tpr_mount)
         JP = C.POINTER(tpr_joint_sections)
-        I, LL = C.c_int, C.c_longlong
-        # One table of signatures, all returning int.  The dense-row passes: a source's leading arguments (the problem; the boxed
-        # entries' low, high), the pass's own, the stream ...
-        DP = C.POINTER(tpr_dense_problem)
+        # the structs the library reports the size of, one <struct>_bytes() each (tpr_abi_sizes reports the first three at once)
+        sized = (tpr_second_order_block, tpr_sampled_problem, tpr_bound_source, tpr_chain, tpr_payload, tpr_chain_points, tpr_mount,
+                 tpr_joint_sections)
+        # One table of signatures, all returning int.  The entries that do not end in a stream ...
+        signatures = {"tpr_abi_sizes": [C.POINTER(C.c_int32)] * 3, "tpr_solve_batch_timed": [P, R, V, I, C.POINTER(C.c_float)]}
+        signatures.update({struct.__name__ + "_bytes": [] for struct in sized})
+        # ... and (..., void *stream).  The five passes on their four sources: a source's leading arguments (the problem; the
+        # boxed entries' low, high), the pass's own, ...
         passes = {"solve": [R], "solve_desired_duration": [V, C.c_double, R, V], "controllable_sets": [V, V, V],
                   "feasible_sets": [V], "reachable_sets": [V, V, V, V]}
-        signatures = {"tpr_%s_%s_batch" % (name, source): lead + own + [V]
-                      for source, lead in (("dense", [DP]), ("sampled", [SP]), ("sampled_boxed", [SP, V, V])) for name, own in passes.items()}
+        streamed = {"tpr_%s%s_batch" % (name, source): lead + own
+                    for source, lead in (("", [P]), ("_dense", [DP]), ("_sampled", [SP]), ("_sampled_boxed", [SP, V, V]))
+                    for name, own in passes.items()}
+        # ... the other solver entries ...
+        streamed.update({
+            "tpr_robust_solve_batch": [P, V, R, V],
+            "tpr_constraint_params_batch": [P, V, V, V, V, V, V, V, V],
+            "tpr_solve_stagewise_batch": [P, V, V, V, V, I, V],
+            "tpr_lp1d_batch": [I, I] + [V] * 9,
+            "tpr_lp2d_batch": [I, I] + [V] * 11,
+            "tpr_spline_fit_batch": [I, I, I, V, I, V, I, I, V, V, V, I],
+            "tpr_const_accel_times_batch": [P, V, V, V],
+            "tpr_const_accel_eval_batch": [P, V, V, V, I, V, I, V],
+            "tpr_param_spline_batch": [P, V, V, V, V],
+            "tpr_param_spline_sample_batch": [P, V, I, V, I, I, V, V, V, V],
+            "tpr_param_spline_samples_batch": [SP, V, V, V, V],
+            "tpr_ppoly_eval_batch": [I, I, I, V, V, V, I, V, I, V, I],
+            "tpr_path_eval_batch": [P, V, V, V],
+            "tpr_second_order_rows_batch": [P, I, SO, V, V, V, V, V, V],
+            "tpr_sampled_rows_batch": [SP, I, SO, V, V, V, V, V, V, V],
+            "tpr_stage_boxes_batch": [I, I, I, V, I, BS, I, V, V]})
         # ... and the rigid-body family: (..., int flags, void *stream)
-        signatures.update({name: argtypes + [I, V] for name, argtypes in {
+        streamed.update({name: argtypes + [I] for name, argtypes in {
                 "tpr_chain_inverse_dynamics_batch": [CP, LL, V, V, V, V],
                 "tpr_chain_torque_terms_batch": [CP, I, I, V, V, V, V, V, V],
                 "tpr_chain_tool_velocity_batch": [CP, I, I, V, V, V, V, V, V],
@@ -283,13 +236,27 @@ def load():
                 "tpr_tree_joint_wrench_batch": [CP, V, JP, LL, V, V, V, V],
                 "tpr_tree_joint_wrench_terms_batch": [CP, V, JP, I, I, V, V, V, V, V, V],
                 "tpr_tree_momentum_batch": [CP, V, MP, C.c_uint32, I, I, V, V, V, V, V, V]}.items()})
-        for name, argtypes in signatures.items():
+        signatures.update({name: argtypes + [V] for name, argtypes in streamed.items()})
+
+        def declare(name):
             entry = getattr(L, name)
-            entry.restype, entry.argtypes = C.c_int, argtypes
-        L.tpr_lp1d_batch.restype = C.c_int
-        L.tpr_lp1d_batch.argtypes = [C.c_int, C.c_int] + [V] * 10
-        L.tpr_lp2d_batch.restype = C.c_int
-        L.tpr_lp2d_batch.argtypes = [C.c_int, C.c_int] + [V] * 12
+            entry.restype, entry.argtypes = C.c_int, signatures[name]
+            return entry
+
+        # the sizes first: a library built from another header is refused as such, not at an entry it lacks
+        sizes = [C.c_int32(0), C.c_int32(0), C.c_int32(0)]
+        declare("tpr_abi_sizes")(*[C.byref(v) for v in sizes])
+        mine = [C.sizeof(tpr_problem), C.sizeof(tpr_result), C.sizeof(tpr_dense_problem)]
+        if [v.value for v in sizes] != mine:
+            raise ToppraHipError("libtoppra_hip.so was built from another header: its tpr_problem / tpr_result / "
+                                 "tpr_dense_problem take %s bytes, this binding declares %s" % ([v.value for v in sizes], mine))
+        for struct in sized:
+            size = declare(struct.__name__ + "_bytes")
+            if size() != C.sizeof(struct):
+                raise ToppraHipError("libtoppra_hip.so was built from another header: its %s takes %d bytes, this "
+                                     "binding declares %d" % (struct.__name__, size(), C.sizeof(struct)))
+        for name in signatures:
+            declare(name)
         _lib = L
         return _lib
 
@@ -341,10 +308,10 @@ def ptr(x):
     return x.data_ptr()
 
 
-def _per_traj(name, arr, B, like, dev):
-    """A per-trajectory vector ([B], or a scalar broadcast to it) as a contiguous fp64 array on the
-    problem's device."""
-    if dev:
+def per_traj_vector(name, arr, B, like):
+    """A per-trajectory vector ([B], or a scalar broadcast to it) as a contiguous fp64 array of the kind of ``like``, on its
+    device: sd_start / sd_end of the builders, sdmin / sdmax / desired_duration / limit of the batch entries."""
+    if is_torch_cuda(like):
         import torch
         if not (hasattr(arr, "is_cuda") and arr.is_cuda):
             arr = torch.as_tensor(arr, dtype=torch.float64, device=like.device)
@@ -362,6 +329,36 @@ def _per_traj(name, arr, B, like, dev):
     return np.ascontiguousarray(arr)
 
 
+def _limits(p, keep, conv, vlim, alim, interpolation):
+    """vlim / alim [B, d, 2] of a spline-table or sampled problem ``p``: checked, kept, pointed to; returns their flag bits."""
+    flags = 0
+    for name, arr, flag in (("vlim", vlim, HAS_VELOCITY), ("alim", alim, HAS_ACCELERATION)):
+        if arr is not None:
+            arr = conv(name, arr)
+            if tuple(arr.shape) != (p.B, p.d, 2):
+                raise ValueError("%s must have shape [B, d, 2] = [%d, %d, 2], got %s" % (name, p.B, p.d, tuple(arr.shape)))
+            keep.append(arr)
+            setattr(p, name, ptr(arr))
+            flags |= flag
+    if alim is not None and interpolation:
+        flags |= ACC_INTERPOLATION
+    return flags
+
+
+def _finish(p, keep, like, sd_start, sd_end, active):
+    """What every builder ends with: sd_start / sd_end as per-trajectory vectors and ``active``, the [B, 4] int32 warm-start
+    state of the reference's wrapper object (updated in place), checked, kept and pointed to by ``p``: (p, keep)."""
+    for name, arr in (("sd_start", sd_start), ("sd_end", sd_end)):
+        if arr is not None:
+            arr = per_traj_vector(name, arr, p.B, like)
+            keep.append(arr)
+            setattr(p, name, ptr(arr))
+    if active is not None:
+        keep.append(_check_active(active, p.B, like, is_torch_cuda(like)))
+        p.active = ptr(active)
+    return p, keep
+
+
 def make_dense_problem(a, b, c, low, high, deltas, sd_start=None, sd_end=None, squared=False, keep=None, active=None):
     """Build a tpr_dense_problem from the arrays of the reference's seidelWrapper (all numpy or all torch-CUDA):
     a, b, c [B, N+1, nC] (a_arr, b_arr, c_arr: nC counts the two reserved x_next rows), low, high [B, N+1, 2],
@@ -369,16 +366,7 @@ def make_dense_problem(a, b, c, low, high, deltas, sd_start=None, sd_end=None, s
     in / out).  Shapes and dtypes are validated here: the C-ABI takes raw pointers."""
     dev = is_torch_cuda(a)
     keep = keep if keep is not None else []
-    if dev:
-        def conv(name, x):
-            if not (hasattr(x, "is_cuda") and x.is_cuda):
-                raise ValueError("%s must be a CUDA tensor like a (mixing host and device arrays is not supported)" % name)
-            check_tensor(name, x, a)
-            return x.contiguous()
-        check_tensor("a", a, a)
-    else:
-        def conv(name, x):
-            return f64(x)
+    conv = converter(a, "a")
     a = conv("a", a)
     if a.ndim != 3:
         raise ValueError("a must have shape [B, N+1, nC]")
@@ -386,8 +374,8 @@ def make_dense_problem(a, b, c, low, high, deltas, sd_start=None, sd_end=None, s
     N = N1 - 1
     if N < 1:
         raise ValueError("dense rows need at least two gridpoints")
-    if not 2 <= nC <= 122:
-        raise ValueError("nC = %d rows per stage (incl. the two x_next rows) is outside 2..122" % nC)
+    if not 2 <= nC <= MAX_DENSE_ROWS:
+        raise ValueError("nC = %d rows per stage (incl. the two x_next rows) is outside 2..%d" % (nC, MAX_DENSE_ROWS))
     b, c = conv("b", b), conv("c", c)
     low, high = conv("low", low), conv("high", high)
     for name, arr, shape in (("b", b, (B, N1, nC)), ("c", c, (B, N1, nC)), ("low", low, (B, N1, 2)), ("high", high, (B, N1, 2))):
@@ -404,15 +392,7 @@ def make_dense_problem(a, b, c, low, high, deltas, sd_start=None, sd_end=None, s
     p = tpr_dense_problem(B=B, N=N, nC=nC, flags=(DEVICE_PTRS if dev else 0) | (BOUNDARY_SQUARED if squared else 0))
     keep += [a, b, c, low, high, deltas]
     p.a, p.b, p.c, p.low, p.high, p.deltas = ptr(a), ptr(b), ptr(c), ptr(low), ptr(high), ptr(deltas)
-    for name, arr in (("sd_start", sd_start), ("sd_end", sd_end)):
-        if arr is not None:
-            arr = _per_traj(name, arr, B, a, dev)
-            keep.append(arr)
-            setattr(p, name, ptr(arr))
-    if active is not None:  # [B, 4] int32 warm-start state of the reference's wrapper object, updated in place
-        keep.append(_check_active(active, B, a, dev))
-        p.active = ptr(active)
-    return p, keep
+    return _finish(p, keep, a, sd_start, sd_end, active)
 
 
 def converter(like, like_name):
@@ -444,6 +424,13 @@ def _check_active(active, B, like, dev):
 def sampled_rows_per_stage(d, alim, interpolation):
     """nC of a sampled problem without second-order blocks: the two x_next rows and the acceleration block."""
     return 2 + ((4 if interpolation else 2) * d if alim is not None else 0)
+
+
+def check_row_limit(nC):
+    """The refusal of a constraint list with more rows per stage than the dense-row kernels hold."""
+    if nC > MAX_DENSE_ROWS:
+        raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
+                                  % (nC, MAX_DENSE_ROWS))
 
 
 def make_sampled_problem(grid, q, qs, qss, vlim, alim, sd_start=None, sd_end=None, interpolation=True, keep=None,
@@ -486,26 +473,8 @@ def make_sampled_problem(grid, q, qs, qss, vlim, alim, sd_start=None, sd_end=Non
     p = tpr_sampled_problem(B=B, d=d, N=N, flags=0)
     keep += [grid, q, qs, qss]
     p.grid, p.q, p.qs, p.qss = ptr(grid), ptr(q), ptr(qs), ptr(qss)
-    for name, arr, flag in (("vlim", vlim, HAS_VELOCITY), ("alim", alim, HAS_ACCELERATION)):
-        if arr is not None:
-            arr = conv(name, arr)
-            if tuple(arr.shape) != (B, d, 2):
-                raise ValueError("%s must have shape [B, d, 2] = [%d, %d, 2], got %s" % (name, B, d, tuple(arr.shape)))
-            keep.append(arr)
-            setattr(p, name, ptr(arr))
-            flags |= flag
-    if alim is not None and interpolation:
-        flags |= ACC_INTERPOLATION
-    for name, arr in (("sd_start", sd_start), ("sd_end", sd_end)):
-        if arr is not None:
-            arr = _per_traj(name, arr, B, qs, dev)
-            keep.append(arr)
-            setattr(p, name, ptr(arr))
-    if active is not None:
-        keep.append(_check_active(active, B, qs, dev))
-        p.active = ptr(active)
-    p.flags = flags
-    return p, keep
+    p.flags = flags | _limits(p, keep, conv, vlim, alim, interpolation)
+    return _finish(p, keep, qs, sd_start, sd_end, active)
 
 
 def _no_nan(name, arr):
@@ -591,11 +560,6 @@ def check_weight(S):
         raise ValueError("S must be positive semi-definite (smallest eigenvalue %g)" % eig.min())
 
 
-def per_traj_vector(name, arr, B, like):
-    """Public form of the per-trajectory check for the other batch entries (sdmin, sdmax, ...)."""
-    return _per_traj(name, arr, B, like, is_torch_cuda(like))
-
-
 def make_problem(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, interpolation=True,
                  variant=0, keep=None, strict=False, active=None, squared=False, sound=False):
     """Build a tpr_problem from arrays (all numpy or all torch-CUDA).  `keep` collects the
@@ -606,18 +570,8 @@ def make_problem(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, int
     on coef's device."""
     dev = is_torch_cuda(coef)
     keep = keep if keep is not None else []
-    if dev:
-        def conv(name, x):
-            if not (hasattr(x, "is_cuda") and x.is_cuda):
-                raise ValueError("%s must be a CUDA tensor like coef (mixing host and device arrays is not supported)" % name)
-            check_tensor(name, x, coef)
-            return x.contiguous()
-        check_tensor("coef", coef, coef)
-        coef = coef.contiguous()
-    else:
-        def conv(name, x):
-            return f64(x)
-        coef = f64(coef)
+    conv = converter(coef, "coef")
+    coef = conv("coef", coef)
     breaks = conv("breaks", breaks)
     grid = conv("grid", grid)
     if coef.ndim != 4 or coef.shape[1] != 4:
@@ -643,23 +597,5 @@ def make_problem(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, int
     p = tpr_problem(B=B, d=d, nseg=nseg, N=N, flags=0, variant=int(variant))
     keep += [coef, breaks, grid]
     p.coef, p.breaks, p.grid = ptr(coef), ptr(breaks), ptr(grid)
-    for name, arr, flag in (("vlim", vlim, HAS_VELOCITY), ("alim", alim, HAS_ACCELERATION)):
-        if arr is not None:
-            arr = conv(name, arr)
-            if tuple(arr.shape) != (B, d, 2):
-                raise ValueError("%s must have shape [B, d, 2] = [%d, %d, 2], got %s" % (name, B, d, tuple(arr.shape)))
-            keep.append(arr)
-            setattr(p, name, ptr(arr))
-            flags |= flag
-    if alim is not None and interpolation:
-        flags |= ACC_INTERPOLATION
-    for name, arr in (("sd_start", sd_start), ("sd_end", sd_end)):
-        if arr is not None:
-            arr = _per_traj(name, arr, B, coef, dev)
-            keep.append(arr)
-            setattr(p, name, ptr(arr))
-    if active is not None:  # [B, 4] int32 warm-start state of the reference's wrapper object, updated in place
-        keep.append(_check_active(active, B, coef, dev))
-        p.active = ptr(active)
-    p.flags = flags
-    return p, keep
+    p.flags = flags | _limits(p, keep, conv, vlim, alim, interpolation)
+    return _finish(p, keep, coef, sd_start, sd_end, active)

@@ -315,16 +315,11 @@ class BatchTOPPRA(object):
     # warm-start state like a fresh reference object.
     def _check_constraints(self):
         """Everything that can be refused from shapes alone, before any launch."""
-        if self._samples is not None:
-            B, N, d = int(self._samples[1].shape[0]), int(self._samples[1].shape[1]) - 1, int(self._samples[1].shape[2])
-        else:
-            if getattr(self.coef, "ndim", 0) != 4:
-                raise ValueError("coef must have shape [B, 4, nseg, d]")
-            B, d, N = int(self.coef.shape[0]), int(self.coef.shape[3]), int(self.gridpoints.shape[-1]) - 1
+        B, N, d = self._sizes()
         if len(self.constraints) > _capi.SO_MAX_BLOCKS:
             raise NotImplementedError("%d second-order constraints in one list: the row kernel takes %d"
                                       % (len(self.constraints), _capi.SO_MAX_BLOCKS))
-        nC = 2 + ((4 if self.interpolation else 2) * d if self.alim is not None else 0)
+        nC = _capi.sampled_rows_per_stage(d, self.alim, self.interpolation)
         for con in self.constraints:
             if not (hasattr(con, "block") and hasattr(con, "rows_per_stage")):
                 raise NotImplementedError("%s is outside BatchTOPPRA (BatchJointTorqueConstraint, BatchSecondOrderConstraint, "
@@ -332,9 +327,7 @@ class BatchTOPPRA(object):
                                           "BatchBaseWrenchConstraint and BatchToolWrenchConstraint are supported)" % type(con).__name__)
             con.check(B, N, d)
             nC += con.rows_per_stage(d) or 0
-        if nC > _capi.MAX_DENSE_ROWS:
-            raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
-                                      % (nC, _capi.MAX_DENSE_ROWS))
+        _capi.check_row_limit(nC)
 
     # -- first-order constraints: BatchJointVelocityConstraintVarying / BatchBoundConstraint -------------------------------
     # They add no rows.  The bound sources [vlim (if given), then the first-order constraints in list order] are folded into

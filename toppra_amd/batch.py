@@ -70,6 +70,21 @@ def _prepare(coef):
         _capi.init()
 
 
+def _result(like, B, N, sd=True, u=True, K=True):
+    """The outputs of a solve for B trajectories of N stages, made like ``like`` -- dict(sd2 [B, N+1], status [B] and, where
+    wanted, sd [B, N+1], u [B, N], K [B, N+1, 2]) -- and the tpr_result that points into them (null where not wanted)."""
+    out = {"sd2": _empty(like, (B, N + 1))}
+    if sd:
+        out["sd"] = _empty(like, (B, N + 1))
+    if u:
+        out["u"] = _empty(like, (B, N))
+    if K:
+        out["K"] = _empty(like, (B, N + 1, 2))
+    out["status"] = _empty(like, (B,), "i32")
+    return out, _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out.get("u")),
+                                 K=_capi.ptr(out.get("K")), status=_capi.ptr(out["status"]))
+
+
 def solve_batch(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, interpolation=True,
                 want_sd=False, variant=0, strict=False, want_K=True, want_u=True, active=None, sound=False):
     """compute_parameterization for B trajectories.
@@ -88,19 +103,10 @@ def solve_batch(coef, breaks, grid, vlim, alim, sd_start=None, sd_end=None, inte
 
     ``active`` [B, 4] int32 (in/out): the warm-start state ``active_c_up[2], active_c_down[2]`` of the
     reference's wrapper object, for sequences of passes on one instance (``None`` = a fresh instance)."""
-    _prepare(coef)
+    _prepare(coef)  # (spelled out, not a _Source: the host-buffer call of one trajectory is all latency)
     p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, sd_start, sd_end, interpolation,
                                  variant, strict=strict, active=active, sound=sound)
-    B, N = p.B, p.N
-    out = {"sd2": _empty(coef, (B, N + 1)), "status": _empty(coef, (B,), "i32")}
-    if want_u:
-        out["u"] = _empty(coef, (B, N))
-    if want_K:
-        out["K"] = _empty(coef, (B, N + 1, 2))
-    if want_sd:
-        out["sd"] = _empty(coef, (B, N + 1))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out.get("u")),
-                         K=_capi.ptr(out.get("K")), status=_capi.ptr(out["status"]))
+    out, r = _result(coef, p.B, p.N, want_sd, want_u, want_K)
     _capi.check(_capi.load().tpr_solve_batch(C.byref(p), C.byref(r), _stream_ptr(coef)))
     return out
 
@@ -114,17 +120,9 @@ def solve_desired_duration_batch(coef, breaks, grid, vlim, alim, desired_duratio
     ``variant``: 0 = auto (from 9216 trajectories up to 8 dof, 14336 .. 36864 at 9 .. 15 dof: the certified lane kernel runs the backward scan and both
     forward profiles in one launch; rows across lanes otherwise), 2 / 3 force one.  ``squared``: sd_start / sd_end already
     hold sd^2 (TPR_BOUNDARY_SQUARED)."""
-    _prepare(coef)
-    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, sd_start, sd_end, interpolation, variant=variant, squared=squared)
-    B, N = p.B, p.N
-    desired = _capi.per_traj_vector("desired_duration", desired_duration, B, coef)
-    out = {"sd2": _empty(coef, (B, N + 1)), "sd": _empty(coef, (B, N + 1)), "u": _empty(coef, (B, N)),
-           "K": _empty(coef, (B, N + 1, 2)), "status": _empty(coef, (B,), "i32"), "alpha": _empty(coef, (B,))}
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
-    _capi.check(_capi.load().tpr_solve_desired_duration_batch(C.byref(p), _capi.ptr(desired), float(atol), C.byref(r),
-                                                              _capi.ptr(out["alpha"]), _stream_ptr(coef)))
-    return out
+    source = _table_source(coef, breaks, grid, vlim, alim, sd_start=sd_start, sd_end=sd_end, interpolation=interpolation,
+                           variant=variant, squared=squared)
+    return _rows_solve_desired_duration(source, desired_duration, atol)
 
 
 def robust_solve_batch(coef, breaks, grid, vlim, alim, ellipsoid, sd_start=None, sd_end=None, interpolation=True,
@@ -139,12 +137,9 @@ def robust_solve_batch(coef, breaks, grid, vlim, alim, ellipsoid, sd_start=None,
     p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, sd_start, sd_end, interpolation, variant=variant)
     B, N = p.B, p.N
     ell = np.ascontiguousarray(np.asarray(ellipsoid, dtype=np.float64).reshape(3))  # always a host array
-    out = {"sd2": _empty(coef, (B, N + 1)), "sd": _empty(coef, (B, N + 1)), "u": _empty(coef, (B, N)),
-           "K": _empty(coef, (B, N + 1, 2)), "status": _empty(coef, (B,), "i32")}
+    out, r = _result(coef, B, N)
     if want_X:
         out["X"] = _empty(coef, (B, N + 1, 2))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
     _capi.check(_capi.load().tpr_robust_solve_batch(C.byref(p), ell.ctypes.data, C.byref(r), _capi.ptr(out.get("X")),
                                                     _stream_ptr(coef)))
     return out
@@ -169,58 +164,53 @@ def controllable_sets_batch(coef, breaks, grid, vlim, alim, sdmin, sdmax, interp
                             variant=0, strict=False, sound=False):
     """compute_controllable_sets(sdmin, sdmax) for B trajectories -> K[B,N+1,2] (``active``: see solve_batch;
     ``squared``: sdmin / sdmax already hold sd^2 -- TPR_BOUNDARY_SQUARED; ``variant`` / ``strict`` / ``sound``: as solve_batch)."""
-    _prepare(coef)
-    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation, active=active, squared=squared,
-                                 variant=variant, strict=strict, sound=sound)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, coef)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, coef)
-    K = _empty(coef, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_controllable_sets_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax),
-                                                         _capi.ptr(K), _stream_ptr(coef)))
-    return K
+    source = _table_source(coef, breaks, grid, vlim, alim, interpolation=interpolation, active=active, squared=squared,
+                           variant=variant, strict=strict, sound=sound)
+    return _rows_sets(source, "controllable_sets", sdmin, sdmax)
 
 
 # --------------------------------------------------------------------------------------------
-# the dense-row passes (solve, TOPPRAsd, controllable / feasible / reachable sets) on each of their three sources: the public
-# functions below are their signatures and docstrings; a source adaptor builds the problem, a pass helper does the rest
+# the five passes (solve, TOPPRAsd, controllable / feasible / reachable sets) on each of their four sources -- the spline table,
+# dense rows, samples, samples with stage boxes: the public functions are their signatures and docstrings; a source adaptor builds
+# the problem (and decides whether it is validated before or after the device is initialised), a pass helper does the rest
 
 # the entries' suffix, the problem, the array that outputs are made like, the C arguments between the problem and the pass's
 # own, the converted arrays the problem points to (alive as long as the source is)
 _Source = collections.namedtuple("_Source", "family p like lead keep")
 
 
+def _table_source(coef, breaks, grid, vlim, alim, **problem):
+    _prepare(coef)
+    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, **problem)
+    return _Source("", p, coef, (), keep)
+
+
 def _dense_source(a, b, c, low, high, deltas, **problem):
     _prepare(a)
     p, keep = _capi.make_dense_problem(a, b, c, low, high, deltas, **problem)
-    return _Source("dense", p, a, (), keep)
+    return _Source("_dense", p, a, (), keep)
 
 
 def _sampled_source(grid, qs, qss, vlim, alim, **problem):
     p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, **problem)
     _prepare(keep[2])
-    return _Source("sampled", p, keep[2], (), keep)
+    return _Source("_sampled", p, keep[2], (), keep)
 
 
 def _boxed_source(grid, qs, qss, alim, low, high, **problem):
     p, keep, low, high = _capi.make_boxed_problem(grid, qs, qss, alim, low, high, **problem)
     _prepare(keep[2])
-    return _Source("sampled_boxed", p, keep[2], (_capi.ptr(low), _capi.ptr(high)), keep)
+    return _Source("_sampled_boxed", p, keep[2], (_capi.ptr(low), _capi.ptr(high)), keep)
 
 
 def _rows_call(source, name, *args):
-    """tpr_<name>_<family>_batch on ``source``: the problem, the source's leading arguments, ``args``, the stream."""
-    entry = getattr(_capi.load(), "tpr_%s_%s_batch" % (name, source.family))
+    """tpr_<name><family>_batch on ``source``: the problem, the source's leading arguments, ``args``, the stream."""
+    entry = getattr(_capi.load(), "tpr_%s%s_batch" % (name, source.family))
     _capi.check(entry(C.byref(source.p), *source.lead, *args, _stream_ptr(source.like)))
 
 
 def _rows_solve(source, want_sd):
-    p, like = source.p, source.like
-    out = {"sd2": _empty(like, (p.B, p.N + 1)), "u": _empty(like, (p.B, p.N)), "K": _empty(like, (p.B, p.N + 1, 2)),
-           "status": _empty(like, (p.B,), "i32")}
-    if want_sd:
-        out["sd"] = _empty(like, (p.B, p.N + 1))
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out.get("sd")), u=_capi.ptr(out["u"]), K=_capi.ptr(out["K"]),
-                         status=_capi.ptr(out["status"]))
+    out, r = _result(source.like, source.p.B, source.p.N, sd=want_sd)
     _rows_call(source, "solve", C.byref(r))
     return out
 
@@ -229,10 +219,8 @@ def _rows_solve_desired_duration(source, desired_duration, atol):
     p, like = source.p, source.like
     B, N = p.B, p.N
     desired = _capi.per_traj_vector("desired_duration", desired_duration, B, like)
-    out = {"sd2": _empty(like, (B, N + 1)), "sd": _empty(like, (B, N + 1)), "u": _empty(like, (B, N)),
-           "K": _empty(like, (B, N + 1, 2)), "status": _empty(like, (B,), "i32"), "alpha": _empty(like, (B,))}
-    r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                         K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
+    out, r = _result(like, B, N)
+    out["alpha"] = _empty(like, (B,))
     _rows_call(source, "solve_desired_duration", _capi.ptr(desired), float(atol), C.byref(r), _capi.ptr(out["alpha"]))
     return out
 
@@ -295,15 +283,8 @@ def feasible_sets_dense_batch(a, b, c, low, high, deltas, active=None):
 def reachable_sets_batch(coef, breaks, grid, vlim, alim, sdmin, sdmax, interpolation=True, want_X=False, squared=False):
     """compute_reachable_sets(sdmin, sdmax) for B trajectories -> L[B,N+1,2] (and the feasible sets
     X[B,N+1,2] it computes on the way with ``want_X``)."""
-    _prepare(coef)
-    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation, squared=squared)
-    sdmin = _capi.per_traj_vector("sdmin", sdmin, p.B, coef)
-    sdmax = _capi.per_traj_vector("sdmax", sdmax, p.B, coef)
-    L = _empty(coef, (p.B, p.N + 1, 2))
-    X = _empty(coef, (p.B, p.N + 1, 2)) if want_X else None
-    _capi.check(_capi.load().tpr_reachable_sets_batch(C.byref(p), _capi.ptr(sdmin), _capi.ptr(sdmax), _capi.ptr(L),
-                                                      _capi.ptr(X), _stream_ptr(coef)))
-    return (L, X) if want_X else L
+    source = _table_source(coef, breaks, grid, vlim, alim, interpolation=interpolation, squared=squared)
+    return _rows_sets(source, "reachable_sets", sdmin, sdmax, bool(want_X))
 
 
 def feasible_sets_batch(coef, breaks, grid, vlim, alim, interpolation=True, active=None, variant=0, strict=False,
@@ -314,12 +295,8 @@ def feasible_sets_batch(coef, breaks, grid, vlim, alim, interpolation=True, acti
     kernel from 8192 trajectories up to 8 dof, 14336 .. 36864 at 9 .. 15 dof; rows across lanes otherwise), 2 / 3 / 4 force a
     kernel family.
     ``strict`` (TPR_STRICT_SEIDEL): the reference's full iteration for every LP; ``sound``: see solve_batch."""
-    _prepare(coef)
-    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation, active=active, variant=variant,
-                                 strict=strict, sound=sound)
-    X = _empty(coef, (p.B, p.N + 1, 2))
-    _capi.check(_capi.load().tpr_feasible_sets_batch(C.byref(p), _capi.ptr(X), _stream_ptr(coef)))
-    return X
+    return _rows_feasible_sets(_table_source(coef, breaks, grid, vlim, alim, interpolation=interpolation, active=active,
+                                             variant=variant, strict=strict, sound=sound))
 
 
 def constraint_params_batch(coef, breaks, grid, vlim, alim, interpolation=True):
@@ -328,7 +305,7 @@ def constraint_params_batch(coef, breaks, grid, vlim, alim, interpolation=True):
     Returns dict(a,b,c [B,N+1,nC], low, high, xbound [B,N+1,2], qs, qss [B,N+1,d])."""
     _prepare(coef)
     p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation)
-    nC = 2 + ((4 if interpolation else 2) * p.d if alim is not None else 0)
+    nC = _capi.sampled_rows_per_stage(p.d, alim, interpolation)
     B, N, d = p.B, p.N, p.d
     out = {k: _empty(coef, (B, N + 1, nC)) for k in ("a", "b", "c")}
     out.update({k: _empty(coef, (B, N + 1, 2)) for k in ("low", "high", "xbound")})
@@ -354,7 +331,7 @@ def path_eval_batch(coef, breaks, grid, orders=(0, 1, 2)):
 
 def second_order_rows_per_stage(d, alim, interpolation, blocks):
     """nC of the dense problem :func:`second_order_rows_batch` writes: the two x_next rows, the acceleration block, the blocks."""
-    nC = 2 + ((4 if interpolation else 2) * d if alim is not None else 0)
+    nC = _capi.sampled_rows_per_stage(d, alim, interpolation)
     for blk in blocks:
         m = 2 * int(blk["w0"].shape[-1]) if blk.get("F") is None else int(blk["F"].shape[-2])
         nC += (2 if blk.get("interpolation", True) else 1) * m
@@ -401,6 +378,30 @@ def _stage_blocks(blocks, B, N, d, conv):
     return structs, keep, staged
 
 
+def _stage_rows(blocks, sizes, like, like_name, alim, interpolation):
+    """The first half of the two row builders, before the device is touched: the blocks staged, the rows of a stage counted
+    and refused above the limit; then the device initialisation.  Returns (structs, the arrays they point to, blocks, nC)."""
+    B, N, d = sizes
+    structs, keep, staged = _stage_blocks(blocks, B, N, d, _capi.converter(like, like_name))
+    nC = second_order_rows_per_stage(d, alim, interpolation, staged)
+    _capi.check_row_limit(nC)
+    _prepare(like)
+    return structs, keep, len(staged), nC
+
+
+def _write_rows(entry, p, like, rows, more=()):
+    """The second half: the outputs a, b, c, low, high, ``more``, deltas made like ``like``, and the call of ``entry`` on the
+    problem ``p`` with the ``rows`` of :func:`_stage_rows`."""
+    structs, keep, nblocks, nC = rows
+    B, N = p.B, p.N
+    out = {k: _empty(like, (B, N + 1, nC)) for k in ("a", "b", "c")}
+    out.update({k: _empty(like, (B, N + 1, 2)) for k in ("low", "high") + more})
+    out["deltas"] = _empty(like, (B, N))
+    pointers = [_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas") + more]
+    _capi.check(getattr(_capi.load(), entry)(C.byref(p), nblocks, structs, *pointers, _stream_ptr(like)))
+    return out
+
+
 def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolation=True):
     """The dense problem of the constraint list [velocity, acceleration, second-order blocks ...] for B trajectories, built on
     the GPU: dict(a, b, c [B, N+1, nC], low, high [B, N+1, 2], deltas [B, N]) -- the arguments of :func:`solve_dense_batch` and
@@ -415,23 +416,12 @@ def second_order_rows_batch(coef, breaks, grid, vlim, alim, blocks, interpolatio
       ``friction``: None or [B, p] (dry friction, p == d);  ``interpolation``: the block's discretisation (default True).
     ``interpolation`` is the acceleration constraint's.  All arrays numpy, or all torch tensors on coef's device.  Shapes are
     checked, and more than 122 rows per stage refused (NotImplementedError), before anything is launched."""
-    conv = _capi.converter(coef, "coef")
     if coef.ndim != 4:
         raise ValueError("coef must have shape [B, 4, nseg, d]")
-    B, d, N = int(coef.shape[0]), int(coef.shape[3]), int(grid.shape[-1]) - 1
-    structs, keep, staged = _stage_blocks(blocks, B, N, d, conv)
-    nC = second_order_rows_per_stage(d, alim, interpolation, staged)
-    if nC > _capi.MAX_DENSE_ROWS:
-        raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
-                                  % (nC, _capi.MAX_DENSE_ROWS))
-    _prepare(coef)
-    p, keep2 = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation)
-    out = {k: _empty(coef, (B, N + 1, nC)) for k in ("a", "b", "c")}
-    out.update({k: _empty(coef, (B, N + 1, 2)) for k in ("low", "high")})
-    out["deltas"] = _empty(coef, (B, N))
-    _capi.check(_capi.load().tpr_second_order_rows_batch(
-        C.byref(p), len(staged), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas")], _stream_ptr(coef)))
-    return out
+    sizes = int(coef.shape[0]), int(grid.shape[-1]) - 1, int(coef.shape[3])
+    rows = _stage_rows(blocks, sizes, coef, "coef", alim, interpolation)
+    p, keep = _capi.make_problem(coef, breaks, grid, vlim, alim, None, None, interpolation)  # (validated after the device init)
+    return _write_rows("tpr_second_order_rows_batch", p, coef, rows)
 
 
 # --------------------------------------------------------------------------------------------
@@ -445,22 +435,8 @@ def sampled_rows_batch(grid, qs, qss, vlim, alim, blocks=(), interpolation=True)
     if qss is None:
         raise ValueError("the rows need qss = path(grid, 2)")
     p, keep = _capi.make_sampled_problem(grid, None, qs, qss, vlim, alim, interpolation=interpolation, solver=False)
-    like = keep[2]
-    conv = _capi.converter(like, "qs")
-    B, N, d = p.B, p.N, p.d
-    structs, keep2, staged = _stage_blocks(blocks, B, N, d, conv)
-    nC = second_order_rows_per_stage(d, alim, interpolation, staged)
-    if nC > _capi.MAX_DENSE_ROWS:
-        raise NotImplementedError("%d constraint rows per stage (incl. the two x_next rows): the dense-row kernels hold %d"
-                                  % (nC, _capi.MAX_DENSE_ROWS))
-    _prepare(like)
-    out = {k: _empty(like, (B, N + 1, nC)) for k in ("a", "b", "c")}
-    out.update({k: _empty(like, (B, N + 1, 2)) for k in ("low", "high", "xbound")})
-    out["deltas"] = _empty(like, (B, N))
-    _capi.check(_capi.load().tpr_sampled_rows_batch(
-        C.byref(p), len(staged), structs, *[_capi.ptr(out[k]) for k in ("a", "b", "c", "low", "high", "deltas", "xbound")],
-        _stream_ptr(like)))
-    return out
+    rows = _stage_rows(blocks, (p.B, p.N, p.d), keep[2], "qs", alim, interpolation)
+    return _write_rows("tpr_sampled_rows_batch", p, keep[2], rows, ("xbound",))
 
 
 def solve_sampled_batch(grid, qs, qss, vlim, alim, sd_start=None, sd_end=None, interpolation=True, want_sd=False,
@@ -511,13 +487,7 @@ def param_spline_samples_batch(grid, q, qs, sd):
         raise ValueError("the spline parametrizer needs the path positions q at the gridpoints")
     p, keep = _capi.make_sampled_problem(grid, q, qs, None, None, None, solver=False)
     like = keep[2]
-    if _capi.is_torch_cuda(like):
-        _capi.check_tensor("sd", sd, like)
-        sd = sd.contiguous()
-    else:
-        sd = _capi.f64(sd)
-    if tuple(sd.shape) != (p.B, p.N + 1):
-        raise ValueError("sd must have shape [B, N+1] = [%d, %d]" % (p.B, p.N + 1))
+    sd, = _sd_of(p, like, sd)
     _prepare(like)
     out = {"knot_times": _empty(like, (p.B, p.N + 1)), "counts": _empty(like, (p.B,), "i32"),
            "coef": _empty(like, (p.B, 4, p.N, p.d))}
@@ -614,9 +584,6 @@ def reachable_sets_sampled_boxed_batch(grid, qs, qss, alim, low, high, sdmin, sd
     source = _boxed_source(grid, qs, qss, alim, low, high, interpolation=interpolation, active=active, squared=squared, vlim=vlim)
     return _rows_sets(source, "reachable_sets", sdmin, sdmax, bool(want_X))
 
-
-# --------------------------------------------------------------------------------------------
-# host-side input preparation (outside the hot path)
 
 # --------------------------------------------------------------------------------------------
 # a rigid-body chain evaluated on the GPU (include/toppra_hip.h: tpr_chain; the model object is toppra_amd.chain.SerialChain)
@@ -990,6 +957,22 @@ def const_accel_eval_batch(coef, breaks, grid, sd, ts, us, times, order=0):
     return out
 
 
+def _sd_of(p, like, sd, *more):
+    """``sd`` as [B, N+1] of the kind of the problem ``p``, whose arrays are like ``like``: contiguous fp64, a tensor checked to
+    live on like's device.  ``more``: (name, array) pairs converted the same way, all before sd's shape is checked.  Returns
+    the converted arrays, sd first."""
+    arrays = [("sd", sd)] + list(more)
+    if _capi.is_torch_cuda(like):
+        for name, arr in arrays:
+            _capi.check_tensor(name, arr, like)
+        arrays = [arr.contiguous() for name, arr in arrays]
+    else:
+        arrays = [_capi.f64(arr) for name, arr in arrays]
+    if tuple(arrays[0].shape) != (p.B, p.N + 1):
+        raise ValueError("sd must have shape [B, N+1] = [%d, %d]" % (p.B, p.N + 1))
+    return arrays
+
+
 def param_spline_batch(coef, breaks, grid, sd, variant=0):
     """ParametrizeSpline (the reference's default output parametrizer, parametrizer.py:161-196) for B
     trajectories: sd [B, N+1] -> dict(knot_times [B, N+1], counts [B], coef [B, 4, N, d]): the cubic spline in
@@ -1001,14 +984,7 @@ def param_spline_batch(coef, breaks, grid, sd, variant=0):
     fits).  Knot times and counts are the same bits in every variant."""
     _prepare(coef)
     p, keep = _capi.make_problem(coef, breaks, grid, None, None, variant=variant)
-    dev = _capi.is_torch_cuda(coef)
-    if dev:
-        _capi.check_tensor("sd", sd, coef)
-        sd = sd.contiguous()
-    else:
-        sd = _capi.f64(sd)
-    if tuple(sd.shape) != (p.B, p.N + 1):
-        raise ValueError("sd must have shape [B, N+1] = [%d, %d]" % (p.B, p.N + 1))
+    sd, = _sd_of(p, coef, sd)
     out = {"knot_times": _empty(coef, (p.B, p.N + 1)), "counts": _empty(coef, (p.B,), "i32"),
            "coef": _empty(coef, (p.B, 4, p.N, p.d))}
     _capi.check(_capi.load().tpr_param_spline_batch(C.byref(p), _capi.ptr(sd), _capi.ptr(out["knot_times"]),
@@ -1024,15 +1000,7 @@ def param_spline_sample_batch(coef, breaks, grid, sd, times, fractions=True, ord
     :func:`param_spline_batch` (variant 3) followed by :func:`ppoly_eval_batch`.  d <= 16, knots in LDS."""
     _prepare(coef)
     p, keep = _capi.make_problem(coef, breaks, grid, None, None)
-    dev = _capi.is_torch_cuda(coef)
-    if dev:
-        _capi.check_tensor("sd", sd, coef)
-        _capi.check_tensor("times", times, coef)
-        sd, times = sd.contiguous(), times.contiguous()
-    else:
-        sd, times = _capi.f64(sd), _capi.f64(times)
-    if tuple(sd.shape) != (p.B, p.N + 1):
-        raise ValueError("sd must have shape [B, N+1] = [%d, %d]" % (p.B, p.N + 1))
+    sd, times = _sd_of(p, coef, sd, ("times", times))
     if times.ndim not in (1, 2) or (times.ndim == 2 and int(times.shape[0]) != p.B):
         raise ValueError("times must have shape [T] or [B, T]")
     if times.ndim == 1 and not fractions:

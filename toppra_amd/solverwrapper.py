@@ -79,7 +79,50 @@ class SolverWrapper(object):
         pass
 
 
-class hipSeidelWrapper(SolverWrapper):
+class _RowPassesWrapper(SolverWrapper):
+    """The five passes of a wrapper object on the batch entries of its source, each a batch of one: the class names the
+    ``_family`` of its ``batch.*<family>_batch`` functions, :meth:`_source` gives their leading arguments and the keywords every
+    call takes.  Boundary velocities are squared HERE, with the reference's own expression on the caller's own objects
+    (``sd ** 2``: libm pow for Python floats, which is one ulp off sd * sd now and then; numpy's square for numpy scalars), and
+    handed over as x = sd^2 (``squared=True``: no sqrt / square round trip).  ``_active`` is the object's warm-start state: every
+    pass reads and updates it, so a sequence of passes on one instance (examples/plot_kinematics.py:48,72) pivots in the
+    reference's order and returns its bits -- but for the passes named in ``_stateless``, whose entries of this family take
+    no state."""
+
+    _stateless = ()
+
+    def _pass(self, name, *args, **kw):
+        lead, common = self._source()
+        if name not in self._stateless:
+            kw["active"] = self._active
+        return getattr(batch, "%s%s_batch" % (name, self._family))(*lead, *args, **common, **kw)
+
+    @staticmethod
+    def _squared(sd):
+        return np.array([sd ** 2], dtype=np.float64)
+
+    def controllable_sets(self, sdmin, sdmax):
+        return self._pass("controllable_sets", self._squared(sdmin), self._squared(sdmax), squared=True)[0]
+
+    def feasible_sets(self):
+        return self._pass("feasible_sets")[0]
+
+    def reachable_sets(self, sdmin, sdmax):
+        L, X = self._pass("reachable_sets", self._squared(sdmin), self._squared(sdmax), want_X=True, squared=True)
+        return L[0], X[0]
+
+    def parameterization(self, sd_start, sd_end):
+        out = self._pass("solve", self._squared(sd_start), self._squared(sd_end), want_sd=True, squared=True)
+        res = {k: v[0] for k, v in out.items() if k != "status"}
+        res["status"] = int(out["status"][0])
+        return res
+
+    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
+        out = self._pass("solve_desired_duration", desired_duration, self._squared(sd_start), self._squared(sd_end), atol, squared=True)
+        return {k: v[0] for k, v in out.items()}
+
+
+class hipSeidelWrapper(_RowPassesWrapper):
     """Seidel LP wrapper running on the MI355X.
 
     Parameters as seidelWrapper: ``constraint_list``, ``path``, ``path_discretization``,
@@ -99,7 +142,7 @@ class hipSeidelWrapper(SolverWrapper):
         vlim, alim, self._interp = extract_limits(constraint_list, self.dof)
         self._vlim = None if vlim is None else vlim[None]
         self._alim = None if alim is None else alim[None]
-        self.nC = 2 + (0 if alim is None else (4 if self._interp else 2) * self.dof)
+        self.nC = _capi.sampled_rows_per_stage(self.dof, alim, self._interp)
         # warm-start state of the two LP "solvers", as in the reference object
         self._active = np.zeros((1, 4), dtype=np.int32)
         self._params = None  # device init is lazy: every compute entry calls _capi.init()
@@ -116,23 +159,19 @@ class hipSeidelWrapper(SolverWrapper):
     def _args(self):
         return self._coef, self._breaks, self.path_discretization, self._vlim, self._alim
 
-    # (every pass reads and updates self._active, the reference object's warm-start state: a sequence of passes on
-    # one instance -- examples/plot_kinematics.py:48,72 -- pivots in the reference's order and returns its bits)
-    # Boundary velocities are squared HERE, with the reference's own expression on the caller's own objects
-    # (`sd ** 2`: libm pow for Python floats, which is one ulp off sd * sd now and then; numpy's square for numpy
-    # scalars), and handed down as x = sd^2 (TPR_BOUNDARY_SQUARED).
-    def controllable_sets(self, sdmin, sdmax):
-        return batch.controllable_sets_batch(*self._args(), np.array([sdmin ** 2], dtype=np.float64),
-                                             np.array([sdmax ** 2], dtype=np.float64), self._interp, active=self._active,
-                                             squared=True)[0]
+    # the spline-table entries: the reachable sets take no warm-start state
+    _family, _stateless = "", ("reachable_sets",)
 
-    def feasible_sets(self):
-        return batch.feasible_sets_batch(*self._args(), self._interp, active=self._active)[0]
+    def _source(self):
+        return self._args(), {"interpolation": self._interp}
 
-    def reachable_sets(self, sdmin, sdmax):
-        L, X = batch.reachable_sets_batch(*self._args(), np.array([sdmin ** 2], dtype=np.float64),
-                                          np.array([sdmax ** 2], dtype=np.float64), self._interp, want_X=True, squared=True)
-        return L[0], X[0]
+    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
+        # Spelled out: this pass has never been given the object's warm-start state NOR the acceleration constraint's
+        # discretisation -- it runs the entry's default, Interpolation, under Collocation too.  Whether that is right is a
+        # question of its own (the reference honours the constraint); answering it moves returned values.
+        out = batch.solve_desired_duration_batch(*self._args(), desired_duration, self._squared(sd_start), self._squared(sd_end),
+                                                 atol, squared=True)
+        return {k: v[0] for k, v in out.items()}
 
     def parameterization(self, sd_start, sd_end):
         """One compute_parameterization: sd2, sd, u, K [copies of the per-instance result buffers], status.  A single
@@ -143,11 +182,7 @@ class hipSeidelWrapper(SolverWrapper):
         if st is None:
             sd0, sd1 = np.zeros(1), np.zeros(1)
             p, keep = _capi.make_problem(*self._args(), sd0, sd1, self._interp, active=self._active, squared=True)
-            N = self.N
-            out = {"sd2": np.empty((1, N + 1)), "sd": np.empty((1, N + 1)), "u": np.empty((1, N)),
-                   "K": np.empty((1, N + 1, 2)), "status": np.empty((1,), dtype=np.int32)}
-            r = _capi.tpr_result(sd2=_capi.ptr(out["sd2"]), sd=_capi.ptr(out["sd"]), u=_capi.ptr(out["u"]),
-                                 K=_capi.ptr(out["K"]), status=_capi.ptr(out["status"]))
+            out, r = batch._result(self._coef, 1, self.N)
             views = {k: v[0] for k, v in out.items() if k != "status"}
             st = self._call_state = (sd0, sd1, C.byref(p), C.byref(r), _capi.load().tpr_solve_batch, views,
                                      out["status"], (p, r, keep, out))
@@ -161,12 +196,6 @@ class hipSeidelWrapper(SolverWrapper):
         res = {k: v.copy() for k, v in views.items()}  # (the buffers are reused by the next call: never hand out views)
         res["status"] = int(status[0])
         return res
-
-    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
-        out = batch.solve_desired_duration_batch(*self._args(), desired_duration,
-                                                 np.array([sd_start ** 2], dtype=np.float64),
-                                                 np.array([sd_end ** 2], dtype=np.float64), atol, squared=True)
-        return {k: v[0] for k, v in out.items()}
 
     # -- single-LP compatibility entry ---------------------------------------------------------
     def solve_stagewise_optim(self, i, H, g, x_min, x_max, x_next_min, x_next_max):
@@ -221,41 +250,6 @@ def dense_rows(constraint_list, path, path_discretization):
     return out
 
 
-class _RowPassesWrapper(SolverWrapper):
-    """The five passes of a wrapper object on the dense-row entries, each a batch of one: the class names the ``_family`` of its
-    ``batch.*_<family>_batch`` functions, :meth:`_source` gives their leading arguments and the keywords every call takes.
-    Boundary velocities are handed over squared (``squared=True``: no sqrt / square round trip); ``_active`` is the object's
-    warm-start state, carried from pass to pass as the reference object carries it."""
-
-    def _pass(self, name, *args, **kw):
-        lead, common = self._source()
-        return getattr(batch, "%s_%s_batch" % (name, self._family))(*lead, *args, active=self._active, **common, **kw)
-
-    @staticmethod
-    def _squared(sd):
-        return np.array([sd ** 2], dtype=np.float64)
-
-    def controllable_sets(self, sdmin, sdmax):
-        return self._pass("controllable_sets", self._squared(sdmin), self._squared(sdmax), squared=True)[0]
-
-    def feasible_sets(self):
-        return self._pass("feasible_sets")[0]
-
-    def reachable_sets(self, sdmin, sdmax):
-        L, X = self._pass("reachable_sets", self._squared(sdmin), self._squared(sdmax), want_X=True, squared=True)
-        return L[0], X[0]
-
-    def parameterization(self, sd_start, sd_end):
-        out = self._pass("solve", self._squared(sd_start), self._squared(sd_end), want_sd=True, squared=True)
-        res = {k: v[0] for k, v in out.items() if k != "status"}
-        res["status"] = int(out["status"][0])
-        return res
-
-    def parameterization_sd(self, sd_start, sd_end, desired_duration, atol=1e-5):
-        out = self._pass("solve_desired_duration", desired_duration, self._squared(sd_start), self._squared(sd_end), atol, squared=True)
-        return {k: v[0] for k, v in out.items()}
-
-
 class hipDenseSeidelWrapper(_RowPassesWrapper):
     """seidelWrapper for ANY list of canonical-linear constraints (SecondOrderConstraint, JointTorqueConstraint, the
     reference's own constraint objects, hand-written ones): the constraints' parameters are evaluated on the host, as in
@@ -280,8 +274,8 @@ class hipDenseSeidelWrapper(_RowPassesWrapper):
         self.deltas = rows["deltas"]
         self.nC = rows["nC"]
         self.params = rows["params"]
-        if self.nC > 122:
-            raise NotImplementedError("%d constraint rows per stage: the dense-row kernels hold 122" % self.nC)
+        if self.nC > _capi.MAX_DENSE_ROWS:
+            raise NotImplementedError("%d constraint rows per stage: the dense-row kernels hold %d" % (self.nC, _capi.MAX_DENSE_ROWS))
         self._rows = tuple(np.ascontiguousarray(rows[k][None]) for k in ("a", "b", "c", "low", "high")) + (self.deltas,)
         self._solve_lp1d = int(solve_lp1d)
         # warm-start state of the two LP "solvers", as in the reference object: every pass and every per-stage call reads
@@ -289,7 +283,7 @@ class hipDenseSeidelWrapper(_RowPassesWrapper):
         self._active = np.zeros((1, 4), dtype=np.int32) if active is None else active
         self._active_up, self._active_down = self._active[0, 0:2], self._active[0, 2:4]
 
-    _family = "dense"
+    _family = "_dense"
 
     def _source(self):
         return self._rows, {}
@@ -374,7 +368,7 @@ class hipSampledSeidelWrapper(_RowPassesWrapper):
             self._params = [c.compute_constraint_params(self.path, self.path_discretization) for c in self.constraints]
         return self._params
 
-    _family = "sampled"
+    _family = "_sampled"
 
     def _source(self):
         return self._args, {"interpolation": self._interp}
