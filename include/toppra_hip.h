@@ -659,7 +659,9 @@ int tpr_tree_joint_wrench_terms_batch(const tpr_chain *links, const int32_t *par
  * point's state in registers at any dof.  One wave of 64 points per block; dynamic LDS stages a block's q, qs rows and its outputs
  * (one row of 9 doubles per point) and keeps one bank of 18 doubles per lane and fork: at most 33 792 + 4 * 18 * 512 = 70 656 bytes.
  * Refused before any launch, in this order: B, N; what tpr_tree_base_wrench_batch refuses of links, parent and the mount; an empty
- * link_mask, a bit at or above d (TPR_E_BADARG); a NULL q or qs; all three outputs NULL; xbound without limit.               */
+ * link_mask, a bit at or above d (TPR_E_BADARG); a NULL q or qs; all three outputs NULL; xbound without limit.
+ * T2 bounds what a contact can take up at ANY point and direction at once; the energy at given control points, through the
+ * robot's effective (reflected) mass there, is the entry of toppra_hip_contact.h.                                              */
 int tpr_tree_momentum_batch(const tpr_chain *links, const int32_t *parent, const tpr_mount *mount, uint32_t link_mask, int B, int N,
                             const double *q, const double *qs, const double *limit, double *momentum, double *energy2,
                             double *xbound, int flags, void *stream);

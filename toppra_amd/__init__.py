@@ -15,11 +15,12 @@ gfx950 behind the C-ABI of ``include/toppra_hip.h``); there is no CPU fallback.
 """
 import logging
 
-from . import algorithm, batch, chain, constants, constraint, exceptions, interpolator, parametrizer, simplepath, solverwrapper
+from . import algorithm, batch, chain, constants, constraint, contact, exceptions, interpolator, parametrizer, simplepath, solverwrapper
 from .interpolator import PolynomialPath, SplineInterpolator, UnivariateSplineInterpolator
 from .simplepath import SimplePath
 from .chain import ControlPoints, JointSections, KinematicTree, Mount, Payload, SerialChain
-from .constraint import BatchBaseWrenchConstraint, BatchJointLoadConstraint, BatchMomentumConstraint, BatchToolWrenchConstraint
+from .constraint import (BatchBaseWrenchConstraint, BatchContactEnergyConstraint, BatchJointLoadConstraint, BatchMomentumConstraint,
+                         BatchToolWrenchConstraint)
 from .parametrizer import ParametrizeConstAccel, ParametrizeSpline
 
 logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
@@ -27,4 +28,5 @@ logging.getLogger("toppra_amd").addHandler(logging.NullHandler())
 __all__ = ["algorithm", "batch", "chain", "constants", "constraint", "exceptions", "interpolator", "parametrizer",
            "simplepath", "solverwrapper", "SplineInterpolator", "UnivariateSplineInterpolator", "PolynomialPath", "SimplePath",
            "ParametrizeConstAccel", "ParametrizeSpline", "SerialChain", "Payload", "BatchToolWrenchConstraint", "ControlPoints", "KinematicTree",
-           "Mount", "BatchBaseWrenchConstraint", "JointSections", "BatchJointLoadConstraint", "BatchMomentumConstraint"]
+           "Mount", "BatchBaseWrenchConstraint", "JointSections", "BatchJointLoadConstraint", "BatchMomentumConstraint",
+           "BatchContactEnergyConstraint", "contact"]

@@ -609,13 +609,14 @@ def _chain_points(chain, arrays, names):
     return out, shape, npoints
 
 
-def _rigid_call(model, entry, arrays, names, tails, structs=(), by_grid=False, limits=None):
+def _rigid_call(model, entry, arrays, names, tails, structs=(), by_grid=False, limits=None, host=()):
     """One call of the rigid-body entry ``entry`` on ``model`` (a :class:`toppra_amd.chain.SerialChain` or ``KinematicTree``).
     ``arrays``, named ``names``, are its inputs [..., d].  ``structs`` is what it takes by value after the model: a ready ctypes
     struct, or an object whose ``c_struct(model)`` makes one.  ``tails`` are the last axes of its outputs, each of the inputs'
     shape otherwise; None in place of a tail leaves that output out (a null pointer).  ``by_grid``: the entry takes (B, N) in
     place of npoints -- (npoints, 0), unless ``limits(q, shape, npoints)`` -> ((B, N), further inputs, tails) says otherwise; it
-    runs after the inputs are converted and before anything touches the device.  Returns the list of outputs."""
+    runs after the inputs are converted and before anything touches the device.  ``host``: host arrays (or None = a null pointer)
+    the entry takes by pointer after the structs and reads on the host.  Returns the list of outputs."""
     arrays, shape, npoints = _chain_points(model, arrays, names)
     q = arrays[0]
     structs = [s if isinstance(s, C.Structure) else s.c_struct(model) for s in structs]
@@ -627,6 +628,7 @@ def _rigid_call(model, entry, arrays, names, tails, structs=(), by_grid=False, l
     # (tpr_chain, what it points to) for a chain entry; a tree-walking one takes the host parent array between the two
     links = model.as_tree(q) if entry.startswith("tpr_tree_") else model.c_struct(q)
     head = [C.byref(links[0])] + [parent.ctypes.data for parent in links[1:-1]] + [C.byref(s) for s in structs]
+    head += [None if a is None else a.ctypes.data for a in host]
     outs = [None if tail is None else _empty(q, shape[:-1] + tuple(tail)) for tail in tails]
     _capi.check(getattr(_capi.load(), entry)(*head, *size, *[_capi.ptr(a) for a in arrays + outs],
                                              _capi.DEVICE_PTRS if _capi.is_torch_cuda(q) else 0, _stream_ptr(q)))

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtoppra_hip.so")
-SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_sampled_tu.hip", "tpr_rows_tu.hip", "tpr_boxed_tu.hip", "tpr_chain_tu.hip", "tpr_tree_tu.hip", "tpr_mount_tu.hip", "tpr_joint_tu.hip", "tpr_momentum_tu.hip"]
+SOURCES = ["tpr_kernels.hip", "tpr_cert_tu.hip", "tpr_robust_tu.hip", "tpr_dense_tu.hip", "tpr_sampled_tu.hip", "tpr_rows_tu.hip", "tpr_boxed_tu.hip", "tpr_chain_tu.hip", "tpr_tree_tu.hip", "tpr_mount_tu.hip", "tpr_joint_tu.hip", "tpr_momentum_tu.hip", "tpr_effmass_tu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-Wno-unused-variable"]
 
@@ -30,6 +30,7 @@ def deps():
         if name.endswith((".hip", ".hpp", ".inc", ".h")):
             out.append(os.path.join(CSRC, name))
     out.append(os.path.join(HERE, "..", "include", "toppra_hip.h"))
+    out.append(os.path.join(HERE, "..", "include", "toppra_hip_contact.h"))
     return out
 
 
@@ -105,6 +106,7 @@ def compile_jobs(measurement=False):
     jobs.append(("mount", "tpr_mount_tu.hip", []))  # the base reaction of a chain or tree: the wrench on its mount at every gridpoint
     jobs.append(("joint", "tpr_joint_tu.hip", []))  # joint loads of a chain or tree: the wrench across any joint at every gridpoint
     jobs.append(("momentum", "tpr_momentum_tu.hip", []))  # momentum and kinetic energy of a set of links at every gridpoint
+    jobs.append(("effmass", "tpr_effmass_tu.hip", []))  # effective mass and contact energy at control points at every gridpoint
     for d in range(1, max_dof + 1):
         for part, flags in sorted(({0: []} if measurement else CERT_UNITS[d]).items()):
             if part == 0:
@@ -153,7 +155,7 @@ def _compile_and_link(target, flags, defines, verbose):
             name, src, extra = job
             src = os.path.join(CSRC, src)
             obj = os.path.join(tmp, name + ".o")
-            verify = check and name.startswith(("cert", "rows", "boxed", "chain", "tree", "mount", "joint", "momentum"))  # family 3, the row-assembly, stage-box, chain, tree, mount, joint and momentum units
+            verify = check and name.startswith(("cert", "rows", "boxed", "chain", "tree", "mount", "joint", "momentum", "effmass"))  # family 3, the row-assembly, stage-box, chain, tree, mount, joint, momentum and effective-mass units
             fkey = hashlib.sha256((cc_id + " ".join(cflags + extra) + (" [checked]" if verify else "")).encode()).hexdigest()[:12]
             skey = hashlib.sha256((dep_hash.hexdigest() + os.path.basename(src)).encode()).hexdigest()[:12]
             cached = os.path.join(cache, "%s_%s_%s.o" % (name, fkey, skey))

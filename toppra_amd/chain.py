@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
+from . import contact as _contact
 
 REVOLUTE, PRISMATIC = "revolute", "prismatic"
 _JOINT_CODES = {REVOLUTE: _capi.JOINT_REVOLUTE, "r": _capi.JOINT_REVOLUTE, _capi.JOINT_REVOLUTE: _capi.JOINT_REVOLUTE,
@@ -363,8 +364,34 @@ class _Robot(object):
 
     def kinetic_energy(self, q, qd, links=None):
         """The kinetic energy [...] = 1/2 qd' M(q) qd of the links of ``links`` (as in :meth:`momentum`; None = the whole
-        robot), in J: what the structure can transfer on contact, whatever the contact point and direction."""
+        robot), in J: what the structure can transfer on contact, whatever the contact point and direction -- the upper envelope of
+        :meth:`contact_energy`, which is the energy at given points."""
         return 0.5 * _batch.momentum_batch(self, q, qd, None, links)[1]
+
+    def effective_mass(self, q, qd, points, directions=None):
+        """The effective (reflected) mass [..., P] of the robot at the points of ``points`` (a :class:`ControlPoints`), in kg: what
+        a contact there has to stop, m_R with 1 / m_R = u' J M(q)^-1 J' u.  ``directions`` None: u is the direction of each point's
+        velocity at ``qd`` -- speed2 / mobility of :func:`toppra_amd.contact.effective_mass_batch`, NaN (0 / 0) where the point
+        stands still, which has no direction.  ``directions`` [P, 3] (unit vectors in the points' link axes): 1 / mobility along
+        them; ``qd`` is not read then and may be None."""
+        speed2, mobility, _ = _contact.effective_mass_batch(self, q, qd, points, directions=directions)
+        with np.errstate(divide="ignore", invalid="ignore"):  # (a standstill: 0 / 0, documented; tensors are not numpy's to warn about)
+            return 1.0 / mobility if directions is not None else speed2 / mobility
+
+    def contact_energy(self, q, qd, points, body_mass=None):
+        """The energy [..., P] in J that a contact at each point of ``points`` can transfer at velocity ``qd``: 1/2 mu v^2 with v the
+        point's speed, mu = (1 / m_body + 1 / m_R)^-1 the reduced mass of the body part (``body_mass`` in kg: a scalar or [P];
+        None or inf = a clamped body part, 1 / m = 0) and of the robot's effective mass m_R along the point's velocity
+        (:meth:`effective_mass`); 0 where the point stands still.  What ISO/TS 15066 power and force limiting caps per body
+        region; :meth:`kinetic_energy` is its upper envelope."""
+        speed2, mobility, _ = _contact.effective_mass_batch(self, q, qd, points)
+        inv = _contact.inverse_body_mass(body_mass, int(speed2.shape[-1]))
+        if not isinstance(speed2, np.ndarray):
+            import torch
+            inv = torch.as_tensor(inv, device=speed2.device)
+            return torch.where(speed2 == 0, torch.zeros_like(speed2), 0.5 * speed2 / (inv + mobility / speed2))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(speed2 == 0, 0.0, 0.5 * speed2 / (inv + mobility / speed2))
 
     def joint_wrenches(self, q, qd, qdd, sections):
         """The wrench across the joints of ``sections`` (a :class:`JointSections`), [..., S, 6] in the set's order: per section

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _capi
 from . import batch as _batch
+from . import contact as _contact
 from .chain import KinematicTree, SerialChain
 from .interpolator import path_samples, spline_tables
 
@@ -1142,8 +1143,9 @@ class BatchMomentumConstraint(_BatchChainBound):
 
     The bound (0, min(linear^2 / |P|^2, angular^2 / |L|^2, 2 energy / q'' M q')) comes from one launch and is ONE ``xbound`` source
     of the stage boxes; a term that vanishes drops out of the minimum, and where the robot stands still the box keeps its 1e8.
-    Needs the path positions: a ``from_path_samples`` batch must be given ``q``.  Per-trajectory robots or mounts, a floating
-    base, power limits and the effective mass at a contact point are out of scope."""
+    Needs the path positions: a ``from_path_samples`` batch must be given ``q``.  The energy a contact at a given point can
+    transfer -- the robot's effective mass there -- is :class:`BatchContactEnergyConstraint`; this one is its upper envelope.
+    Per-trajectory robots or mounts, a floating base and power limits are out of scope."""
     no_q = "a momentum or energy limit evaluates the robot at q: give the path positions"
 
     def __init__(self, robot, linear=None, angular=None, energy=None, mount=None, links=None):
@@ -1181,6 +1183,63 @@ class BatchMomentumConstraint(_BatchChainBound):
     def bound_sources(self, gridpoints, B, N, d, like, q=None):
         limit = self._limit_like(B, N, d, like, q)
         return [("xbound", _batch.momentum_bound_batch(self.robot, q, like, limit, self.mount, self.links))]
+
+
+class BatchContactEnergyConstraint(_BatchChainBound):
+    """A cap on the energy a contact at control points of a robot can transfer, for a batch -- what ISO/TS 15066 power and force
+    limiting sets per body region:  1/2 mu_p v_p^2 <= energy_p  at every gridpoint and for every point p of ``points``, where v_p is
+    the point's speed, mu_p = (1 / m_body + 1 / m_R)^-1 the reduced mass of the body part and the robot, and m_R the robot's
+    effective (reflected) mass at the point along its velocity, 1 / m_R = u' J M(q)^-1 J' u
+    (:meth:`toppra_amd.chain.SerialChain.effective_mass`, ``contact_energy``).  The total kinetic energy that
+    :class:`BatchMomentumConstraint` bounds is this quantity's upper envelope: at equal ``energy`` this limit is never slower.
+
+    ``robot``: a :class:`toppra_amd.chain.SerialChain` or :class:`toppra_amd.chain.KinematicTree`; ``points``: a
+    :class:`toppra_amd.chain.ControlPoints` (1 .. 16 points on any links).  ``energy``: in J -- a scalar, [P] or [B, P], > 0.
+    ``body_mass``: in kg -- a scalar or [P], > 0; None or ``inf`` = a clamped or fixed body part, 1 / m = 0.  Both are in PHYSICAL
+    UNITS, as :class:`BatchMomentumConstraint`'s are (not squares): the class forms ``2.0 * energy`` and ``1.0 / body_mass`` on the
+    host and hands the kernel what it multiplies and divides.  No table of body regions is shipped; :meth:`from_force` turns a
+    region's force limit and stiffness into its energy.
+
+    The bound (0, min_p 2 energy_p (1 / m_body + 1 / m_R) / |v_p|^2) comes from one launch and is ONE ``xbound`` source of the
+    stage boxes however many points the set has; a point that stands still drops out of the minimum, and where all of them do
+    the box keeps its 1e8.  Needs the path positions: a ``from_path_samples`` batch must be given ``q``.  A robot whose mass
+    matrix is singular (a weightless leaf link) gives a non-finite bound: the caller's responsibility.  Directions in world axes,
+    a true friction or conic model, per-trajectory robots, a floating base and the ISO tables of body-region limits are out of
+    scope."""
+    no_q = "a contact-energy limit evaluates the robot at q: give the path positions"
+
+    def __init__(self, robot, points, energy, body_mass=None):
+        super(BatchContactEnergyConstraint, self).__init__()
+        _need_robot(robot)
+        _need_points(points, robot)
+        P = points.count
+        host = _host(energy)
+        if host.shape not in ((), (P,)) and not (host.ndim == 2 and host.shape[1] == P):
+            raise ValueError("energy must be a scalar or have shape [P] or [B, P] with P = %d, got %s" % (P, list(host.shape)))
+        if not np.all(host > 0):
+            raise ValueError("energy must be > 0 (NaN is refused; 0 / 0 at a standstill would be a NaN bound)")
+        inv = _contact.inverse_body_mass(body_mass, P)
+        self.robot, self.points, self.energy, self.body_mass = robot, points, energy, body_mass
+        self.dof = robot.dof
+        self._limit_batch = int(host.shape[0]) if host.ndim == 2 else None
+        lead = () if self._limit_batch is None else (self._limit_batch,)
+        # what the kernel multiplies and divides: (2 E_max, 1 / m_body), [P, 2] or [B, P, 2]
+        self.limit = np.ascontiguousarray(np.stack([np.broadcast_to(2.0 * host, lead + (P,)), np.broadcast_to(inv, lead + (P,))], -1))
+        self._format_string = "    Batched contact-energy limit, %d dof, %d points\n" % (self.dof, P)
+
+    @classmethod
+    def from_force(cls, robot, points, force, stiffness, body_mass=None):
+        """The limit a body region's force limit implies: a contact that compresses a region of stiffness k (N / m) up to the
+        force F (N) has stored E = F^2 / (2 k) -- the relation ISO/TS 15066 derives its energy limits with.  ``force`` and
+        ``stiffness``: each a scalar, [P] or [B, P], > 0."""
+        F, k = _host(force), _host(stiffness)
+        if not (np.all(F > 0) and np.all(k > 0)):
+            raise ValueError("force and stiffness must be > 0 (NaN is refused)")
+        return cls(robot, points, F * F / (2.0 * k), body_mass)
+
+    def bound_sources(self, gridpoints, B, N, d, like, q=None):
+        limit = self._limit_like(B, N, d, like, q)
+        return [("xbound", _contact.effective_mass_bound_batch(self.robot, q, like, self.points, limit))]
 
 
 class ConicConstraint(Constraint):

@@ -1607,12 +1607,15 @@ int tpr_reachable_sets_sampled_boxed_batch(const tpr_sampled_problem *p, const d
 }  // extern "C"
 
 // ---- a rigid-body chain or tree evaluated on the GPU (tpr_chain.hip.inc, tpr_chain_tu.hip; tpr_tree.hip.inc, tpr_tree_tu.hip;
-// tpr_mount.hip.inc, tpr_mount_tu.hip; tpr_joint.hip.inc, tpr_joint_tu.hip; tpr_momentum.hip.inc, tpr_momentum_tu.hip) -------------
+// tpr_mount.hip.inc, tpr_mount_tu.hip; tpr_joint.hip.inc, tpr_joint_tu.hip; tpr_momentum.hip.inc, tpr_momentum_tu.hip;
+// tpr_effmass.hip.inc, tpr_effmass_tu.hip) ---------------------------------------------------------------------------------------
 // One host path for the family: an entry is its argument checks, in an order that is its own and is behaviour (which refusal
 // wins when two arguments are bad: tests/test_rigid_refusal_order.py), then run_rigid() with what it stages and what it launches.
 #include "tpr_mount_args.hpp"
 #include "tpr_joint_args.hpp"
 #include "tpr_momentum_args.hpp"
+#include "tpr_effmass_args.hpp"
+#include "../../include/toppra_hip_contact.h"
 extern "C" {
 __attribute__((visibility("hidden"))) int tpr_tu_chain_dynamics_launch(const tpr::ChainDynArgs *, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_chain_terms_launch(const tpr::ChainTermsArgs *, hipStream_t);
@@ -1630,6 +1633,7 @@ __attribute__((visibility("hidden"))) int tpr_tu_mount_wrench_terms_launch(const
 __attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_launch(const tpr::JointWrenchArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_joint_wrench_terms_launch(const tpr::JointWrenchTermsArgs *, int forks, hipStream_t);
 __attribute__((visibility("hidden"))) int tpr_tu_momentum_launch(const tpr::MomentumArgs *, int forks, hipStream_t);
+__attribute__((visibility("hidden"))) int tpr_tu_effmass_launch(const tpr::EffMassArgs *, int forks, hipStream_t);
 }
 namespace {
 // The gridpoints of a batch given as (B, N).
@@ -2154,5 +2158,53 @@ int tpr_tree_momentum_batch(const tpr_chain *links, const int32_t *parent, const
         A.xbound = S.out(xbound, 2 * (size_t)npoints);
         return A;
     }, [reached](const tpr::MomentumArgs *A, hipStream_t stream) { return tpr_tu_momentum_launch(A, reached, stream); });
+}
+
+// (declared in include/toppra_hip_contact.h)
+int tpr_tree_effective_mass_batch(const tpr_chain *links, const int32_t *parent, const tpr_chain_points *points, const double *direction,
+                                  int B, int N, const double *q, const double *qs, const double *limit, double *speed2, double *mobility,
+                                  double *xbound, int flags, void *stream_) {
+    const char *who = "tpr_tree_effective_mass_batch";
+    tpr::TreeTables T;
+    int forks = 0;
+    long long npoints = 0;
+    if (int rc = batch_points(B, N, who, npoints)) return rc;
+    if (int rc = check_tree(links, parent, npoints, who, T, forks)) return rc;
+    if (int rc = check_points(links, points, who)) return rc;
+    if (direction) {
+        if (int rc = refuse_device_pointer(direction, who, "direction")) return rc;
+        for (int k = 0; k < 3 * points->count; ++k)
+            if (!std::isfinite(direction[k])) return fail(TPR_E_BADARG, std::string(who) + ": every direction must be finite");
+    }
+    if (!q) return fail(TPR_E_BADARG, std::string(who) + ": q is required");
+    if (!qs && (!direction || speed2 || xbound))
+        return fail(TPR_E_BADARG, std::string(who) + ": qs is required (but for the mobility alone along given directions)");
+    if (!speed2 && !mobility && !xbound) return fail(TPR_E_BADARG, std::string(who) + ": one of speed2, mobility, xbound is required");
+    if (xbound && !limit) return fail(TPR_E_BADARG, std::string(who) + ": xbound needs limit");
+    return run_rigid(flags, speed2 ? speed2 : mobility ? mobility : xbound, stream_, npoints,
+                     "tpr_tree_effective_mass_batch: the kernel's LDS could not be reserved", [&](Staging &S) {
+        auto A = rigid_args<tpr::EffMassArgs>(links, npoints, S, false);
+        const size_t count = (size_t)points->count;
+        A.T = T;
+        A.P = stage_points(points);
+        A.directed = direction ? 1 : 0;
+        for (int p = 0; p < points->count; ++p) {
+            for (int j = 0; j < 3; ++j) A.direction[p][j] = direction ? direction[3 * p + j] : 0.0;
+            // the point's own link, the links from it to its root, and that root's whole tree
+            A.own[points->link[p]] |= (uint16_t)(1u << p);
+            int i = points->link[p];
+            for (; parent[i] >= 0; i = parent[i]) A.active[i] |= (uint16_t)(1u << p);
+            A.active[i] |= (uint16_t)(1u << p);
+        }
+        for (int i = 0; i < links->d; ++i)  // (parents come first: a link is walked when it is a root with a point, or its parent is)
+            if (parent[i] < 0 ? A.active[i] != 0 : (A.walk >> parent[i] & 1u)) A.walk |= 1u << i;
+        A.n1 = N + 1;
+        A.q = S.in(q, (size_t)npoints * (size_t)links->d);
+        A.qs = qs ? S.in(qs, (size_t)npoints * (size_t)links->d) : A.q;  // (no qs: s2 is not asked for, and g does not read it)
+        A.limit = xbound ? S.in(limit, 2 * count * (size_t)B) : nullptr;
+        A.speed2 = S.out(speed2, count * (size_t)npoints); A.mobility = S.out(mobility, count * (size_t)npoints);
+        A.xbound = S.out(xbound, 2 * (size_t)npoints);
+        return A;
+    }, [forks](const tpr::EffMassArgs *A, hipStream_t stream) { return tpr_tu_effmass_launch(A, forks, stream); });
 }
 }  // extern "C"
